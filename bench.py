@@ -14,9 +14,20 @@ N > 1    : weak scaling - the grid grows to (1000 N) x 1000, node-range sharded,
            cases with the same JSON contract: C2 (100k-node G(n,p), RK4 on linspace(0,5,100)), C3 (1M-node
            Barabasi-Albert m=5, dopri5), C5 (dgnn hot path: Pubmed topology, no_control, dopri5 rtol=atol=.1, 16 ticks).
 
-Prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed on the
-launch stream during a second, instrumented pass over the same K steps; `traffic` from the committed PMC summary of THIS
-configuration or null) and `cpu_baseline` (the CPU oracle timed on a bounded sample of this configuration, rank 0, N = 1 only).
+Prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step) and the
+workload.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.
+--full   : also the measurements beyond the headline, in the same line: `spmm_standalone` (the workload's CSR SpMM alone, HIP
+           events), `roofline` + `kernels` (dominant kernel, HIP-event timed on the launch stream during a second, instrumented
+           pass over K more steps; `traffic` from the committed PMC summary of THIS configuration or null; the measured HBM copy
+           ceiling), `halo_exchange` (N > 1 / --sharded: a short instrumented pass) and `cpu_baseline` + `parity` (the CPU oracle
+           timed on a bounded sample of this configuration and the HIP path on that sample, rank 0, N = 1 only).
+           NDCN_BENCH_FULL=1 makes --full the default (tools/gpu.sh, whose lab modes read those figures).
+--dump-outputs DIR : after the timed steps, the solution the last timed step led to, as a caller of the solver receives it
+           (y at the tick that step was heading for; when the step budget ended between two ticks the solve is carried to that
+           tick first, outside the timed region): DIR/t.npy (float64, the tick times), DIR/y_sample.npy (float32, ticks x rows x
+           H: every row, or a fixed seeded sample of rows when the panels exceed 32 MiB), DIR/y_sample_rows.npy (float64, the
+           sampled row indices) and DIR/y_column_mean.npy (float64, ticks x H: the mean over ALL rows).  Inputs are seeded, so
+           the same arguments give the same inputs on every run.  Single-GPU path only.
 `--gpus N` without a launcher re-executes itself under torch.distributed.run (one rank per GPU).
 """
 import argparse
@@ -98,11 +109,16 @@ def parse():
     p.add_argument('--T', type=float, default=5.0)
     p.add_argument('--rtol', type=float, default=0.01)
     p.add_argument('--atol', type=float, default=0.001)
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true', default=os.environ.get('NDCN_BENCH_FULL', '') == '1',
+                   help='also the standalone SpMM, the instrumented roofline pass, the HBM copy ceiling, the halo timing and the '
+                        'CPU baseline + parity (a plain run prints the headline alone)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the solution the last timed step led to as DIR/<name>.npy (float32 / float64, <= 64 MB)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     p.add_argument('--cpu-threads', type=int, default=32, help='host threads of the CPU-baseline leg')
     p.add_argument('--cpu-nodes', type=int, default=0, help='nodes of the bounded CPU-baseline sample (0: per-configuration default)')
     p.add_argument('--no-at-scale', action='store_true', help='skip cpu_baseline.at_scale (one oracle RHS + one solver step at ~10^5 nodes)')
-    p.add_argument('--no-profile-pass', action='store_true')
+    p.add_argument('--no-profile-pass', action='store_true', help='--full without the instrumented roofline pass')
     p.add_argument('--sharded', action='store_true', help='force the multi-GPU code path (works with 1 rank)')
     p.add_argument('--sharded-impl', default=os.environ.get('NDCN_SHARDED_IMPL', 'device'), choices=['device', 'python'],
                    help='N > 1: the sharded device-resident solver behind the C ABI (default: the form DESIGN section 6 projects - the '
@@ -138,6 +154,8 @@ class SingleGpuRunner:
         self.traj = torch.empty((len(self.ticks) - 1,) + tuple(x0.shape), device=x0.device) if len(self.ticks) > 2 and method == 'dopri5' else None
         self.restarts = 0
         self.nfe_done = 0
+        self.last = None                                 # (ticks, panel) a caller received last
+        self.pending = False                             # the step budget ran out between two ticks
 
     def run_steps(self, k):
         done = 0
@@ -148,23 +166,43 @@ class SingleGpuRunner:
                 # step count is known from the previous solve of the same initial value
                 self.solver.advance_many(self.ticks[1:], self.traj)
                 done += int(self.solver.stats()['steps'])
+                self.last = (self.ticks[1:], self.traj)
                 reached_end = True
             else:
                 before = self.solver.stats()['steps']
                 dst = self.out if (self.out2 is None or self.pos % 2) else self.out2
                 reached = self.solver.advance(self.ticks[self.pos], dst, step_budget=k - done)
                 done += int(self.solver.stats()['steps'] - before)
-                reached_end = False
-                if reached:
-                    self.pos += 1
-                    reached_end = self.pos == len(self.ticks)
+                self.pending = not reached
+                reached_end = reached and self._reached(dst)
             if reached_end:
-                self.solve_steps = int(self.solver.stats()['steps'])
-                self.nfe_done += int(self.solver.stats()['nfe'])
-                self.solver.begin(self.x0, self.ticks[0], borrow=True)        # resets the solver's own counters
-                self.pos = 1
-                self.restarts += 1
+                self._restart()
         return done
+
+    def _reached(self, dst):
+        """The tick self.pos was written to dst; True at the end of the time grid."""
+        self.last = ([self.ticks[self.pos]], dst)
+        self.pos += 1
+        return self.pos == len(self.ticks)
+
+    def _restart(self):
+        self.solve_steps = int(self.solver.stats()['steps'])
+        self.nfe_done += int(self.solver.stats()['nfe'])
+        self.solver.begin(self.x0, self.ticks[0], borrow=True)        # resets the solver's own counters
+        self.pos = 1
+        self.restarts += 1
+
+    def last_output(self):
+        """(ticks, panels) a caller of the solver receives from the solve the last step belongs to: y at the tick that step was
+        heading for.  A step budget that ran out between two ticks (dopri5) is carried on to that tick here, without a budget."""
+        if self.pending:
+            dst = self.out if (self.out2 is None or self.pos % 2) else self.out2
+            reached = self.solver.advance(self.ticks[self.pos], dst)
+            assert reached
+            self.pending = False
+            if self._reached(dst):
+                self._restart()
+        return self.last
 
     def nfe(self):
         return self.nfe_done + int(self.solver.stats()['nfe'])
@@ -332,6 +370,29 @@ def cpu_baseline(cfg, H, T, rtol, atol, threads, runs=5, nodes=0, dev=None, at_s
     return base, parity
 
 
+DUMP_SAMPLE_BYTES = 32 << 20      # y_sample.npy: every row while the panels fit, a seeded sample of rows beyond
+
+
+def dump_outputs(out_dir, ticks, panels):
+    """--dump-outputs: the panels a caller received (n x H, or one per tick) as float32 / float64 .npy files under out_dir."""
+    P = panels if panels.dim() == 3 else panels.unsqueeze(0)
+    k, n, H = P.shape
+    R = min(n, max(1, DUMP_SAMPLE_BYTES // (4 * H * k)))
+    rows = np.arange(n) if R == n else np.sort(np.random.default_rng(0).choice(n, R, replace=False))
+    acc = torch.zeros(k, H, dtype=torch.float64, device=P.device)
+    chunk = max(1, (1 << 16) // k)
+    for a in range(0, n, chunk):                          # float64 column sums without a float64 copy of the panels
+        acc += P[:, a:a + chunk].double().sum(1)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'t': np.asarray(ticks, dtype=np.float64),
+              'y_sample': P.index_select(1, torch.from_numpy(rows).to(P.device)).cpu().numpy().astype(np.float32),
+              'y_sample_rows': rows.astype(np.float64),
+              'y_column_mean': (acc / n).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    print('[bench] outputs of the last timed step: %s (%d tick(s), %d of %d rows, H=%d)' % (out_dir, k, R, n, H), file=sys.stderr, flush=True)
+
+
 C4_NODES_PER_GPU = int(os.environ.get('NDCN_C4_NODES', '500000'))    # BASELINE config 4: a 4M-node small world over 8 GPUs (override: tests)
 
 
@@ -451,6 +512,8 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
     assert world == args.gpus, '--gpus %d but WORLD_SIZE %d' % (args.gpus, world)
+    assert not (args.dump_outputs and (world > 1 or args.sharded)), '--dump-outputs: the single-GPU path only'
+    assert not (args.dump_outputs and args.steps < 1), '--dump-outputs needs a timed step'
 
     from ndcn_amd import _lib, graphs, device_info
     from ndcn_amd.neural_dynamics import ODEFunc
@@ -462,7 +525,7 @@ def main():
         f, A_op, x0, kw, nnz, what, step_desc = build_workload(args, dev)
         n_local = x0.shape[0]
         runner = SingleGpuRunner(f, x0, kw['T'], kw['rtol'], kw['atol'], method=kw['method'], ticks=kw.get('ticks'))
-        if H == 256 and not f.no_graph:
+        if args.full and H == 256 and not f.no_graph:
             # the north-star's own kernel figure: the standalone CSR SpMM of this workload's operator (HIP events)
             from ndcn_amd import hip as _hip
             Y = torch.empty_like(x0)
@@ -566,6 +629,10 @@ def main():
         wall = time.perf_counter() - t0
     assert done == args.steps
     nfe = runner.nfe() - nfe0
+    if args.dump_outputs:
+        with torch.no_grad():
+            ticks, panels = runner.last_output()
+        dump_outputs(args.dump_outputs, ticks, panels)
     if dist is not None:
         tw = torch.tensor([wall], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
@@ -575,7 +642,7 @@ def main():
 
     # ---- instrumented pass over the same K steps: HIP events around every kernel launch
     roofline, breakdown = None, {}
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         nk = lib.ndcn_prof_kinds()
         buf = (_lib.ctypes.c_double * (4 * nk))()
         lib.ndcn_prof_enable(1)
@@ -654,7 +721,7 @@ def main():
             roofline['traffic_frac_of_measured_copy'] = round(tg / copy_gbps, 4)
         del src_p, dst_p
     halo = None
-    if hasattr(runner, 'plan') and (world > 1 or runner.plan.n_halo > 0):
+    if args.full and hasattr(runner, 'plan') and (world > 1 or runner.plan.n_halo > 0):
         hb = int(runner.plan.bytes_per_exchange(H))
         # a short instrumented pass: per exchange, its duration on the side stream, the launch it hides behind, and what
         # the main stream still waited for (exposed).  The device-resident solver is timed through its Python twin: the
@@ -696,18 +763,16 @@ def main():
                    'step': step_desc},
         'node_rhs_per_s': round(n_total * nfe / wall, 1),
         'rhs_evals': nfe,
-        'roofline': roofline,
-        'kernels': breakdown,
-        'spmm_standalone': spmm_line,
         'device': device_info(),
-        'halo_exchange': halo,
     }
-    if world == 1 and not args.sharded and not args.no_cpu_baseline:
-        cfg_name = 'NC' if (args.config == 'M' and args.no_control) else args.config
-        out['cpu_baseline'], out['parity'] = cpu_baseline(cfg_name, H, args.T, args.rtol, args.atol, args.cpu_threads,
-                                                           args.cpu_runs, args.cpu_nodes, dev=dev, at_scale=not args.no_at_scale)
-    else:
-        out['cpu_baseline'] = out['parity'] = None
+    if args.full:
+        out.update({'roofline': roofline, 'kernels': breakdown, 'spmm_standalone': spmm_line, 'halo_exchange': halo})
+        if world == 1 and not args.sharded and not args.no_cpu_baseline:
+            cfg_name = 'NC' if (args.config == 'M' and args.no_control) else args.config
+            out['cpu_baseline'], out['parity'] = cpu_baseline(cfg_name, H, args.T, args.rtol, args.atol, args.cpu_threads,
+                                                               args.cpu_runs, args.cpu_nodes, dev=dev, at_scale=not args.no_at_scale)
+        else:
+            out['cpu_baseline'] = out['parity'] = None
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -710,7 +710,7 @@ def test_bench_two_ranks_on_one_device(dev, config):
     launcher = [] if config == 'M' else ['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                                          '127.0.0.1', '--master-port', str(port)]
     cmd = [sys.executable] + launcher + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--side', '96', '--steps', '6',
-                                         '--warmup', '2', '--config', config]
+                                         '--warmup', '2', '--config', config, '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
@@ -719,6 +719,49 @@ def test_bench_two_ranks_on_one_device(dev, config):
     assert out['halo_exchange']['bytes_received_per_rhs_per_gpu'] > 0 and out['cpu_baseline'] is None
     assert out['halo_exchange']['two_phase_own_columns_under_exchange'] == (config == 'C4')
     assert out['roofline']['kernel'] == 'rhs_fused' and out['roofline']['traffic'] is None
+
+
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain `bench.py` run prints the headline alone (no roofline / CPU-baseline passes); `--dump-outputs` writes the solution
+    the last timed step led to - here y(T) of the metric's dopri5 solve on a 48 x 48 grid - equal to odeint() on the same seeded
+    inputs, and the same on a second run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    from ndcn_amd import torchdiffeq as ode
+    env = dict(os.environ)
+    env.pop('NDCN_BENCH_FULL', None)
+    argv = ['--side', '48', '--steps', '7', '--warmup', '2']
+    runs = []
+    for i in range(2):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py')] + argv + ['--dump-outputs', str(tmp_path / str(i))]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
+        out = json.loads(lines[0])
+        assert out['steps'] == 7 and out['ms_per_step'] > 0 and out['value'] > 0 and out['dtype'] == 'f32' and out['higher_is_better']
+        assert not {'roofline', 'kernels', 'spmm_standalone', 'cpu_baseline', 'parity'} & set(out)
+        d = {k: np.load(str(tmp_path / str(i) / (k + '.npy'))) for k in ('t', 'y_sample', 'y_sample_rows', 'y_column_mean')}
+        assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+        runs.append(d)
+    d = runs[0]
+    assert d['t'].tolist() == [5.0] and d['y_sample'].shape == (1, 48 * 48, 256)
+    assert np.array_equal(d['y_sample_rows'], np.arange(48 * 48))
+    for k in d:
+        assert np.allclose(d[k], runs[1][k], rtol=1e-6, atol=1e-7), k
+    old = sys.argv
+    sys.argv = ['bench.py'] + argv
+    try:
+        args = bench.parse()
+    finally:
+        sys.argv = old
+    f, _, x0, kw, _, _, _ = bench.build_workload(args, dev)
+    with torch.no_grad():
+        ref = ode.odeint(f, x0, torch.tensor([0., kw['T']], device=dev), rtol=kw['rtol'], atol=kw['atol'], method='dopri5')[-1].cpu()
+    assert np.abs(d['y_sample'][0] - ref.numpy()).max() <= 1e-6 * max(1.0, float(ref.abs().max()))
+    assert np.abs(d['y_column_mean'][0] - ref.double().mean(0).numpy()).max() < 1e-6
 
 
 def test_tuple_state_generic_path(dev):

@@ -192,18 +192,37 @@ def test_column_sweep_plan_restatement_reconstructs_the_operator(shape, avg):
     assert np.array_equal(back.indptr, m.indptr) and np.array_equal(back.indices, m.indices) and np.array_equal(back.data, m.data)
 
 
-def test_planetoid_loader_against_reference_steps():
-    """ndcn_amd/planetoid.py vs the fixture assembled from the reference's data files (tools/gen_golden.py G8).
-    Needs the reference's data directory; skipped where it is absent (GPU box)."""
+def _write_planetoid_files(data_dir, name, raw):
+    """The ind.<name>.* files of a Planetoid data directory (pickled scipy CSR / numpy parts, a dict of neighbour lists, the test
+    index as text) rebuilt from the plain arrays of tests/golden/planetoid_<name>_raw.npz (tools/gen_golden.py gen_planetoid_raw)."""
+    import collections
     import os
-    import pytest
-    import torch
-    ref_data = '/root/reference/data'
-    if not os.path.isdir(ref_data):
-        pytest.skip('reference data directory not present')
+    import pickle
+    os.makedirs(os.path.join(data_dir, name))
+    parts = {}
+    for part in ('x', 'tx', 'allx'):
+        parts[part] = sp.csr_matrix((raw[part + '_data'], raw[part + '_indices'].astype(np.int32), raw[part + '_indptr']),
+                                    shape=tuple(raw[part + '_shape']))
+    for part in ('y', 'ty', 'ally'):
+        parts[part] = raw[part].astype(np.int32)
+    graph = collections.defaultdict(list)
+    offsets = np.concatenate([[0], np.cumsum(raw['graph_counts'])])
+    for i, k in enumerate(raw['graph_keys'].tolist()):
+        graph[k] = raw['graph_neighbours'][offsets[i]:offsets[i + 1]].tolist()
+    parts['graph'] = graph
+    for part, obj in parts.items():
+        with open(os.path.join(data_dir, name, 'ind.%s.%s' % (name, part)), 'wb') as fh:
+            pickle.dump(obj, fh)
+    np.savetxt(os.path.join(data_dir, name, 'ind.%s.test.index' % name), raw['test_index'], fmt='%d')
+
+
+def test_planetoid_loader_against_reference_steps(tmp_path):
+    """ndcn_amd/planetoid.py vs the fixture assembled from the reference's data files (tools/gen_golden.py G8), reading Cora's
+    raw files as they are laid out in a Planetoid data directory (rebuilt from tests/golden/planetoid_cora_raw.npz)."""
     from ndcn_amd import planetoid
+    _write_planetoid_files(str(tmp_path), 'cora', load_golden('planetoid_cora_raw'))
     d = load_golden('dataset_cora')
-    adj, feats, labels, itr, iva, ite = planetoid.load_data('cora', 0.0, ref_data)
+    adj, feats, labels, itr, iva, ite = planetoid.load_data('cora', 0.0, str(tmp_path))
     ref_feat = sp.csr_matrix((d['feat_data'], d['feat_indices'].astype(np.int64), d['feat_indptr']), shape=tuple(d['feat_shape']))
     assert np.abs(feats.numpy() - ref_feat.toarray()).max() < 1e-7
     assert np.array_equal(labels.numpy(), d['labels'].astype(np.int64))

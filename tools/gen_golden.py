@@ -388,6 +388,30 @@ def gen_dataset():
          idx_val=np.arange(len(y), len(y) + 500, dtype=np.int32), idx_test=test_idx_range.astype(np.int32))
 
 
+def gen_planetoid_raw():
+    """Cora's raw Planetoid parts as plain arrays (x / tx / allx as CSR, y / ty / ally dense, graph as keys + neighbour lists in
+    their order, the test index): tests/test_graphs.py writes them back as the ind.cora.* files planetoid.load_data reads."""
+    name = 'cora'
+    arrays = {}
+    for part in ('x', 'y', 'tx', 'ty', 'allx', 'ally', 'graph'):
+        with open(os.path.join(REF, 'data', name, 'ind.%s.%s' % (name, part)), 'rb') as fh:
+            o = pickle.load(fh, encoding='latin1')
+        if part == 'graph':
+            keys = list(o.keys())
+            arrays.update(graph_keys=np.array(keys, dtype=np.int32),
+                          graph_counts=np.array([len(o[k]) for k in keys], dtype=np.int32),
+                          graph_neighbours=np.array([c for k in keys for c in o[k]], dtype=np.int32))
+        elif sp.issparse(o):
+            assert o.format == 'csr'
+            arrays.update({part + '_indptr': o.indptr.astype(np.int32), part + '_indices': o.indices.astype(np.int16),
+                           part + '_data': o.data, part + '_shape': np.array(o.shape, dtype=np.int64)})
+        else:
+            assert np.array_equal(o.astype(np.int8), o)
+            arrays[part] = o.astype(np.int8)
+    arrays['test_index'] = np.loadtxt(os.path.join(REF, 'data', name, 'ind.%s.test.index' % name), dtype=np.int64).astype(np.int32)
+    save('planetoid_cora_raw', **arrays)
+
+
 # ----------------------------------------------------------------------------- G9
 def gen_adjoint():
     """Gradients of the reference's odeint_adjoint (torchdiffeq/_impl/adjoint.py:105-133) on a small case."""
@@ -531,6 +555,6 @@ def gen_adams():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'adjoint', 'resgcn', 'adams']
+    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams']
     for w in which:
         globals()['gen_' + w]()
