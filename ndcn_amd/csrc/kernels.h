@@ -21,8 +21,11 @@ namespace ndcn {
 //          combine launch in front (3 panels); same product-then-sum rounding per element.
 //   no_k   (a hint; COMBINE / RK4 modes) the caller reads only y_next: a kernel that can skips the store of K - an Euler step's K, the
 //          fourth stage of an RK4 step.  Honoured by rhs_fused3 (one panel of HBM writes less); K must still point at a panel.
+//   c_mid  (COMBINE with 4 earlier stages and no_k, rhs_dense_supported()) the K panel receives sum_{m<4} c_mid[m] kprev[m] + c_mid[4] K
+//          instead of K - dopri5's midpoint sum M, formed by the launch that produces k6 for a step that covers a requested tick.
 struct RkOpt { const float *y1; int accum; float *y_aux; const float *c_aux; const float *xadd; float xadd_c;
-               const float *xmask; float *s_out; int no_k; };      // (xmask, s_out: rhs_adj_supported)
+               const float *xmask; float *s_out; int no_k;      // (xmask, s_out: rhs_adj_supported)
+               const float *c_mid; };
 
 int spmm_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, float *Y, int H, float alpha,
              uint32_t flags, hipStream_t st);
@@ -69,6 +72,7 @@ int partials_finish(const double *partials, int n, double *d_out, hipStream_t st
 int rhs_fused3_supported(const ndcn_csr *A);
 int rhs_xadd_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev);   // RkOpt::xadd can be honoured
 int rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev);    // RkOpt::xmask / s_out can be honoured
+int rhs_dense_supported(const ndcn_csr *A, int H, uint32_t flags);                         // RkOpt::c_mid can be honoured
 int rhs_fused3_variant(int mode, int n_prev);
 int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const void *Wq, const float *b, float *K,
                    uint32_t flags, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,

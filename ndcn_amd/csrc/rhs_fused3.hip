@@ -63,6 +63,9 @@ constexpr int kF3R = 16, kF3Cap = 40, kF3RecW = 2;       // the plan shape this 
 #define NDCN_F3_HEAVY_4P 0
 #endif
 enum { F3_PLAIN = 0, F3_COMBINE = 1, F3_ERROR = 2, F3_RK4 = 3 };
+// dopri5 dense output riding in a step's launches (rhs_fused3_dense_kernel): MID - the launch that produces k6 (COMBINE, 4 earlier
+// stages) stores the midpoint sum M = dt sum_j c_mid[j] k_j into the K panel instead of k6
+enum { F3_DO_NONE = 0, F3_DO_MID = 1 };
 // The wave split is a function of the variant (f3_producers).  Shipped: 16 waves everywhere (8 producers | 8 MFMA waves, 128
 // registers: 10 resident weight k-steps).  NDCN_F3_HEAVY_4P = 1 gives the launches with >= 3 earlier stages the 12-wave form
 // (4 producers | 8 MFMA waves, 168 registers: ALL 16 k-steps resident, no weight stream at all) - correct since the epilogue
@@ -143,6 +146,7 @@ struct F3Epi {
     const float *y1;                 // ERROR: the state of the error record, by row of this launch
     float *y_aux;                    // COMBINE, nullable: second linear combination (no y0), coefficients c2[]
     float c2[kF3MaxPrev + 1];
+    float c3[kF3MaxPrev + 1];        // DO_MID: the K panel receives sum_m c3[m] kprev[m] + c3[n_prev] K (left to right) instead of K
 };
 
 // The epilogue arguments (8 pointers, 14 scalars) are NOT read through the kernel-parameter object: the compiler would keep all
@@ -167,11 +171,13 @@ constexpr int kF3EpiKernargOffset = (int)((sizeof(F3Args) + 7) / 8 * 8);       /
 // NOK: the store of K compiled out (RkOpt::no_k) - a template argument, instantiated only for the two launches that use it (COMBINE
 // with no earlier stage: an Euler step / midpoint's second stage; RK4's fourth stage), so that the dopri5 variants carry no branch
 // for it (as a run-time test of a.K it cost every variant 241 instructions and 33 waits: round-5 review)
-template <bool HALO, int MODE, int NP, int XOP = 0, bool NT = true, bool SOUT = false, bool NOK = false>
-__global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fused3_kernel(F3Args a, F3Epi epi_by_kernarg_only) {
+// DO (F3_DO_*): the dense-output epilogues, instantiated in rhs_fused3_dense_kernel only
+template <bool HALO, int MODE, int NP, int XOP, bool NT, bool SOUT, bool NOK, int DO>
+__device__ __forceinline__ void rhs_fused3_body(F3Args a) {
     constexpr bool XADD = XOP != 0;                          // a second panel is gathered alongside X
     static_assert(!(XADD && HALO), "the halo rows of Xadd are not exchanged");
-    (void)epi_by_kernarg_only;
+    static_assert(DO == F3_DO_NONE || (!HALO && !XADD && !SOUT && MODE == F3_COMBINE && NP == 4 && NOK),
+                  "dense output: <COMBINE, 4> without K, lattice plan");
     constexpr int kF3WP = f3_producers(MODE, NP), kF3Waves = kF3WP + kF3WM;   // producer waves (LDS-DMA + fold + epilogue) | MFMA waves
     constexpr int kF3CapD = kF3Cap / kF3WP;
     static_assert(kF3Cap % kF3WP == 0 && kF3R % kF3WP == 0 && kF3WP >= 4, "wave split");
@@ -494,6 +500,13 @@ __global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fus
                 stp(e->y_aux, voff, w2);
                 issued(1);
             }
+            if constexpr (DO == F3_DO_MID) {                         // the same stages in the same order, into K's panel
+                f32x4 u3 = p.km[0] * e->c3[0];
+#pragma unroll
+                for (int m = 1; m < NP; ++m) u3 = u3 + p.km[m] * e->c3[m];
+                stp(a.K, voff, u3 + kn * e->c3[NP]);
+                issued(1);
+            }
             return;
         }
 #pragma unroll
@@ -637,6 +650,19 @@ __global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fus
     }
 }
 
+template <bool HALO, int MODE, int NP, int XOP = 0, bool NT = true, bool SOUT = false, bool NOK = false>
+__global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fused3_kernel(F3Args a, F3Epi epi_by_kernarg_only) {
+    (void)epi_by_kernarg_only;
+    rhs_fused3_body<HALO, MODE, NP, XOP, NT, SOUT, NOK, F3_DO_NONE>(a);
+}
+
+// the dopri5 dense-output variants (F3_DO_*): a symbol of their own, audited by tests/test_isa_audit_dense.py
+template <int MODE, int NP, bool NT, bool NOK, int DO>
+__global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fused3_dense_kernel(F3Args a, F3Epi epi_by_kernarg_only) {
+    (void)epi_by_kernarg_only;
+    rhs_fused3_body<false, MODE, NP, 0, NT, false, NOK, DO>(a);
+}
+
 static int env_int_f3(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -680,6 +706,23 @@ int rhs_xadd_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n
     return ((mode == F3_COMBINE || mode == F3_ERROR) && n_prev == 1) ? 1 : 0;
 }
 
+// RkOpt::c_mid (dopri5 dense output in the step's launches): the lattice plan without a halo panel, hub rows or sweep
+int rhs_dense_supported(const ndcn_csr *A, int H, uint32_t flags) {
+    if (H != 256 || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || !rhs_fused3_supported(A)) return 0;
+    return (A->hub_n > 0 || A->sweep_S) ? 0 : 1;
+}
+
+template <int MODE, int NP, bool NT, bool NOK, int DO>
+static int launch_f3d(const F3Args &a, const F3Epi &e, dim3 grid, hipStream_t st) {
+    auto kern = rhs_fused3_dense_kernel<MODE, NP, NT, NOK, DO>;
+    static std::atomic<unsigned long long> attr_seen{0};
+    if (once_per_device(attr_seen)) {
+        NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF3Lds));
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(64 * (f3_producers(MODE, NP) + kF3WM)), kF3Lds, st, a, e);
+    return NDCN_OK;
+}
+
 template <bool HALO, int MODE, int NP, int XOP = 0, bool NT = true, bool SOUT = false, bool NOK = false>
 static int launch_f3(const F3Args &a, const F3Epi &e, dim3 grid, hipStream_t st) {
     auto kern = rhs_fused3_kernel<HALO, MODE, NP, XOP, NT, SOUT, NOK>;
@@ -703,6 +746,13 @@ int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     const bool skip_k = opt && opt->no_k && y_next && !opt->xmask && !opt->xadd && !opt->s_out && !(opt->y_aux && opt->c_aux) &&
                         ((mode == F3_COMBINE && n_prev == 0) || (mode == F3_RK4 && n_prev == 3));
     const bool masked = opt && opt->xmask;
+    // dopri5 dense output (rhs_dense_supported): <COMBINE, 4> without the store of K - and with M in its place (c_mid)
+    const bool plain_in = !Xh && !(opt && (opt->xmask || opt->xadd || opt->s_out));
+    const bool dense4 = plain_in && opt && opt->no_k && y_next && mode == F3_COMBINE && n_prev == 4;
+    if (opt && opt->c_mid && !dense4) {
+        set_error("rhs_fused3: the midpoint sum is formed by <COMBINE, 4> without K of an operator without a halo panel");
+        return NDCN_EINVAL;
+    }
     a.Xadd = masked ? opt->xmask : ((opt && opt->xadd) ? opt->xadd : nullptr);
     a.xadd_c = (a.Xadd && !masked) ? opt->xadd_c : 0.f;
     a.S_out = (opt && opt->s_out) ? opt->s_out : nullptr;
@@ -730,6 +780,7 @@ int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     for (int m = 0; m <= kF3MaxPrev; ++m) e.c2[m] = (e.y_aux && m <= n_prev) ? opt->c_aux[m] : 0.f;
     for (int m = 0; m < kF3MaxPrev; ++m) e.kprev[m] = (m < n_prev && h_kprev) ? h_kprev[m] : nullptr;
     for (int m = 0; m <= kF3MaxPrev; ++m) e.c[m] = (mode != F3_PLAIN && mode != F3_RK4 && m <= n_prev) ? h_c[m] : 0.f;
+    for (int m = 0; m <= kF3MaxPrev; ++m) e.c3[m] = (dense4 && opt->c_mid && m <= n_prev) ? opt->c_mid[m] : 0.f;
     if (mode == F3_RK4) e.c[0] = h_c[0];
     int per_xcd = kCus / kXcds;
     const int need = (a.n_groups + kXcds - 1) / kXcds;
@@ -741,7 +792,7 @@ int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     if (e.y_aux) bytes += P;
     if (a.Xadd) bytes += P;                                          // the second gather
     if (a.S_out) bytes += P;
-    if (skip_k) bytes -= P;
+    if (skip_k || (dense4 && !opt->c_mid)) bytes -= P;
     ProfScope prof(masked ? PROF_RHS_ADJ_T : (a.S_out ? PROF_RHS_ADJ_FWD : PROF_RHS_FUSED), st, bytes, 2.0 * A->nnz * 256 + 2.0 * (double)A->n_rows * 256 * 256);
     int rc = NDCN_OK;
     // panels that fit the Infinity Cache with room for the next launch's (<= 128 MiB): plain stores (operators without a halo panel)
@@ -780,7 +831,10 @@ int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
             default: if (cached) rc = launch_f3<false, F3_COMBINE, 4, XOP_, false, SOUT_>(a, e, grid, st); else rc = launch_f3<false, F3_COMBINE, 4, XOP_, true, SOUT_>(a, e, grid, st); break; \
         }                                                                                           \
     } while (0)
-    if (skip_k) {
+    if (dense4) {
+        if (opt->c_mid) rc = cached ? launch_f3d<F3_COMBINE, 4, false, true, F3_DO_MID>(a, e, grid, st) : launch_f3d<F3_COMBINE, 4, true, true, F3_DO_MID>(a, e, grid, st);
+        else rc = cached ? launch_f3d<F3_COMBINE, 4, false, true, F3_DO_NONE>(a, e, grid, st) : launch_f3d<F3_COMBINE, 4, true, true, F3_DO_NONE>(a, e, grid, st);
+    } else if (skip_k) {
         if (mode == F3_COMBINE) {
             if (Xh) rc = launch_f3<true, F3_COMBINE, 0, 0, true, false, true>(a, e, grid, st);
             else if (cached) rc = launch_f3<false, F3_COMBINE, 0, 0, false, false, true>(a, e, grid, st);

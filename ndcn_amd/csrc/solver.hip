@@ -54,6 +54,9 @@ struct ndcn_solver {
     bool fit_valid = false;
     int evals_in_step = 0;         // ticks already evaluated inside the current accepted step
     float fit_dt = 0;
+    // dopri5 dense output kept by a step (eager single-rank rhs_fused3 path, rhs_dense_supported): kDenseAll - the seven k panels;
+    // kDenseNone - k6 was not stored (the step covers no requested tick); kDenseMid - the midpoint sum M in k[5] in place of k6
+    int att_dense = 0, fit_dense = 0;   // of the attempt in flight / of the accepted step
     bool cur_is_borrowed = false;  // ycur points into a caller buffer (fixed grid)
     float *ycur_own = nullptr;
     float *own3[3] = {};           // dopri5: the solver's three state panels {ycur_own, ynext, yold as allocated}
@@ -93,6 +96,14 @@ struct ndcn_solver {
 namespace {
 
 constexpr int kDtRing = 4096;
+enum { kDenseAll = 0, kDenseNone = 1, kDenseMid = 2 };
+
+// what the caller of a dopri5 attempt wants kept: the next requested tick, and whether this may be the last attempt of the call
+// (a step budget / max_num_steps: a later call may then sample the step below next_t)
+struct StepWant {
+    double next_t;
+    bool last;
+};
 constexpr int kCoefCap = 64;
 
 inline size_t align_up(size_t v) { return (v + 255u) & ~(size_t)255u; }
@@ -391,10 +402,12 @@ void dt_coeffs(float dt32, const double *beta, int n, const float *const *kall, 
 // dt_dev == nullptr: dt32 is the step size and rides in the kernel arguments.  dt_dev != nullptr (hipGraph capture):
 // dt32 must be 1 - the coefficients passed are the bare tableau entries and every kernel forms fl(dt * c) from the
 // device-resident step size, the same single rounding.
-int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_dev) {
+// keep_mid (eager attempts): the step's dense output may be sampled - keep M; else nothing beyond y1 / k7 (nullptr: keep all stages)
+int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_dev, const bool *keep_mid_p = nullptr) {
     const float *kp[8];
     float cp[8];
     int m, rc;
+    s->att_dense = kDenseAll;
     if (s->fused2) {
         // Stage algebra rides in the RHS epilogues: the evaluation that produces k[i+1] also forms the NEXT stage
         // input y0 + dt * sum_m beta[i+1][m] k[m] (its own K as the last term), the last one the error record.
@@ -435,6 +448,23 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         // y0 + (1 * P + dt beta_65 k5), the same roundings, instead of {y0, k1, k2, k3, k4}: 2 panels less per step.
         static const bool partial_on = [] { const char *e = getenv("NDCN_STAGE_PARTIAL"); return !(e && e[0] == '0'); }();
         const bool use_partial = partial_on && !dt_dev;
+        // Dense output (rk_common.py:41-61 -> dopri5.py:42, interp.py).  After the launch that produces k6 nothing but the midpoint sum
+        // M = dt sum_j c_mid[j] k_j reads k6, and M is needed only when the step covers a requested tick: that launch - holding k1, k3,
+        // k4, k5, k6 - writes M (the same stages in the same order as interp_direct's terms) into k6's panel, or, when the step covers
+        // no tick, stores nothing there (1 P less); the dense output then reads {y0, y1, k1, M, k7} instead of nine panels.
+        static const bool mid_on = [] { const char *e = getenv("NDCN_DENSE_MID"); return !(e && e[0] == '0'); }();
+        bool dense = mid_on && keep_mid_p && use_aux && !s->sharded && !s->rec_epi && !s->exact32 &&
+                     rhs_dense_supported(&s->d.A, s->d.H, s->d.rhs_flags);
+        float c3[8];
+        {
+            int m3 = 0;
+            for (int j = 0; j <= 5; ++j) {                 // k6's launch sums the stages with beta[5][j] != 0: exactly those with c_mid[j] != 0
+                const bool in_sum = j == 5 || (float)kBeta[5][j] != 0.f;
+                dense = dense && in_sum == ((float)kCMid[j] != 0.f);
+                if (in_sum) c3[m3++] = dt32 * (float)kCMid[j];
+            }
+        }
+        const bool keep_mid = dense && *keep_mid_p;
         float *e_panel = nullptr, *p_panel = nullptr;
         float *in = xadd ? s->ycur : s->ytmp;
         for (int i = 0; i < 6; ++i) {
@@ -473,6 +503,10 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
                         opt.c_aux = c2;
                     }
                 }
+                if (i == 4 && dense) {
+                    opt.no_k = 1;
+                    if (keep_mid) opt.c_mid = c3;
+                }
                 if (i == 4 && use_aux) {
                     // the same stages in the same order: beta[5][j] and c_err[j] vanish for the same j (= 1) only
                     int m2 = 0;
@@ -486,7 +520,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
                     opt.c_aux = c2;
                 }
                 rc = rhs_epi(s, in, s->k[i + 1], 1, s->ycur, kp, cp, mp, out, 0.f, 0.f, nullptr, nullptr, st, dt_dev,
-                             (opt.y_aux || opt.xadd) ? &opt : nullptr);
+                             (opt.y_aux || opt.xadd || opt.no_k) ? &opt : nullptr);
                 if (rc) return rc;
                 in = out;
             } else if (split_error) {
@@ -517,6 +551,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
                 if (rc) return rc;
             }
         }
+        s->att_dense = dense ? (keep_mid ? kDenseMid : kDenseNone) : kDenseAll;
         return NDCN_OK;
     }
     for (int i = 0; i < 6; ++i) {
@@ -535,7 +570,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
 int graph_setup_dopri5(ndcn_solver *s);
 
 // dopri5.py:94-122
-int dopri5_step(ndcn_solver *s, hipStream_t st) {
+int dopri5_step(ndcn_solver *s, hipStream_t st, const StepWant *want) {
     const double t_start = s->t1, dt = s->dt;
     if (!(t_start + dt > t_start)) {
         set_error("underflow in dt %g", dt);
@@ -557,7 +592,9 @@ int dopri5_step(ndcn_solver *s, hipStream_t st) {
         NDCN_HIP(hipGraphLaunch(s->gexec, st));
         s->n_rhs += 6;
     } else {
-        rc = enqueue_attempt(s, st, dt32, nullptr);
+        // the attempt covers the requested tick when its t1 (the same fp64 sum as below) reaches it
+        const bool keep = !want || want->next_t <= t_start + dt || want->last;
+        rc = enqueue_attempt(s, st, dt32, nullptr, &keep);
         if (rc) return rc;
     }
     double sum, bad;
@@ -591,6 +628,7 @@ int dopri5_step(ndcn_solver *s, hipStream_t st) {
         s->fit_valid = false;
         s->evals_in_step = 0;
         s->fit_dt = dt32;
+        s->fit_dense = s->graph_on ? kDenseAll : s->att_dense;
         s->t0 = t_start;
         s->t1 = t_start + dt;
         s->pending_bad = (int64_t)bad;
@@ -630,11 +668,30 @@ int rotate_after_accept(ndcn_solver *s, hipStream_t st) {
     return NDCN_OK;
 }
 
+// The accepted step's dense-output terms in the slot layout of interp_*_f32 (f0 in slot 0, f1 in slot 6; zero coefficients are
+// dropped): the seven stages with dt c_mid[j], or - kDenseMid - the midpoint sum M in slot 1 with coefficient 1 (exact) and k7 with
+// dt c_mid[6]: wsum forms 1 * M + c k7, i.e. the seven-term sum of the same roundings.  Called BEFORE the rotation.
+int dense_terms(const ndcn_solver *s, const float **kk, float *cm) {
+    if (s->fit_dense == kDenseNone) { set_error("dopri5: the accepted step kept no dense output"); return NDCN_ESTATE; }
+    for (int j = 0; j < 7; ++j) {
+        kk[j] = s->k[j];
+        cm[j] = s->fit_dt * (float)kCMid[j];
+    }
+    if (s->fit_dense == kDenseMid) {
+        for (int j = 0; j < 6; ++j) cm[j] = 0.f;             // (k1 stays in slot 0 as f0; its term is part of M)
+        kk[1] = s->k[5];
+        cm[1] = 1.f;
+    }
+    return NDCN_OK;
+}
+
 int do_fit(ndcn_solver *s, hipStream_t st) {
     // called BEFORE the rotation: ycur = y0, ynext = y1
+    const float *kk[7];
     float cm[7];
-    for (int j = 0; j < 7; ++j) cm[j] = s->fit_dt * (float)kCMid[j];
-    int rc = interp_fit_f32(s->ycur, s->ynext, s->k, cm, s->fit_dt, s->ca, s->cb, s->cc, s->cd, s->n_elem, st);
+    int rc = dense_terms(s, kk, cm);
+    if (rc) return rc;
+    rc = interp_fit_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, s->ca, s->cb, s->cc, s->cd, s->n_elem, st);
     if (rc) return rc;
     return NDCN_OK;
 }
@@ -875,6 +932,7 @@ int solver_begin(ndcn_solver *s, const float *y0, double t0, hipStream_t st, boo
     s->n_attempt = s->n_accept = s->n_rhs = 0;
     s->log.clear();
     s->fit_pending = s->fit_valid = false;
+    s->fit_dense = kDenseAll;
     s->pending_bad = 0;
     s->last_ratio = 0;
     s->t0 = s->t1 = t0;
@@ -1111,7 +1169,9 @@ static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t bud
             if (rcr) return rcr;
             s->fit_pending = false;
         }
-        int rc = dopri5_step(s, st);
+        const StepWant want = {next_t, (budget > 0 && done + 1 >= budget) ||
+                                           (s->d.max_num_steps > 0 && n_here + 1 >= s->d.max_num_steps)};
+        int rc = dopri5_step(s, st, &want);
         if (rc) return rc;
         ++done;
         ++n_here;
@@ -1131,9 +1191,11 @@ static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t bud
         if (s->evals_in_step++ == 0) {
             // first tick inside this step: fit + evaluate in one pass, coefficients not materialised (most steps
             // are sampled at most once); a second tick in the same step pays for the stored fit below
+            const float *kk[7];
             float cm[7];
-            for (int j = 0; j < 7; ++j) cm[j] = s->fit_dt * (float)kCMid[j];
-            return interp_direct_f32(s->ycur, s->ynext, s->k, cm, s->fit_dt, xp, out, s->n_elem, st);
+            int rc = dense_terms(s, kk, cm);
+            if (rc) return rc;
+            return interp_direct_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, xp, out, s->n_elem, st);
         }
         int rc = do_fit(s, st);
         if (rc) return rc;
@@ -1202,8 +1264,9 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
         int64_t j = i;
         while (j < n_ticks && !(h_ticks[j] > s->t1)) ++j;                // the ticks this accepted step covers
         const float a0 = (float)s->t0, a1 = (float)s->t1;
+        const float *kk[7];
         float cm[7];
-        for (int q = 0; q < 7; ++q) cm[q] = s->fit_dt * (float)kCMid[q];
+        if ((rc = dense_terms(s, kk, cm))) return rc;
         while (i < j) {
             const int nt = (int)((j - i) < 8 ? (j - i) : 8);
             float xp[8][5];
@@ -1219,7 +1282,7 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
                 xp[t][4] = 1.f; xp[t][3] = x; xp[t][2] = xp[t][3] * x; xp[t][1] = xp[t][2] * x; xp[t][0] = xp[t][1] * x;
                 outs[t] = out + (i + t) * stride;
             }
-            rc = interp_direct_multi_f32(s->ycur, s->ynext, s->k, cm, s->fit_dt, &xp[0][0], outs, nt, s->n_elem, st);
+            rc = interp_direct_multi_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, &xp[0][0], outs, nt, s->n_elem, st);
             if (rc) return rc;
             s->evals_in_step += nt;
             i += nt;
