@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 18
+#define NDCN_ABI_VERSION 19
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -241,7 +241,7 @@ NDCN_API int64_t ndcn_gcn_work_bytes(int64_t n_cols, int H_out);
 
 /* Backward of Y = act(S W^T + b) - the reference trains by plain autograd through every solver op
  * (heat_dynamics.py:333, dgnn.py:204; neural_dynamics.py:33,36,143-148).  gZ = g (.) [Y > 0] when the ReLU output Y is
- * given (nullable: no activation), then
+ * given (nullable: no activation; zero where Y <= 0, g elsewhere, a NaN Y included - torch's threshold_backward), then
  *   gS [n, H_in]      = gZ W               (nullable)
  *   gW [H_out, H_in]  = gZ^T S             (nullable; reduction over rows split into chunks, partials summed in a fixed
  *                                           order: deterministic, no atomics)
@@ -257,7 +257,8 @@ NDCN_API int ndcn_linear_bwd_f32(const float *g, const float *Y, const float *S,
 NDCN_API int64_t ndcn_linear_bwd_work_bytes(int64_t n, int H_in, int H_out);
 /* out = w * x: the VJP of one term of the Runge-Kutta linear combinations (rk_common.py:51,75-78; interp.py:21-35). */
 NDCN_API int ndcn_scale_f32(float *out, const float *x, float w, int64_t n_elem, void *stream);
-/* out = g where y > 0, else 0: the VJP of relu given its OUTPUT y (neural_dynamics.py:36; the no_control RHS). */
+/* out = 0 where y <= 0, else g: the VJP of relu given its OUTPUT y (neural_dynamics.py:36; the no_control RHS) - torch's
+ * threshold_backward, so a NaN output passes g. */
 NDCN_API int ndcn_relu_bwd_f32(float *out, const float *g, const float *y, int64_t n_elem, void *stream);
 /* dst = src, the library's plain streaming pass (16 bytes per lane, non-temporal): what `x.clone()` / the solver's state
  * hand-overs cost, and the measured HBM ceiling bench.py quotes next to the 8 TB/s spec peak.                            */
@@ -647,6 +648,29 @@ NDCN_API int ndcn_prof_kinds(void);
                                * switches the guard (and the 32-byte read-back per packed image) off                              */
 #define NDCN_PATH_RANGE  512 /* such weights on a launch that exists only fused (x_add / x_mask / s_out): split product, warned once */
 NDCN_API int ndcn_debug_last_rhs_path(void);
+/* Which kernels the LAST ndcn_linear_f32 / ndcn_linear_bwd_f32 call of this thread launched (tests: every dispatch route of the dense
+ * Linear is reached on purpose, not merely some correct one); each call replaces the set, 0 for n = 0 and before the first call.
+ * forward (linear.hip): */
+#define NDCN_LIN_ROWDOT    1        /* Ho < 16, 64 <= Hi <= 512: a wave per row (linear_rowdot_kernel<ceil(Hi / 64)>)               */
+#define NDCN_LIN_SMALL     2        /* other Hi < 16 or Ho < 16: a thread per output element                                      */
+#define NDCN_LIN_MFMA64    4        /* fp32 MFMA tile kernel, 64 / 128 / 256 output features per workgroup (grid.y > 1 past 256)    */
+#define NDCN_LIN_MFMA128   8
+#define NDCN_LIN_MFMA256  16
+#define NDCN_LIN_VEC      32        /* ... staging its operands by float4 (Hi % 4 == 0, S and W 16-byte aligned)                    */
+/* backward, gS (linear_bwd.hip): */
+#define NDCN_LIN_GS_SMALL  256      /* Hi < 16 or Ho < 16                                                                          */
+#define NDCN_LIN_GS_FP32   512      /* fp32 MFMA GEMM (linear_gs_kernel<BN>): other shapes, and H = 256 without scratch, misaligned,
+                                     * wide-range W (range guard) or NDCN_GS_SPLIT=0                                                */
+#define NDCN_LIN_GS_RES    1024     /* H = 256 split product, resident weights (linear_gs_256_res_kernel), g already masked (Y null)  */
+#define NDCN_LIN_GS_RES_MASK 2048   /* ... the same with the ReLU mask formed from Y                                                */
+#define NDCN_LIN_GS_SPLIT32 4096    /* H = 256 split product, tile kernel of 32 rows (NDCN_GS_ROWS=32)                              */
+#define NDCN_LIN_GS_SPLIT64 8192    /* ... of 64 rows (n x 1 KiB >= 4 GiB, or NDCN_GS_ROWS=64)                                      */
+/* backward, gW / gb: */
+#define NDCN_LIN_GW_SMALL  65536    /* Hi < 16 or Ho < 16                                                                          */
+#define NDCN_LIN_GW_FP32   131072   /* fp32 MFMA (linear_wgrad_kernel<NI>): other shapes, and H = 256 with NDCN_GW_SPLIT=0          */
+#define NDCN_LIN_GW_SPLIT  262144   /* H = 256: three bf16 pieces per operand (linear_wgrad_256_split_kernel)                       */
+#define NDCN_LIN_GW_SUM2   524288   /* gW and gb summed over the chunks in one launch (chunk_sum2_kernel; otherwise chunk_sum_kernel) */
+NDCN_API int ndcn_debug_last_linear_path(void);
 /* The range guard of the H = 256 Linear (NDCN_PATH_EXACT32 above): on = 1 / 0 switches it PROCESS-WIDE at run time, on < 0 returns to the
  * default (on, unless the environment says NDCN_RANGE_GUARD=0); returns the previous state (1 / 0).  Off, every packed image takes the
  * split fp16 product whatever its range, and packing does not read back.  Images packed while the guard was off are judged when

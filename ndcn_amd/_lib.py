@@ -11,8 +11,12 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+# ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
+LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
+LIN_GS_SMALL, LIN_GS_FP32, LIN_GS_RES, LIN_GS_RES_MASK, LIN_GS_SPLIT32, LIN_GS_SPLIT64 = 256, 512, 1024, 2048, 4096, 8192
+LIN_GW_SMALL, LIN_GW_FP32, LIN_GW_SPLIT, LIN_GW_SUM2 = 65536, 131072, 262144, 524288
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6
@@ -191,6 +195,7 @@ SIGNATURES = {
     'ndcn_prof_read': (_I, [ctypes.POINTER(_D), _I]),
     'ndcn_prof_kinds': (_I, []),
     'ndcn_debug_last_rhs_path': (_I, []),
+    'ndcn_debug_last_linear_path': (_I, []),
     'ndcn_set_range_guard': (_I, [_I]),
 }
 

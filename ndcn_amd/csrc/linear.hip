@@ -9,6 +9,7 @@
 //   D: 16 regs, D[m = (r & 3) + 8 (r >> 2) + 4 (l >> 5)][n = l & 31]
 // Here m = node row, n = output feature, k = input feature; A = S tile, B[k][n] = W[n][k].
 #include "common.h"
+#include "kernels.h"
 
 namespace ndcn {
 
@@ -161,8 +162,11 @@ __global__ __launch_bounds__(256) void linear_rowdot_kernel(const float *__restr
     }
 }
 
+thread_local int g_last_linear_path = 0;
+
 int linear_f32(const float *S, const float *W, const float *b, float *Y, int64_t n, int Hi, int Ho, uint32_t flags,
                hipStream_t st) {
+    g_last_linear_path = 0;
     if (n == 0) return NDCN_OK;
     const int relu = (flags & NDCN_F_RELU) ? 1 : 0;
     ProfScope prof(PROF_LINEAR, st, 4.0 * n * (double)(Hi + Ho) + 4.0 * Hi * Ho, 2.0 * n * (double)Hi * Ho);
@@ -180,6 +184,7 @@ int linear_f32(const float *S, const float *W, const float *b, float *Y, int64_t
             default: NDCN_RD(8); break;
         }
 #undef NDCN_RD
+        g_last_linear_path = NDCN_LIN_ROWDOT;
         NDCN_LAUNCH_CHECK();
         return NDCN_OK;
     }
@@ -187,6 +192,7 @@ int linear_f32(const float *S, const float *W, const float *b, float *Y, int64_t
         const int64_t total = n * (int64_t)Ho;
         hipLaunchKernelGGL(linear_small_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, st, S, W, b, Y, n, Hi, Ho,
                            relu);
+        g_last_linear_path = NDCN_LIN_SMALL;
         NDCN_LAUNCH_CHECK();
         return NDCN_OK;
     }
@@ -204,6 +210,7 @@ int linear_f32(const float *S, const float *W, const float *b, float *Y, int64_t
     if (Ho > 128) NDCN_LIN(256);
     else if (Ho > 64) NDCN_LIN(128);
     else NDCN_LIN(64);
+    g_last_linear_path = (Ho > 128 ? NDCN_LIN_MFMA256 : Ho > 64 ? NDCN_LIN_MFMA128 : NDCN_LIN_MFMA64) | (vec ? NDCN_LIN_VEC : 0);
 #undef NDCN_LIN
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;

@@ -1,7 +1,8 @@
 // Backward of the Linear on the path:  Y = act(S W^T + b)   (neural_dynamics.py:33,36 under autograd - the reference
 // trains by backpropagating through every solver step, heat_dynamics.py:333, dgnn.py:204 - and the encoder / decoder
 // Linears :143-148).  With gZ = g (.) [Y > 0] when the ReLU output Y is given (mask fused into the operand loads, no
-// separate pass), gZ = g otherwise:
+// separate pass), gZ = g otherwise.  The mask is torch's threshold_backward (what the reference trains through): g is zeroed
+// where Y <= 0 and passed everywhere else, a NaN output included (Y > 0 is false for NaN, Y <= 0 too):
 //
 //   gS [n, Hi]  = gZ W                fp32 MFMA GEMM, W read transposed while it is staged (no W^T copy); Hi = Ho = 256: the
 //                                     forward's two-piece fp16 product with the planes of W^T (linear_gs_256_split_kernel)
@@ -32,7 +33,7 @@ constexpr int kGwMaxChunks = 256;
 
 __device__ __forceinline__ float masked(const float *__restrict__ g, const float *__restrict__ Y, int64_t idx) {
     const float v = g[idx];
-    return (Y && !(Y[idx] > 0.f)) ? 0.f : v;
+    return (Y && Y[idx] <= 0.f) ? 0.f : v;                      // (NaN passes, as in threshold_backward)
 }
 
 // ---------------------------------------------------------------------------------------------------- gW, gb
@@ -104,6 +105,18 @@ __global__ __launch_bounds__(64 * kGwWaves) void linear_wgrad_kernel(const float
 // them and writes the 16-byte operand chunks - A[m = c][k = 8 h ..] and B[k = 8 h ..][n = c] have the SAME lane layout - into
 // LDS ([k-step of the pair][plane][h][column][16 B]: conflict-free b128 on both sides); wave w then owns the o-strip
 // [32 w, 32 w + 32) against all eight i-tiles: 3 + 24 ds_read_b128 and 48 MFMAs per k-step.
+//
+// BOUND (what tests/test_gpu_linear_routes.py holds every element of gW to).  gw_split8 rounds to nearest: x = p1 + r1 with
+// |r1| <= 2^-8 |x| (exact in fp32: a multiple of ulp(x) below 2^-8 |x|, 16 bits); p2 = bf16(r1), r2 = r1 - p2 with |r2| <= 2^-16 |x|,
+// a multiple of ulp(x) with <= 8 significant bits, so p3 = r2 and x = p1 + p2 + p3 EXACTLY (for |x| >= 2^-103: nothing of r2 falls
+// below bf16's normal range).  Every bf16 x bf16 product is exact in fp32.  The three dropped products (2,3) (3,2) (3,3) are at most
+// (2 + 2^-8) 2^-24 |a b|; the six kept ones sum to at most (1 + 2^-7) |a b|.  Each chunk accumulates its 6 x rows non-zero exact
+// products in one fp32 accumulator and the chunk partials are added in order (chunk_sum): whatever order the matrix core adds
+// within an instruction, a sum of m non-zero terms is off by at most (m - 1) 2^-24 of their magnitudes (first order), so
+//   |gW_oi - sum_r gZ_ro S_ri| <= 1.01 (2^-23 + 2^-24 (6 rows_per_chunk + chunks)) sum_r |gZ_ro| |S_ri|
+// (rows_per_chunk: the rows of the fullest chunk, <= n; wgrad_chunks below).  gb rides in plain fp32 adds of gZ:
+//   |gb_o - sum_r gZ_ro| <= 1.01 2^-24 (rows_per_chunk + chunks + 1) sum_r |gZ_ro|.
+// Measured: 2.0e-7 of sum |a b| at 10^6 rows (above); the bound is the worst case of the accumulation order, not the typical error.
 typedef __bf16 bf16x8_gw __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned gw_cvt_pk_bf16(float lo, float hi) {
     unsigned r;
@@ -189,7 +202,7 @@ __global__ __launch_bounds__(512) void linear_wgrad_256_split_kernel(const float
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const bool ok = whole || r0 + e < r_hi;
-                gz[e] = (ok && q.yv[u][e] > 0.f) ? q.gv[u][e] : 0.f;         // gZ = g where Y > 0 (masked())
+                gz[e] = (ok && !(q.yv[u][e] <= 0.f)) ? q.gv[u][e] : 0.f;     // gZ = g except where Y <= 0 (masked())
                 sz[e] = ok ? q.sv[u][e] : 0.f;
                 bsum += gz[e];
             }
@@ -412,10 +425,10 @@ __global__ __launch_bounds__(256) void linear_gs_256_split_kernel(const float *_
             const int r = kRpw * wave + i0 + i;
             const bool ok = row0 + r < n;
             f32x4 v;
-            v.x = (ok && yv[i].x > 0.f) ? gv[i].x : 0.f;
-            v.y = (ok && yv[i].y > 0.f) ? gv[i].y : 0.f;
-            v.z = (ok && yv[i].z > 0.f) ? gv[i].z : 0.f;
-            v.w = (ok && yv[i].w > 0.f) ? gv[i].w : 0.f;
+            v.x = (ok && !(yv[i].x <= 0.f)) ? gv[i].x : 0.f;
+            v.y = (ok && !(yv[i].y <= 0.f)) ? gv[i].y : 0.f;
+            v.z = (ok && !(yv[i].z <= 0.f)) ? gv[i].z : 0.f;
+            v.w = (ok && !(yv[i].w <= 0.f)) ? gv[i].w : 0.f;
             *reinterpret_cast<f32x4 *>(s_A + r * kGsLd + 4 * lane) = v;
             unsigned sb, ub;
             s16_scale_bits(s16_wave_umax(s16_row_max_bits(v)), sb, ub);
@@ -528,11 +541,13 @@ __global__ __launch_bounds__(512) void linear_gs_256_res_kernel(const float *__r
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(gS, 0, (int)(unsigned)(n * 1024), 0x00020000);
     auto request = [&](int tile, Rows &q) {
         // (the row offset rides in the VECTOR offset: a raw buffer's range check covers vector + immediate offset, not the scalar one)
-        const int vo = (tile * 32 + 4 * wave) * 1024 + lane * 16;
+        // (unsigned: past 2^21 rows the byte offset exceeds 2^31; the last tile's rows end at 4194303 x 1024 + 1023 = 2^32 - 1, so it
+        // never wraps - tests/test_gpu_linear_routes.py runs n = 4194274 .. 4194303)
+        const unsigned vo = ((unsigned)tile * 32u + 4u * (unsigned)wave) * 1024u + (unsigned)lane * 16u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            q.gv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, vo + 1024 * i, 0, 2));
-            if constexpr (MASK) q.yv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsY, vo + 1024 * i, 0, 2));
+            q.gv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, (int)(vo + 1024u * i), 0, 2));
+            if constexpr (MASK) q.yv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsY, (int)(vo + 1024u * i), 0, 2));
         }
     };
     auto stage = [&](int tile, int buf, const Rows &q) {     // mask, scale, split, write the pieces
@@ -542,10 +557,10 @@ __global__ __launch_bounds__(512) void linear_gs_256_res_kernel(const float *__r
             const bool ok = (int64_t)tile * 32 + r < n;
             f32x4 v;
             if constexpr (MASK) {
-                v.x = (ok && q.yv[i].x > 0.f) ? q.gv[i].x : 0.f;
-                v.y = (ok && q.yv[i].y > 0.f) ? q.gv[i].y : 0.f;
-                v.z = (ok && q.yv[i].z > 0.f) ? q.gv[i].z : 0.f;
-                v.w = (ok && q.yv[i].w > 0.f) ? q.gv[i].w : 0.f;
+                v.x = (ok && !(q.yv[i].x <= 0.f)) ? q.gv[i].x : 0.f;
+                v.y = (ok && !(q.yv[i].y <= 0.f)) ? q.gv[i].y : 0.f;
+                v.z = (ok && !(q.yv[i].z <= 0.f)) ? q.gv[i].z : 0.f;
+                v.w = (ok && !(q.yv[i].w <= 0.f)) ? q.gv[i].w : 0.f;
             } else {
                 v.x = ok ? q.gv[i].x : 0.f;
                 v.y = ok ? q.gv[i].y : 0.f;
@@ -586,11 +601,12 @@ __global__ __launch_bounds__(512) void linear_gs_256_res_kernel(const float *__r
         // D[m = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)][n = lane & 31]: column scale, then row scale (both exact)
         // stores through the output's descriptor: rows past n fall outside its range and are dropped - no branch per store, ONE offset
         // register (the per-store 64-bit addresses used to spill, and their reloads waited for every request in flight)
-        const int o0 = (tile * 32 + 4 * (lane >> 5)) * 1024 + (32 * wave + (lane & 31)) * 4;
+        const unsigned o0 = ((unsigned)tile * 32u + 4u * (unsigned)(lane >> 5)) * 1024u + (unsigned)(32 * wave + (lane & 31)) * 4u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (acc[r] * wu) * s_un[buf][m]), rsS, o0 + 1024 * ((r & 3) + 8 * (r >> 2)), 0, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (acc[r] * wu) * s_un[buf][m]), rsS,
+                                                  (int)(o0 + 1024u * (unsigned)((r & 3) + 8 * (r >> 2))), 0, 2);
         }
         if (next < n_tiles) stage(next, buf ^ 1, cur);
         __syncthreads();
@@ -643,6 +659,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
                    int64_t n, int Hi, int Ho, hipStream_t st, uint32_t flags, float acc_scale, bool accumulate) {
     // accumulate: gW / gb hold a running total: total + acc_scale * (this call's), each rounded on its own (the native reverse passes
     // of tape.hip: one small launch per evaluation instead of three)
+    g_last_linear_path = 0;
     if (n == 0 && accumulate) return NDCN_OK;
     if (n == 0) {
         if (gW) NDCN_HIP(hipMemsetAsync(gW, 0, (size_t)Ho * Hi * sizeof(float), st));
@@ -665,6 +682,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
         }
         if (small) {
             hipLaunchKernelGGL(linear_gs_small_kernel, dim3(stream_grid(n * (int64_t)Hi, 256)), dim3(256), 0, st, g, Y, W, gS, n, Hi, Ho);
+            g_last_linear_path |= NDCN_LIN_GS_SMALL;
         } else if (split) {
             // (a caller without scratch - gS only, older bindings - keeps the fp32 MFMA kernel below)
             static const int gs_rows = [] { const char *e = getenv("NDCN_GS_ROWS"); return e ? atoi(e) : 0; }();     // 0: resident weights (default); 32 / 64: the tile kernels
@@ -672,14 +690,20 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
             if (gs_rows != 32 && gs_rows != 64 && n * (int64_t)1024 < (1ll << 32)) {
                 if (Y) hipLaunchKernelGGL(linear_gs_256_res_kernel<true>, dim3((unsigned)(n_tiles < kCus ? n_tiles : kCus)), dim3(512), 0, st, g, Y, Wq, gS, n, n_tiles);
                 else hipLaunchKernelGGL(linear_gs_256_res_kernel<false>, dim3((unsigned)(n_tiles < kCus ? n_tiles : kCus)), dim3(512), 0, st, g, Y, Wq, gS, n, n_tiles);
+                g_last_linear_path |= Y ? NDCN_LIN_GS_RES_MASK : NDCN_LIN_GS_RES;
+            } else if (gs_rows != 32) {
+                hipLaunchKernelGGL(linear_gs_256_split_kernel<2>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, g, Y, Wq, gS, n);
+                g_last_linear_path |= NDCN_LIN_GS_SPLIT64;
+            } else {
+                hipLaunchKernelGGL(linear_gs_256_split_kernel<1>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, g, Y, Wq, gS, n);
+                g_last_linear_path |= NDCN_LIN_GS_SPLIT32;
             }
-            else if (gs_rows != 32) hipLaunchKernelGGL(linear_gs_256_split_kernel<2>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, g, Y, Wq, gS, n);
-            else hipLaunchKernelGGL(linear_gs_256_split_kernel<1>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, g, Y, Wq, gS, n);
         } else {
             const unsigned gx = (unsigned)((n + kBM2 - 1) / kBM2);
             if (Hi > 128) hipLaunchKernelGGL((linear_gs_kernel<256>), dim3(gx, (unsigned)((Hi + 255) / 256)), dim3(256), 0, st, g, Y, W, gS, n, Hi, Ho);
             else if (Hi > 64) hipLaunchKernelGGL((linear_gs_kernel<128>), dim3(gx, (unsigned)((Hi + 127) / 128)), dim3(256), 0, st, g, Y, W, gS, n, Hi, Ho);
             else hipLaunchKernelGGL((linear_gs_kernel<64>), dim3(gx, (unsigned)((Hi + 63) / 64)), dim3(256), 0, st, g, Y, W, gS, n, Hi, Ho);
+            g_last_linear_path |= NDCN_LIN_GS_FP32;
         }
         NDCN_LAUNCH_CHECK();
     }
@@ -695,11 +719,13 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
         static const bool wsplit_on = [] { const char *e = getenv("NDCN_GW_SPLIT"); return !(e && e[0] == '0'); }();
         if (small) {
             hipLaunchKernelGGL(linear_wgrad_small_kernel, dim3((unsigned)used), dim3(256), 0, st, g, Y, S, part_w, gb ? part_b : nullptr, n, Hi, Ho, rpc);
+            g_last_linear_path |= NDCN_LIN_GW_SMALL;
         } else if (wsplit_on && Hi == 256 && Ho == 256) {
             // (a role-split form - 4 fetch / split waves + 8 product waves - was built and measured in round 5: no faster, because a
             // SIMD's VALU work and MFMA work add up on gfx950 whichever wave issues them: profiles/r05_wgrad_roles.txt)
             hipLaunchKernelGGL(linear_wgrad_256_split_kernel, dim3((unsigned)used), dim3(512), 0, st, g, Y, S, part_w,
                                gb ? part_b : nullptr, n, rpc);
+            g_last_linear_path |= NDCN_LIN_GW_SPLIT;
         } else {
             const dim3 grid((unsigned)used, (unsigned)((Ho + 255) / 256), (unsigned)((Hi + 255) / 256));
             const int ni = Hi >= 256 ? 8 : (Hi + 31) / 32;
@@ -715,8 +741,10 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
                 default: NDCN_GW(8); break;
             }
 #undef NDCN_GW
+            g_last_linear_path |= NDCN_LIN_GW_FP32;
         }
         NDCN_LAUNCH_CHECK();
+        if (gW && gb) g_last_linear_path |= NDCN_LIN_GW_SUM2;
         if (gW && gb)
             hipLaunchKernelGGL(chunk_sum2_kernel, dim3((unsigned)((Ho * Hi + Ho + 255) / 256)), dim3(256), 0, st, part_w, gW, Ho * Hi, part_b, gb,
                                Ho, (int)used, acc_scale, accumulate ? 1 : 0);

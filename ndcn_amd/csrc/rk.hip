@@ -600,10 +600,11 @@ int copy_f32(float *dst, const float *src, int64_t n, hipStream_t st) {
     return NDCN_OK;
 }
 
-// out = g where y > 0, else 0  (VJP of relu given its output; neural_dynamics.py:36)
+// out = 0 where y <= 0, else g  (VJP of relu given its output; neural_dynamics.py:36): torch's threshold_backward, so a NaN output
+// passes the gradient
 __global__ __launch_bounds__(256) void relu_bwd_kernel(float *__restrict__ out, const float *__restrict__ g, const float *__restrict__ y, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = y[i] > 0.f ? g[i] : 0.f;
+        out[i] = y[i] <= 0.f ? 0.f : g[i];
 }
 
 int relu_bwd_f32(float *out, const float *g, const float *y, int64_t n, hipStream_t st) {

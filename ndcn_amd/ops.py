@@ -340,7 +340,7 @@ class HipOps:
 
     @staticmethod
     def relu_bwd(g, y):
-        """g where y > 0 else 0 (VJP of relu from its output)."""
+        """0 where y <= 0 else g (VJP of relu from its output; threshold_backward: a NaN y passes g)."""
         g, y = _panel(g), _panel(y)
         out = torch.empty_like(g)
         with torch.cuda.device(g.device):
