@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 19
+#define NDCN_ABI_VERSION 20
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -286,6 +286,13 @@ NDCN_API int64_t ndcn_rk_bwd_ws_bytes(void);
 NDCN_API int ndcn_rk_combine_bwd_f32(const float *g, const float *const *h_k, const float *h_c, int n_k, float *const *h_gk,
                                      const float *const *h_acc, float *gy0, const float *acc_y0, double *d_dots, void *d_ws,
                                      int64_t n_elem, void *stream);
+/* The total gradient of a stage derivative in the reverse pass of an attempted step (the tape's pull), ONE pass (ABI 20):
+ *   out = base + ((c_0 p_0 + c_1 p_1) + ...)  - ndcn_rk_combine_f32's order and arithmetic (the same bits);
+ *         base nullable; with mask (nullable, a ReLU output) 0 where mask <= 0 (torch's threshold_backward: a NaN mask passes)
+ *   d_dots[0] = <p_0, ua - ub>  (ua nullable: no product, d_dots / d_ws may be NULL then; ub nullable: <p_0, ua>; 0 for n = 0)
+ * 1 <= n_p <= 8 terms; h_p / h_c are HOST arrays of device panels / coefficients.                                                  */
+NDCN_API int ndcn_rk_pull_f32(float *out, const float *base, const float *const *h_p, const float *h_c, int n_p, const float *mask,
+                              const float *ua, const float *ub, double *d_dots, void *d_ws, int64_t n_elem, void *stream);
 /* d_dots[0] = <g, a - b> (b nullable: <g, a>), fp64 partial sums in a fixed order.  For a stage sum u = y0 + dt sum_j beta_j k_j the
  * gradient of dt is <g_u, u - y0> / dt - three panels read instead of one per term (rk_common.py:41-51 differentiated).            */
 NDCN_API int ndcn_rk_dot_diff_f32(const float *g, const float *a, const float *b, double *d_dots, void *d_ws, int64_t n_elem,
@@ -671,6 +678,17 @@ NDCN_API int ndcn_debug_last_rhs_path(void);
 #define NDCN_LIN_GW_SPLIT  262144   /* H = 256: three bf16 pieces per operand (linear_wgrad_256_split_kernel)                       */
 #define NDCN_LIN_GW_SUM2   524288   /* gW and gb summed over the chunks in one launch (chunk_sum2_kernel; otherwise chunk_sum_kernel) */
 NDCN_API int ndcn_debug_last_linear_path(void);
+/* Which kernel the LAST solver-VJP call of this thread launched (ABI 20; tests: each case reaches the element path and grid it targets),
+ * as (grid << 16) | kernel | NDCN_RKB_VEC.  Each call replaces it; 0 before the first call and for ndcn_rk_pull_f32 with n = 0.         */
+#define NDCN_RKB_COMBINE      1     /* ndcn_rk_combine_bwd_f32                                                                      */
+#define NDCN_RKB_ERROR        2     /* ndcn_rk_error_bwd_f32                                                                        */
+#define NDCN_RKB_RMS          4     /* ndcn_rk_rms_bwd_f32                                                                          */
+#define NDCN_RKB_DENSE        8     /* ndcn_dopri5_interp_bwd_f32                                                                   */
+#define NDCN_RKB_DENSE_MULTI 16     /* ndcn_dopri5_interp_bwd_multi_f32                                                             */
+#define NDCN_RKB_DOT_DIFF    32     /* ndcn_rk_dot_diff_f32                                                                         */
+#define NDCN_RKB_PULL        64     /* ndcn_rk_pull_f32                                                                             */
+#define NDCN_RKB_VEC        128     /* ... by 16 bytes per lane (n % 4 == 0, every panel 16-byte aligned); the grid counts float4 items then */
+NDCN_API int ndcn_debug_last_rk_bwd_path(void);
 /* The range guard of the H = 256 Linear (NDCN_PATH_EXACT32 above): on = 1 / 0 switches it PROCESS-WIDE at run time, on < 0 returns to the
  * default (on, unless the environment says NDCN_RANGE_GUARD=0); returns the previous state (1 / 0).  Off, every packed image takes the
  * split fp16 product whatever its range, and packing does not read back.  Images packed while the guard was off are judged when

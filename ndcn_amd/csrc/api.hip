@@ -44,6 +44,7 @@ extern "C" {
 int ndcn_abi_version(void) { return NDCN_ABI_VERSION; }
 int ndcn_debug_last_rhs_path(void) { return g_last_rhs_path; }
 int ndcn_debug_last_linear_path(void) { return g_last_linear_path; }
+int ndcn_debug_last_rk_bwd_path(void) { return g_last_rk_bwd_path; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
 const char *ndcn_last_error(void) { return g_err; }
 
@@ -177,6 +178,12 @@ int64_t ndcn_rk_bwd_ws_bytes(void) { return rk_bwd_ws_bytes(); }
 int ndcn_rk_dot_diff_f32(const float *g, const float *a, const float *b, double *d_dots, void *d_ws, int64_t n_elem, void *stream) {
     NDCN_CHECK_ARG(n_elem >= 0 && g && a && d_dots && d_ws, "bad argument");
     return rk_dot_diff_f32(g, a, b, d_dots, d_ws, n_elem, ST(stream));
+}
+
+int ndcn_rk_pull_f32(float *out, const float *base, const float *const *h_p, const float *h_c, int n_p, const float *mask, const float *ua,
+                     const float *ub, double *d_dots, void *d_ws, int64_t n_elem, void *stream) {
+    NDCN_CHECK_ARG(n_elem >= 0 && out && h_p && h_c && (!ua || (d_dots && d_ws)), "bad argument");
+    return rk_pull_f32(out, base, h_p, h_c, n_p, mask, ua, ub, d_dots, d_ws, n_elem, ST(stream));
 }
 
 int ndcn_rk_combine_bwd_f32(const float *g, const float *const *h_k, const float *h_c, int n_k, float *const *h_gk,

@@ -422,8 +422,8 @@ __device__ __forceinline__ void rhs_fused3_body(F3Args a) {
             asm volatile("" : "+v"(xk[k]));
             if constexpr (XOP == 2) {
                 f32x4 v = xb[k * 64];
-                v.x = xk[k].x > 0.f ? v.x : 0.f; v.y = xk[k].y > 0.f ? v.y : 0.f;
-                v.z = xk[k].z > 0.f ? v.z : 0.f; v.w = xk[k].w > 0.f ? v.w : 0.f;
+                v.x = xk[k].x <= 0.f ? 0.f : v.x; v.y = xk[k].y <= 0.f ? 0.f : v.y;
+                v.z = xk[k].z <= 0.f ? 0.f : v.z; v.w = xk[k].w <= 0.f ? 0.f : v.w;
                 xb[k * 64] = v;
             } else {
                 xb[k * 64] = xb[k * 64] + xk[k] * a.xadd_c;
@@ -553,7 +553,7 @@ __device__ __forceinline__ void rhs_fused3_body(F3Args a) {
                         f32x4 w;
                         asm volatile("global_load_dwordx4 %0, %1, %2\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(lane_off), "s"(a.Xadd + (size_t)c * 256) : "memory");
                         if constexpr (XOP == 2) {
-                            v.x = w.x > 0.f ? v.x : 0.f; v.y = w.y > 0.f ? v.y : 0.f; v.z = w.z > 0.f ? v.z : 0.f; v.w = w.w > 0.f ? v.w : 0.f;
+                            v.x = w.x <= 0.f ? 0.f : v.x; v.y = w.y <= 0.f ? 0.f : v.y; v.z = w.z <= 0.f ? 0.f : v.z; v.w = w.w <= 0.f ? 0.f : v.w;
                         } else {
                             v = v + w * a.xadd_c;
                         }

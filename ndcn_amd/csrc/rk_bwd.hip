@@ -79,6 +79,9 @@ static int bwd_grid(int64_t n, int cap = kBwdBlocks / 2) {
     return g > cap ? cap : g;
 }
 
+thread_local int g_last_rk_bwd_path = 0;
+static void record_path(int kernel, bool vec, int grid) { g_last_rk_bwd_path = kernel | (vec ? NDCN_RKB_VEC : 0) | (grid << 16); }
+
 // ------------------------------------------------------------------------------------------------ combine
 // VEC: 16 bytes per lane (n counts float4 items then).  gy0 = acc_y0 + g when both are given (the identity branch of the sum).
 template <bool VEC>
@@ -367,6 +370,7 @@ int rk_combine_bwd_f32(const float *g, const float *const *h_k, const float *h_c
     const int grid = bwd_grid(vec ? n / 4 : n);
     if (vec) hipLaunchKernelGGL(combine_bwd_kernel<true>, dim3(grid), dim3(256), 0, st, g, t, gy0, acc_y0, n / 4, static_cast<double *>(d_ws));
     else hipLaunchKernelGGL(combine_bwd_kernel<false>, dim3(grid), dim3(256), 0, st, g, t, gy0, acc_y0, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_COMBINE, vec, grid);
     hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
@@ -395,8 +399,11 @@ __global__ __launch_bounds__(256) void dot_diff_kernel(const float *__restrict__
 
 // ------------------------------------------------------------------------------------------------ pull (tape.hip)
 // The total gradient of a stage derivative in the reverse pass of an attempted step, as ONE pass:
-//   out = [mask > 0 ?] base + ((c_0 p_0 + c_1 p_1) + ...)        (rk_combine's order and rounding; base nullable; mask nullable: the ReLU
-//                                                                 output of the evaluation this gradient enters - its VJP then reads no mask)
+//   out = [mask <= 0 ? 0 :] base + ((c_0 p_0 + c_1 p_1) + ...)   (rk_combine's order and rounding: every product and sum rounded on its own -
+//                                                                 contraction is off in the kernel, as in rk.hip; HIP's __fmul_rn /
+//                                                                 __fadd_rn do not prevent it; base nullable; mask nullable: the ReLU
+//                                                                 output of the evaluation this gradient enters - its VJP then reads no mask;
+//                                                                 torch's threshold_backward, so a NaN output passes the gradient)
 //   d_dots[0] = <p_0, ua - ub>                                    (ua nullable: no product; the step size's gradient through the stage sum
 //                                                                 whose input's gradient p_0 is: rk_dot_diff_f32's sum)
 // instead of a combine pass, a dot_diff pass and two reads of the mask by the Linear backward's kernels.
@@ -410,42 +417,43 @@ struct PullArgs {
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void pull_kernel(PullArgs a, int64_t n, double *__restrict__ partial) {
+#pragma clang fp contract(off)
     double d[kBwdDots] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         if (VEC) {
             const bw_f4 p0 = ld4(a.p[0], i);
             bw_f4 s;
-            s.x = __fmul_rn(a.c[0], p0.x); s.y = __fmul_rn(a.c[0], p0.y); s.z = __fmul_rn(a.c[0], p0.z); s.w = __fmul_rn(a.c[0], p0.w);
+            s.x = a.c[0] * p0.x; s.y = a.c[0] * p0.y; s.z = a.c[0] * p0.z; s.w = a.c[0] * p0.w;
 #pragma unroll
             for (int j = 1; j < kBwdMaxK; ++j)
                 if (j < a.n) {
                     const bw_f4 k = ld4(a.p[j], i);
                     const float c = a.c[j];
-                    s.x = __fadd_rn(s.x, __fmul_rn(c, k.x)); s.y = __fadd_rn(s.y, __fmul_rn(c, k.y));
-                    s.z = __fadd_rn(s.z, __fmul_rn(c, k.z)); s.w = __fadd_rn(s.w, __fmul_rn(c, k.w));
+                    s.x = s.x + c * k.x; s.y = s.y + c * k.y;
+                    s.z = s.z + c * k.z; s.w = s.w + c * k.w;
                 }
             if (a.base) {
                 const bw_f4 y = ld4(a.base, i);
-                s.x = __fadd_rn(y.x, s.x); s.y = __fadd_rn(y.y, s.y); s.z = __fadd_rn(y.z, s.z); s.w = __fadd_rn(y.w, s.w);
+                s.x = y.x + s.x; s.y = y.y + s.y; s.z = y.z + s.z; s.w = y.w + s.w;
             }
             if (a.mask) {
                 const bw_f4 m = ld4(a.mask, i);
-                s.x = m.x > 0.f ? s.x : 0.f; s.y = m.y > 0.f ? s.y : 0.f; s.z = m.z > 0.f ? s.z : 0.f; s.w = m.w > 0.f ? s.w : 0.f;
+                s.x = m.x <= 0.f ? 0.f : s.x; s.y = m.y <= 0.f ? 0.f : s.y; s.z = m.z <= 0.f ? 0.f : s.z; s.w = m.w <= 0.f ? 0.f : s.w;
             }
             st4(a.out, i, s);
             if (a.ua) {
                 bw_f4 e = ld4(a.ua, i);
                 if (a.ub) e = e - ld4(a.ub, i);
-                d[0] += (double)__fmul_rn(p0.x, e.x) + (double)__fmul_rn(p0.y, e.y) + (double)__fmul_rn(p0.z, e.z) + (double)__fmul_rn(p0.w, e.w);
+                d[0] += (double)(p0.x * e.x) + (double)(p0.y * e.y) + (double)(p0.z * e.z) + (double)(p0.w * e.w);
             }
         } else {
             const float p0 = a.p[0][i];
-            float s = __fmul_rn(a.c[0], p0);
-            for (int j = 1; j < a.n; ++j) s = __fadd_rn(s, __fmul_rn(a.c[j], a.p[j][i]));
-            if (a.base) s = __fadd_rn(a.base[i], s);
-            if (a.mask && !(a.mask[i] > 0.f)) s = 0.f;
+            float s = a.c[0] * p0;
+            for (int j = 1; j < a.n; ++j) s = s + a.c[j] * a.p[j][i];
+            if (a.base) s = a.base[i] + s;
+            if (a.mask && a.mask[i] <= 0.f) s = 0.f;
             a.out[i] = s;
-            if (a.ua) d[0] += (double)__fmul_rn(p0, a.ub ? a.ua[i] - a.ub[i] : a.ua[i]);
+            if (a.ua) d[0] += (double)(p0 * (a.ub ? a.ua[i] - a.ub[i] : a.ua[i]));
         }
     }
     if (a.ua) block_store_dots(d, partial);
@@ -463,11 +471,16 @@ int rk_pull_f32(float *out, const float *base, const float *const *h_p, const fl
         if (j < n_p && !h_p[j]) { set_error("rk pull: null term"); return NDCN_EINVAL; }
         if (j < n_p) vec = vec && aligned16(h_p[j]);
     }
-    if (n == 0) return NDCN_OK;
+    g_last_rk_bwd_path = 0;
+    if (n == 0) {                                            // no launch; the (empty) product is still 0
+        if (ua) NDCN_HIP(hipMemsetAsync(d_dots, 0, sizeof(double), st));
+        return NDCN_OK;
+    }
     ProfScope prof(PROF_COMBINE_BWD, st, 4.0 * n * (n_p + 1 + (base ? 1 : 0) + (mask ? 1 : 0) + (ua ? (ub ? 2 : 1) : 0)), 2.0 * n * (n_p + 1));
     const int grid = bwd_grid(vec ? n / 4 : n);
     if (vec) hipLaunchKernelGGL(pull_kernel<true>, dim3(grid), dim3(256), 0, st, a, n / 4, static_cast<double *>(d_ws));
     else hipLaunchKernelGGL(pull_kernel<false>, dim3(grid), dim3(256), 0, st, a, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_PULL, vec, grid);
     if (ua) hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
@@ -480,6 +493,7 @@ int rk_dot_diff_f32(const float *g, const float *a, const float *b, double *d_do
     const int grid = bwd_grid(vec ? n / 4 : n);
     if (vec) hipLaunchKernelGGL(dot_diff_kernel<true>, dim3(grid), dim3(256), 0, st, g, a, b, n / 4, static_cast<double *>(d_ws));
     else hipLaunchKernelGGL(dot_diff_kernel<false>, dim3(grid), dim3(256), 0, st, g, a, b, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_DOT_DIFF, vec, grid);
     hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
@@ -500,6 +514,7 @@ int rk_error_bwd_f32(const float *y0, const float *y1, const float *const *h_k, 
     ProfScope prof(PROF_ERROR_BWD, st, 4.0 * n * (2 * n_k + 4), 2.0 * n * (3 * n_k + 12));
     if (vec) hipLaunchKernelGGL(error_bwd_kernel<true>, dim3(grid), dim3(256), 0, st, p, n / 4, static_cast<double *>(d_ws));
     else hipLaunchKernelGGL(error_bwd_kernel<false>, dim3(grid), dim3(256), 0, st, p, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_ERROR, vec, grid);
     hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
@@ -509,6 +524,7 @@ int rk_rms_bwd_f32(const float *a, const float *b, const float *y, float rtol, f
                    float *gy, int64_t n, hipStream_t st) {
     ProfScope prof(PROF_SUMSQ_BWD, st, 4.0 * n * 5, 10.0 * n);
     hipLaunchKernelGGL(rms_bwd_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, st, a, b, y, rtol, atol, coef, ga, gb, gy, n);
+    record_path(NDCN_RKB_RMS, false, stream_grid(n, 256));
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -535,6 +551,7 @@ int rk_dense_bwd_f32(const float *g, const float *y0, const float *y1, const flo
     const int grid = bwd_grid(n, kBwdBlocks);
     ProfScope prof(PROF_DENSE_BWD, st, 4.0 * n * 19, 2.0 * n * 60);
     hipLaunchKernelGGL(dense_bwd_kernel, dim3(grid), dim3(256), 0, st, p, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_DENSE, false, grid);
     hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
@@ -563,6 +580,7 @@ int rk_dense_bwd_multi_f32(const float *const *h_g, int nt, const float *y0, con
     const int grid = bwd_grid(n, kBwdBlocks);
     ProfScope prof(PROF_DENSE_BWD, st, 4.0 * n * (27 + nt), 2.0 * n * (30 + 30 * nt));
     hipLaunchKernelGGL(dense_bwd_multi_kernel, dim3(grid), dim3(256), 0, st, p, n, static_cast<double *>(d_ws));
+    record_path(NDCN_RKB_DENSE_MULTI, false, grid);
     hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(d_ws), grid, d_dots);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;

@@ -477,7 +477,7 @@ __global__ __launch_bounds__(1024) void solve_small_bwd_kernel(BwdArgs b, int sy
             }
             if (valid) {
                 S[r * H + o] = s;
-                if (b.relu && !(k > 0.f)) Z[r * H + o] = 0.f;
+                if (b.relu && k <= 0.f) Z[r * H + o] = 0.f;
             }
         }
         lds_barrier();
@@ -662,7 +662,7 @@ __global__ __launch_bounds__(1024) void solve_small_bwd_rk_kernel(BwdArgs b, int
         const float k_ = linear(s_, valid);                                                    \
         if (valid) {                                                                           \
             S[r * H + o] = s_;                                                                 \
-            if (b.relu && !(k_ > 0.f)) Z[r * H + o] = 0.f;                                     \
+            if (b.relu && k_ <= 0.f) Z[r * H + o] = 0.f;                                     \
         }                                                                                      \
     }                                                                                          \
     lds_barrier();                                                                             \
@@ -838,11 +838,11 @@ __global__ __launch_bounds__(1024) void solve_small_bwd_fast_kernel(BwdArgs b, i
         const float dt = b.dt[i];
         long long t_ = b.dbg ? (long long)__builtin_readcyclecounter() : 0;
         if (KEEP) {
-            // ---- S holds S_i, Z holds K_i (put there by their owners at the end of the previous tick): gZ = dt a (.) [K_i > 0] in place
+            // ---- S holds S_i, Z holds K_i (put there by their owners at the end of the previous tick): gZ = dt a, zero where K_i <= 0 (NaN passes), in place
 #pragma unroll
             for (int it = 0; it < MAXIT; ++it) {
                 const int e = e0 + it * estride;
-                if (e < n_elem) Z[e] = (b.relu && !(Z[e] > 0.f)) ? 0.f : dt * Adj[e];
+                if (e < n_elem) Z[e] = (b.relu && Z[e] <= 0.f) ? 0.f : dt * Adj[e];
             }
         } else {
         // ---- T <- y_i (requested during the previous step's last phase, by the owners);  Z <- dt a
@@ -875,7 +875,7 @@ __global__ __launch_bounds__(1024) void solve_small_bwd_fast_kernel(BwdArgs b, i
             k = k + bias_o;
             if (valid) {
                 S[r * H + o] = s;
-                if (b.relu && !(k > 0.f)) Z[r * H + o] = 0.f;
+                if (b.relu && k <= 0.f) Z[r * H + o] = 0.f;
             }
         }
         }

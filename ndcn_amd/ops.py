@@ -604,6 +604,20 @@ class HipOps:
         return (gk, dots) if acc_y0 is None else (gk, dots, gy0)
 
     @staticmethod
+    def pull(ps, cs, base=None, mask=None, ua=None, ub=None, out=None):
+        """The tape's pull: (out, <p_0, ua - ub> as a host float or None).  out = base + ((c_0 p_0 + c_1 p_1) + ...) with combine's
+        order and rounding, zeroed where mask <= 0 (threshold_backward: a NaN mask passes); ua / ub / base / mask nullable."""
+        ps = [_panel(p) for p in ps]
+        base, mask, ua, ub = (None if t is None else _panel(t) for t in (base, mask, ua, ub))
+        arr_p, arr_c, n = _terms(ps, cs)
+        out = torch.empty_like(ps[0]) if out is None else out
+        d = _BwdDots.get(ps[0].device)
+        with _REDUCE_LOCK, torch.cuda.device(ps[0].device):
+            check(_lib.load().ndcn_rk_pull_f32(ptr(out), ptr(base), arr_p, arr_c, n, ptr(mask), ptr(ua), ptr(ub), ptr(d.out), ptr(d.ws),
+                                               ps[0].numel(), stream_ptr()))
+            return out, (d.fetch()[0] if ua is not None else None)
+
+    @staticmethod
     def dot_diff(g, a, b=None, scale=1.0, lazy=False):
         """scale * <g, a - b> (fp64 sum, fixed order): a float, or with lazy a deferred 0-d float32 host tensor (_BwdDots.lazy)"""
         g, a = _panel(g), _panel(a)

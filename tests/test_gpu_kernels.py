@@ -1172,3 +1172,46 @@ def test_adjoint_halves_of_the_fused_launch_equal_the_composed_kernels(dev, side
         got = hip.rhs_rk(A, X, Wt, None, mode, y0, kprev, cs, *tol, x_mask=M, **kw)
         assert torch.equal(got[0], ref[0])
         assert torch.equal(got[1], ref[1]) if mode == 'combine' else got[1] == ref[1]
+
+
+@pytest.mark.parametrize('graph', ['grid', 'random'])
+@pytest.mark.parametrize('mode,n_prev', [('combine', 1), ('combine', 4), ('error', 5)])
+def test_adjoint_half_mask_is_threshold_backward(dev, graph, mode, n_prev):
+    """The transposed half's mask with +0, -0, a subnormal, a tiny positive value and NaN in M: bit-equal to the same launch over
+    ndcn_relu_bwd_f32(X, M) (torch's threshold_backward: zero where M <= 0, NaN passes).  The lattice stages every row group (the
+    staged-row form); the mixed operator - the lattice with rows 1000..1199 replaced by random rows of ~14 entries, under the record
+    plan the kernel is written for (16 rows, 40 columns, 2 KiB) - has groups that hold more distinct columns than a group stages:
+    their rows are gathered one by one from the CSR arrays (the per-row form)."""
+    import scipy.sparse as sp
+    from ndcn_amd import hip, CsrOperator, graphs, _lib
+    H = 256
+    m = graphs.normalized_laplacian(graphs.grid_8_neighbor(48)).tocsr().astype(np.float32)
+    if graph == 'random':
+        rnd = sp.random(m.shape[0], m.shape[1], density=0.006, random_state=np.random.RandomState(4), format='csr', dtype=np.float32)
+        m = sp.vstack([m[:1000], rnd[1000:1200], m[1200:]]).tocsr()
+    A = CsrOperator.from_scipy(m, dev)
+    if graph == 'random':
+        A.build_rec_plan(16, 40, 2)
+    n = A.shape[0]
+    g = torch.Generator().manual_seed(n + n_prev)
+    X = torch.rand(n, H, generator=g).to(dev)
+    M = (torch.rand(n, H, generator=g) - 0.4)
+    r = torch.arange(n)
+    M[r, (7 * r) % H] = torch.tensor((0.0, -0.0, 1e-40, 1e-37, float('nan')))[r % 5]
+    M = M.to(dev)
+    Wt = ((torch.rand(H, H, generator=g) - 0.5) / 8).to(dev).t().contiguous()
+    y0 = torch.rand(n, H, generator=g).to(dev)
+    kprev = [torch.rand(n, H, generator=g).to(dev) for _ in range(n_prev)]
+    cs = [np.float32(0.1 * (j + 1)) for j in range(n_prev + 1)]
+    assert hip.rhs_adj_supported(A, H, mode, n_prev)
+    gm = hip.relu_bwd(X, M)
+    assert int((gm[r.to(dev), (7 * r.to(dev)) % H] != 0).sum()) >= 3 * n // 5 - 1      # subnormal, tiny and NaN pass
+    with torch.no_grad():
+        tol = (1e-2, 1e-3) if mode == 'error' else (0.0, 0.0)
+        kw = dict(relu=False, y1=X) if mode == 'error' else dict(relu=False)
+        ref = hip.rhs_rk(A, gm, Wt, None, mode, y0, kprev, cs, *tol, **kw)
+        got = hip.rhs_rk(A, X, Wt, None, mode, y0, kprev, cs, *tol, x_mask=M, **kw)
+        assert int(_lib.load().ndcn_debug_last_rhs_path()) == _lib.PATH_FUSED3
+        assert torch.isfinite(got[0]).all()
+        assert torch.equal(got[0], ref[0])
+        assert torch.equal(got[1], ref[1]) if mode == 'combine' else got[1] == ref[1]

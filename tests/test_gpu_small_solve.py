@@ -250,3 +250,67 @@ def test_euler_reverse_sweep_on_kept_intermediates_is_bit_identical(dev, side, H
             del os.environ['NDCN_SOLVE_SMALL_KEEP']
     for a, b in zip(res['1'], res['0']):
         assert torch.equal(a, b)
+
+
+SOLVE_ROUTES = [('euler', 'generic', 12, 12), ('euler', 'fast_keep', 17, 16), ('euler', 'fast', 17, 16), ('midpoint', 'rk', 12, 16),
+                ('rk4', 'rk', 12, 16)] + [(m, r, 12, 16) for m in ('euler', 'midpoint', 'rk4') for r in ('tape', 'per_op')]
+
+
+@pytest.mark.parametrize('method,route,side,H', SOLVE_ROUTES)
+def test_nan_bias_channel_backward_is_threshold_backward(dev, method, route, side, H):
+    """One fixed-grid step with b[o] = NaN: K is NaN in column o (and, for midpoint / rk4, everywhere from the second stage on).
+    relu's VJP is torch's threshold_backward - zero where K <= 0, so a NaN K passes the gradient: y0.grad and b.grad stay finite,
+    W.grad is finite for Euler, NaN exactly in column o for midpoint (the second stage's A u carries the NaN there) and NaN
+    everywhere for rk4 (its third stage's input holds the all-NaN k2).  Against
+    fp64 autograd through the oracle's restated solver: the same NaN positions, finite elements within the bound of the tests above.
+    Routes: the one-launch reverse kernels (generic: H = 12; fast with kept S / K and fast re-forming them: H = 16 on a symmetric
+    operator, NDCN_SOLVE_SMALL_KEEP; rk: midpoint / rk4), the native fixed-grid reverse sweep (NDCN_SOLVE_SMALL_GRAD=0) and the
+    per-operation autograd path (NDCN_FIXED_GRID_GRAD=0 too)."""
+    from ndcn_amd import _lib
+    from ndcn_amd import torchdiffeq as ode
+    f, L, x0 = _case(dev, side, H, seed=21)
+    o = H // 3
+    with torch.no_grad():
+        f.wt.bias[o] = float('nan')
+    t = torch.tensor([0.0, 0.5])
+    w = torch.randn(2, x0.shape[0], H, generator=torch.Generator().manual_seed(8))
+    env = {'fast': {'NDCN_SOLVE_SMALL_KEEP': '0'}, 'tape': {'NDCN_SOLVE_SMALL_GRAD': '0'},
+           'per_op': {'NDCN_SOLVE_SMALL_GRAD': '0', 'NDCN_FIXED_GRID_GRAD': '0'}}.get(route, {})
+    if route.startswith('fast'):
+        from ndcn_amd.csr import as_csr
+        assert _lib.load().ndcn_solve_small_keep_supported(as_csr(f.A).view_ref(need_symmetric=True), H, _lib.F_RELU) == 1
+    os.environ.update(env)
+    try:
+        y0 = x0.to(dev).requires_grad_(True)
+        y = ode.odeint(f, y0, t.to(dev), method=method)
+        name = type(y.grad_fn).__name__
+        if route in ('generic', 'fast_keep', 'fast', 'rk'):
+            assert name == '_SmallEulerSolveBackward', name
+        elif route == 'tape':
+            assert name == '_NativeFixedGridBackward', name
+        else:
+            assert name not in ('_SmallEulerSolveBackward', '_NativeFixedGridBackward'), name
+        (y * w.to(dev)).sum().backward()
+    finally:
+        for k in env:
+            del os.environ[k]
+    A = orc.coo_from_csr(L.indptr, L.indices, L.data, L.shape).double()
+    Wo = f.wt.weight.detach().cpu().double().requires_grad_(True)
+    bo = f.wt.bias.detach().cpu().double().requires_grad_(True)
+    yo0 = x0.double().requires_grad_(True)
+    yo = orc.odeint(orc.OracleODEFunc(A, Wo, bo), yo0, t.double(), method=method)
+    (yo * w.double()).sum().backward()
+    for got, ref, what in ((y0.grad, yo0.grad, 'g_y0'), (f.wt.weight.grad, Wo.grad, 'g_W'), (f.wt.bias.grad, bo.grad, 'g_b')):
+        got = got.cpu().double()
+        assert torch.equal(torch.isnan(got), torch.isnan(ref)), (what, int(torch.isnan(got).sum()), int(torch.isnan(ref).sum()))
+        fin = ~torch.isnan(ref)
+        if bool(fin.any()):
+            scale = max(1.0, float(ref[fin].abs().max()))
+            assert float((got[fin] - ref[fin]).abs().max()) <= 2e-4 * scale, (what, float((got[fin] - ref[fin]).abs().max()), scale)
+    assert torch.isfinite(y0.grad).all() and torch.isfinite(f.wt.bias.grad).all()
+    nan_w = torch.zeros(H, H, dtype=torch.bool)
+    if method == 'midpoint':
+        nan_w[:, o] = True
+    elif method == 'rk4':
+        nan_w[:] = True
+    assert torch.equal(torch.isnan(f.wt.weight.grad.cpu()), nan_w)
