@@ -32,6 +32,22 @@ PROF_KINDS = ('spmm', 'linear', 'rhs_fused', 'combine', 'error', 'sumsq', 'inter
               'linear_wgrad', 'relu_bwd', 'rhs_adjoint_forward_half', 'rhs_adjoint_transposed_half')
 
 
+# Run-time switches ("Run-time switches"): the package's only reads of the environment.  Callers read per solve -
+# tests set and unset os.environ around single calls.
+def env_on(name):
+    """A flag: on unless the value is '0'."""
+    return os.environ.get(name, '1') != '0'
+
+
+def env_int(name, default):
+    v = os.environ.get(name)
+    return int(v) if v else default
+
+
+def env_str(name, default):
+    return os.environ.get(name, default)
+
+
 class NdcnHipError(RuntimeError):
     def __init__(self, code, text):
         super().__init__('libndcn_hip: error %d: %s' % (code, text))

@@ -17,8 +17,6 @@ void set_error(const char *fmt, ...) {
 }
 
 int stream_grid_full(int64_t n_items, int block) {
-    static const bool full = [] { const char *e = getenv("NDCN_STREAM_FULL"); return !(e && e[0] == '0'); }();
-    if (!full) return stream_grid(n_items, block);
     int64_t g = (n_items + block - 1) / block;
     if (g > (1ll << 24)) g = 1ll << 24;             // (grid-stride loops take the rest)
     return g < 1 ? 1 : (int)g;

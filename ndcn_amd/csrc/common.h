@@ -2,8 +2,10 @@
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/ndcn_hip.h"
 #include "prof.h"
 
@@ -36,6 +38,21 @@ void set_error(const char *fmt, ...);
             return NDCN_EHIP;                                                                 \
         }                                                                                     \
     } while (0)
+
+// Run-time switches ("Run-time switches"): the library's only reads of the environment.  A site that reads once per
+// process keeps the value in a function-local `static const`; the ones tests flip inside one process call these per solve.
+inline bool env_on(const char *name) {                       // a flag: on unless the value starts with '0'
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+}
+inline int env_int(const char *name, int dflt) {             // (unset or empty: the default)
+    const char *e = getenv(name);
+    return (e && *e) ? atoi(e) : dflt;
+}
+inline int64_t env_i64(const char *name, int64_t dflt) {
+    const char *e = getenv(name);
+    return (e && *e) ? atoll(e) : dflt;
+}
 
 constexpr int kWave = 64;       // CDNA wavefront
 constexpr int kXcds = 8;        // MI355X: 8 XCDs, block b is dispatched to XCD b % 8 (speed only)
@@ -88,7 +105,7 @@ inline int stream_grid(int64_t n_items, int block) {
 // (tools/micro/copy_lab.hip, 1 GiB float4 copy): one float4 per thread with non-temporal accesses 6.49 TB/s; the same
 // loop body on a persistent grid of 2048-16384 workgroups 4.1-5.7 TB/s - a grid-stride loop makes every wave of the chip
 // alternate between a burst of loads and a burst of stores in step, while the dispatcher's stream of short-lived
-// workgroups keeps reads and writes mixed.  NDCN_STREAM_FULL=0 restores the capped grid (A/B).
+// workgroups keeps reads and writes mixed.
 int stream_grid_full(int64_t n_items, int block);
 
 // A per-kernel one-off (hipFuncSetAttribute is per DEVICE): true exactly once per device of this process for the flag word it

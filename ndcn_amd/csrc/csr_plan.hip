@@ -75,11 +75,6 @@ void dev_release(ndcn_csr_handle *h, void *p) {
     (void)hipFree(p);
 }
 
-bool env_off(const char *name) {
-    const char *e = getenv(name);
-    return e && e[0] == '0';
-}
-
 // ------------------------------------------------------------------------------------------------ stencil detection
 
 // table[0..64): distinct offsets (kEmpty = free); table_n[0] = entries taken, table_n[1] = overflow flag
@@ -192,8 +187,7 @@ int detect_stencil(ndcn_csr_handle *h, int64_t row_base, int64_t n_own, bool hin
     const int64_t np = PX * PY;
     std::vector<int32_t> perm((size_t)np);
     std::iota(perm.begin(), perm.end(), 0);
-    const char *se = getenv("NDCN_PATCH_STRIP");
-    const int64_t strip = se ? atoll(se) : 32;
+    const int64_t strip = env_i64("NDCN_PATCH_STRIP", 32);
     if (strip > 0 && PX > 1 && PY > strip) {
         const int64_t per = (np + n_chunks - 1) / n_chunks;
         std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) {
@@ -708,9 +702,9 @@ int choose_hub_threshold(ndcn_csr_handle *h, int forced, int *thr_out, hipStream
     *thr_out = 0;
     const ndcn_csr &A = h->v;
     if (A.nnz == 0 || A.n_rows == 0) return NDCN_OK;
-    const char *env = getenv("NDCN_HUB_THRESHOLD");
     if (forced > 0) { *thr_out = forced; return NDCN_OK; }
-    if (env) { *thr_out = atoi(env) > 0 ? atoi(env) : 0; return NDCN_OK; }
+    const int env = env_int("NDCN_HUB_THRESHOLD", INT_MIN);      // (INT_MIN: not set)
+    if (env != INT_MIN) { *thr_out = env > 0 ? env : 0; return NDCN_OK; }
     unsigned long long *cnt;
     int rc = dev_alloc(h, &cnt, 3);
     if (rc) return rc;
@@ -759,7 +753,7 @@ int csr_create_plans(ndcn_csr_handle *h, int H, const ndcn_csr_hints *hints, hip
         if (thr > 0 && (rc = build_hub_plan(h, H, thr, hi.flags & NDCN_PLAN_EXTERNAL_SCRATCH, st))) return rc;
     }
     const bool order_only = hi.flags & NDCN_PLAN_ORDER_ONLY;
-    if (A.nnz == 0 || (!order_only && ((hi.flags & NDCN_PLAN_NO_REC) || env_off("NDCN_REC_PLAN")))) return NDCN_OK;
+    if (A.nnz == 0 || (!order_only && ((hi.flags & NDCN_PLAN_NO_REC) || !env_on("NDCN_REC_PLAN")))) return NDCN_OK;
     // ---- walk order: the caller's, or the patches of a detected lattice
     const int32_t *order = nullptr;
     int64_t M = A.n_rows;
@@ -769,12 +763,12 @@ int csr_create_plans(ndcn_csr_handle *h, int H, const ndcn_csr_hints *hints, hip
         order = hi.group_order, M = hi.n_group_order, hinted = true;
     } else if (hi.row_order) {
         order = hi.row_order, hinted = true;
-    } else if (!(hi.flags & NDCN_PLAN_NO_STENCIL) && !env_off("NDCN_REC_STENCIL")) {
+    } else if (!(hi.flags & NDCN_PLAN_NO_STENCIL) && env_on("NDCN_REC_STENCIL")) {
         if ((rc = detect_stencil(h, lattice_hint ? hi.lattice_row_base : 0, lattice_hint ? hi.lattice_n_own : A.n_cols, lattice_hint, st)))
             return rc;
         if (h->group_order) {
             order = h->group_order, M = h->n_group_order, hinted = true;
-            if (!(hi.flags & NDCN_PLAN_NO_TILE_ORDER) && !env_off("NDCN_TILE_ORDER") && !lattice_hint &&
+            if (!(hi.flags & NDCN_PLAN_NO_TILE_ORDER) && env_on("NDCN_TILE_ORDER") && !lattice_hint &&
                 (rc = lattice_tile_order(h, h->stencil_stride, st)))
                 return rc;
         }
@@ -820,7 +814,7 @@ int csr_create(ndcn_csr_handle *h, int H, const ndcn_csr_hints *hints, hipStream
     ndcn_csr &A = h->v;
     const uint32_t flags = hints ? hints->flags : 0;
     const bool whole = !hints || (hints->lattice_n_own == 0 && hints->n_halo == 0);
-    if (H != 256 || A.nnz == 0 || A.n_rows == 0 || !whole || A.rec || (flags & (NDCN_PLAN_NO_SWEEP | NDCN_PLAN_ORDER_ONLY)) || env_off("NDCN_SWEEP_PLAN"))
+    if (H != 256 || A.nnz == 0 || A.n_rows == 0 || !whole || A.rec || (flags & (NDCN_PLAN_NO_SWEEP | NDCN_PLAN_ORDER_ONLY)))
         return NDCN_OK;
     if (A.n_cols * (int64_t)1024 >= (1ll << 32) || A.n_cols >= (1 << 24)) return NDCN_OK;
     const int passes = (int)((A.n_rows + (int64_t)kSweepSlabs * kSweepRows - 1) / ((int64_t)kSweepSlabs * kSweepRows));

@@ -18,7 +18,7 @@ namespace ndcn {
 constexpr uint64_t kRecSentinel = 0x7ff8dead0000beefull;       // a NaN payload no arithmetic produces
 
 inline bool poll_records_enabled() {
-    static const bool on = [] { const char *e = getenv("NDCN_POLL_RECORD"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("NDCN_POLL_RECORD");
     return on;
 }
 

@@ -669,7 +669,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
     const bool small = Hi < 16 || Ho < 16;
     if (gS) {
         ProfScope prof(PROF_LINEAR_GS, st, 4.0 * n * (double)(Hi + Ho * (Y ? 2 : 1)) + 4.0 * Hi * Ho, 2.0 * n * (double)Hi * Ho);
-        static const bool split_on = [] { const char *e = getenv("NDCN_GS_SPLIT"); return !(e && e[0] == '0'); }();
+        static const bool split_on = env_on("NDCN_GS_SPLIT");
         const bool a16 = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(gS) | reinterpret_cast<uintptr_t>(W)) & 15) == 0;
         bool split = !small && split_on && Hi == 256 && Ho == 256 && work && a16;
         void *Wq = split ? static_cast<char *>(work) + wgrad_work_bytes(n, Hi, Ho) : nullptr;
@@ -685,7 +685,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
             g_last_linear_path |= NDCN_LIN_GS_SMALL;
         } else if (split) {
             // (a caller without scratch - gS only, older bindings - keeps the fp32 MFMA kernel below)
-            static const int gs_rows = [] { const char *e = getenv("NDCN_GS_ROWS"); return e ? atoi(e) : 0; }();     // 0: resident weights (default); 32 / 64: the tile kernels
+            static const int gs_rows = env_int("NDCN_GS_ROWS", 0);     // 0: resident weights (default); 32 / 64: the tile kernels
             const int n_tiles = (int)((n + 31) / 32);
             if (gs_rows != 32 && gs_rows != 64 && n * (int64_t)1024 < (1ll << 32)) {
                 if (Y) hipLaunchKernelGGL(linear_gs_256_res_kernel<true>, dim3((unsigned)(n_tiles < kCus ? n_tiles : kCus)), dim3(512), 0, st, g, Y, Wq, gS, n, n_tiles);
@@ -716,7 +716,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
         float *part_w = static_cast<float *>(work);
         float *part_b = part_w + (size_t)used * Ho * Hi;
         ProfScope prof(PROF_LINEAR_WGRAD, st, 4.0 * n * (double)(Hi + Ho * (Y ? 2 : 1)) + 4.0 * (used + 1) * (double)Hi * Ho, 2.0 * n * (double)Hi * Ho);
-        static const bool wsplit_on = [] { const char *e = getenv("NDCN_GW_SPLIT"); return !(e && e[0] == '0'); }();
+        static const bool wsplit_on = env_on("NDCN_GW_SPLIT");
         if (small) {
             hipLaunchKernelGGL(linear_wgrad_small_kernel, dim3((unsigned)used), dim3(256), 0, st, g, Y, S, part_w, gb ? part_b : nullptr, n, Hi, Ho, rpc);
             g_last_linear_path |= NDCN_LIN_GW_SMALL;

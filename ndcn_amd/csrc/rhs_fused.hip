@@ -195,14 +195,7 @@ __global__ __launch_bounds__(256 + 64 * NPROD) void rhs_fused_256_kernel(
     }
 }
 
-static int env_int2(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
-
 int rhs_fused_supported(int H, uint32_t flags) {
-    static const int enabled = env_int2("NDCN_RHS_FUSED", 1);
-    if (!enabled) return 0;
     if (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) return 0;
     return H == kH ? 1 : 0;
 }
@@ -283,7 +276,7 @@ std::mutex g_wide_mu;
 std::unordered_map<const void *, bool> g_wide;          // key: the packed image (a caller's scratch: few, long-lived)
 std::atomic<int> g_guard_override{-1};                  // ndcn_set_range_guard: -1 = the environment's default
 bool range_guard_on() {
-    static const bool dflt = [] { const char *e = getenv("NDCN_RANGE_GUARD"); return !(e && e[0] == '0'); }();
+    static const bool dflt = env_on("NDCN_RANGE_GUARD");
     const int o = g_guard_override.load(std::memory_order_relaxed);
     return o < 0 ? dflt : o != 0;
 }
@@ -346,7 +339,7 @@ int rhs_fused_packed_f32(const ndcn_csr *A, const float *X, const float *Xh, int
     const int n_rows = (int)A->n_rows;
     if (n_rows == 0) return NDCN_OK;
     const int n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-    static const int nprod = env_int2("NDCN_RHS_PRODUCERS", 8);   // measured: 4 -> 2.3 ms, 8 -> 1.84 ms, 12 -> 1.88 ms (1M grid)
+    constexpr int kProducers = 8;                                // gather waves.  Measured: 4 -> 2.3 ms, 8 -> 1.84 ms, 12 -> 1.88 ms (1M grid)
     int per_xcd = kCus / kXcds;                                  // one workgroup per CU
     const int need = (n_tiles + kXcds - 1) / kXcds;
     if (per_xcd > need) per_xcd = need;
@@ -364,8 +357,10 @@ int rhs_fused_packed_f32(const ndcn_csr *A, const float *X, const float *Xh, int
             hipLaunchKernelGGL((rhs_fused_256_kernel<NP, false>), grid, dim3(256 + 64 * NP), 0, st, A->rowptr,      \
                                A->colidx, A->val, X, Xh, (int)n_own, Wp, b, Y, n_rows, n_tiles, relu);              \
     } while (0)
-    if (nprod >= 12) NDCN_FUSED(12);
-    else if (nprod >= 8) NDCN_FUSED(8);
+    // (The 4- and 12-wave instantiations are never launched.  They stay named here because dropping them from this code object
+    // changes the code generated for the 8-wave kernel; removing them is a device-code change of its own.)
+    if (kProducers >= 12) NDCN_FUSED(12);
+    else if (kProducers >= 8) NDCN_FUSED(8);
     else NDCN_FUSED(4);
 #undef NDCN_FUSED
     NDCN_LAUNCH_CHECK();

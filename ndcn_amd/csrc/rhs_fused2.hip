@@ -103,8 +103,8 @@ struct Fused2Args {
     float *K;                               // relu(...) output panel
     int n_rows, n_tiles, relu;
     const int *tile_order;                  // nullable: walk position -> 64-row tile (ndcn_csr::tile_order)
-    unsigned long long *dbg_cycles;         // NDCN_FUSED_TIMING: per (block, wave) {work cycles, barrier-wait cycles}
-    int dbg;                                // cycle-accounting experiments only (NDCN_FUSED_DBG): 1 skip MFMA, 2 skip gather,
+    unsigned long long *dbg_cycles;         // cycle accounting (null from the host): per (block, wave) {work cycles, barrier-wait cycles}
+    int dbg;                                // cycle-accounting experiments only (0 from the host): 1 skip MFMA, 2 skip gather,
                                             // 4 skip epilogue, 64 no weight refills, 8192 report MFMA loop | dump separately
 };
 typedef const __attribute__((address_space(4))) EpiArgs *EpiPtr;
@@ -605,14 +605,9 @@ int partials_finish(const double *partials, int n, double *d_out, hipStream_t st
 thread_local int g_last_rhs_path = 0;
 #endif
 
-static int env_int3(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
-
 #if !NDCN_F2_EXACT
 int rhs_fused2_supported(const ndcn_csr *A, int H, uint32_t flags) {
-    static const int enabled = env_int3("NDCN_RHS_FUSED2", 1);
+    static const int enabled = env_int("NDCN_RHS_FUSED2", 1);
     if (!enabled || H != kH2 || !A) return 0;
     if (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) return 0;
     // every panel must fit a buffer descriptor with a 32-bit row offset: < 4 GiB, i.e. < 4 Mi rows of 1 KiB
@@ -716,13 +711,7 @@ int rhs_fused2_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     ea.y1 = (opt && opt->y1) ? opt->y1 : X;
     ea.y_aux = (mode == MODE_COMBINE && opt && opt->y_aux && opt->c_aux) ? opt->y_aux : nullptr;
     for (int m = 0; m <= kMaxPrev; ++m) ea.c2[m] = (ea.y_aux && m <= n_prev) ? opt->c_aux[m] : 0.f;
-    static const int dbg = env_int3("NDCN_FUSED_DBG", 0);
-    a.dbg = dbg;
-    static const int timing = env_int3("NDCN_FUSED_TIMING", 0);
-    static unsigned long long *d_cyc = nullptr;
-    static int timing_prints = 0;
-    if (timing && !d_cyc) (void)hipMalloc(&d_cyc, (size_t)kCus * kWaves * 2 * sizeof(unsigned long long));
-    a.dbg_cycles = timing ? d_cyc : nullptr;
+    a.dbg = 0; a.dbg_cycles = nullptr;                          // (the kernels' debug word and cycle counters: no host code sets them)
     for (int m = 0; m < kMaxPrev; ++m) ea.kprev[m] = (m < n_prev) ? h_kprev[m] : nullptr;
     for (int m = 0; m <= kMaxPrev; ++m) ea.c[m] = (mode != MODE_PLAIN && mode != MODE_RK4 && m <= n_prev) ? h_c[m] : 0.f;
     if (mode == MODE_RK4) ea.c[0] = h_c[0];                     // the step size
@@ -765,20 +754,6 @@ int rhs_fused2_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     if (mode == MODE_ERROR) {
         int rcf = partials_finish(ea.partials, (int)grid.x * kProd, d_out, st, (opt && opt->accum) ? 1 : 0);
         if (rcf) return rcf;
-    }
-    if (timing && timing_prints < timing) {                          // debugging aid: s_memtime accounting of block 0 and 100
-        (void)hipStreamSynchronize(st);
-        unsigned long long h[2 * kWaves];
-        for (int bi = 0; bi < 2; ++bi) {
-            const int blk = bi == 0 ? 0 : 100;
-            (void)hipMemcpy(h, d_cyc + (size_t)blk * 2 * kWaves, sizeof(unsigned long long) * 2 * kWaves, hipMemcpyDeviceToHost);
-            double cw = 0, cq = 0, pw = 0, pq = 0;
-            for (int w = 0; w < 4; ++w) { cw += h[2 * w] / 4.0; cq += h[2 * w + 1] / 4.0; }
-            for (int w = 4; w < 4 + kProd; ++w) { pw += h[2 * w] / (double)kProd; pq += h[2 * w + 1] / (double)kProd; }
-            fprintf(stderr, "[fused2 timing] mode %d n_prev %d block %3d: mfma waves work %.0f wait %.0f | gather waves work %.0f wait %.0f\n",
-                    mode, n_prev, blk, cw, cq, pw, pq);
-        }
-        ++timing_prints;
     }
     return NDCN_OK;
 }

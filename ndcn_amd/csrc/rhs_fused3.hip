@@ -663,15 +663,9 @@ __global__ __launch_bounds__(64 * (f3_producers(MODE, NP) + kF3WM)) void rhs_fus
     rhs_fused3_body<false, MODE, NP, 0, NT, false, NOK, DO>(a);
 }
 
-static int env_int_f3(const char *name, int dflt) {
-    const char *s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
-
 // the operator carries the 16-row plan; no halo panel in the hub sense (Xh is served), H = 256 is the caller's check
 int rhs_fused3_supported(const ndcn_csr *A) {
-    static const int enabled = env_int_f3("NDCN_RHS_FUSED3", 1);
-    if (!enabled || !A || !A->rec || A->rec_groups <= 0) return 0;
+    if (!A || !A->rec || A->rec_groups <= 0) return 0;
     if (!(A->rec_rows == kF3R && A->rec_cap == kF3Cap && A->rec_kib == kF3RecW)) return 0;
     return (A->n_cols * (int64_t)1024 < (1ll << 32) && A->n_rows * (int64_t)1024 < (1ll << 32)) ? 1 : 0;
 }
@@ -690,8 +684,7 @@ int rhs_adj_variant(int mode, int n_prev) {
 }
 
 int rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev) {
-    static const int enabled = env_int_f3("NDCN_F3_ADJ", 1);
-    if (!enabled || H != 256 || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || !rhs_fused3_supported(A)) return 0;
+    if (H != 256 || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || !rhs_fused3_supported(A)) return 0;
     if (A->hub_n > 0 || A->sweep_S) return 0;
     return rhs_adj_variant(mode, n_prev);
 }
@@ -699,8 +692,7 @@ int rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_
 // RkOpt::xadd: the lattice plan, no halo panel, the launch that opens a dopri5 step (COMBINE with one earlier stage: k2) and the
 // second evaluation of the initial step (ERROR with one earlier stage: f(y0 + h0 f0) carrying the d2 norm)
 int rhs_xadd_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev) {
-    static const int enabled = env_int_f3("NDCN_F3_XADD", 1);
-    if (!enabled || H != 256 || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || !rhs_fused3_supported(A)) return 0;
+    if (H != 256 || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || !rhs_fused3_supported(A)) return 0;
     if (A->hub_n > 0) return 0;                                          // no second panel (hub sums); the caller vouches that
                                                                          // every column lies in the panels it passes (no X_halo)
     return ((mode == F3_COMBINE || mode == F3_ERROR) && n_prev == 1) ? 1 : 0;
@@ -766,9 +758,9 @@ int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n
     }
     a.relu = (flags & NDCN_F_RELU) ? 1 : 0;
     a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val;
-    static const int dbg = env_int_f3("NDCN_FUSED3_DBG", 0);
+    static const int dbg = env_int("NDCN_FUSED3_DBG", 0);
     a.dbg = dbg;
-    static const int timing = kF3Timing ? env_int_f3("NDCN_FUSED3_TIMING", 0) : 0;
+    static const int timing = kF3Timing ? env_int("NDCN_FUSED3_TIMING", 0) : 0;
     static unsigned long long *d_cyc = nullptr;
     static int timing_prints = 0;
     if (timing && !d_cyc) (void)hipMalloc(&d_cyc, (size_t)kCus * kF3WavesMax * 2 * sizeof(unsigned long long));

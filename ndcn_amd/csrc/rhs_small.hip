@@ -189,8 +189,8 @@ __global__ __launch_bounds__(256) void rhs_small_kernel(SmallArgs a, SmallEpi e)
 // 32 000: n H <= 2^18).  Both give the same bits, so the switch is invisible; rhs_work_bytes() asks the same question to size
 // the scratch.
 int rhs_small_wanted(int64_t n_rows, int H, uint32_t flags) {
-    static const bool enabled = [] { const char *e = getenv("NDCN_RHS_SMALL"); return !(e && e[0] == '0'); }();
-    static const int64_t max_elems = [] { const char *e = getenv("NDCN_RHS_SMALL_MAX"); return (e && *e) ? atoll(e) : (int64_t)1 << 18; }();
+    static const bool enabled = env_on("NDCN_RHS_SMALL");
+    constexpr int64_t max_elems = (int64_t)1 << 18;              // the crossovers above
     if (!enabled || H < 1 || H > kSmMaxH) return 0;
     if (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) return 0;
     return n_rows * (int64_t)H <= max_elems ? 1 : 0;

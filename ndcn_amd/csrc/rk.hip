@@ -670,10 +670,8 @@ int64_t aten_order_max_elems() {
     const int64_t ov = g_aten_override.load(std::memory_order_relaxed);
     if (ov >= 0) return ov;
     static const int64_t bound = []() -> int64_t {
-        const char *e = getenv("NDCN_ATEN_NORM");
-        if (e && e[0] == '0') return (int64_t)0;
-        const char *m = getenv("NDCN_ATEN_NORM_MAX");
-        const int64_t v = m ? atoll(m) : kAtenNormMaxDefault;
+        if (!env_on("NDCN_ATEN_NORM")) return (int64_t)0;
+        const int64_t v = env_i64("NDCN_ATEN_NORM_MAX", kAtenNormMaxDefault);
         const int64_t cap = (int64_t)1 << 24;
         return v < 0 ? (int64_t)0 : (v > cap ? cap : v);
     }();

@@ -1009,8 +1009,7 @@ int set_lds_cap(K kern) {
 // enough rows per thread for the row-local panels to stay in registers (<= 12 passes of 16 waves: 576 rows at H = 20; the
 // 32-pass build spilled 80-120 registers and is not shipped).
 int solve_small_supported(const ndcn_csr *A, int H, uint32_t flags, int method) {
-    static const bool enabled = [] { const char *e = getenv("NDCN_SOLVE_SMALL"); return !(e && e[0] == '0'); }();
-    if (!enabled || !A || H < 1 || H > 64 || A->n_rows < 1) return 0;
+    if (!A || H < 1 || H > 64 || A->n_rows < 1) return 0;
     if (method != NDCN_M_EULER && method != NDCN_M_MIDPOINT && method != NDCN_M_RK4) return 0;
     if (!(flags & NDCN_F_NO_GRAPH) && A->n_cols != A->n_rows) return 0;
     const int64_t n_elem = A->n_rows * (int64_t)H;
@@ -1035,10 +1034,7 @@ static int ell_width(const ndcn_csr *A, hipStream_t st, int *out) {
 // Do the forward AND the reverse launch of an Euler solve take their fast forms, so that the forward may keep S_i / K_i for the sweep?
 // (Decided from the view alone - ndcn_csr::max_row_len and ::symmetric filled - so that asking costs no synchronisation.)
 int solve_small_keep_supported(const ndcn_csr *A, int H, uint32_t flags) {
-    const char *env = getenv("NDCN_SOLVE_SMALL_KEEP");               // (read per call: once per solve)
-    const bool on = !(env && env[0] == '0');
-    static const bool fast_on = [] { const char *e = getenv("NDCN_SOLVE_SMALL_FAST"); return !(e && e[0] == '0'); }();
-    if (!on || !fast_on || !solve_small_bwd_supported(A, H, flags, NDCN_M_EULER)) return 0;
+    if (!env_on("NDCN_SOLVE_SMALL_KEEP") || !solve_small_bwd_supported(A, H, flags, NDCN_M_EULER)) return 0;   // (read per call: once per solve)
     if (!(H == 16 || H == 20) || (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) || A->symmetric != 1) return 0;
     const int width = (A->max_row_len + 2) / 3 * 3;
     const int64_t n_elem = A->n_rows * (int64_t)H;
@@ -1057,9 +1053,8 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
     const bool no_graph = flags & NDCN_F_NO_GRAPH;
     const int64_t nnz = no_graph ? 0 : A->nnz;
     const bool csr = !no_graph && lds_bytes(n_elem, H, A->n_rows, nnz, true) <= kLdsMax;
-    static const bool fast_on = [] { const char *e = getenv("NDCN_SOLVE_SMALL_FAST"); return !(e && e[0] == '0'); }();
     int width = 0;
-    bool fast = fast_on && (H == 16 || H == 20) && !no_graph && !(flags & NDCN_F_NO_CONTROL);
+    bool fast = (H == 16 || H == 20) && !no_graph && !(flags & NDCN_F_NO_CONTROL);
     if (fast) {
         int rc = ell_width(A, st, &width);
         if (rc) return rc;
@@ -1080,7 +1075,7 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
         a.width = width;
         a.keep = keep ? keep + (size_t)done * 2 * n_elem : nullptr;
         for (int i = 0; i < a.n_ticks; ++i) a.dt[i] = h_dt[done + i];
-        static const bool dbg_on = [] { const char *e = getenv("NDCN_SS_DEBUG"); return e && e[0] == '1'; }();
+        static const bool dbg_on = env_int("NDCN_SS_DEBUG", 0) == 1;
         static long long *dbg_buf = nullptr;
         if (dbg_on && !dbg_buf) NDCN_HIP(hipMalloc(&dbg_buf, 4 * sizeof(long long)));
         a.dbg = dbg_on ? dbg_buf : nullptr;
@@ -1142,8 +1137,7 @@ int solve_small_bwd_supported(const ndcn_csr *A, int H, uint32_t flags, int meth
         // midpoint / RK4 have the generic sweep only (no register-resident weights, no ELL image): one compute unit beats the library's
         // multi-launch loops (ndcn_fixed_grid_backward_f32: ~28 dependent launches per RK4 step whatever the size) up to ~4 600
         // state elements - tools/micro/small_rk_ab.py: 1.4 against 5.9 ms at 64 x 16, 5.9 / 8.3 at 196 x 20, 11.2 / 8.7 at 400 x 20
-        const char *env = getenv("NDCN_SOLVE_SMALL_RK_MAX");              // (read per call: once per solve)
-        const int64_t rk_max = env ? atoll(env) : (int64_t)4608;
+        const int64_t rk_max = env_i64("NDCN_SOLVE_SMALL_RK_MAX", 4608);  // (read per call: once per solve)
         if (n_elem > rk_max) return 0;
     }
     return lds_bytes(n_elem, H, A->n_rows, 0, false, 2 * n_elem) <= kLdsMax && 2 * (H * H + H) <= 1024 && n_elem <= 12 * 1024 ? 1 : 0;
@@ -1213,13 +1207,12 @@ int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, c
         a.n_rows = (int)A->n_rows; a.H = H; a.nnz = (int)A->nnz; a.n_ticks = (int)(hi - lo);
         a.relu = (flags & NDCN_F_RELU) ? 1 : 0; a.no_graph = no_graph ? 1 : 0; a.no_control = no_control ? 1 : 0;
         for (int i = 0; i < a.n_ticks; ++i) a.dt[i] = h_dt[lo + i];
-        static const bool dbg_on = [] { const char *e = getenv("NDCN_SS_DEBUG"); return e && e[0] == '1'; }();
+        static const bool dbg_on = env_int("NDCN_SS_DEBUG", 0) == 1;
         static long long *dbg_buf = nullptr;
         if (dbg_on && !dbg_buf) NDCN_HIP(hipMalloc(&dbg_buf, 4 * sizeof(long long)));
         a.dbg = dbg_on ? dbg_buf : nullptr;
         ProfScope prof(PROF_RHS_FUSED, st, 4.0 * n_elem * (2.0 * a.n_ticks + 3), 3.0 * a.n_ticks * (2.0 * A->nnz * H + 2.0 * (double)A->n_rows * H * H));
-        static const bool fast_on = [] { const char *e = getenv("NDCN_SOLVE_SMALL_FAST"); return !(e && e[0] == '0'); }();
-        const bool fast_shape = fast_on && (H == 16 || H == 20) && !no_graph && !no_control && symmetric;
+        const bool fast_shape = (H == 16 || H == 20) && !no_graph && !no_control && symmetric;
         const int NBh = fast_shape ? H / 4 : 1;
         const int n_groups = std::max(1, std::min<int>(1024 / (NBh * NBh + NBh), (int)A->n_rows));
         const int rows_per_group = (int)((A->n_rows + n_groups - 1) / n_groups);

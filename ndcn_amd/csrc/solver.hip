@@ -242,8 +242,8 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
     float d0, d1, d2;
     double bad0, bad;
     int rc;
-    static const bool fuse_on = [] { const char *e = getenv("NDCN_INIT_FUSED"); return !(e && e[0] == '0'); }();
-    if (fuse_on && (s->sharded || s->n_elem > aten_order_max_elems())) {
+    const bool big = s->sharded || s->n_elem > aten_order_max_elems();
+    if (big) {
         // d0 = || y0 / scale || and d1 = || f0 / scale || in one pass over {y0, f0}, one read-back (large panels: the
         // double-precision sums of scaled_sumsq_f32; small ones keep ATen's float32 order, section 2)
         arm(s, 4);
@@ -278,9 +278,8 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
     const float *kp[1] = {s->k[0]};
     const float cp[1] = {h0};
     // (on the lattice plan the launch that produces f1 forms y0 + h0 f0 on the rows it stages: RkOpt::xadd)
-    const bool fuse_d2 = fuse_on && s->fused2 && (s->sharded || s->n_elem > aten_order_max_elems());
-    static const bool xadd_on = [] { const char *e = getenv("NDCN_STAGE_XADD"); return !(e && e[0] == '0'); }();
-    const bool xadd = xadd_on && fuse_d2 && !s->sharded && !s->rec_epi && !s->exact32 && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 2, 1);
+    const bool fuse_d2 = big && s->fused2;
+    const bool xadd = fuse_d2 && !s->sharded && !s->rec_epi && !s->exact32 && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 2, 1);
     if (!xadd) {
         rc = rk_combine_f32(s->ytmp, s->ycur, kp, cp, 1, s->n_elem, st);
         if (rc) return rc;
@@ -413,8 +412,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         // input y0 + dt * sum_m beta[i+1][m] k[m] (its own K as the last term), the last one the error record.
         // The first stage input y0 + dt beta_21 k1 is a kernel of its own (3 panels) - unless the launch that produces k2 can
         // form it on the rows it stages (RkOpt::xadd: the lattice plan of rhs_fused3.hip, one more gather instead)
-        static const bool xadd_on = [] { const char *e = getenv("NDCN_STAGE_XADD"); return !(e && e[0] == '0'); }();
-        const bool xadd = xadd_on && !dt_dev && !s->rec_epi && !s->exact32 &&
+        const bool xadd = !dt_dev && !s->rec_epi && !s->exact32 &&
                           (s->sharded ? s->xadd_block >= 0 : rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 1, 1));
         dt_coeffs(dt32, kBeta[0], 1, s->k, kp, cp, m);
         const float xadd_c = cp[0];
@@ -436,23 +434,22 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         // the stage-input buffer that is free at that point; the error launch reads {y0, E, y1} instead of 7 panels.
         // (Replayed steps keep the one-launch form: their coefficients are fl(dt * c) of a device-resident dt, and E's
         // coefficient in the error launch is the constant 1.)
-        static const bool aux_on = [] { const char *e = getenv("NDCN_ERR_PARTIAL"); return !(e && e[0] == '0'); }();
         // Small panels (<= 2^20 elements: the reference's own drivers, every fixture) form the error record in a launch
         // of its own, in the summation order of ATen's float32 mean (rk.hip: rk_error_aten_kernel): at the truth solves'
         // rtol 1e-7 the accept / reject decision hangs on the last bit of that mean.
         const bool split_error = !s->sharded && s->n_elem >= 8 && s->n_elem <= aten_order_max_elems();
-        const bool use_aux = aux_on && !dt_dev && !split_error;
+        const bool use_aux = !dt_dev && !split_error;
         // The launch that produces k4 (i == 2) holds k1, k2, k3 in its epilogue: besides the stage-5 input it writes
         // P = dt (beta_61 k1 + beta_62 k2 + beta_63 k3 + beta_64 k4) - the first four terms of the stage-6 sum, left to right -
         // into the panel that will hold y1 two launches later; the launch that produces k5 then reads {y0, P} and forms
         // y0 + (1 * P + dt beta_65 k5), the same roundings, instead of {y0, k1, k2, k3, k4}: 2 panels less per step.
-        static const bool partial_on = [] { const char *e = getenv("NDCN_STAGE_PARTIAL"); return !(e && e[0] == '0'); }();
-        const bool use_partial = partial_on && !dt_dev;
+        // (Replayed steps, again, keep the five-panel form.)
+        const bool use_partial = !dt_dev;
         // Dense output (rk_common.py:41-61 -> dopri5.py:42, interp.py).  After the launch that produces k6 nothing but the midpoint sum
         // M = dt sum_j c_mid[j] k_j reads k6, and M is needed only when the step covers a requested tick: that launch - holding k1, k3,
         // k4, k5, k6 - writes M (the same stages in the same order as interp_direct's terms) into k6's panel, or, when the step covers
         // no tick, stores nothing there (1 P less); the dense output then reads {y0, y1, k1, M, k7} instead of nine panels.
-        static const bool mid_on = [] { const char *e = getenv("NDCN_DENSE_MID"); return !(e && e[0] == '0'); }();
+        static const bool mid_on = env_on("NDCN_DENSE_MID");
         bool dense = mid_on && keep_mid_p && use_aux && !s->sharded && !s->rec_epi && !s->exact32 &&
                      rhs_dense_supported(&s->d.A, s->d.H, s->d.rhs_flags);
         float c3[8];

@@ -341,18 +341,14 @@ __global__ __launch_bounds__(256) void spmm_wide_kernel(const int *__restrict__ 
     }
 }
 
-static int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
+constexpr int kWideBlocksPerCu = 4;     // spmm_wide_kernel: workgroups of 4 waves per compute unit
 
 template <int NV, int MODE = WIDE_PLAIN>
 static int launch_wide(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, float *Y, float alpha,
                        uint32_t flags, hipStream_t st, const WideEpi *epi = nullptr, int *n_partials = nullptr) {
     const int n_rows = (int)A->n_rows;
     if (n_rows == 0) return NDCN_OK;
-    static const int bpc = env_int("NDCN_SPMM_BLOCKS_PER_CU", 4);          // 4 waves each
-    int per_xcd = (kCus / kXcds) * bpc;
+    int per_xcd = (kCus / kXcds) * kWideBlocksPerCu;
     const int need = ((n_rows + kXcds - 1) / kXcds + 3) / 4;               // no more waves than rows
     if (per_xcd > need) per_xcd = need < 1 ? 1 : need;
     const int relu = (flags & NDCN_F_RELU) ? 1 : 0;
@@ -371,8 +367,7 @@ static int launch_wide(const ndcn_csr *A, const float *X, const float *Xh, int64
 }
 
 int spmm_wide_rk_supported(const ndcn_csr *A, int H) {
-    static const int enabled = env_int("NDCN_SPMM_WIDE_RK", 1);
-    return enabled && A && H == 256 && A->n_rows > 0;
+    return A && H == 256 && A->n_rows > 0;
 }
 
 // K = relu(A X) plus the RK algebra in the row SpMM's epilogue (modes and arguments as spmm_rec_f32 / rhs_fused2_f32)
@@ -447,8 +442,7 @@ int spmm_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, 
     // hub's finished row as ONE entry of a second panel.
     // Column-sweep plan (struct ndcn_csr; spmm_sweep.hip): operators without locality whose partial sums fit the register files
     if (vec && !Xh && alpha == 1.f && !(flags & NDCN_F_RELU) && spmm_sweep_supported(A, H)) return spmm_sweep_f32(A, X, Y, st);
-    static const int use_hub = env_int("NDCN_SPMM_HUB", 1);
-    if (use_hub && vec && !Xh && A->hub_n > 0 && A->hub_H == H && A->hub_S && A->hub_Sseg && A->lt_rowptr) {
+    if (vec && !Xh && A->hub_n > 0 && A->hub_H == H && A->hub_S && A->hub_Sseg && A->lt_rowptr) {
         ndcn_csr seg = {};
         seg.n_rows = A->hub_nseg; seg.n_cols = A->n_cols; seg.nnz = A->hub_nnz;
         seg.rowptr = A->hub_seg_rowptr; seg.colidx = A->hub_colidx; seg.val = A->hub_val;
@@ -470,13 +464,10 @@ int spmm_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, 
     ProfScope prof(PROF_SPMM, st, 8.0 * A->nnz + 4.0 * (A->n_rows + 1) + 4.0 * H * (double)(A->n_rows + A->n_cols),
                    2.0 * A->nnz * H);
     if (vec && H % 256 == 0 && H <= 1024) {
-        static const int use_wide = env_int("NDCN_SPMM_WIDE", 1);
-        if (use_wide) {
-            if (H == 256) return launch_wide<1>(A, X, Xh, n_own, Y, alpha, flags, st);
-            if (H == 512) return launch_wide<2>(A, X, Xh, n_own, Y, alpha, flags, st);
-            if (H == 768) return launch_wide<3>(A, X, Xh, n_own, Y, alpha, flags, st);
-            return launch_wide<4>(A, X, Xh, n_own, Y, alpha, flags, st);
-        }
+        if (H == 256) return launch_wide<1>(A, X, Xh, n_own, Y, alpha, flags, st);
+        if (H == 512) return launch_wide<2>(A, X, Xh, n_own, Y, alpha, flags, st);
+        if (H == 768) return launch_wide<3>(A, X, Xh, n_own, Y, alpha, flags, st);
+        return launch_wide<4>(A, X, Xh, n_own, Y, alpha, flags, st);
     }
     if (vec) return dispatch_lpr<4>(H / 4, A, X, Xh, n_own, Y, H, alpha, flags, st);
     return dispatch_lpr<1>(H, A, X, Xh, n_own, Y, H, alpha, flags, st);

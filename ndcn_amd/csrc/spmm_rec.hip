@@ -62,7 +62,7 @@ struct RecArgs {
     int relu;
     const int *rowptr, *colidx;      // direct gather of groups the plan could not stage
     const float *val;
-    int dbg;                         // NDCN_REC_DBG (experiments): 1 request the panels in their own step, 2 wait for everything
+    int dbg;                         // debug word, 0 from every caller (experiments): 1 request the panels in their own step, 2 wait for everything
 };
 struct RecEpi {
     const float *y0;
@@ -352,14 +352,8 @@ __global__ __launch_bounds__(64 * (kRecWC + kRecWD)) void spmm_rec_kernel(RecArg
     }
 }
 
-static int env_int_rec(const char *name, int dflt) {
-    const char *s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
-
 int spmm_rec_supported(const ndcn_csr *A, int H) {
-    static const int enabled = env_int_rec("NDCN_SPMM_REC", 1);
-    if (!enabled || H != 256 || !A || !A->rec || A->rec_groups <= 0) return 0;
+    if (H != 256 || !A || !A->rec || A->rec_groups <= 0) return 0;
     return (A->rec_rows == 8 && A->rec_cap == 32 && A->rec_kib == 1) || (A->rec_rows == 16 && A->rec_cap == 40 && A->rec_kib == 2) ||
            (A->rec_rows == 8 && A->rec_cap == 48 && A->rec_kib == 2);      // ring + shortcuts: small-world graphs
 }
@@ -415,7 +409,7 @@ int spmm_rec_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_o
     a.rec = A->rec; a.n_groups = A->rec_groups; a.X = X; a.Xh = Xh; a.n_own = (int)n_own; a.Y = Y; a.alpha = alpha;
     a.relu = (flags & NDCN_F_RELU) ? 1 : 0;
     a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val;
-    a.dbg = env_int_rec("NDCN_REC_DBG", 0);
+    a.dbg = 0;
     RecEpi e = {};
     e.y0 = y0; e.y_next = y_next; e.n_prev = n_prev; e.rtol = rtol; e.atol = atol; e.partials = static_cast<double *>(d_ws);
     e.c_dev = c_dev;

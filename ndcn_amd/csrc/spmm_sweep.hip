@@ -226,18 +226,15 @@ __global__ __launch_bounds__(kSweepWaves * 64) void spmm_sweep_kernel(SweepArgs 
 
 
 int spmm_sweep_supported(const ndcn_csr *A, int H) {
-    static const int enabled = [] { const char *e = getenv("NDCN_SWEEP"); return e ? atoi(e) : 1; }();
     // (256 workgroups of a pass wait on each other's progress words: all of them must be resident, one per CU of the whole chip)
-    return enabled && A && H == 256 && A->sweep_ent && A->sweep_slab && A->sweep_prog && A->sweep_passes > 0 &&
+    return A && H == 256 && A->sweep_ent && A->sweep_slab && A->sweep_prog && A->sweep_passes > 0 &&
            A->sweep_rpw > 0 && A->sweep_rpw <= kSweepRows && A->n_cols * (int64_t)1024 < (1ll << 32) && device_is_whole_chip();
 }
 
 // Y = A X through the operator's column-sweep plan (H = 256, no halo panel, alpha = 1, no activation)
 int spmm_sweep_f32(const ndcn_csr *A, const float *X, float *Y, hipStream_t st) {
     if (A->n_rows == 0) return NDCN_OK;
-    static const int logb_env = [] { const char *e = getenv("NDCN_SWEEP_LOGB"); return e ? atoi(e) : 0; }();
-    static const int win_env = [] { const char *e = getenv("NDCN_SWEEP_WINDOW"); return e ? atoi(e) : 0; }();
-    const int logb = logb_env > 0 ? logb_env : A->sweep_logb, window = win_env > 0 ? win_env : A->sweep_window;
+    const int logb = A->sweep_logb, window = A->sweep_window;
     ProfScope prof(PROF_SPMM, st, 8.0 * A->nnz + 4.0 * (A->n_rows + 1) + 4.0 * 256 * (double)(A->n_rows + A->n_cols), 2.0 * A->nnz * 256);
     for (int p = 0; p < A->sweep_passes; ++p) {
         SweepArgs a;
@@ -256,7 +253,7 @@ int spmm_sweep_f32(const ndcn_csr *A, const float *X, float *Y, hipStream_t st) 
         a.logb = logb;
         a.nblk = (int)((A->n_cols + (1ll << logb) - 1) >> logb);
         a.window = window;
-        static const int dbg_env = [] { const char *e = getenv("NDCN_SWEEP_DBG"); return e ? atoi(e) : 0; }();
+        static const int dbg_env = env_int("NDCN_SWEEP_DBG", 0);
         a.dbg = dbg_env;
         if (a.nblk >= 65536 || a.rpw > kSweepRows) { set_error("spmm_sweep: plan does not fit the kernel"); return NDCN_EINVAL; }
         hipLaunchKernelGGL(spmm_sweep_kernel, dim3(kCus), dim3(kSweepWaves * 64), 0, st, a);

@@ -756,7 +756,6 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
         }
         int row_slot[8];
         for (int m = 2; m <= 7; ++m) row_slot[m] = -1;
-        static const bool fused_pull = [] { const char *e = getenv("NDCN_TAPE_PULL_FUSED"); return !(e && e[0] == '0'); }();
         for (int e = 6; e >= 1; --e) {
             // total gradient of k_e: received + sum_{m' > e} dt beta[m' - 2][e - 1] g_u_m', and the step size through stage sum
             // m = e + 1 (all its g_u is known now): <g_u_m, u_m - y0> / dt
@@ -772,7 +771,7 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
             float *dst = (e == 1) ? CF[1 - pp] : T;
             const float *tot;
             bool premasked = false;
-            if (fused_pull && gu[m]) {
+            if (gu[m]) {
                 // one pass: the sum, the ReLU mask of evaluation e (none for k_1: that evaluation belongs to the previous attempt), the product
                 const float *kp[8];
                 float cp[8];
@@ -785,12 +784,7 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
                 if (rc) return rc;
                 tot = dst;
                 premasked = mask != nullptr;
-            } else {
-                if (gu[m]) {
-                    row_slot[m] = slot++;
-                    rc = rk_dot_diff_f32(gu[m], a.u[m], a.y0, dots_at(row_slot[m]), t->d_bws, n, st);
-                    if (rc) return rc;
-                }
+            } else {                                              // stage sum m received nothing: no step-size term, the sum alone
                 rc = gather_sum(t, dst, cur_gk[e - 1], pp_, cc_, np, st, &tot, e == 1);
                 if (rc) return rc;
             }

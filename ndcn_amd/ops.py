@@ -8,7 +8,6 @@ logic is written against (ndcn_amd/torchdiffeq/_impl/core.py).  Tests drive that
 an oracle-backed double to check the control flow without a GPU; product code never does.
 """
 import ctypes
-import os
 import threading
 import weakref
 
@@ -89,10 +88,9 @@ class _PackedWeights:
     call therefore starts a new epoch (`new_epoch`): the first use of a weight inside it re-packs (two small launches, ~10 us
     per solve), the thousands that follow hit.  What is left to the caller: such a write BETWEEN two direct `hip.rhs` calls
     outside any solve (or in the middle of one - which no autograd graph survives either): call
-    `ndcn_amd.ops.invalidate_packed_weights()` after it, or run with NDCN_PACK_CACHE=0 (re-pack at every call)."""
+    `ndcn_amd.ops.invalidate_packed_weights()` after it."""
     _cache = {}
     _epoch = 0
-    enabled = os.environ.get('NDCN_PACK_CACHE', '1') != '0'
 
     @classmethod
     def invalidate(cls):
@@ -104,8 +102,6 @@ class _PackedWeights:
 
     @classmethod
     def get(cls, W, nbytes, tag='fwd'):
-        if not cls.enabled:
-            return torch.empty(nbytes, dtype=torch.uint8, device=W.device), 0
         # a whole-tensor alias (the training path hands W on from evaluation to evaluation as `W.view_as(W)`: a new tensor object each
         # time) is the tensor it views: same storage, same version counter
         base = W._base

@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ._lib import env_str
 from .csr import CsrOperator
 
 
@@ -30,15 +31,13 @@ def even_bounds(n, world):
 class HaloPlan:
     """What this rank must send / receive before each A X, and the operator remapped to [own | halo] columns."""
 
-    def __init__(self, rows_block, bounds, rank, device, group=None, self_halo=0, two_phase=None):
+    def __init__(self, rows_block, bounds, rank, device, group=None, self_halo=0, two_phase=True):
         """rows_block: scipy CSR, this rank's rows x ALL global columns.
         self_halo (test hook, NDCN_SELF_HALO): the first `self_halo` OWN columns are additionally routed through the
         exchange as if a peer owned them (this rank sends them to itself), so that a single rank drives a non-empty
         all-to-all-v over the real backend - on a 1-GPU box that is the only way RCCL's collective ever executes."""
         self.group = group
         self.rank, self.world = rank, len(bounds) - 1
-        if two_phase is None:
-            two_phase = os.environ.get('NDCN_TWO_PHASE', '1') != '0'
         self.bounds = list(bounds)
         lo, hi = bounds[rank], bounds[rank + 1]
         self.n_own = hi - lo
@@ -534,7 +533,7 @@ class DeviceShard:
         # broadcast whatever happened before it (a rank that raised earlier would leave its peers waiting in it): rank 0's
         # failure travels as an all-zero id with a set flag byte, and then every rank raises together.
         self.comm = ctypes.c_void_p()
-        self.transport = transport or os.environ.get('NDCN_COMM_TRANSPORT', 'rccl')
+        self.transport = transport or env_str('NDCN_COMM_TRANSPORT', 'rccl')
         if self.transport == 'loopback':
             # TEST transport (include/ndcn_hip.h: ndcn_comm_create_loopback): host-staged shared memory with the RCCL communicator's
             # call sequence - several ranks on ONE device.  Rank 0 draws the name, everybody learns it over the caller's group.
@@ -657,7 +656,7 @@ class ShardedDeviceBench:
 def bench_plan(block, bounds, rank, device, group=None):
     """The HaloPlan of a bench shard (collective on `group`: every rank builds its plan at the same time), honouring the
     NDCN_SELF_HALO test hook."""
-    sh = os.environ.get('NDCN_SELF_HALO', '0')
+    sh = env_str('NDCN_SELF_HALO', '0')
     return HaloPlan(block, bounds, rank, device, group, self_halo=sh if sh.startswith('scatter:') else int(sh))
 
 

@@ -35,10 +35,10 @@ class _TupleFunc(nn.Module):
 def _native_odefunc(func, n_state, ans):
     """This package's ODEFunc behind the tuple wrapper, when the closed-form adjoint right-hand side applies: one N x H
     device panel as state, the deterministic ODEFunc (dropout inactive), a square operator."""
-    import os
+    from ... import _lib
     from ...neural_dynamics import ODEFunc
     base = getattr(func, 'base_func', None)
-    if os.environ.get('NDCN_ADJOINT_NATIVE', '1') == '0' or n_state != 1 or type(base) is not ODEFunc:
+    if not _lib.env_on('NDCN_ADJOINT_NATIVE') or n_state != 1 or type(base) is not ODEFunc:
         return None
     y = ans[0]
     if y.dim() != 3 or y.shape[2] != base.hidden_size or not y.is_cuda or (base.training and base.dropout > 0):

@@ -32,9 +32,8 @@ Scope: dopri5 - ODEFunc with H = 256 (the fused kernels' width), graph on, dropo
 (round 6: euler / midpoint / rk4, `FusedAdjointFixed` below) - any width with the graph on: the same two launches per evaluation with the
 method's stage algebra in their epilogues (`rk4` / `combine` modes of ndcn_rhs_rk_f32; the narrow widths run rhs_small.hip).  Everything
 else - dopri5 on narrow panels, whose accept / reject decisions hang on ATen-order norms of every state tensor - keeps the generic
-path.  NDCN_ADJOINT_FUSED=0 switches this off (A/B)."""
+path."""
 import math
-import os
 
 import numpy as np
 import torch
@@ -42,7 +41,7 @@ import torch
 from . import core
 from .core import DP_ALPHA, DP_BETA, DP_C_ERR, DP_C_MID, dt_terms, f32
 
-ENABLED = os.environ.get('NDCN_ADJOINT_FUSED', '1') != '0'
+ENABLED = True            # tests and tools/bench_adjoint.py clear it to reach the generic reverse pass they compare with
 
 
 def applicable(f0, y):

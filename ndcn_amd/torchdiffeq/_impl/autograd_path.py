@@ -13,12 +13,12 @@ every panel op's backward is ONE analytic VJP kernel (csrc/rk_bwd.hip: panel gra
 the gradients of the scalar coefficients).  The RHS itself (`func`) is differentiated by its own autograd Function (HIP SpMM / Linear).
 """
 import math
-import os
 import threading
 
 import numpy as np
 import torch
 
+from ..._lib import env_int, env_on, env_str
 from ...autograd_ops import autograd_ops
 from ...ops import hip
 from . import core
@@ -79,7 +79,7 @@ def _on(dev, s):
 # tests use to check the analytic kernels.
 
 def _analytic():
-    return os.environ.get('NDCN_VJP', 'hip') != 'torch'
+    return env_str('NDCN_VJP', 'hip') != 'torch'
 
 
 def _scalar_like(ref, v):
@@ -312,7 +312,7 @@ def _dense_output(y0, y1, ks, dts, x, cache):
 # formed in a different order than autograd's, to fp32 rounding.  NDCN_GRAD_CARRY=0 restores the fan-out forms (A/B test).
 
 def _carry():
-    return _analytic() and os.environ.get('NDCN_GRAD_CARRY', '1') != '0'
+    return _analytic() and env_on('NDCN_GRAD_CARRY')
 
 
 # ---- deferred scalar gradients -----------------------------------------------------------------------------------------
@@ -325,7 +325,7 @@ def _carry():
 # the wait blocks the scalar chain only, the worker keeps queueing panel launches.  NDCN_GRAD_LAZY=0: eager reads.
 
 def _lazy():
-    return os.environ.get('NDCN_GRAD_LAZY', '1') != '0'
+    return env_on('NDCN_GRAD_LAZY')
 
 
 class _LazyFlag(threading.local):
@@ -336,6 +336,10 @@ class _LazyFlag(threading.local):
 
 
 _LAZY = _LazyFlag()
+
+# Smaller states - the reference's own 400 x 20 - are host-bound: the one-node-per-evaluation form costs them 35 %, 14.1 against
+# 10.4 ms per README-sized dopri5 step (profiles/r04i_train_ab.txt); they keep one node per operation.
+_FUSED_STAGE_MIN_ELEMS = 1 << 16
 
 
 class _Await(torch.autograd.Function):
@@ -583,7 +587,7 @@ class _StepPull:
 
 
 def _pull_enabled():
-    return os.environ.get('NDCN_GRAD_PULL', '1') != '0'
+    return env_on('NDCN_GRAD_PULL')
 
 
 def _keep_s(op, mode, n_prev, x):
@@ -598,7 +602,7 @@ def _keep_s(op, mode, n_prev, x):
 def _keep_s_enabled(y):
     """NDCN_GRAD_KEEP_S = 1 / 0 / auto (default): keep S when ~60 more panels (a long solve's evaluations) fit the free device memory
     four times over; otherwise the SpMM is recomputed in backward as before"""
-    v = os.environ.get('NDCN_GRAD_KEEP_S', 'auto')
+    v = env_str('NDCN_GRAD_KEEP_S', 'auto')
     if v in ('0', '1'):
         return v == '1'
     free, _ = torch.cuda.mem_get_info(y.device)
@@ -606,7 +610,7 @@ def _keep_s_enabled(y):
 
 
 def _row_dot_enabled():
-    return os.environ.get('NDCN_GRAD_ROW_DOT', '1') != '0'
+    return env_on('NDCN_GRAD_ROW_DOT')
 
 
 class _StagePullFn(torch.autograd.Function):
@@ -948,24 +952,22 @@ def _integrate_dopri5_grad(func, y0, t, rtol, atol, autonomous=False, step_log=N
     carry = _carry()
     # deferred scalar gradients pay where a read-back stalls real GPU work; on the reference's own sizes (400 x 20) the extra
     # autograd node per coefficient costs more than the stall (README-sized dopri5 step 11 -> 19 ms, tools/micro/train_ab.py)
-    lazy = carry and _lazy() and y0[0].numel() >= int(os.environ.get('NDCN_GRAD_LAZY_MIN', 1 << 20))
+    lazy = carry and _lazy() and y0[0].numel() >= env_int('NDCN_GRAD_LAZY_MIN', 1 << 20)
     # a plain ODEFunc on one state tensor (odeint checked): its evaluations carry the next stage input in their epilogue
     fused = None
-    # (reference-sized states - 400 x 20 - are host-bound: the one-node-per-evaluation form costs them 35 %, 14.1 against 10.4 ms
-    # per README-sized dopri5 step, profiles/r04i_train_ab.txt; they keep one node per operation)
-    if carry and odefunc is not None and len(y0) == 1 and os.environ.get('NDCN_GRAD_FUSED_STAGE', '1') != '0' and \
-            y0[0].numel() >= int(os.environ.get('NDCN_GRAD_FUSED_STAGE_MIN', 1 << 16)):
+    if carry and odefunc is not None and len(y0) == 1 and env_on('NDCN_GRAD_FUSED_STAGE') and \
+            y0[0].numel() >= _FUSED_STAGE_MIN_ELEMS:
         from ...csr import as_csr
         fused = ((None if odefunc.no_graph else as_csr(odefunc.A), bool(odefunc.no_graph), bool(odefunc.no_control)),
                  odefunc.wt.weight, odefunc.wt.bias)
     # the error record rides in the last evaluation's epilogue where the inference solver puts it there too (rk.hip: panels beyond
     # the range of the ATen-order reductions), so that both paths see the same ratio
-    fuse_err = fused is not None and y0[0].numel() > int(os.environ.get('NDCN_ATEN_NORM_MAX', 1 << 18)) and \
-        os.environ.get('NDCN_GRAD_FUSED_ERROR', '1') != '0'
+    fuse_err = fused is not None and y0[0].numel() > env_int('NDCN_ATEN_NORM_MAX', 1 << 18) and \
+        env_on('NDCN_GRAD_FUSED_ERROR')
     _LAZY.on = lazy
     pull_on = fused is not None and _pull_enabled()
     _LAZY.keep_s = fused is not None and _keep_s_enabled(y0[0])
-    multi_tick = os.environ.get('NDCN_GRAD_MULTI_TICK', '1') != '0'
+    multi_tick = env_on('NDCN_GRAD_MULTI_TICK')
     # ---- the first evaluation and the initial step (dopri5.py:76-83).  y0 has four consumers - this evaluation, the initial-step
     # selection, the first stage chain, the trajectory's first tick: one alias each (_FanOut: a fixed summation order for its
     # gradient); in the fused path every evaluation goes through a carry node that hands W and b on (a chain instead of a dozen

@@ -316,7 +316,7 @@ class _FixedGridSolve(torch.autograd.Function):
 
 def _fixed_grid_with_grad(odefunc, y0, t, method):
     """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size)."""
-    if t.requires_grad or os.environ.get('NDCN_FIXED_GRID_GRAD', '1') == '0' or t.numel() < 2:
+    if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
         return None
     op = _small_operator(odefunc, y0)
     if op is None:
@@ -337,7 +337,7 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler'):
     """The one-launch training path when the library supports the shape (H <= 31, the state and three work panels in one
     CU's LDS: the reference's README commands), else None - the caller falls back to the per-step autograd path."""
     from ...csr import as_csr
-    if t.requires_grad or os.environ.get('NDCN_SOLVE_SMALL_GRAD', '1') == '0' or t.numel() < 2:
+    if t.requires_grad or not _lib.env_on('NDCN_SOLVE_SMALL_GRAD') or t.numel() < 2:
         return None
     lib = _lib.load()
     H = odefunc.hidden_size
@@ -350,7 +350,7 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler'):
     view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(y0.shape[0]))
     if not lib.ndcn_solve_small_supported(view, H, flags, _lib.METHODS[method], 1):
         return None
-    if method != 'euler' and os.environ.get('NDCN_SOLVE_SMALL_RK_GRAD', '1') == '0':
+    if method != 'euler' and not _lib.env_on('NDCN_SOLVE_SMALL_RK_GRAD'):
         return None
     core.assert_increasing(t)
     tt = core.host_grid(t).to(y0.dtype)                    # solvers.py:81: the grid in the state dtype
@@ -532,7 +532,7 @@ def _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph):
         return DeviceSolver(odefunc, y0.shape[0], method, rtol, atol, opt.get('max_num_steps', 2 ** 31 - 1), use_graph=use_graph,
                             safety=opt.get('safety', core.SAFETY), ifactor=opt.get('ifactor', core.IFACTOR),
                             dfactor=opt.get('dfactor', core.DFACTOR))
-    if not use_graph or y0.numel() > _SOLVER_CACHE_MAX_ELEMS or os.environ.get('NDCN_SOLVER_CACHE', '1') == '0':
+    if not use_graph or y0.numel() > _SOLVER_CACHE_MAX_ELEMS:
         return make(), None
     W, b = odefunc.wt.weight, odefunc.wt.bias
     key = (id(odefunc), W.data_ptr(), None if b is None else b.data_ptr(), id(getattr(odefunc, 'A', None)), tuple(y0.shape), method,
@@ -577,7 +577,7 @@ def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log):
             return out
     # launch-bound sizes replay ONE captured hipGraph per step - a fixed-grid step, or one attempted dopri5 step - with the
     # step size in device memory (the library declines where a path has no replayable form)
-    use_graph = y0.numel() <= GRAPH_MAX_ELEMS and os.environ.get('NDCN_HIPGRAPH', '1') != '0'
+    use_graph = y0.numel() <= GRAPH_MAX_ELEMS
     opt = core.dopri5_options(options, 1) if method == 'dopri5' else {}
     solver, cache_key = _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph)
     try:

@@ -7,7 +7,6 @@ differentiates: dt, the initial step, the interpolation abscissa are tensors wit
 ~130 (`autograd_path.integrate_dopri5_grad`, which stays the path of tuple states, plain callables, `t` with gradient and the A/B:
 NDCN_GRAD_TAPE=0)."""
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -20,7 +19,7 @@ ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64)
 
 
 def enabled():
-    return os.environ.get('NDCN_GRAD_TAPE', '1') != '0' and os.environ.get('NDCN_VJP', 'hip') != 'torch'
+    return _lib.env_on('NDCN_GRAD_TAPE') and _lib.env_str('NDCN_VJP', 'hip') != 'torch'
 
 
 class Tape:
@@ -227,7 +226,7 @@ class _NativeFixedGrid(torch.autograd.Function):
 
 def fixed_grid(y0, W, b, csr, flags, method, dts):
     """-> trajectory (T, N, H), or None when the native loops are switched off (NDCN_FIXED_GRID_NATIVE=0)"""
-    if os.environ.get('NDCN_FIXED_GRID_NATIVE', '1') == '0' or os.environ.get('NDCN_VJP', 'hip') == 'torch':
+    if not _lib.env_on('NDCN_FIXED_GRID_NATIVE') or _lib.env_str('NDCN_VJP', 'hip') == 'torch':
         return None
     if csr is not None:
         csr.ensure_plans(y0.shape[1])

@@ -29,6 +29,28 @@ def test_library_loads_and_exports_every_symbol():
     assert exported == header_functions()
 
 
+def test_switch_table_lists_exactly_what_the_sources_read():
+    """INTEGRATION.md, "Run-time switches" = the names handed to the env readers of csrc/common.h and ndcn_amd/_lib.py - and nothing
+    reads the environment past those readers."""
+    pkg = os.path.join(ROOT, 'ndcn_amd')
+    read, direct = set(), []
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith(('.py', '.hip', '.h')):
+                continue
+            path = os.path.join(d, f)
+            text = open(path).read()
+            read.update(re.findall(r'\benv_(?:on|int|i64|str)\(\s*[\'"](NDCN_\w+)[\'"]', text))
+            if f not in ('common.h', '_lib.py') and re.search(r'\bgetenv\b|os\.environ|os\.getenv', text):
+                direct.append(os.path.relpath(path, ROOT))
+    assert direct == [], 'environment read past the shared readers'
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    section = doc.split('## Run-time switches', 1)[1].split('\n## ', 1)[0]
+    listed = re.findall(r'^\| `(NDCN_\w+)` \|', section, re.M)
+    assert len(listed) == len(set(listed))
+    assert set(listed) == read and read
+
+
 def test_library_has_gfx950_code_object():
     from ndcn_amd import _lib
     out = subprocess.run(['strings', '-a', _lib.LIB_PATH], capture_output=True, text=True).stdout

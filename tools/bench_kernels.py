@@ -16,9 +16,7 @@ VARIANTS = {
     'spmm_rec': {},                                                # group-record plan (default on lattices)
     'spmm_rec_rows8': {'NDCN_REC_STENCIL': '0'},                   # ... without the lattice patch order
     'spmm_wide': {'NDCN_REC_PLAN': '0'},                           # direct gather, one row per wave (v_readlane broadcast)
-    'spmm_blocked': {'NDCN_REC_PLAN': '0', 'NDCN_SPMM_WIDE': '0'},
     'rhs_fused': {},
-    'rhs_unfused': {'NDCN_RHS_FUSED': '0'},
 }
 
 
@@ -78,21 +76,10 @@ def one(name, side=1000, H=256, reps=20):
         ms = timeit(lambda: hip.rhs(A, X, W, b, out=Y))
         fl = 2.0 * L.nnz * H + 2.0 * n * H * H
         res.update(ms=ms, TFLOPs=fl / ms / 1e9, GBps=graphs.spmm_bytes(n, L.nnz, H) / ms / 1e6)
-        # cross-check fused vs unfused result on a row sample
+        # cross-check the fused result on a row sample
         S = hip.spmm(A, X)
         ref = torch.relu(torch.nn.functional.linear(S[:4096].double(), W.double(), b.double()))
         res['max_err_vs_fp64'] = float((Y[:4096].double() - ref).abs().max())
-    if name == 'rhs_unfused':
-        S = torch.empty_like(X)
-        res['linear_ms'] = timeit(lambda: hip.linear(X, W, b, relu=True))
-        ks = [torch.rand_like(X) for _ in range(6)]
-        cs = [0.1 * (i + 1) for i in range(6)]
-        for nk in (1, 3, 6):
-            ms = timeit(lambda: hip.combine(X, ks[:nk], cs[:nk]))
-            res['combine%d_ms' % nk] = ms
-            res['combine%d_GBps' % nk] = 4.0 * n * H * (nk + 2) / ms / 1e6
-        ms = timeit(lambda: Y.copy_(X))
-        res['copy_GBps'] = 8.0 * n * H / ms / 1e6
     print(json.dumps(res), flush=True)
 
 
