@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 20
+#define NDCN_ABI_VERSION 21
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -689,6 +689,22 @@ NDCN_API int ndcn_debug_last_linear_path(void);
 #define NDCN_RKB_PULL        64     /* ndcn_rk_pull_f32                                                                             */
 #define NDCN_RKB_VEC        128     /* ... by 16 bytes per lane (n % 4 == 0, every panel 16-byte aligned); the grid counts float4 items then */
 NDCN_API int ndcn_debug_last_rk_bwd_path(void);
+/* Which SpMM kernel the LAST SpMM of this thread launched (ABI 21; tests: each case reaches the route it targets): ndcn_spmm_f32, and the
+ * no_control epilogues of ndcn_rhs_rk_f32 (NDCN_PATH_REC / NDCN_PATH_WIDE above).  A family bit | NDCN_SPMM_VEC | NDCN_SPMM_HALO |
+ * (LPR or NV) << NDCN_SPMM_LANES_SHIFT | record shape << NDCN_SPMM_REC_SHIFT | mode << NDCN_SPMM_MODE_SHIFT | rows_per_block <<
+ * NDCN_SPMM_RPB_SHIFT.  ndcn_spmm_f32 clears it first: 0 for an operator without rows and before the first call.                      */
+#define NDCN_SPMM_CSR        1      /* spmm_csr_kernel<VW, LPR, HALO>: a block of rows per workgroup, LPR lanes per row                */
+#define NDCN_SPMM_WIDE       2      /* spmm_wide_kernel<NV, HALO, MODE>: H = 256 NV, one row per wave                                 */
+#define NDCN_SPMM_REC        4      /* spmm_rec_kernel<R, CAP, RECW, HALO, MODE>: the group-record plan                               */
+#define NDCN_SPMM_SWEEP      8      /* spmm_sweep_kernel: the column-sweep plan                                                       */
+#define NDCN_SPMM_HUB       16      /* long-row plan: segments and their combine ran first; the other bits are the light launch's     */
+#define NDCN_SPMM_VEC       32      /* 16 bytes per lane slot (VW = 4; always for WIDE / REC / SWEEP)                                */
+#define NDCN_SPMM_HALO      64      /* the kernel's HALO form (a halo panel was passed)                                               */
+#define NDCN_SPMM_LANES_SHIFT 8     /* bits 8..15: LPR of CSR (1..64), NV of WIDE (1..4)                                               */
+#define NDCN_SPMM_REC_SHIFT  16     /* bits 16..17: REC shape {R, CAP, KiB}: 1 {8, 32, 1}, 2 {16, 40, 2}, 3 {8, 48, 2}                 */
+#define NDCN_SPMM_MODE_SHIFT 18     /* bits 18..19: REC / WIDE epilogue: 0 plain, NDCN_RK_COMBINE, NDCN_RK_ERROR, NDCN_RK_RK4          */
+#define NDCN_SPMM_RPB_SHIFT  20     /* bits 20..28: rows_per_block of CSR (16..256)                                                    */
+NDCN_API int ndcn_debug_last_spmm_path(void);
 /* The range guard of the H = 256 Linear (NDCN_PATH_EXACT32 above): on = 1 / 0 switches it PROCESS-WIDE at run time, on < 0 returns to the
  * default (on, unless the environment says NDCN_RANGE_GUARD=0); returns the previous state (1 / 0).  Off, every packed image takes the
  * split fp16 product whatever its range, and packing does not read back.  Images packed while the guard was off are judged when

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
@@ -19,6 +19,10 @@ LIN_GS_SMALL, LIN_GS_FP32, LIN_GS_RES, LIN_GS_RES_MASK, LIN_GS_SPLIT32, LIN_GS_S
 LIN_GW_SMALL, LIN_GW_FP32, LIN_GW_SPLIT, LIN_GW_SUM2 = 65536, 131072, 262144, 524288
 # ndcn_debug_last_rk_bwd_path: (grid << 16) | kernel | RKB_VEC of the last solver-VJP call (include/ndcn_hip.h NDCN_RKB_*)
 RKB_COMBINE, RKB_ERROR, RKB_RMS, RKB_DENSE, RKB_DENSE_MULTI, RKB_DOT_DIFF, RKB_PULL, RKB_VEC = 1, 2, 4, 8, 16, 32, 64, 128
+# ndcn_debug_last_spmm_path: family | SPMM_VEC | SPMM_HALO | lanes << 8 | rec shape << 16 | mode << 18 | rows_per_block << 20 of the last
+# SpMM launch (include/ndcn_hip.h NDCN_SPMM_*)
+SPMM_CSR, SPMM_WIDE, SPMM_REC, SPMM_SWEEP, SPMM_HUB, SPMM_VEC, SPMM_HALO = 1, 2, 4, 8, 16, 32, 64
+SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 20
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6
@@ -216,6 +220,7 @@ SIGNATURES = {
     'ndcn_debug_last_rhs_path': (_I, []),
     'ndcn_debug_last_linear_path': (_I, []),
     'ndcn_debug_last_rk_bwd_path': (_I, []),
+    'ndcn_debug_last_spmm_path': (_I, []),
     'ndcn_set_range_guard': (_I, [_I]),
 }
 

@@ -43,6 +43,7 @@ int ndcn_abi_version(void) { return NDCN_ABI_VERSION; }
 int ndcn_debug_last_rhs_path(void) { return g_last_rhs_path; }
 int ndcn_debug_last_linear_path(void) { return g_last_linear_path; }
 int ndcn_debug_last_rk_bwd_path(void) { return g_last_rk_bwd_path; }
+int ndcn_debug_last_spmm_path(void) { return g_last_spmm_path; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
 const char *ndcn_last_error(void) { return g_err; }
 
@@ -147,6 +148,7 @@ int ndcn_spmm_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_
     NDCN_CHECK_ARG(A->n_rows == 0 || (X && Y), "null panel");
     NDCN_CHECK_ARG(X != Y, "Y must not alias X");
     NDCN_CHECK_ARG(X_halo || n_own >= A->n_cols, "columns beyond n_own need a halo panel");
+    g_last_spmm_path = 0;
     return spmm_f32(A, X, X_halo, n_own, Y, H, alpha, flags, ST(stream));
 }
 

@@ -146,6 +146,7 @@ int rk_dense_bwd_multi_f32(const float *const *h_g, int nt, const float *y0, con
 bool prof_pause(bool on);     // returns the previous state
 extern thread_local int g_last_linear_path;  // ndcn_debug_last_linear_path (linear.hip)
 extern thread_local int g_last_rk_bwd_path;  // ndcn_debug_last_rk_bwd_path (rk_bwd.hip)
+extern thread_local int g_last_spmm_path;    // ndcn_debug_last_spmm_path (spmm.hip)
 extern thread_local int g_last_rhs_path;     // ndcn_debug_last_rhs_path     // no launch timing while a stream is being captured
 int scaled_sumsq_f32(const float *a, const float *b, const float *y, float rtol, float atol, int64_t n, double *d_out,
                      void *d_ws, hipStream_t st);

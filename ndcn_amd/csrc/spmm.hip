@@ -23,6 +23,8 @@ constexpr int kSpmmThreads = 256;
 constexpr int kStageCap = 2048;     // staged non-zeros per workgroup (16 KiB of LDS -> 8 workgroups per CU)
 constexpr int kMaxRowsPerBlock = 256;
 
+thread_local int g_last_spmm_path = 0;
+
 template <int VW> struct VecT;
 template <> struct VecT<4> { using type = float4; };
 template <> struct VecT<1> { using type = float; };
@@ -356,6 +358,7 @@ static int launch_wide(const ndcn_csr *A, const float *X, const float *Xh, int64
     WideEpi e = {};
     if (epi) e = *epi;
     if (n_partials) *n_partials = (int)grid.x * 4;
+    g_last_spmm_path = NDCN_SPMM_WIDE | NDCN_SPMM_VEC | (Xh ? NDCN_SPMM_HALO : 0) | (NV << NDCN_SPMM_LANES_SHIFT) | (MODE << NDCN_SPMM_MODE_SHIFT);
     if (Xh)
         hipLaunchKernelGGL((spmm_wide_kernel<NV, true, MODE>), grid, block, 0, st, A->rowptr, A->colidx, A->val,
                            A->row_order, X, Xh, (int)n_own, Y, n_rows, alpha, relu, e);
@@ -411,6 +414,8 @@ static int launch_spmm(const ndcn_csr *A, const float *X, const float *Xh, int64
     const int nblk = (n_rows + rpb - 1) / rpb;
     if (nblk == 0) return NDCN_OK;
     const int relu = (flags & NDCN_F_RELU) ? 1 : 0;
+    g_last_spmm_path = NDCN_SPMM_CSR | (VW == 4 ? NDCN_SPMM_VEC : 0) | (Xh ? NDCN_SPMM_HALO : 0) | (LPR << NDCN_SPMM_LANES_SHIFT) |
+                       (rpb << NDCN_SPMM_RPB_SHIFT);
     if (Xh)
         hipLaunchKernelGGL((spmm_csr_kernel<VW, LPR, true>), dim3(nblk), dim3(kSpmmThreads), 0, st, A->rowptr,
                            A->colidx, A->val, X, Xh, (int)n_own, Y, n_rows, H, alpha, relu, rpb);
@@ -456,7 +461,9 @@ int spmm_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, 
         ndcn_csr light = {};
         light.n_rows = A->n_rows; light.n_cols = A->n_cols + A->hub_n; light.nnz = A->lt_nnz;
         light.rowptr = A->lt_rowptr; light.colidx = A->lt_colidx; light.val = A->lt_val;
-        return spmm_f32(&light, X, A->hub_S, A->n_cols, Y, H, alpha, flags, st);
+        rc = spmm_f32(&light, X, A->hub_S, A->n_cols, Y, H, alpha, flags, st);
+        if (rc == NDCN_OK) g_last_spmm_path |= NDCN_SPMM_HUB;
+        return rc;
     }
     if (vec && spmm_rec_supported(A, H) && A->n_rows * (int64_t)1024 < (1ll << 32))     // operator carries a group-record plan
         return spmm_rec_f32(A, X, Xh, n_own, Y, alpha, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr,

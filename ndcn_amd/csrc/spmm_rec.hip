@@ -423,6 +423,8 @@ int spmm_rec_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_o
     double bytes = 8.0 * A->nnz + 4.0 * (A->n_rows + 1) + 4.0 * 256 * (double)(A->n_rows + A->n_cols);
     if (mode != REC_PLAIN) bytes += P * (n_prev + 2 + (e.y_aux ? 1 : 0));
     ProfScope prof(mode == REC_PLAIN ? PROF_SPMM : PROF_RHS_FUSED, st, bytes, 2.0 * A->nnz * 256);
+    const int shape = A->rec_rows == 8 && A->rec_cap == 48 ? 3 : A->rec_rows == 8 ? 1 : 2;
+    g_last_spmm_path = NDCN_SPMM_REC | NDCN_SPMM_VEC | (Xh ? NDCN_SPMM_HALO : 0) | (shape << NDCN_SPMM_REC_SHIFT) | (mode << NDCN_SPMM_MODE_SHIFT);
     dim3 grid;
     int rc;
     if (A->rec_rows == 8 && A->rec_cap == 48) rc = launch_rec<8, 48, 2>(a, e, mode, Xh != nullptr, st, grid);

@@ -236,6 +236,7 @@ int spmm_sweep_f32(const ndcn_csr *A, const float *X, float *Y, hipStream_t st) 
     if (A->n_rows == 0) return NDCN_OK;
     const int logb = A->sweep_logb, window = A->sweep_window;
     ProfScope prof(PROF_SPMM, st, 8.0 * A->nnz + 4.0 * (A->n_rows + 1) + 4.0 * 256 * (double)(A->n_rows + A->n_cols), 2.0 * A->nnz * 256);
+    g_last_spmm_path = NDCN_SPMM_SWEEP | NDCN_SPMM_VEC;
     for (int p = 0; p < A->sweep_passes; ++p) {
         SweepArgs a;
         a.X = X;
