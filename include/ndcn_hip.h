@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 21
+#define NDCN_ABI_VERSION 22
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -468,6 +468,22 @@ NDCN_API int ndcn_interp_eval_f32(const float *a, const float *b, const float *c
 NDCN_API int ndcn_fixed_stage_f32(int op, float *out, const float *y, const float *k1, const float *k2,
                          const float *k3, const float *k4, float dt, int64_t n_elem, void *stream);
 
+/* The ticks a step of a SUB-STEPPED fixed grid reports (options={'step_size': h}: solvers.py:55-68 builds the grid, :79-108 reports).
+ * After the step [t0, t1] the reference hands out every tick t with t1 >= t - and, because it has overwritten y0 with y1 before
+ * calling `_linear_interp` (:93-96), the "interpolated" value is
+ *     out_q = y1 + ((y1 - y1) / (t1 - t0)) * (t_q - t0)            three roundings, no contraction
+ * i.e. the state at the END of the step with -0.0 turned into +0.0 and Inf into NaN, while a tick that equals t1 (or t0) returns
+ * y1 itself (:102-105): a plain copy.  One pass reads y once and writes <= 8 tick panels per launch (any n_ticks: a launch per 8).
+ *   dt = t1 - t0, h_tick_dt[q] = t_q - t0 (HOST arrays, formed in the state dtype), h_coincident[q] != 0: plain copy,
+ *   h_out: HOST array of n_ticks device panels, none of them y.
+ * ndcn_fixed_stage_emit_f32: ndcn_fixed_stage_f32 op 0 or op 5 - the stage that ENDS a step - writing the new state to `out`
+ * (may alias y) and the step's ticks in the same pass, so that an emitting step does not read y1 again.                      */
+NDCN_API int ndcn_tick_emit_f32(const float *y, float dt, const float *h_tick_dt, const int *h_coincident, float *const *h_out,
+                                int n_ticks, int64_t n_elem, void *stream);
+NDCN_API int ndcn_fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3,
+                                       const float *k4, float dt, const float *h_tick_dt, const int *h_coincident,
+                                       float *const *h_out, int n_ticks, int64_t n_elem, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Truth dynamics of the three drivers on an N x 1 state, O(nnz).
  *   heat   : ndcn_spmm_f32 with H = 1, alpha = -k on L                    heat_dynamics.py:197-204
@@ -592,6 +608,16 @@ NDCN_API int ndcn_solver_advance(ndcn_solver *s, double next_t, float *out, int6
  * steps: heat_dynamics.py:35,123; dgnn.py:173-182); same arithmetic per element as ndcn_solver_advance.  Fixed grid:
  * one step per tick.                                                                                     */
 NDCN_API int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, void *stream);
+/* Fixed grid only (NDCN_EINVAL for dopri5 and for a sharded solver): FixedGridODESolver.integrate with the step_size option
+ * (solvers.py:55-68,79-108) from the solver's current time.  h_grid (HOST, fp32, n_grid points, h_grid[0] = the current time in the
+ * state dtype) is the solver's own grid; every one of its n_grid - 1 steps runs with the state INSIDE the solver - eager: the launches
+ * of ndcn_solver_advance; replay mode: one replay of the captured step per grid step, its size through the pinned ring - and tick j
+ * (h_tick_time[j], fp32; h_tick_step non-decreasing) is written to out[j] after step h_tick_step[j]: as the new state itself when
+ * the tick equals an end of that step, else through the expression of ndcn_tick_emit_f32.  Device memory: the workspace plus the
+ * n_ticks output panels, whatever n_grid is.  States that fit one compute unit run as one launch per 128 steps
+ * (ndcn_solve_small_grid_f32).  Bit-identical to ndcn_solver_advance_many over all of h_grid, taken at the emitting steps.        */
+NDCN_API int ndcn_solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step,
+                                      const float *h_tick_time, int64_t n_ticks, float *out, void *stream);
 /* h_stats = {steps attempted, steps accepted, rhs evaluations, t1, dt_next, last mean_sq_error_ratio} */
 NDCN_API int ndcn_solver_stats(const ndcn_solver *s, double h_stats[6]);
 /* Copies up to `cap` rows {t0, dt, accepted, ratio, dt_next} of the per-attempt log; returns the count. */
@@ -617,6 +643,16 @@ NDCN_API int ndcn_solve_small_f32(const ndcn_csr *A, const float *W, const float
 NDCN_API int ndcn_solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *A_t, const float *W, const float *b, int H, uint32_t flags,
                                       int method, const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks,
                                       float *g_y0, float *g_W, float *g_b, void *stream);
+/* The one-launch solve on a grid finer than the ticks (the step_size option, solvers.py:55-68,79-108): n_steps steps of sizes h_dt,
+ * still ONE launch per 128 steps, and only the ticks are written: tick j goes to out[j] after step h_tick_step[j] (HOST, non-
+ * decreasing) - the new state as it is when h_tick_same[j] != 0 (the tick is an end of the step; only the LAST tick of a step can
+ * be), else y1 + ((y1 - y1) / dt) * (t_j - t0) (ndcn_tick_emit_f32; its value does not depend on 0 < t_j - t0).  y_end (device,
+ * one panel, NULL allowed while n_steps <= 128) receives the state after the last step.  Same support as the plain solve
+ * (ndcn_solve_small_grid_supported); every emitted state is bit-identical to ndcn_solve_small_f32 on the same step sizes.          */
+NDCN_API int ndcn_solve_small_grid_supported(const ndcn_csr *A, int H, uint32_t flags, int method);
+NDCN_API int ndcn_solve_small_grid_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method,
+                                       const float *y0, const float *h_dt, int64_t n_steps, const int64_t *h_tick_step,
+                                       const int *h_tick_same, int64_t n_ticks, float *out, float *y_end, void *stream);
 /* Euler training with the evaluations' intermediates KEPT (the README commands' shape: H = 16 / 20, a symmetric operator whose view has
  * max_row_len and symmetric filled - ndcn_solve_small_keep_supported says whether both launches take the form): the forward launch also
  * writes, per step, S_i = A y_i and K_i = f(y_i) into `keep` (n_ticks x 2 panels); the reverse sweep reads them instead of re-forming

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
@@ -182,6 +182,9 @@ SIGNATURES = {
     'ndcn_rhs_rk_xadd_f32': (_I, [_CSR, _P, _P, _F, _P, _P, _P, _P, _I, _U, _P, _P, ctypes.POINTER(_F), _P, _P]),
     'ndcn_solve_small_supported': (_I, [_CSR, _I, _U, _I, _I]),
     'ndcn_solve_small_f32': (_I, [_CSR, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_F), _L, _P, _P]),
+    'ndcn_solve_small_grid_supported': (_I, [_CSR, _I, _U, _I]),
+    'ndcn_solve_small_grid_f32': (_I, [_CSR, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I), _L, _P,
+                                       _P, _P]),
     'ndcn_solve_small_bwd_f32': (_I, [_CSR, _CSR, _P, _P, _I, _U, _I, _P, _P, ctypes.POINTER(_F), _L, _P, _P, _P, _P]),
     'ndcn_gather_rows_f32': (_I, [_P, _P, _L, _I, _P, _P]),
     'ndcn_rk_combine_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _L, _P]),
@@ -192,6 +195,8 @@ SIGNATURES = {
     'ndcn_dopri5_interp_direct_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _F, ctypes.POINTER(_F), _P, _L, _P]),
     'ndcn_interp_eval_f32': (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(_F), _P, _L, _P]),
     'ndcn_fixed_stage_f32': (_I, [_I, _P, _P, _P, _P, _P, _P, _F, _L, _P]),
+    'ndcn_tick_emit_f32': (_I, [_P, _F, ctypes.POINTER(_F), ctypes.POINTER(_I), ctypes.POINTER(_P), _I, _L, _P]),
+    'ndcn_fixed_stage_emit_f32': (_I, [_I, _P, _P, _P, _P, _P, _P, _F, ctypes.POINTER(_F), ctypes.POINTER(_I), ctypes.POINTER(_P), _I, _L, _P]),
     'ndcn_row_l1_normalize_f32': (_I, [_P, _P, _L, _I, _P]),
     'ndcn_row_l1_normalize_bwd_f32': (_I, [_P, _P, _P, _L, _I, _P]),
     'ndcn_gene_rhs_f32': (_I, [_CSR, _P, _P, _F, _F, _F, _P]),
@@ -212,6 +217,7 @@ SIGNATURES = {
     'ndcn_solver_begin_borrowed': (_I, [_P, _P, _D, _P]),
     'ndcn_solver_advance': (_I, [_P, _D, _P, _L, _P]),
     'ndcn_solver_advance_many': (_I, [_P, ctypes.POINTER(_D), _L, _P, _P]),
+    'ndcn_solver_advance_grid': (_I, [_P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_F), _L, _P, _P]),
     'ndcn_solver_stats': (_I, [_P, ctypes.POINTER(_D)]),
     'ndcn_solver_steplog': (_L, [_P, ctypes.POINTER(_D), _L]),
     'ndcn_prof_enable': (_I, [_I]),

@@ -115,6 +115,20 @@ class _LinMap(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+class _TickEmit(torch.autograd.Function):
+    """forward = ndcn_tick_emit_f32 (one pass, all ticks of the step); backward = the sum of the ticks' gradients (identity VJP each)"""
+
+    @staticmethod
+    def forward(ctx, y, dt, tms):
+        return tuple(hip.tick_emit(y.detach(), dt, tms))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        gs = [g.contiguous() for g in gs]
+        g = gs[0] if len(gs) == 1 else hip.lincomb(gs, [1.0] * len(gs))
+        return g, None, None
+
+
 # fixed_stage op -> weights of (y, k1, k2, k3, k4) as functions of dt (the formulas in include/ndcn_hip.h)
 _STAGE_W = {
     0: lambda dt: (1, dt),
@@ -145,6 +159,12 @@ class AutogradOps:
         w = _STAGE_W[op](float(dt))
         ins = [t for t in (y, k1, k2, k3, k4) if t is not None][:len(w)]
         return _LinMap.apply(lambda yy, *k: hip.fixed_stage(op, yy, *k, dt=dt), w, *ins)
+
+    @staticmethod
+    def tick_emit(y, dt, tms, outs=None):
+        # y + ((y - y) / dt) * tm: the derivative with respect to y is 1 wherever the state is finite (the slope term is a constant
+        # zero there), so every tick hands its gradient to the state that ended the step, unchanged
+        return list(_TickEmit.apply(y, dt, tuple(tms)))
 
     @staticmethod
     def error(y0, y1, ks, cs, rtol, atol):

@@ -92,6 +92,20 @@ int ndcn_solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int 
     return solve_small_f32(A, W, b, H, flags, method, y0, h_dt, n_ticks, out, ST(stream));
 }
 
+int ndcn_solve_small_grid_supported(const ndcn_csr *A, int H, uint32_t flags, int method) {
+    return A ? solve_small_supported(A, H, flags, method) : 0;
+}
+
+int ndcn_solve_small_grid_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
+                              const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, int64_t n_ticks,
+                              float *out, float *y_end, void *stream) {
+    NDCN_CHECK_ARG(A && y0 && n_steps >= 0 && n_ticks >= 0 && (n_steps == 0 || h_dt), "null argument");
+    NDCN_CHECK_ARG(n_ticks == 0 || (h_tick_step && h_tick_same && out), "null tick table");
+    NDCN_CHECK_ARG((flags & NDCN_F_NO_CONTROL) || W, "weight missing");
+    if (!(flags & NDCN_F_NO_GRAPH)) { int rc = check_csr(A, __func__); if (rc) return rc; }
+    return solve_small_grid_f32(A, W, b, H, flags, method, y0, h_dt, n_steps, h_tick_step, h_tick_same, n_ticks, out, y_end, ST(stream));
+}
+
 int ndcn_solve_small_keep_supported(const ndcn_csr *A, int H, uint32_t flags) { return A ? solve_small_keep_supported(A, H, flags) : 0; }
 
 int ndcn_solve_small_keep_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
@@ -395,6 +409,22 @@ int ndcn_fixed_stage_f32(int op, float *out, const float *y, const float *k1, co
     return fixed_stage_f32(op, out, y, k1, k2, k3, k4, dt, n_elem, ST(stream));
 }
 
+int ndcn_tick_emit_f32(const float *y, float dt, const float *h_tick_dt, const int *h_coincident, float *const *h_out, int n_ticks,
+                       int64_t n_elem, void *stream) {
+    NDCN_CHECK_ARG(n_elem >= 0 && n_ticks >= 0, "bad size");
+    NDCN_CHECK_ARG(n_ticks == 0 || (y && h_tick_dt && h_coincident && h_out), "null argument");
+    for (int q = 0; q < n_ticks; ++q) NDCN_CHECK_ARG(h_out[q] && h_out[q] != y, "a tick panel is null or aliases the state");
+    return tick_emit_f32(y, dt, h_tick_dt, h_coincident, h_out, n_ticks, n_elem, ST(stream));
+}
+
+int ndcn_fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3, const float *k4,
+                              float dt, const float *h_tick_dt, const int *h_coincident, float *const *h_out, int n_ticks,
+                              int64_t n_elem, void *stream) {
+    NDCN_CHECK_ARG(n_elem >= 0, "bad size");
+    NDCN_CHECK_ARG(out && y, "null panel");
+    return fixed_stage_emit_f32(op, out, y, k1, k2, k3, k4, dt, h_tick_dt, h_coincident, h_out, n_ticks, n_elem, ST(stream));
+}
+
 int ndcn_row_l1_normalize_f32(const float *X, float *Y, int64_t n_rows, int H, void *stream) {
     NDCN_CHECK_ARG(n_rows >= 0 && H >= 0, "negative size");
     NDCN_CHECK_ARG(n_rows == 0 || H == 0 || (X && Y), "null panel");
@@ -430,6 +460,10 @@ int ndcn_solver_advance(ndcn_solver *s, double next_t, float *out, int64_t step_
 }
 int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, void *stream) {
     return solver_advance_many(s, h_ticks, n_ticks, out, ST(stream));
+}
+int ndcn_solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step, const float *h_tick_time,
+                             int64_t n_ticks, float *out, void *stream) {
+    return solver_advance_grid(s, h_grid, n_grid, h_tick_step, h_tick_time, n_ticks, out, ST(stream));
 }
 int ndcn_solver_stats(const ndcn_solver *s, double h_stats[6]) { return solver_stats(s, h_stats); }
 int64_t ndcn_solver_steplog(const ndcn_solver *s, double *h_rows, int64_t cap) { return solver_steplog(s, h_rows, cap); }

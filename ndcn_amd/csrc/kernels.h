@@ -107,6 +107,11 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
 int solve_small_supported(const ndcn_csr *A, int H, uint32_t flags, int method);
 int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
                     const float *h_dt, int64_t n_ticks, float *out, hipStream_t st, float *keep = nullptr);
+// ... on a grid finer than the ticks: n_steps steps, tick j (n_ticks of them, h_tick_step non-decreasing) is written after step
+// h_tick_step[j] - as it is (h_tick_same[j]) or through the reference's expression; y_end (nullable while n_steps <= one chunk): the last state
+int solve_small_grid_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
+                         const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, int64_t n_ticks,
+                         float *out, float *y_end, hipStream_t st);
 int solve_small_keep_supported(const ndcn_csr *A, int H, uint32_t flags);
 int solve_small_bwd_supported(const ndcn_csr *A, int H, uint32_t flags, int method);
 int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, int method,
@@ -166,6 +171,11 @@ int interp_eval_f32(const float *a, const float *b, const float *c, const float 
                     float *out, int64_t n, hipStream_t st);
 int fixed_stage_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3,
                     const float *k4, float dt, int64_t n, hipStream_t st, const float *dt_dev = nullptr);
+// the ticks a sub-stepped fixed-grid step reports (solvers.py:92-108): h_tm[q] = t_q - t0, h_same[q] != 0: the tick is an end of the
+// step (a plain copy); any nt (kMaxTicks = 8 panels per launch).  fixed_stage_emit: op 0 / 5 writing the new state and the ticks at once
+int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st);
+int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3, const float *k4,
+                         float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st);
 
 int row_l1_normalize_f32(const float *X, float *Y, int64_t n_rows, int H, hipStream_t st);
 int row_l1_normalize_bwd_f32(const float *G, const float *X, float *GX, int64_t n_rows, int H, hipStream_t st);
@@ -187,6 +197,8 @@ int solver_destroy(ndcn_solver *s);
 int solver_begin(ndcn_solver *s, const float *y0, double t0, hipStream_t st, bool borrow = false);
 int solver_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st);
 int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, hipStream_t st);
+int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step, const float *h_tick_time,
+                        int64_t n_ticks, float *out, hipStream_t st);
 int solver_stats(const ndcn_solver *s, double h[6]);
 int64_t solver_steplog(const ndcn_solver *s, double *rows, int64_t cap);
 

@@ -591,6 +591,74 @@ __global__ __launch_bounds__(256) void copy_kernel(float *__restrict__ dst, cons
     for (int64_t j = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += stride) dst[j] = src[j];
 }
 
+// -------------------------------------------------------------------------------- ticks of a sub-stepped fixed grid
+// solvers.py:92-108 with options={'step_size': h}: after a step [t0, t1] every tick t with t1 >= t is reported, and because y0 was
+// overwritten with y1 before `_linear_interp` is called the "interpolation" is y1 + ((y1 - y1) / (t1 - t0)) * (t - t0) - the state at
+// the END of the step with -0.0 turned into +0.0 and Inf into NaN - while a tick that equals t1 (or t0) is y1 itself.  One pass reads
+// y1 once and writes up to kMaxTicks tick panels (the batching of interp_direct_multi); FP contraction is off in this file, so the
+// expression keeps its three roundings.
+struct EmitArgs {
+    float *out[kMaxTicks];
+    float tm[kMaxTicks];            // t - t0 in the state dtype
+    unsigned same;                  // bit q: tick q coincides with an end of the step - a plain copy
+    int nt;
+    float dt;                       // t1 - t0
+};
+
+__device__ __forceinline__ float emit1(float v, float dt, float tm) { return v + ((v - v) / dt) * tm; }
+
+__device__ __forceinline__ void emit_store4(const EmitArgs &e, int64_t i, const float4 v) {
+#pragma unroll
+    for (int q = 0; q < kMaxTicks; ++q)
+        if (q < e.nt) {
+            const bool same = (e.same >> q) & 1u;
+            cp_f32x4 o;
+            o.x = same ? v.x : emit1(v.x, e.dt, e.tm[q]);
+            o.y = same ? v.y : emit1(v.y, e.dt, e.tm[q]);
+            o.z = same ? v.z : emit1(v.z, e.dt, e.tm[q]);
+            o.w = same ? v.w : emit1(v.w, e.dt, e.tm[q]);
+            __builtin_nontemporal_store(o, reinterpret_cast<cp_f32x4 *>(e.out[q]) + i);
+        }
+}
+__device__ __forceinline__ void emit_store1(const EmitArgs &e, int64_t i, const float v) {
+#pragma unroll
+    for (int q = 0; q < kMaxTicks; ++q)
+        if (q < e.nt) __builtin_nontemporal_store(((e.same >> q) & 1u) ? v : emit1(v, e.dt, e.tm[q]), e.out[q] + i);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void tick_emit_kernel(const float *__restrict__ y, EmitArgs e, int64_t n_items) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * blockDim.x) {
+        if (VEC) emit_store4(e, i, ld4(y, i));
+        else emit_store1(e, i, y[i]);
+    }
+}
+
+// the final stage of a step (op 0: Euler / midpoint update, op 5: RK4 update) that writes the new state AND the step's ticks in the
+// same pass: an emitting step does not read y1 again.  The state's arithmetic is fixed_stage_kernel's.
+template <int OP, bool VEC>
+__global__ __launch_bounds__(256) void fixed_stage_emit_kernel(float *out, const float *y, const float *k1, const float *k2,
+                                                               const float *k3, const float *k4, EmitArgs e, int64_t n_items) {
+    const float dt = e.dt;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * blockDim.x) {
+        if (VEC) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 yv = ld4(y, i), a = ld4(k1, i);
+            const float4 b = (OP >= 3) ? ld4(k2, i) : z;
+            const float4 c = (OP >= 4) ? ld4(k3, i) : z;
+            const float4 d = (OP >= 5) ? ld4(k4, i) : z;
+            const float4 v = make_float4(stage1<OP>(yv.x, a.x, b.x, c.x, d.x, dt), stage1<OP>(yv.y, a.y, b.y, c.y, d.y, dt),
+                                         stage1<OP>(yv.z, a.z, b.z, c.z, d.z, dt), stage1<OP>(yv.w, a.w, b.w, c.w, d.w, dt));
+            st4(out, i, v);
+            emit_store4(e, i, v);
+        } else {
+            const float v = stage1<OP>(y[i], k1[i], OP >= 3 ? k2[i] : 0.f, OP >= 4 ? k3[i] : 0.f, OP >= 5 ? k4[i] : 0.f, dt);
+            out[i] = v;
+            emit_store1(e, i, v);
+        }
+    }
+}
+
 int copy_f32(float *dst, const float *src, int64_t n, hipStream_t st) {
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_STAGE, st, 8.0 * n, 0.0);
@@ -877,6 +945,71 @@ int fixed_stage_f32(int op, float *out, const float *y, const float *k1, const f
         default: set_error("fixed_stage: unknown op %d", op); return NDCN_EINVAL;
     }
     NDCN_LAUNCH_CHECK();
+    return NDCN_OK;
+}
+
+// fills e from the host tables of ONE launch (nt <= kMaxTicks); vec: cleared when a tick panel is not 16-byte aligned
+static bool fill_emit(EmitArgs &e, float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, bool &vec) {
+    if (nt < 1 || nt > kMaxTicks) return false;
+    e.nt = nt;
+    e.dt = dt;
+    e.same = 0;
+    for (int q = 0; q < kMaxTicks; ++q) {
+        const int u = q < nt ? q : 0;
+        if (!h_out[u]) return false;
+        e.out[q] = h_out[u];
+        e.tm[q] = h_tm[u];
+        if (q < nt && h_same[u]) e.same |= 1u << q;
+        vec = vec && aligned16(h_out[u]);
+    }
+    return true;
+}
+
+int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st) {
+    if (nt < 0 || (nt > 0 && (!y || !h_tm || !h_same || !h_out))) { set_error("tick_emit: null argument"); return NDCN_EINVAL; }
+    for (int lo = 0; lo < nt; lo += kMaxTicks) {                // more than kMaxTicks ticks in one step: one launch per kMaxTicks
+        const int m = nt - lo < kMaxTicks ? nt - lo : kMaxTicks;
+        EmitArgs e;
+        bool vec = (n % 4 == 0) && aligned16(y);
+        if (!fill_emit(e, dt, h_tm + lo, h_same + lo, h_out + lo, m, vec)) { set_error("tick_emit: null tick panel"); return NDCN_EINVAL; }
+        if (n == 0) continue;
+        ProfScope prof(PROF_STAGE, st, 4.0 * n * (1 + m), 3.0 * n * m);
+        if (vec) hipLaunchKernelGGL((tick_emit_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, y, e, n / 4);
+        else hipLaunchKernelGGL((tick_emit_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, y, e, n);
+        NDCN_LAUNCH_CHECK();
+    }
+    return NDCN_OK;
+}
+
+int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3, const float *k4,
+                         float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st) {
+    if (op != 0 && op != 5) { set_error("fixed_stage_emit: op %d does not end a step (0 or 5)", op); return NDCN_EINVAL; }
+    if (nt < 1 || !h_tm || !h_same || !h_out) { set_error("fixed_stage_emit: needs at least one tick"); return NDCN_EINVAL; }
+    const int need = op == 0 ? 1 : 4;
+    const float *ks[4] = {k1, k2, k3, k4};
+    bool vec = (n % 4 == 0) && aligned16(out) && aligned16(y);
+    for (int j = 0; j < need; ++j) {
+        if (!ks[j]) { set_error("fixed_stage_emit: op %d needs %d stage pointers", op, need); return NDCN_EINVAL; }
+        vec = vec && aligned16(ks[j]);
+    }
+    if (!out || !y) { set_error("fixed_stage_emit: null state"); return NDCN_EINVAL; }
+    const int m = nt < kMaxTicks ? nt : kMaxTicks;              // the first kMaxTicks ticks ride along; the rest read the new state
+    for (int q = 0; q < m; ++q)
+        if (h_out[q] == out || h_out[q] == y) { set_error("fixed_stage_emit: a tick panel aliases the state"); return NDCN_EINVAL; }
+    EmitArgs e;
+    if (!fill_emit(e, dt, h_tm, h_same, h_out, m, vec)) { set_error("fixed_stage_emit: null tick panel"); return NDCN_EINVAL; }
+    if (n > 0) {
+        ProfScope prof(PROF_STAGE, st, 4.0 * n * (need + 2 + m), 2.0 * n * need + 3.0 * n * m);
+        if (op == 0) {
+            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<0, true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
+            else hipLaunchKernelGGL((fixed_stage_emit_kernel<0, false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
+        } else {
+            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<5, true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
+            else hipLaunchKernelGGL((fixed_stage_emit_kernel<5, false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
+        }
+        NDCN_LAUNCH_CHECK();
+    }
+    if (nt > m) return tick_emit_f32(out, dt, h_tm + m, h_same + m, h_out + m, nt - m, n, st);
     return NDCN_OK;
 }
 

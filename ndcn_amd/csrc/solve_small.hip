@@ -73,6 +73,12 @@ struct SolveArgs {
     long long *dbg;                  // NDCN_SS_DEBUG=1: {shader cycles total, in evaluations, in stage updates, 100 MHz ticks total}
     float *keep;                     // nullable (Euler, fast path): [n_ticks][2][n] - S = A y_i and K_i = f(y_i) of every step, for the reverse sweep
     float dt[kChunk];
+    // a grid finer than the ticks (GRID kernels; solve_small_grid_f32): step i of this launch writes its state to the out slots
+    // emit_first[i] .. + (emit_cnt[i] & 0x7fff) - the last of them as it is when bit 15 is set, the others through the reference's
+    // expression - and the launch leaves its last state in y_end
+    int emit_first[kChunk];
+    unsigned short emit_cnt[kChunk];
+    float *y_end;
 };
 
 struct Lds {
@@ -210,7 +216,7 @@ inline size_t lds_bytes_fast(int64_t n_elem, int64_t n_rows, int64_t width, int 
 }
 
 // METHOD: NDCN_M_EULER / MIDPOINT / RK4.  MAXIT: passes a wave makes over its rows (register arrays are indexed by pass)
-template <int METHOD, int MAXIT, bool CSR_LDS, int HT, bool KEEP = false>
+template <int METHOD, int MAXIT, bool CSR_LDS, int HT, bool KEEP = false, bool GRID = false>
 __global__ __launch_bounds__(1024) void solve_small_kernel(SolveArgs a) {
     extern __shared__ float lds_raw[];
     const int H = HT ? HT : a.H, n_elem = a.n_rows * H;
@@ -298,7 +304,19 @@ __global__ __launch_bounds__(1024) void solve_small_kernel(SolveArgs a) {
         if (lane_on && r < a.n_rows) {                                                                         \
             const float v_ = (expr);                                                                           \
             l.T[r * H + o] = v_;                                                                               \
-            if (also_out) { y[it] = v_; a.out[(size_t)tick * n_elem + r * H + o] = v_; }                       \
+            if (also_out) {                                                                                    \
+                y[it] = v_;                                                                                    \
+                if (!GRID) a.out[(size_t)tick * n_elem + r * H + o] = v_;                                      \
+                else {                                                                                         \
+                    /* solvers.py:92-108 (y0 already overwritten with y1): y1 + ((y1 - y1) / (t1 - t0)) * (t - t0); with 0 < t - t0 */ \
+                    /* the value does not depend on t - t0 (the slope is +0 or NaN), so the step size stands in for it             */ \
+                    const int cnt_ = a.emit_cnt[tick] & 0x7fff, same_ = a.emit_cnt[tick] >> 15;                \
+                    float *o_ = a.out + (size_t)a.emit_first[tick] * n_elem + r * H + o;                       \
+                    const float w_ = v_ + ((v_ - v_) / dt) * dt;                                               \
+                    for (int e_ = 0; e_ < cnt_; ++e_) o_[(size_t)e_ * n_elem] = (same_ && e_ == cnt_ - 1) ? v_ : w_; \
+                    if (tick == a.n_ticks - 1 && a.y_end) a.y_end[r * H + o] = v_;                             \
+                }                                                                                              \
+            }                                                                                                  \
         }                                                                                                      \
     }                                                                                                          \
     lds_barrier();
@@ -1045,8 +1063,15 @@ int solve_small_keep_supported(const ndcn_csr *A, int H, uint32_t flags) {
     return (int64_t)n_groups * (H * H + H) <= 3 * n_elem ? 1 : 0;
 }
 
-int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
-                    const float *h_dt, int64_t n_ticks, float *out, hipStream_t st, float *keep) {
+// per-step emission table of a grid solve (null: the plain solve - step i writes out[i])
+struct GridEmit {
+    const int *first;
+    const unsigned short *cnt;
+    float *y_end;
+};
+
+static int solve_small_impl(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
+                            const float *h_dt, int64_t n_ticks, float *out, hipStream_t st, float *keep, const GridEmit *grid) {
     if (!solve_small_supported(A, H, flags, method)) { set_error("solve_small: unsupported shape"); return NDCN_EINVAL; }
     if (keep && (method != NDCN_M_EULER || !solve_small_keep_supported(A, H, flags))) { set_error("solve_small: nothing keeps S / K for this shape (ndcn_solve_small_keep_supported)"); return NDCN_EINVAL; }
     const int64_t n_elem = A->n_rows * (int64_t)H;
@@ -1067,7 +1092,8 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
     for (int64_t done = 0; done < n_ticks; done += kChunk) {
         SolveArgs a;
         a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val; a.W = W; a.bias = b; a.y0 = start;
-        a.out = out + done * n_elem;
+        a.out = grid ? out : out + done * n_elem;
+        a.y_end = grid ? grid->y_end : nullptr;
         a.n_rows = (int)A->n_rows; a.H = H; a.nnz = (int)nnz;
         a.n_ticks = (int)std::min<int64_t>(kChunk, n_ticks - done);
         a.relu = (flags & NDCN_F_RELU) ? 1 : 0; a.no_graph = no_graph ? 1 : 0; a.no_control = (flags & NDCN_F_NO_CONTROL) ? 1 : 0;
@@ -1075,6 +1101,10 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
         a.width = width;
         a.keep = keep ? keep + (size_t)done * 2 * n_elem : nullptr;
         for (int i = 0; i < a.n_ticks; ++i) a.dt[i] = h_dt[done + i];
+        for (int i = 0; i < a.n_ticks; ++i) {
+            a.emit_first[i] = grid ? grid->first[done + i] : 0;
+            a.emit_cnt[i] = grid ? grid->cnt[done + i] : 0;
+        }
         static const bool dbg_on = env_int("NDCN_SS_DEBUG", 0) == 1;
         static long long *dbg_buf = nullptr;
         if (dbg_on && !dbg_buf) NDCN_HIP(hipMalloc(&dbg_buf, 4 * sizeof(long long)));
@@ -1100,7 +1130,27 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
             else if (method == NDCN_M_MIDPOINT) NDCN_GO_IT(NDCN_M_MIDPOINT, C_, HT_);          \
             else NDCN_GO_IT(NDCN_M_RK4, C_, HT_);                                              \
         } while (0)
-        if (fast && a.keep) {                                 // Euler with S / K kept for the reverse sweep
+        if (grid) {
+#define NDCN_GGO(M_, IT_, C_, HT_)                                                             \
+            do {                                                                               \
+                auto kern = solve_small_kernel<M_, IT_, C_, HT_, false, true>;                 \
+                static std::atomic<unsigned long long> cap_seen{0};                            \
+                if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
+                hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a);                     \
+            } while (0)
+#define NDCN_GGO_M(C_, HT_)                                                                    \
+            do {                                                                               \
+                if (method == NDCN_M_EULER) { if (np <= 4) NDCN_GGO(NDCN_M_EULER, 4, C_, HT_); else NDCN_GGO(NDCN_M_EULER, 12, C_, HT_); } \
+                else if (method == NDCN_M_MIDPOINT) { if (np <= 4) NDCN_GGO(NDCN_M_MIDPOINT, 4, C_, HT_); else NDCN_GGO(NDCN_M_MIDPOINT, 12, C_, HT_); } \
+                else { if (np <= 4) NDCN_GGO(NDCN_M_RK4, 4, C_, HT_); else NDCN_GGO(NDCN_M_RK4, 12, C_, HT_); } \
+            } while (0)
+            if (fast && H == 20) NDCN_GGO_M(true, 20);
+            else if (fast) NDCN_GGO_M(true, 16);
+            else if (csr) NDCN_GGO_M(true, 0);
+            else NDCN_GGO_M(false, 0);
+#undef NDCN_GGO_M
+#undef NDCN_GGO
+        } else if (fast && a.keep) {                          // Euler with S / K kept for the reverse sweep
 #define NDCN_KGO(IT_, HT_)                                                                     \
             do {                                                                               \
                 auto kern = solve_small_kernel<NDCN_M_EULER, IT_, true, HT_, true>;            \
@@ -1125,9 +1175,35 @@ int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, ui
             fprintf(stderr, "[solve_small] %d ticks: %lld shader cycles (eval %lld, update %lld), %.1f us by the 100 MHz clock -> %.0f MHz\n",
                     a.n_ticks, h[0], h[1], h[2], h[3] / 100.0, h[3] ? 100.0 * h[0] / h[3] : 0.0);
         }
-        start = a.out + (size_t)(a.n_ticks - 1) * n_elem;
+        start = grid ? grid->y_end : a.out + (size_t)(a.n_ticks - 1) * n_elem;
     }
     return NDCN_OK;
+}
+
+int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
+                    const float *h_dt, int64_t n_ticks, float *out, hipStream_t st, float *keep) {
+    return solve_small_impl(A, W, b, H, flags, method, y0, h_dt, n_ticks, out, st, keep, nullptr);
+}
+
+int solve_small_grid_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
+                         const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, int64_t n_ticks,
+                         float *out, float *y_end, hipStream_t st) {
+    if (n_steps > kChunk && !y_end) { set_error("solve_small_grid: more than %d steps need y_end to hand the state between launches", kChunk); return NDCN_EINVAL; }
+    std::vector<int> first((size_t)n_steps, 0);
+    std::vector<unsigned short> cnt((size_t)n_steps, 0);
+    int64_t prev = 0;
+    for (int64_t j = 0; j < n_ticks; ++j) {
+        const int64_t i = h_tick_step[j];
+        if (i < prev || i >= n_steps) { set_error("solve_small_grid: tick %lld names step %lld (non-decreasing, below %lld)", (long long)j, (long long)i, (long long)n_steps); return NDCN_EINVAL; }
+        if (cnt[(size_t)i] >> 15) { set_error("solve_small_grid: only the last tick of a step can coincide with its end"); return NDCN_EINVAL; }
+        if ((cnt[(size_t)i] & 0x7fff) == 0x7fff || j > 0x7fffffff) { set_error("solve_small_grid: too many ticks in one step"); return NDCN_EINVAL; }
+        if ((cnt[(size_t)i] & 0x7fff) == 0) first[(size_t)i] = (int)j;
+        cnt[(size_t)i] = (unsigned short)(cnt[(size_t)i] + 1);
+        if (h_tick_same[j]) cnt[(size_t)i] |= 0x8000;
+        prev = i;
+    }
+    const GridEmit g = {first.data(), cnt.data(), y_end};
+    return solve_small_impl(A, W, b, H, flags, method, y0, h_dt, n_steps, out, st, nullptr, &g);
 }
 
 int solve_small_bwd_supported(const ndcn_csr *A, int H, uint32_t flags, int method) {

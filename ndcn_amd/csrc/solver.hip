@@ -1051,7 +1051,18 @@ static int graph_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
     return NDCN_OK;
 }
 
-static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t st) {
+// the ticks one step of a sub-stepped grid reports (solver_advance_grid): tm[q] = t_q - t0, same[q]: the tick is an end of the step
+struct StepEmit {
+    const float *tm;
+    const int *same;
+    float *const *out;
+    int nt;
+};
+
+// emit (nullable): the stage that ends the step writes the new state AND these ticks in one pass (fixed_stage_emit_f32) where the
+// step ends in a stage kernel; `emitted` then says so - where it ends in a fused RHS epilogue the caller emits from the new state
+static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t st, const StepEmit *emit = nullptr, bool *emitted = nullptr) {
+    if (emitted) *emitted = false;
     if (s->graph_on) return graph_advance(s, next_t, out, st);
     // solvers.py:81-97 with grid == t: one step of size t1 - t0 formed in the state dtype
     const float t1 = (float)next_t;
@@ -1101,12 +1112,14 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
     if ((rc = rhs(s, s->ycur, s->k[0], st))) return rc;
     switch (s->d.method) {
         case NDCN_M_EULER:
-            rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
+            if (emit) rc = fixed_stage_emit_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
+            else rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
             break;
         case NDCN_M_MIDPOINT:
             if ((rc = fixed_stage_f32(1, s->ytmp, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st))) return rc;
             if ((rc = rhs(s, s->ytmp, s->k[0], st))) return rc;
-            rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
+            if (emit) rc = fixed_stage_emit_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
+            else rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
             break;
         default:  // rk4, 3/8 rule
             if ((rc = fixed_stage_f32(2, s->ytmp, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st))) return rc;
@@ -1115,10 +1128,12 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
             if ((rc = rhs(s, s->ytmp, s->k[2], st))) return rc;
             if ((rc = fixed_stage_f32(4, s->ytmp, s->ycur, s->k[0], s->k[1], s->k[2], nullptr, dt, n, st))) return rc;
             if ((rc = rhs(s, s->ytmp, s->k[3], st))) return rc;
-            rc = fixed_stage_f32(5, dst, s->ycur, s->k[0], s->k[1], s->k[2], s->k[3], dt, n, st);
+            if (emit) rc = fixed_stage_emit_f32(5, dst, s->ycur, s->k[0], s->k[1], s->k[2], s->k[3], dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
+            else rc = fixed_stage_f32(5, dst, s->ycur, s->k[0], s->k[1], s->k[2], s->k[3], dt, n, st);
             break;
     }
     if (rc) return rc;
+    if (emit && emitted) *emitted = true;
     s->ycur = dst;                 // the next step reads the state from where it was written
     s->cur_is_borrowed = (dst != s->ycur_own);
     s->tf = t1;
@@ -1284,6 +1299,84 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
             s->evals_in_step += nt;
             i += nt;
         }
+    }
+    return NDCN_OK;
+}
+
+// FixedGridODESolver.integrate with the step_size option (solvers.py:55-68,79-108): every step of h_grid with the state inside the
+// solver, the ticks written as the steps that report them end.  The step sizes are fixed_advance's own float32 differences, the
+// launches are its launches: bit-identical to solver_advance_many over all of h_grid.
+int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step, const float *h_tick_time,
+                        int64_t n_ticks, float *out, hipStream_t st) {
+    NDCN_CHECK_ARG(s && h_grid && n_grid >= 1 && n_ticks >= 0 && (n_ticks == 0 || (h_tick_step && h_tick_time && out)), "null argument");
+    if (!s->begun) { set_error("ndcn_solver_advance_grid before ndcn_solver_begin"); return NDCN_ESTATE; }
+    if (s->d.method == NDCN_M_DOPRI5 || s->sharded) { set_error("ndcn_solver_advance_grid: fixed-grid methods on an un-sharded solver only"); return NDCN_EINVAL; }
+    if (!(h_grid[0] == s->tf)) { set_error("ndcn_solver_advance_grid: the grid starts at %g, the solver stands at %g", h_grid[0], s->tf); return NDCN_EINVAL; }
+    if (overlaps_borrowed(s, out, n_ticks)) return NDCN_EINVAL;
+    const int64_t n_steps = n_grid - 1;
+    for (int64_t j = 0; j < n_ticks; ++j)
+        if (h_tick_step[j] < (j ? h_tick_step[j - 1] : 0) || h_tick_step[j] >= n_steps) {
+            set_error("ndcn_solver_advance_grid: tick %lld names step %lld (non-decreasing, below %lld)", (long long)j, (long long)h_tick_step[j], (long long)n_steps);
+            return NDCN_EINVAL;
+        }
+    const size_t stride = (size_t)s->n_elem;
+    const int per = s->d.method == NDCN_M_EULER ? 1 : s->d.method == NDCN_M_MIDPOINT ? 2 : 4;
+    std::vector<float> tm((size_t)n_ticks);
+    std::vector<int> same((size_t)n_ticks);
+    std::vector<float *> outs((size_t)n_ticks);
+    for (int64_t j = 0; j < n_ticks; ++j) {
+        const float t0 = h_grid[h_tick_step[j]], t1 = h_grid[h_tick_step[j] + 1], t = h_tick_time[j];
+        tm[(size_t)j] = t - t0;                               // solvers.py:108 in the state dtype
+        same[(size_t)j] = (t == t0 || t == t1) ? 1 : 0;       // solvers.py:102-105
+        outs[(size_t)j] = out + (size_t)j * stride;
+    }
+    if (n_steps == 0) return NDCN_OK;
+    // a state that fits one compute unit: the whole grid in one launch per 128 steps, only the ticks written (solve_small.hip)
+    if (solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+        std::vector<float> dts((size_t)n_steps);
+        for (int64_t i = 0; i < n_steps; ++i) dts[(size_t)i] = h_grid[i + 1] - h_grid[i];
+        int rc = solve_small_grid_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_steps,
+                                      h_tick_step, same.data(), n_ticks, out, s->ycur_own, st);
+        if (rc) return rc;
+        s->ycur = s->ycur_own;
+        s->cur_is_borrowed = false;
+        s->n_rhs += per * n_steps;
+        s->tf = h_grid[n_steps];
+        s->t0 = (double)h_grid[n_steps - 1];
+        s->t1 = (double)h_grid[n_steps];
+        s->n_attempt += n_steps;
+        s->n_accept += n_steps;
+        return NDCN_OK;
+    }
+    // an Euler step whose stage algebra rides in the RHS epilogue cannot update the panel it reads: with the state inside the solver
+    // such steps alternate between its own panel and a stage panel Euler leaves idle (the launches of a step that writes a tick)
+    const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
+    int64_t j = 0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        float *inside = (pingpong && s->ycur == s->ycur_own) ? s->ytmp2 : nullptr;
+        int64_t j1 = j;
+        while (j1 < n_ticks && h_tick_step[j1] == i) ++j1;
+        const int nt = (int)(j1 - j);
+        const double next_t = (double)h_grid[i + 1];
+        const float dt = h_grid[i + 1] - s->tf;
+        int rc;
+        if (nt == 0) {
+            rc = fixed_advance(s, next_t, inside, st);
+        } else if (!s->graph_on && nt == 1 && same[(size_t)j]) {
+            rc = fixed_advance(s, next_t, outs[(size_t)j], st);            // the tick IS the new state: written where the caller wants it
+        } else if (s->graph_on) {
+            // replay keeps the state in the solver's panel; the ticks are read from it on the replay stream
+            // (on the caller's stream, which has waited for the replay; the next replay waits for it in turn)
+            if ((rc = graph_advance(s, next_t, nullptr, st))) return rc;
+            rc = tick_emit_f32(s->ycur_own, dt, tm.data() + j, same.data() + j, outs.data() + j, nt, s->n_elem, st);
+        } else {
+            const StepEmit em = {tm.data() + j, same.data() + j, outs.data() + j, nt};
+            bool emitted = false;
+            if ((rc = fixed_advance(s, next_t, inside, st, &em, &emitted))) return rc;
+            if (!emitted) rc = tick_emit_f32(s->ycur, dt, em.tm, em.same, em.out, nt, s->n_elem, st);
+        }
+        if (rc) return rc;
+        j = j1;
     }
     return NDCN_OK;
 }

@@ -773,6 +773,24 @@ class HipOps:
                                                    ptr(ks[3]), float(dt), y.numel(), stream_ptr()))
         return out
 
+    @staticmethod
+    def tick_emit(y, dt, tms, outs=None):
+        """The ticks a sub-stepped fixed-grid step reports that are NOT an end of the step (solvers.py:92-108, y0 already overwritten
+        with y1): [y + ((y - y) / dt) * tm for tm in tms] - one pass over y per 8 ticks (ndcn_tick_emit_f32)."""
+        y = _panel(y)
+        nt = len(tms)
+        if outs is None:
+            outs = [torch.empty_like(y) for _ in range(nt)]
+        assert len(outs) == nt and all(o.is_contiguous() and o.numel() == y.numel() for o in outs)
+        if nt == 0:
+            return outs
+        arr_t = (_F * nt)(*[float(v) for v in tms])
+        arr_s = (ctypes.c_int * nt)(*([0] * nt))
+        arr_o = (_P * nt)(*[o.data_ptr() for o in outs])
+        with torch.cuda.device(y.device):
+            check(_lib.load().ndcn_tick_emit_f32(ptr(y), float(dt), arr_t, arr_s, arr_o, nt, y.numel(), stream_ptr()))
+        return outs
+
     # ---------------------------------------------------------------- truth dynamics (N x 1 state)
     @staticmethod
     def row_l1_normalize(X, out=None):

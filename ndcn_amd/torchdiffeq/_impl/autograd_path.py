@@ -26,7 +26,7 @@ from . import core
 f32 = np.float32
 
 
-def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False, step_log=None, odefunc=None):
+def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False, step_log=None, odefunc=None, plan=None):
     if method == 'dopri5':
         return integrate_dopri5_grad(func, y0, t, rtol, atol, autonomous=autonomous, step_log=step_log, odefunc=odefunc, **options)
     if method == 'adams':
@@ -34,9 +34,8 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False,
         # chose are constants of the graph (the reference's autograd also follows dt through the error ratios - a
         # deviation that is stated, not hidden: DESIGN section 2)
         return core.integrate_adams(autograd_ops, func, y0, t, rtol, atol, autonomous=autonomous, step_log=step_log, **options)
-    if options:
-        raise NotImplementedError('fixed-grid options %s: only the default grid (grid == t) is provided' % sorted(options))
-    return core.integrate_fixed(autograd_ops, func, y0, t, method, autonomous=autonomous)
+    # plan: the grid and tick placement of the step_size option (core.fixed_plan); None: the default grid
+    return core.integrate_fixed(autograd_ops, func, y0, t, method, autonomous=autonomous, plan=plan)
 
 
 class _HipValue(torch.autograd.Function):

@@ -161,17 +161,108 @@ def assert_increasing(t):
 # fixed grid
 # ---------------------------------------------------------------------------------------------------
 
-def integrate_fixed(ops, func, y0, t, method, autonomous=False):
-    """solvers.py:79-99 with the default grid (grid == t).  Returns a list (per tick) of tuples."""
+FIXED_SOLVER_NAMES = {'euler': 'Euler', 'midpoint': 'Midpoint', 'rk4': 'RK4'}      # fixed_grid.py:5,15,26 (named in the warning)
+MAX_EMIT = 8                                  # tick panels one tick_emit launch writes (csrc/rk.hip: kMaxTicks)
+
+
+def fixed_options(method, options):
+    """FixedGridODESolver.__init__ (solvers.py:39-53) on the caller's `options`: the step size (or None), after the reference's
+    warning about names it does not know and its ValueError for ANY grid_constructor (the `elif grid_constructor is None`
+    branch: with or without step_size)."""
+    options = dict(options or {})
+    step_size = options.pop('step_size', None)
+    grid_constructor = options.pop('grid_constructor', None)
+    options.pop('rtol', None)
+    options.pop('atol', None)
+    if options:
+        warnings.warn('{}: Unexpected arguments {}'.format(FIXED_SOLVER_NAMES[method], options))
+    if grid_constructor is not None:
+        raise ValueError("step_size and grid_constructor are exclusive arguments.")
+    if step_size is not None and torch.is_tensor(step_size):
+        step_size = float(step_size.detach())
+    return step_size
+
+
+class FixedPlan:
+    """What every fixed-grid path needs of (t, step_size), all in float32 as the reference forms it:
+      grid       the solver's own time grid (solvers.py:55-68; `t` itself without a step size)
+      dts        grid[i + 1] - grid[i], the float32 subtraction of solvers.py:91
+      emits      per step i: [(tick index j, coincident, t[j] - grid[i]), ...] - the ticks solvers.py:95-97 reports after step i.
+                 coincident = t[j] equals the step's t1 (or t0): `_linear_interp` returns y1 itself (:102-105); every other tick is
+                 y1 + ((y1 - y1) / (t1 - t0)) * (t[j] - t0), because y0 was overwritten with y1 before the call (:93-96)
+      tick_step  per tick j >= 1 the index of the step that emits it;  tick_coincident likewise"""
+
+    def __init__(self, t32, grid):
+        self.t = t32
+        self.grid = grid
+        self.dts = (grid[1:] - grid[:-1]).astype(f32)
+        n_ticks = len(t32)
+        self.emits = [[] for _ in range(len(grid) - 1)]
+        self.tick_step = np.full(n_ticks, -1, dtype=np.int64)
+        self.tick_coincident = np.zeros(n_ticks, dtype=bool)
+        j = 1
+        for i in range(len(grid) - 1):
+            t0, t1 = grid[i], grid[i + 1]
+            while j < n_ticks and t1 >= t32[j]:
+                same = bool(t32[j] == t0 or t32[j] == t1)
+                self.emits[i].append((j, same, f32(t32[j] - t0)))
+                self.tick_step[j], self.tick_coincident[j] = i, same
+                j += 1
+        self.n_emitted = j                 # (ticks past the grid's end would be dropped as the reference drops them: none, grid[-1] == t[-1])
+
+    @property
+    def default(self):
+        return self.grid is self.t
+
+
+def fixed_plan(t32, step_size=None):
+    """t32: the (increasing) time vector as a float32 numpy array.  step_size None: the default grid (grid == t, solvers.py:51).
+    Else solvers.py:55-68 in float32 - niters = ceil((t[-1] - t[0]) / h + 1), arange(niters) * h + t[0], last point clamped to t[-1] -
+    and the reference's `assert time_grid[0] == t[0] and time_grid[-1] == t[-1]` (:83)."""
+    t32 = np.ascontiguousarray(t32, dtype=f32)
+    if step_size is None:
+        return FixedPlan(t32, t32)
+    h = f32(step_size)
+    with np.errstate(all='ignore'):
+        niters = np.ceil(f32(f32(f32(t32[-1] - t32[0]) / h) + f32(1)))
+        n = int(niters) if np.isfinite(niters) else 0
+        grid = (np.arange(max(n, 0), dtype=f32) * h + t32[0]).astype(f32)
+    if n < 1:
+        raise RuntimeError('step_size %r gives no grid for t in [%r, %r]' % (step_size, float(t32[0]), float(t32[-1])))
+    if grid[-1] > t32[-1]:
+        grid[-1] = t32[-1]
+    assert grid[0] == t32[0] and grid[-1] == t32[-1]
+    return FixedPlan(t32, grid)
+
+
+def emit_ticks(ops, plan, i, y, sol):
+    """solvers.py:95-97 after step i: append the state of every tick the step reports to `sol` (y: the tuple state at its end)."""
+    em = plan.emits[i]
+    loose = [e for e in em if not e[1]]
+    made = {}
+    for lo in range(0, len(loose), MAX_EMIT):
+        part = loose[lo:lo + MAX_EMIT]
+        outs = [ops.tick_emit(y_, plan.dts[i], [e[2] for e in part]) for y_ in y]
+        for q, e in enumerate(part):
+            made[e[0]] = tuple(o[q] for o in outs)
+    for j, same, _ in em:
+        sol.append(y if same else made[j])
+
+
+def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None):
+    """solvers.py:79-99: the default grid (grid == t), or the grid of `plan` (fixed_plan: the step_size option).  Returns a list (per
+    tick) of tuples."""
     assert_increasing(t)
     dtype = y0[0].dtype
-    tg = host_grid(t).to(dtype).numpy()          # solvers.py:81: times in the state dtype
+    if plan is None:
+        plan = fixed_plan(host_grid(t).to(dtype).numpy())          # solvers.py:81: times in the state dtype
+    tg = plan.grid
     targ = TimeArg(y0[0], autonomous)
     sol = [y0]
     y = y0
     for i in range(len(tg) - 1):
-        t0, t1 = tg[i], tg[i + 1]
-        dt = t1 - t0                                      # float32 subtraction, as `t1 - t0` on 0-d tensors
+        t0 = tg[i]
+        dt = plan.dts[i]                                  # float32 subtraction, as `t1 - t0` on 0-d tensors
         if method == 'euler':
             k1 = func(targ(t0), y)
             y = tuple(ops.fixed_stage(0, y_, k_, dt=dt) for y_, k_ in zip(y, k1))
@@ -189,7 +280,7 @@ def integrate_fixed(ops, func, y0, t, method, autonomous=False):
             y4 = tuple(ops.fixed_stage(4, y_, a, b, c, dt=dt) for y_, a, b, c in zip(y, k1, k2, k3))
             k4 = func(targ(t0 + dt), y4)
             y = tuple(ops.fixed_stage(5, y_, a, b, c, d, dt=dt) for y_, a, b, c, d in zip(y, k1, k2, k3, k4))
-        sol.append(y)
+        emit_ticks(ops, plan, i, y, sol)
     return sol
 
 

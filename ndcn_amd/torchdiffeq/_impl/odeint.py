@@ -77,6 +77,13 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / euler / midpoint / rk4 are
     provided (tsit5 / explicit_adams / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
     `step_log` (a list) optionally receives the dopri5 per-attempt log.
+
+    Fixed-grid methods take options={'step_size': h} as the reference's FixedGridODESolver does (solvers.py:39-108): the solver
+    integrates on its own float32 grid t[0], t[0] + h, ... (last point clamped to t[-1]; AssertionError where rounding leaves it
+    short) and every tick gets the state at the END of the first grid step that reaches it - the reference overwrites y0 with y1
+    before it "interpolates", so nothing is interpolated; a tick strictly inside a step additionally has -0.0 turned into +0.0 and
+    Inf into NaN.  Any `grid_constructor` raises the reference's ValueError; other names only warn.  One deviation: `step_size`
+    with a `t` that requires grad raises NotImplementedError (the grid's dependence on t[0] / t[-1] is not differentiated).
     """
     user_func = func
     t_user = t
@@ -94,15 +101,25 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
                                   '(dopri5, adams, euler, midpoint, rk4 are provided)' % method)
     method = SOLVERS[method]                     # KeyError for an unknown name, as the reference's dict lookup
 
+    plan = None
+    if method in core.FIXED_METHODS:
+        step_size = core.fixed_options(method, options)     # solvers.py:39-53: warns about unknown names, ValueError for a grid_constructor
+        options = {} if step_size is None else {'step_size': step_size}
+        if step_size is not None:
+            if t_user.requires_grad:
+                raise NotImplementedError('step_size with a time vector that requires grad: the dependence of the grid on t[0] / t[-1] '
+                                          'is not differentiated')
+            core.assert_increasing(t)
+            plan = core.fixed_plan(core.host_grid(t).to(y0[0].dtype).numpy(), step_size)
     for y in y0:
         _lib.require_device(y, 'state y0')
     needs_grad, f0 = _needs_grad(user_func, y0, probe=lambda: func(t[0].to(y0[0].dtype), y0))
     if f0 is not None:
         func = _reuse_first_evaluation(func, y0, f0)
     if needs_grad and method in ('euler', 'midpoint', 'rk4') and _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        sol = _small_solve_with_grad(user_func, y0[0], t, method)                            # one launch forward, one backward
+        sol = _small_solve_with_grad(user_func, y0[0], t, method, plan)                      # one launch forward, one backward
         if sol is None:
-            sol = _fixed_grid_with_grad(user_func, y0[0], t, method)   # any size: fused launches forward, closed-form sweep backward
+            sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan)   # any size: fused launches forward, closed-form sweep backward
         if sol is not None:
             return sol
     if needs_grad:
@@ -115,9 +132,9 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
             if tape.applicable(user_func, y0[0], t_user):
                 return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log)
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
-                               step_log=step_log, odefunc=user_func if plain else None)
+                               step_log=step_log, odefunc=user_func if plain else None, plan=plan)
     elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log)
+        return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan)
     elif method == 'dopri5':
         sol = core.integrate_dopri5(hip, func, y0, t, rtol, atol, autonomous=_autonomous(user_func),
                                     step_log=step_log, **options)
@@ -125,10 +142,7 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         sol = core.integrate_adams(hip, func, y0, t, rtol, atol, autonomous=_autonomous(user_func),
                                    step_log=step_log, **options)
     else:
-        if options:
-            raise NotImplementedError('fixed-grid options %s: only the default grid (grid == t) is provided'
-                                      % sorted(options))
-        sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func))
+        sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan)
     out = tuple(torch.stack([s[i] for s in sol]) for i in range(len(y0)))
     return out[0] if tensor_input else out
 
@@ -263,6 +277,38 @@ class _FixedGridSolve(torch.autograd.Function):
         return gu, gW, gb
 
     @staticmethod
+    def _sweep_step(method, dt, st, a, vj, acc, extra):
+        """the adjoint before one step from the adjoint `a` after it: st = the step's [(stage input, K), ...], vj / acc as in backward;
+        extra: gradients that enter at the state the step starts from, added in the same pass"""
+        ones = [1.0] * len(extra)
+        if method == 'euler':                                   # y1 = y + dt k1
+            (u1, K1), = st
+            gu1, gW, gb = vj(u1, K1, a, dt)
+            acc(gW, gb, dt)
+            return hip.lincomb([gu1] + extra, [1.0] + ones, y0=a)
+        if method == 'midpoint':                                # ym = y + (dt / 2) k1 ; y1 = y + dt k2
+            (u1, K1), (u2, K2) = st
+            gu2, gW, gb = vj(u2, K2, a, dt)                     # dL/d ym
+            acc(gW, gb, dt)
+            gu1, gW, gb = vj(u1, K1, gu2, dt / 2.0)
+            acc(gW, gb, dt / 2.0)
+            return hip.lincomb([gu2, gu1] + extra, [1.0, 1.0] + ones, y0=a)
+        (u1, K1), (u2, K2), (u3, K3), (u4, K4) = st             # the 3/8 rule, rk_common.py:72-78
+        c8 = dt / 8.0
+        gu4, gW, gb = vj(u4, K4, a, c8)                         # J4^T (c8 a)
+        acc(gW, gb, c8)
+        gk3 = hip.lincomb([a, gu4], [3.0 * c8, dt])
+        gu3, gW, gb = vj(u3, K3, gk3, 1.0)
+        acc(gW, gb, 1.0)
+        gk2 = hip.lincomb([a, gu4, gu3], [3.0 * c8, -dt, dt])
+        gu2, gW, gb = vj(u2, K2, gk2, 1.0)
+        acc(gW, gb, 1.0)
+        gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
+        gu1, gW, gb = vj(u1, K1, gk1, 1.0)
+        acc(gW, gb, 1.0)
+        return hip.lincomb([gu4, gu3, gu2, gu1] + extra, [1.0] * 4 + ones, y0=a)
+
+    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         out, W, b = ctx.saved_tensors
@@ -280,41 +326,115 @@ class _FixedGridSolve(torch.autograd.Function):
                 gW_tot.add_(gW, alpha=scale)
                 gb_tot.add_(gb, alpha=scale)
         for i in range(n_ticks - 1, -1, -1):
-            dt = dts[i]
             st = []
             scratch = torch.empty_like(out[0])
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dt, scratch, keep=st)
-            if method == 'euler':                                   # y1 = y + dt k1
-                (u1, K1), = st
-                gu1, gW, gb = vj(u1, K1, a, dt)
-                acc(gW, gb, dt)
-                a = hip.lincomb([gu1, g[i]], [1.0, 1.0], y0=a)
-            elif method == 'midpoint':                              # ym = y + (dt / 2) k1 ; y1 = y + dt k2
-                (u1, K1), (u2, K2) = st
-                gu2, gW, gb = vj(u2, K2, a, dt)                     # dL/d ym
-                acc(gW, gb, dt)
-                gu1, gW, gb = vj(u1, K1, gu2, dt / 2.0)
-                acc(gW, gb, dt / 2.0)
-                a = hip.lincomb([gu2, gu1, g[i]], [1.0, 1.0, 1.0], y0=a)
-            else:                                                   # the 3/8 rule, rk_common.py:72-78
-                (u1, K1), (u2, K2), (u3, K3), (u4, K4) = st
-                c8 = dt / 8.0
-                gu4, gW, gb = vj(u4, K4, a, c8)                     # J4^T (c8 a)
-                acc(gW, gb, c8)
-                gk3 = hip.lincomb([a, gu4], [3.0 * c8, dt])
-                gu3, gW, gb = vj(u3, K3, gk3, 1.0)
-                acc(gW, gb, 1.0)
-                gk2 = hip.lincomb([a, gu4, gu3], [3.0 * c8, -dt, dt])
-                gu2, gW, gb = vj(u2, K2, gk2, 1.0)
-                acc(gW, gb, 1.0)
-                gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
-                gu1, gW, gb = vj(u1, K1, gk1, 1.0)
-                acc(gW, gb, 1.0)
-                a = hip.lincomb([gu4, gu3, gu2, gu1, g[i]], [1.0] * 5, y0=a)
+            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st)
+            a = _FixedGridSolve._sweep_step(method, dts[i], st, a, vj, acc, [g[i]])
         return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None
 
 
-def _fixed_grid_with_grad(odefunc, y0, t, method):
+class _SubstepSolve(torch.autograd.Function):
+    """_FixedGridSolve on a grid finer than the ticks (options={'step_size': h}; core.FixedPlan) WITHOUT a record per grid step:
+      forward   the same fused launches, step after step; kept are the ticks (the output) and the state each tick interval starts
+                from - the output panel itself where the interval's last tick coincides with the end of its step, else one panel;
+      backward  one tick interval at a time, last first: the interval is run again from its start by the same launches, this time
+                keeping the stages of its steps, then swept backwards in closed form (_FixedGridSolve._sweep_step).  The gradient
+                of a tick enters at the end of the step that reported it (the VJP of ops.tick_emit is the identity).
+    Memory: ticks + interval starts + ONE interval's stages, whatever the number of grid steps."""
+
+    @staticmethod
+    def _segments(plan):
+        """[(first step, last step)]: runs of grid steps that end with a step reporting ticks"""
+        segs, lo = [], 0
+        for i, em in enumerate(plan.emits):
+            if em:
+                segs.append((lo, i))
+                lo = i + 1
+        return segs
+
+    @staticmethod
+    def _run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, last_out, keep=None):
+        """steps lo .. hi from the state y; the last one writes to `last_out`; keep (a list) receives each step's stages"""
+        pp = [None, None]
+        for i in range(lo, hi + 1):
+            if i == hi:
+                dst = last_out
+            else:
+                q = (i - lo) & 1
+                if pp[q] is None or keep is not None:         # (kept stages hold on to the panels they read)
+                    pp[q] = torch.empty_like(last_out)
+                dst = pp[q]
+            st = None if keep is None else []
+            _FixedGridSolve._step(csr, y, W, b, no_graph, no_control, method, float(plan.dts[i]), dst, keep=st)
+            if keep is not None:
+                keep.append(st)
+            y = dst
+        return y
+
+    @staticmethod
+    def forward(ctx, y0, W, b, csr, flags, method, plan):
+        n_ticks = len(plan.t)
+        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
+        segs = _SubstepSolve._segments(plan)
+        starts, own = [], []                 # per segment: where its first state lives - ('out', tick) or ('own', index into `own`)
+        y, where = out[0], ('out', 0)
+        for lo, hi in segs:
+            starts.append(where)
+            em = plan.emits[hi]
+            j_last, same_last, _ = em[-1]
+            if same_last:
+                y1, where = out[j_last], ('out', j_last)
+            else:
+                y1 = torch.empty_like(out[0])
+                own.append(y1)
+                where = ('own', len(own) - 1)
+            y = _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, y1)
+            loose = [e for e in em if not e[1]]
+            for q in range(0, len(loose), core.MAX_EMIT):
+                part = loose[q:q + core.MAX_EMIT]
+                hip.tick_emit(y, plan.dts[hi], [e[2] for e in part], outs=[out[e[0]] for e in part])
+        if own and where[0] == 'own':
+            own.pop()                        # nothing starts from the state after the last step
+        ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts)
+        ctx.save_for_backward(out, W, b, *own)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        out, W, b, *own = ctx.saved_tensors
+        csr, no_graph, no_control, method, plan, segs, starts = ctx.meta
+        g = g.contiguous()
+        H = out.shape[2]
+        gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
+        gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
+        vj = lambda u, K, gk, alpha: _FixedGridSolve._vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha)
+
+        def acc(gW, gb, scale):
+            if gW is not None:
+                gW_tot.add_(gW, alpha=scale)
+                gb_tot.add_(gb, alpha=scale)
+        a = None
+        for (lo, hi), (kind, idx) in zip(reversed(segs), reversed(starts)):
+            gs = [g[e[0]] for e in plan.emits[hi]]                       # the ticks this interval's last step reported
+            if a is None:
+                a, gs = gs[0], gs[1:]
+            for q in range(0, len(gs), 8):
+                a = hip.lincomb(gs[q:q + 8], [1.0] * len(gs[q:q + 8]), y0=a)
+            y = out[idx] if kind == 'out' else own[idx]
+            keep = []
+            _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep)
+            for i in range(hi, lo - 1, -1):
+                a = _FixedGridSolve._sweep_step(method, float(plan.dts[i]), keep.pop(), a, vj, acc, [])
+        if a is None:
+            a = torch.zeros_like(out[0])
+        a = hip.lincomb([g[0]], [1.0], y0=a)                            # the first tick is y0 itself
+        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None
+
+
+def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None):
     """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size)."""
     if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
         return None
@@ -323,6 +443,9 @@ def _fixed_grid_with_grad(odefunc, y0, t, method):
         return None
     csr, _, flags = op
     core.assert_increasing(t)
+    if plan is not None:                                      # the step_size option: checkpointed per tick interval
+        return _SubstepSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
+                                   method, plan)
     tt = core.host_grid(t).to(y0.dtype)
     dts = (tt[1:] - tt[:-1]).tolist()
     from . import tape
@@ -333,7 +456,7 @@ def _fixed_grid_with_grad(odefunc, y0, t, method):
                                  method, dts)
 
 
-def _small_solve_with_grad(odefunc, y0, t, method='euler'):
+def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
     """The one-launch training path when the library supports the shape (H <= 31, the state and three work panels in one
     CU's LDS: the reference's README commands), else None - the caller falls back to the per-step autograd path."""
     from ...csr import as_csr
@@ -353,6 +476,22 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler'):
     if method != 'euler' and not _lib.env_on('NDCN_SOLVE_SMALL_RK_GRAD'):
         return None
     core.assert_increasing(t)
+    if plan is not None:
+        # the step_size option: the one-launch pair on the explicit grid into a scratch trajectory (kilobytes per step at sizes that
+        # fit one compute unit), the ticks gathered from it - coincident ticks are its rows, the others pass through tick_emit
+        from ...autograd_ops import autograd_ops
+        fine = _SmallEulerSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
+                                      plan.dts.tolist(), method)
+        ticks = [fine[0]]
+        for i, em in enumerate(plan.emits):
+            loose = [e for e in em if not e[1]]
+            made = {}
+            for q in range(0, len(loose), core.MAX_EMIT):
+                part = loose[q:q + core.MAX_EMIT]
+                for e, o in zip(part, autograd_ops.tick_emit(fine[i + 1], plan.dts[i], [e[2] for e in part])):
+                    made[e[0]] = o
+            ticks.extend(fine[i + 1] if same else made[j] for j, same, _ in em)
+        return torch.stack(ticks)
     tt = core.host_grid(t).to(y0.dtype)                    # solvers.py:81: the grid in the state dtype
     dts = (tt[1:] - tt[:-1]).tolist()
     return _SmallEulerSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags, dts, method)
@@ -371,7 +510,10 @@ def _device_resident_ok(user_func, tensor_input, y0, t, method, options):
         return False
     if user_func.training and user_func.dropout > 0:
         return False
-    if set(options) - set(core.DOPRI5_OPTIONS) or (method != 'dopri5' and options):
+    if method in core.FIXED_METHODS:
+        if set(options) - {'step_size'}:                      # (odeint hands over what core.fixed_options left: nothing, or the step size)
+            return False
+    elif set(options) - set(core.DOPRI5_OPTIONS) or (method != 'dopri5' and options):
         return False
     if options.get('first_step') is not None:                  # dopri5.py:82: then 0.01 is used; host logic handles it
         return False
@@ -453,6 +595,18 @@ class DeviceSolver:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.ndcn_solver_advance_many(self.handle, arr, len(ticks), _lib.ptr(out), _lib.stream_ptr()))
 
+    def advance_grid(self, plan, out):
+        """A sub-stepped fixed grid (core.FixedPlan) in one library call: every step of plan.grid with the state inside the solver,
+        out: (len(plan.t) - 1, n_rows, H) contiguous - the ticks after the first."""
+        n_emit = len(plan.t) - 1
+        assert out.is_contiguous() and tuple(out.shape) == (n_emit,) + self.shape
+        grid = (ctypes.c_float * len(plan.grid))(*plan.grid.tolist())
+        steps = (ctypes.c_int64 * n_emit)(*plan.tick_step[1:].tolist())
+        times = (ctypes.c_float * n_emit)(*plan.t[1:].tolist())
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ndcn_solver_advance_grid(self.handle, grid, len(plan.grid), steps, times, n_emit, _lib.ptr(out),
+                                                         _lib.stream_ptr()))
+
     def stats(self):
         buf = (ctypes.c_double * 6)()
         _lib.check(self.lib.ndcn_solver_stats(self.handle, buf))
@@ -490,9 +644,10 @@ def _small_operator(odefunc, y0):
     return csr, csr.view_ref(), flags
 
 
-def _small_solve(odefunc, y0, tt, method):
+def _small_solve(odefunc, y0, tt, method, plan=None):
     """ndcn_solve_small_f32 without a solver object (no workspace, no host synchronisation): the inference counterpart of
-    _SmallEulerSolve.  tt: the time grid as Python floats ALREADY rounded to the state dtype (solvers.py:81)."""
+    _SmallEulerSolve.  tt: the time grid as Python floats ALREADY rounded to the state dtype (solvers.py:81).  plan (the step_size
+    option): ndcn_solve_small_grid_f32 - the steps of plan.grid, still one launch per 128 steps, only the ticks written."""
     import numpy as np
     op = _small_operator(odefunc, y0)
     if op is None:
@@ -509,6 +664,16 @@ def _small_solve(odefunc, y0, tt, method):
     no_control = bool(flags & _lib.F_NO_CONTROL)
     W = None if no_control else _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
     b = None if (no_control or odefunc.wt.bias is None) else odefunc.wt.bias.detach().contiguous()
+    if plan is not None:
+        n_steps, n_emit = len(plan.dts), len(tt) - 1
+        arr = (ctypes.c_float * n_steps)(*plan.dts.tolist())
+        steps = (ctypes.c_int64 * n_emit)(*plan.tick_step[1:].tolist())
+        same = (ctypes.c_int * n_emit)(*[int(v) for v in plan.tick_coincident[1:]])
+        y_end = torch.empty_like(out[0]) if n_steps > 128 else None
+        with torch.cuda.device(y0.device):
+            _lib.check(lib.ndcn_solve_small_grid_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.METHODS[method], _lib.ptr(out[0]), arr,
+                                                     n_steps, steps, same, n_emit, _lib.ptr(out[1:]), _lib.ptr(y_end), _lib.stream_ptr()))
+        return out
     arr = (ctypes.c_float * len(dts))(*dts)
     with torch.cuda.device(y0.device):
         _lib.check(lib.ndcn_solve_small_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.METHODS[method], _lib.ptr(out[0]), arr,
@@ -565,27 +730,29 @@ def _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph):
     return solver, None                                      # the kept one is busy (another thread): a solver of its own
 
 
-def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log):
+def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan=None):
     core.assert_increasing(t)
     tt = core.host_grid(t).to(torch.float64).tolist()
     if method != 'dopri5':
         # solvers.py:81: the fixed grid is t in the state dtype
         tt = core.host_grid(t).to(y0.dtype).to(torch.float64).tolist()
     if method != 'dopri5' and len(tt) > 1:
-        out = _small_solve(odefunc, y0, tt, method)       # a state that fits one compute unit: the whole grid in ONE launch
+        out = _small_solve(odefunc, y0, tt, method, plan)       # a state that fits one compute unit: the whole grid in ONE launch
         if out is not None:
             return out
     # launch-bound sizes replay ONE captured hipGraph per step - a fixed-grid step, or one attempted dopri5 step - with the
     # step size in device memory (the library declines where a path has no replayable form)
     use_graph = y0.numel() <= GRAPH_MAX_ELEMS
-    opt = core.dopri5_options(options, 1) if method == 'dopri5' else {}
+    opt = core.dopri5_options(options, 1) if method == 'dopri5' else dict(options)      # (fixed grid: nothing, or the step size)
     solver, cache_key = _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph)
     try:
         out = torch.empty((len(tt),) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
         solver.begin(out[0], tt[0], borrow=True)           # the solution's first panel IS the initial state: read in place
         try:
-            if len(tt) > 1:
+            if len(tt) > 1 and plan is not None:
+                solver.advance_grid(plan, out[1:])                 # the step_size option: every grid step inside the solver
+            elif len(tt) > 1:
                 solver.advance_many(tt[1:], out[1:])               # one library call for the whole time vector
         except _lib.NdcnHipError as e:
             if e.code in (_lib.ENONFINITE, _lib.EUNDERFLOW, _lib.EMAXSTEPS, _lib.ESTATE):

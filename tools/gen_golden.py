@@ -20,6 +20,7 @@ Fixture families:
   G11 layout_*.npz    generate_node_mapping degree/community utils_in_learn_dynamics.py:212-230 (+ the P A P^T of :233-247)
   G12 gconv_dense.npz GraphConvolution (dense A, flattened)  neural_dynamics.py:163-176
   G13 adams_*.npz     odeint adams + per-attempt step log    torchdiffeq/_impl/adams.py:62-170
+  G14 substep_*.npz   fixed grid, options={'step_size': h}   torchdiffeq/_impl/solvers.py:55-68,79-108
 """
 import os
 import sys
@@ -554,7 +555,90 @@ def gen_adams():
              **{'opt_' + k: v for k, v in opts.items()}, **csr_of(OM))
 
 
+# ----------------------------------------------------------------------------- G14
+def ref_step_grid(t, h):
+    """(the reference's own grid for the float32 time vector t and step size h, did its assertion of solvers.py:83 hold)"""
+    import torchdiffeq._impl.fixed_grid as ref_fg
+    g = ref_fg.Euler(None, (torch.zeros(1),), step_size=h).grid_constructor(None, None, t)
+    return g, bool(g[0] == t[0] and g[-1] == t[-1])
+
+
+def gen_substep():
+    """FixedGridODESolver with options={'step_size': h}: trajectories at the caller's ticks, the rows of the reference's own solve on
+    the explicit grid they are equal to (the tick placement of solvers.py:92-97), and a table of grids.  (Names start with
+    substep_, not fixed_: the fixed_*.npz globs of the existing tests must not pick these up without the option.)"""
+    _, OM = grid_operator(20)
+    OMs = ref_u.torch_sensor_to_torch_sparse_tensor(OM)
+    cases = {
+        'multiples': (torch.linspace(0., 2., 9), 0.125),                          # every tick is a grid point
+        'irregular': (torch.tensor([0., .13, .5, .55, .57, 1.0]), 0.1),          # several ticks in one step, steps without a tick
+        'clamped': (torch.tensor([0., .3, .65, 1.03]), 0.25),                    # the last step is cut short by the clamp
+    }
+
+    def one(name, method, t, h, fkw=None):
+        f, x = make_func(20, OMs, 11, **(fkw or {}))
+        tt = -t if bool((t[1:] < t[:-1]).all()) else t
+        grid, ok = ref_step_grid(tt, h)
+        assert ok
+        with torch.no_grad():
+            y = ref_ode.odeint(f, x, t, method=method, options={'step_size': h})
+            fine = ref_ode.odeint(f, x, grid if tt is t else -grid, method=method)
+        rows = []
+        for j in range(len(t)):
+            hit = [r for r in range(len(grid)) if torch.equal(fine[r], y[j])]
+            assert hit, (name, j)
+            rows.append(min(r for r in hit if not rows or r >= rows[-1]))
+        save(name, x0=x, t=t, h=np.float64(h), W=f.wt.weight, b=f.wt.bias, traj=y, grid=grid, rows=np.array(rows, dtype=np.int64),
+             no_control=int(bool(fkw)), **csr_of(OM))
+
+    for method in ('euler', 'midpoint', 'rk4'):
+        for cname, (t, h) in cases.items():
+            one('substep_%s_%s' % (method, cname), method, t, h)
+    one('substep_rk4_decreasing', 'rk4', torch.tensor([1., .6, .35, 0.]), 0.1)
+    one('substep_euler_nocontrol', 'euler', cases['irregular'][0], 0.1, dict(no_control=True))
+
+    # odeint_adjoint with the option: forward and every backward interval solve on their own step_size grids (adjoint.py)
+    _, OM12 = grid_operator(12)
+    OM12s = ref_u.torch_sensor_to_torch_sparse_tensor(OM12)
+    torch.manual_seed(41)
+    f = ref_nd.ODEFunc(8, OM12s, dropout=0.0)
+    x0 = torch.rand(144, 8, requires_grad=True)
+    t = torch.linspace(0., 1., 5)
+    target = torch.rand(len(t), 144, 8)
+    y = ref_ode.odeint_adjoint(f, x0, t, method='rk4', options={'step_size': 0.1})
+    loss = torch.nn.functional.l1_loss(y, target)
+    loss.backward()
+    save('substep_adjoint_rk4', x0=x0.detach(), t=t, h=np.float64(0.1), target=target, W=f.wt.weight.detach(), b=f.wt.bias.detach(),
+         traj=y.detach(), loss=loss.detach(), g_x0=x0.grad, g_W=f.wt.weight.grad, g_b=f.wt.bias.grad, **csr_of(OM12))
+
+    # the grid table: (t0, t1, h) -> length, last three points, did the assertion of solvers.py:83 fire.  A scan of 200 000 random
+    # float32 triples (t0 in [0, 2), +-2, +-100, +-1000 - the negated times of a decreasing t included; half of them with
+    # t1 - t0 a whole multiple of h; h a float32 value or an arbitrary Python float) looks for one where it fires; the table keeps
+    # every such triple and 400 of the others.
+    rng = np.random.RandomState(2024)
+    f32 = np.float32
+    keep, fired = [], []
+    n_scan = int(os.environ.get('NDCN_GEN_SUBSTEP_SCAN', '200000'))
+    for i in range(n_scan):
+        mode = i % 4
+        scale = (2, 100, 2, 1000)[mode]
+        t0 = f32(rng.uniform(0, 2)) if mode == 0 else f32(rng.uniform(-scale, scale))
+        h = f32(10 ** rng.uniform(-2.5, 0))
+        t1 = f32(t0 + f32(rng.randint(1, 60)) * h) if i % 2 else f32(t0 + f32(rng.uniform(0.01, 20)) * h)
+        if not t1 > t0:
+            continue
+        hh = float(h) if i % 3 else float(10 ** rng.uniform(-2.5, 0))
+        g, ok = ref_step_grid(torch.tensor([t0, t1]), hh)
+        row = [float(t0), float(t1), hh, float(len(g)), float(not ok)] + [float(v) for v in ([np.nan] * 3 + g.tolist())[-3:]]
+        if not ok:
+            fired.append(row)
+        elif i % (n_scan // 400) == 0:
+            keep.append(row)
+    print('substep grid scan: %d triples, the assertion fired for %d' % (n_scan, len(fired)))
+    save('substep_grids', table=np.array(fired + keep, dtype=np.float64), n_scanned=n_scan, n_fired=len(fired))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams']
+    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep']
     for w in which:
         globals()['gen_' + w]()
