@@ -5,7 +5,7 @@ import ctypes, torch
 
 import os
 _lib = ctypes.CDLL(os.environ.get('NDCN_HIP_LIB', 'libndcn_hip.so'))   # import torch first: the library binds to torch's HIP runtime
-assert _lib.ndcn_abi_version() == 22
+assert _lib.ndcn_abi_version() == 23
 
 _i64, _p = ctypes.c_int64, ctypes.c_void_p
 
@@ -36,7 +36,7 @@ class Operator:
         _lib.ndcn_csr_destroy(self.handle)
 
 def odefunc_forward(op, x, W, b, no_graph=False, no_control=False):
-    """drop-in for the body of ODEFunc.forward (neural_dynamics.py:27-36, dropout 0)"""
+    """drop-in for the body of ODEFunc.forward (neural_dynamics.py:27-36; dropout 0 or eval mode - ndcn_rhs_drop_f32 takes the training form)"""
     flags = 1 | (2 if no_graph else 0) | (4 if no_control else 0)       # NDCN_F_RELU | NO_GRAPH | NO_CONTROL
     y = torch.empty_like(x)
     work = torch.empty(_lib.ndcn_rhs_work_bytes(x.shape[0], x.shape[1], flags), dtype=torch.uint8, device=x.device)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 22
+#define NDCN_ABI_VERSION 23
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -322,7 +322,7 @@ NDCN_API int ndcn_dopri5_interp_bwd_multi_f32(const float *const *h_g, int n_t, 
                                               void *stream);
 
 /* The whole ODEFunc.forward in one call: Y = relu(W (A X) + b) honouring NO_GRAPH / NO_CONTROL
- * (neural_dynamics.py:20-39, dropout p = 0).  `work`: device scratch of ndcn_rhs_work_bytes() bytes, 16-byte
+ * (neural_dynamics.py:20-39; dropout p = 0 or eval mode - ndcn_rhs_drop_f32 below is the training form with 0 < p < 1).  `work`: device scratch of ndcn_rhs_work_bytes() bytes, 16-byte
  * aligned (H = 256: the fused SpMM->LDS->MFMA kernel keeps its packed weights there; other widths: the
  * S = A X panel between the SpMM and the Linear kernel; 0 bytes when the Linear or the SpMM is skipped). */
 NDCN_API int ndcn_rhs_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own,
@@ -405,6 +405,36 @@ NDCN_API int ndcn_rhs_rk_adj_f32(const ndcn_csr *A, const float *X, const float 
                                  float *K, float *work, int H, uint32_t flags, int rk_mode, const float *y0,
                                  const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, const float *y1,
                                  float rtol, float atol, double *d_out, void *d_ws, void *stream);
+
+/* Dropout on the right-hand side (neural_dynamics.py:34: dropout between the Linear and the ReLU; dgnn.py's default p = 0.5).
+ * The mask is a pure function of (p, seed, evaluation, flat element index i = row * H + col) and of nothing else - not of the
+ * route, the launch geometry or H - so that a reverse pass which re-forms a stage re-creates its mask from three numbers:
+ *   p32 = float32(p), 0 < p32 < 1;  s = 1.0f / (1.0f - p32) in float32;  T = floor(double(p32) * 2^32);
+ *   Philox4x32-10 with counter (lo32(i >> 2), hi32(i >> 2), lo32(evaluation), hi32(evaluation)) and key (lo32(seed), hi32(seed));
+ *   u = output word i & 3;  kept iff u >= T;  m = kept ? s : 0;   K' = relu(z) * m (one rounded product; NaN * 0 stays NaN).
+ * m is 0 or s > 0, so relu(z * m) = relu(z) * m: the factor multiplies the launch's output K before it is stored and before the
+ * stage algebra consumes it.  [K' > 0] = [z > 0 and kept]: the exact gradient is gZ = s * g * [K' > 0], i.e. the existing
+ * backward kernels masked by the stored K' (ndcn_linear_bwd_f32 with Y = K', ndcn_relu_bwd_f32) times the scalar s - no mask is
+ * stored or re-created in the backward.
+ * ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the argument lists of ndcn_rhs_f32 / ndcn_rhs_rk_f32 plus the descriptor (NULL: exactly
+ * those calls).  H <= 128 on the one-launch route: the factor is applied in the launch's epilogue (NDCN_PATH_DROP_EPI); every other
+ * route runs its launch without a stage epilogue, ndcn_dropout_apply_f32 and the un-fused stage kernel.  NDCN_EINVAL: p outside
+ * (0, 1), a halo panel, NDCN_F_RELU off.
+ * ndcn_dropout_apply_f32: K[i] *= m(i) in place for i < n_elem (16 bytes per lane where K is 16-byte aligned; any n_elem).     */
+typedef struct ndcn_dropout {
+    float p;
+    uint64_t seed;
+    uint64_t evaluation;
+} ndcn_dropout;
+NDCN_API int ndcn_dropout_apply_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, void *stream);
+NDCN_API int ndcn_rhs_drop_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own,
+                               const float *W, const float *b, float *Y, float *work, int H, uint32_t flags, void *stream,
+                               const ndcn_dropout *desc);
+NDCN_API int ndcn_rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own,
+                                  const float *W, const float *b, float *K, float *work, int H, uint32_t flags,
+                                  int rk_mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,
+                                  float *y_next, const float *y1, float *y_aux, const float *h_c_aux, float rtol, float atol,
+                                  double *d_out, void *d_ws, void *stream, const ndcn_dropout *desc);
 
 /* Pack rows `idx[0..n_idx)` of X into out (halo send buffers).  out[i, :] = X[idx[i], :] */
 NDCN_API int ndcn_gather_rows_f32(const float *X, const int32_t *idx, int64_t n_idx, int H, float *out, void *stream);
@@ -690,6 +720,8 @@ NDCN_API int ndcn_prof_kinds(void);
                                * nn.Linear in fp32, neural_dynamics.py:33; csrc/rhs_fused2_exact.hip).  NDCN_RANGE_GUARD=0
                                * switches the guard (and the 32-byte read-back per packed image) off                              */
 #define NDCN_PATH_RANGE  512 /* such weights on a launch that exists only fused (x_add / x_mask / s_out): split product, warned once */
+#define NDCN_PATH_DROP_EPI 1024 /* ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the dropout factor was applied inside the launch (clear: by
+                                 * the streaming pass ndcn_dropout_apply_f32 behind it)                                              */
 NDCN_API int ndcn_debug_last_rhs_path(void);
 /* Which kernels the LAST ndcn_linear_f32 / ndcn_linear_bwd_f32 call of this thread launched (tests: every dispatch route of the dense
  * Linear is reached on purpose, not merely some correct one); each call replaces the set, 0 for n = 0 and before the first call.

@@ -11,8 +11,9 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
 LIN_GS_SMALL, LIN_GS_FP32, LIN_GS_RES, LIN_GS_RES_MASK, LIN_GS_SPLIT32, LIN_GS_SPLIT64 = 256, 512, 1024, 2048, 4096, 8192
@@ -85,6 +86,19 @@ class CsrHints(ctypes.Structure):
                 ('row_order', ctypes.c_void_p), ('group_order', ctypes.c_void_p), ('n_group_order', ctypes.c_int64),
                 ('rec_rows', ctypes.c_int32), ('rec_cap', ctypes.c_int32), ('rec_kib', ctypes.c_int32),
                 ('hub_threshold', ctypes.c_int32), ('flags', ctypes.c_uint32)]
+
+
+class DropoutDesc(ctypes.Structure):
+    """struct ndcn_dropout: the mask is a function of (p, seed, evaluation, element index) - csrc/dropout.h"""
+    _fields_ = [('p', ctypes.c_float), ('seed', ctypes.c_uint64), ('evaluation', ctypes.c_uint64)]
+
+
+def dropout_desc(dropout):
+    """byref(struct ndcn_dropout) of a (p, seed, evaluation) triple; None stays NULL"""
+    if dropout is None:
+        return None
+    p, seed, evaluation = dropout
+    return ctypes.byref(DropoutDesc(float(p), int(seed) & (2 ** 64 - 1), int(evaluation) & (2 ** 64 - 1)))
 
 
 PLAN_NO_REC, PLAN_NO_STENCIL, PLAN_NO_TILE_ORDER, PLAN_NO_HUB, PLAN_EXTERNAL_SCRATCH, PLAN_ORDER_ONLY = 1, 2, 4, 8, 16, 32
@@ -174,6 +188,10 @@ SIGNATURES = {
     'ndcn_adjoint_rhs_work_bytes': (_L, [_L, _I, _U]),
     'ndcn_rhs_rk_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I,
                         _P, _P, _P, ctypes.POINTER(_F), _F, _F, _P, _P, _P]),
+    'ndcn_dropout_apply_f32': (_I, [_P, _L, ctypes.POINTER(DropoutDesc), _P]),
+    'ndcn_rhs_drop_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _P, ctypes.POINTER(DropoutDesc)]),
+    'ndcn_rhs_rk_drop_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I,
+                             _P, _P, _P, ctypes.POINTER(_F), _F, _F, _P, _P, _P, ctypes.POINTER(DropoutDesc)]),
     'ndcn_set_aten_norm_max': (_L, [_L]),
     'ndcn_rhs_adj_supported': (_I, [_CSR, _I, _U, _I, _I]),
     'ndcn_rhs_rk_adj_f32': (_I, [_CSR, _P, _P, _P, _P, _P, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _P, _P,

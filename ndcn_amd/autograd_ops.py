@@ -13,6 +13,7 @@ solvers, whose step sizes are data-independent.
 import numpy as np
 import torch
 
+from . import dropout as _dropout
 from .csr import as_csr
 from .ops import hip
 
@@ -43,14 +44,16 @@ class _Linear(torch.autograd.Function):
 
 
 class _Rhs(torch.autograd.Function):
-    """relu(W (A X) + b) with the fused forward; S = A X is recomputed in the backward instead of stored."""
+    """relu(dropout(W (A X) + b)) with the fused forward; S = A X is recomputed in the backward instead of stored.  With an active
+    dropout the saved output is the masked K' = relu(z) * m, and that is all the backward needs (rhs_vjp)."""
 
     @staticmethod
-    def forward(ctx, X, W, b, A, no_graph, no_control):
+    def forward(ctx, X, W, b, A, no_graph, no_control, dropout=None):
         # (W itself, not a detached alias: the packed-weight cache of ops.rhs is keyed on the tensor object and its version
         # counter - every evaluation of a solve then reuses the packed image instead of rebuilding it: two launches per RHS)
-        Y = hip.rhs(A, X.detach(), W, None if b is None else b.detach(), no_graph=no_graph, no_control=no_control)
+        Y = hip.rhs(A, X.detach(), W, None if b is None else b.detach(), no_graph=no_graph, no_control=no_control, dropout=dropout)
         ctx.A, ctx.no_graph, ctx.no_control, ctx.has_b = A, no_graph, no_control, b is not None
+        ctx.scale = 1.0 if dropout is None else _dropout.scale(dropout[0])
         ctx.save_for_backward(X, W, Y)
         return Y
 
@@ -58,15 +61,18 @@ class _Rhs(torch.autograd.Function):
     def backward(ctx, g):
         X, W, Y = ctx.saved_tensors
         gX, gW, gb = rhs_vjp(ctx.A, ctx.no_graph, ctx.no_control, X, W, Y, g.contiguous(), ctx.needs_input_grad[0],
-                             ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2])
-        return gX, gW, gb, None, None, None
+                             ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2], scale=ctx.scale)
+        return gX, gW, gb, None, None, None, None
 
 
-def rhs_vjp(A, no_graph, no_control, X, W, Y, g, need_x, need_w, need_b, S=None):
+def rhs_vjp(A, no_graph, no_control, X, W, Y, g, need_x, need_w, need_b, S=None, scale=1.0):
     """(g_X, g_W, g_b) of Y = relu(W (A X) + b) for the upstream gradient g - the closed form every differentiable wrapper of the
     right-hand side shares: ReLU mask fused into the operand loads of the two GEMMs, g_W = gZ^T S split over row chunks (S = A X
     recomputed instead of stored, unless the caller kept the one the forward launch wrote), g_b with it, g_X = A^T g_S through the
-    SpMM on the transposed CSR."""
+    SpMM on the transposed CSR.
+    scale: Y is the dropout-masked K' = relu(z) * m with m in {0, s}, scale = s.  [K' > 0] = [z > 0 and kept], so the gradient is
+    gZ = s * g * [K' > 0]: the same kernels masked by the stored K', and the scalar folded into the alpha of the transposed SpMM
+    and into the two small parameter gradients - no mask is re-created, no panel pass is added while the graph is on."""
     gW = gb = None
     if not no_control:
         if not need_w:
@@ -75,11 +81,17 @@ def rhs_vjp(A, no_graph, no_control, X, W, Y, g, need_x, need_w, need_b, S=None)
             S = X.detach() if no_graph else hip.spmm(A, X.detach())
         # (W itself, not a detached alias: linear_bwd keeps the packed planes of W^T per weight tensor object and version)
         gS, gW, gb = hip.linear_bwd(g, W, S=S, Y=Y, need_gS=need_x, need_gW=need_w, need_gb=need_b)
+        if scale != 1.0:
+            gW = gW.mul_(scale) if gW is not None else None
+            gb = gb.mul_(scale) if gb is not None else None
     else:
         gS = hip.relu_bwd(g, Y) if need_x else None
     gX = None
     if need_x:
-        gX = gS if no_graph else hip.spmm(A.transpose(), gS.contiguous())
+        if no_graph:
+            gX = gS if scale == 1.0 else hip.scale(gS, scale)
+        else:
+            gX = hip.spmm(A.transpose(), gS.contiguous(), alpha=scale)
     return gX, gW, gb
 
 
@@ -91,8 +103,9 @@ def linear(x, W, b):
     return _Linear.apply(x, W, b)
 
 
-def rhs(A, x, W, b, no_graph, no_control):
-    return _Rhs.apply(x, W, b, None if no_graph else as_csr(A), no_graph, no_control)
+def rhs(A, x, W, b, no_graph, no_control, dropout=None):
+    """dropout: None or (p, seed, evaluation) - see ops.HipOps.rhs"""
+    return _Rhs.apply(x, W, b, None if no_graph else as_csr(A), no_graph, no_control, dropout)
 
 
 # ---------------------------------------------------------------------------------------------------

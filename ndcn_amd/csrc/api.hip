@@ -282,7 +282,7 @@ static int rhs_rk_entry(const ndcn_csr *A, const float *X, const float *X_halo, 
                         float *K, float *work, int H, uint32_t flags, int rk_mode, const float *y0,
                         const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, const float *y1, float *y_aux,
                         const float *h_c_aux, float rtol, float atol, double *d_out, void *d_ws, const float *x_add, float x_add_c,
-                        void *stream, const float *x_mask = nullptr, float *s_out = nullptr) {
+                        void *stream, const float *x_mask = nullptr, float *s_out = nullptr, const ndcn_dropout *drop = nullptr) {
     NDCN_CHECK_ARG(A, "null operator descriptor");
     NDCN_CHECK_ARG(H > 0, "H must be positive");
     NDCN_CHECK_ARG(rk_mode >= 0 && rk_mode <= 3, "rk_mode must be 0, NDCN_RK_COMBINE, NDCN_RK_ERROR or NDCN_RK_RK4");
@@ -313,6 +313,13 @@ static int rhs_rk_entry(const ndcn_csr *A, const float *X, const float *X_halo, 
                        "x_mask / s_out: not supported for this operator / mode (ndcn_rhs_adj_supported), both given, or aliased");
     }
     const RkOpt opt = {y1, (flags & NDCN_F_ACCUM) ? 1 : 0, y_aux, h_c_aux, x_add, x_add_c, x_mask, s_out};
+    if (drop) {
+        DropArgs d;
+        int rc = drop_args(drop, &d);
+        if (rc) return rc;
+        return rhs_rk_drop_f32(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol,
+                               d_out, d_ws, ST(stream), &opt, d);
+    }
     return rhs_rk_f32(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol,
                       d_out, d_ws, ST(stream), &opt);
 }
@@ -323,6 +330,30 @@ int ndcn_rhs_rk_f32(const ndcn_csr *A, const float *X, const float *X_halo, int6
                     const float *h_c_aux, float rtol, float atol, double *d_out, void *d_ws, void *stream) {
     return rhs_rk_entry(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, y1, y_aux, h_c_aux,
                         rtol, atol, d_out, d_ws, nullptr, 0.f, stream);
+}
+
+int ndcn_rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own, const float *W, const float *b,
+                         float *K, float *work, int H, uint32_t flags, int rk_mode, const float *y0,
+                         const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, const float *y1, float *y_aux,
+                         const float *h_c_aux, float rtol, float atol, double *d_out, void *d_ws, void *stream,
+                         const ndcn_dropout *desc) {
+    return rhs_rk_entry(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, y1, y_aux, h_c_aux,
+                        rtol, atol, d_out, d_ws, nullptr, 0.f, stream, nullptr, nullptr, desc);
+}
+
+int ndcn_rhs_drop_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own, const float *W, const float *b,
+                      float *Y, float *work, int H, uint32_t flags, void *stream, const ndcn_dropout *desc) {
+    if (!desc) return ndcn_rhs_f32(A, X, X_halo, n_own, W, b, Y, work, H, flags, stream);
+    return rhs_rk_entry(A, X, X_halo, n_own, W, b, Y, work, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                        0.f, 0.f, nullptr, nullptr, nullptr, 0.f, stream, nullptr, nullptr, desc);
+}
+
+int ndcn_dropout_apply_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, void *stream) {
+    NDCN_CHECK_ARG(n_elem >= 0 && desc && (n_elem == 0 || K), "bad argument");
+    DropArgs d;
+    int rc = drop_args(desc, &d);
+    if (rc) return rc;
+    return dropout_apply_f32(K, n_elem, d, ST(stream));
 }
 
 int ndcn_rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int rk_mode, int n_prev) {

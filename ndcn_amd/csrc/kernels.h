@@ -2,6 +2,7 @@
 // forwards here.
 #pragma once
 #include "common.h"
+#include "dropout.h"
 
 namespace ndcn {
 
@@ -101,7 +102,17 @@ int rhs_small_wanted(int64_t n_rows, int H, uint32_t flags);      // the same de
 int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                   int H, uint32_t flags, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,
                   float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st, const float *c_dev = nullptr,
-                  const RkOpt *opt = nullptr);
+                  const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);     // drop: the factor of csrc/dropout.h in the epilogue
+// dropout (csrc/dropout.h; rhs.hip): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1), the streaming pass K *= m, and
+// rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch, by the streaming pass behind every other route
+int drop_args(const ndcn_dropout *desc, DropArgs *out);
+int dropout_apply_f32(float *K, int64_t n, const DropArgs &d, hipStream_t st);
+int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
+                 float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st);
+int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
+                    float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
+                    const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
+                    hipStream_t st, const RkOpt *opt, const DropArgs &d);
 // solve_small.hip: a whole fixed-grid solve (all ticks) in ONE launch for states that fit one CU; h_dt: the n_ticks step sizes in
 // the state dtype; out: n_ticks panels.  Euler also has the reverse sweep (traj / g_out: n_ticks + 1 panels, y_0 first).
 int solve_small_supported(const ndcn_csr *A, int H, uint32_t flags, int method);

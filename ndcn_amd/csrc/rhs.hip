@@ -1,6 +1,7 @@
-// ODEFunc.forward as one entry point: Y = relu(W (A X) + b)   (neural_dynamics.py:20-39, dropout p = 0).
+// ODEFunc.forward as one entry point: Y = relu(W (A X) + b)   (neural_dynamics.py:20-39).
 // H = 256 runs the fused kernel (rhs_fused.hip); other widths compose the SpMM and the MFMA Linear through a
-// scratch panel.
+// scratch panel.  rhs_f32 / rhs_rk_f32 are the p = 0 (and eval-mode) forms; rhs_drop_f32 / rhs_rk_drop_f32 at the end of the file
+// add the dropout factor of csrc/dropout.h - inside the narrow-panel launch, as a streaming pass behind every other route.
 #include <stdio.h>
 
 #include <atomic>
@@ -94,6 +95,24 @@ int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, c
     return NDCN_OK;
 }
 
+// the stage algebra over {kprev..., K} by the un-fused kernels, in the term order of the fused epilogues (K is the last term)
+static int rk_stage_f32(int64_t n, const float *X, const float *K, int rk_mode, const float *y0, const float *const *h_kprev, const float *h_c,
+                        int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st, const RkOpt *opt) {
+    const float *kk[6];
+    for (int m = 0; m < n_prev; ++m) kk[m] = h_kprev[m];
+    kk[n_prev] = K;
+    if (rk_mode == 3)
+        return fixed_stage_f32(2 + n_prev, y_next, y0, kk[0], n_prev > 0 ? kk[1] : nullptr, n_prev > 1 ? kk[2] : nullptr,
+                               n_prev > 2 ? kk[3] : nullptr, h_c[0], n, st, nullptr);
+    if (rk_mode == 1) {
+        int rc = rk_combine_f32(y_next, y0, kk, h_c, n_prev + 1, n, st);
+        if (!rc && opt && opt->y_aux && opt->c_aux) rc = rk_combine_f32(opt->y_aux, nullptr, kk, opt->c_aux, n_prev + 1, n, st);
+        return rc;
+    }
+    return rk_error_f32(y0, (opt && opt->y1) ? opt->y1 : X, kk, h_c, n_prev + 1, rtol, atol, n, d_out, d_ws, st, nullptr,
+                        (opt && opt->accum) ? 1 : 0);
+}
+
 int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
                const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
@@ -148,20 +167,49 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
     // composition with the same term order: K first, then the algebra over {kprev..., K}
     int rc = rhs_f32(A, X, Xh, n_own, W, b, K, work, H, flags, st);
     if (rc) return rc;
-    const float *kk[6];
-    for (int m = 0; m < n_prev; ++m) kk[m] = h_kprev[m];
-    kk[n_prev] = K;
-    const int64_t n = A->n_rows * (int64_t)H;
-    if (rk_mode == 3)
-        return fixed_stage_f32(2 + n_prev, y_next, y0, kk[0], n_prev > 0 ? kk[1] : nullptr, n_prev > 1 ? kk[2] : nullptr,
-                               n_prev > 2 ? kk[3] : nullptr, h_c[0], n, st, nullptr);
-    if (rk_mode == 1) {
-        rc = rk_combine_f32(y_next, y0, kk, h_c, n_prev + 1, n, st);
-        if (!rc && opt && opt->y_aux && opt->c_aux) rc = rk_combine_f32(opt->y_aux, nullptr, kk, opt->c_aux, n_prev + 1, n, st);
-        return rc;
+    return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
+}
+
+// ---------------------------------------------------------------------------------------------------- dropout
+// K' = relu(z) * m (csrc/dropout.h).  Narrow panels: the factor in the epilogue of the one launch (NDCN_PATH_DROP_EPI).  Every other
+// route: the launch without a stage epilogue, the streaming pass K *= m, then the un-fused stage kernel - the composition rhs_rk_f32
+// itself falls back to, hence the same bits as the fused epilogues would give on the masked K.
+static int drop_check(const float *Xh, uint32_t flags) {
+    if (Xh) { set_error("dropout with a halo panel (sharded graphs) is not supported"); return NDCN_EINVAL; }
+    if (!(flags & NDCN_F_RELU)) { set_error("dropout without NDCN_F_RELU is not supported"); return NDCN_EINVAL; }
+    return NDCN_OK;
+}
+
+int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
+                 float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st) {
+    int rc = drop_check(Xh, flags);
+    if (rc) return rc;
+    if (!(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags)) {
+        g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
+        return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st,
+                             nullptr, nullptr, &d);
     }
-    return rk_error_f32(y0, (opt && opt->y1) ? opt->y1 : X, kk, h_c, n_prev + 1, rtol, atol, n, d_out, d_ws, st, nullptr,
-                        (opt && opt->accum) ? 1 : 0);
+    g_last_rhs_path = 0;
+    if ((rc = rhs_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, st))) return rc;
+    return dropout_apply_f32(Y, A->n_rows * (int64_t)H, d, st);
+}
+
+int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
+                    float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
+                    const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
+                    hipStream_t st, const RkOpt *opt, const DropArgs &d) {
+    if (rk_mode == 0) return rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st);
+    int rc = drop_check(Xh, flags);
+    if (rc) return rc;
+    if (n_prev < 0 || n_prev > 5) { set_error("rhs_rk: n_prev must be 0..5"); return NDCN_EINVAL; }
+    if (opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid)) { set_error("dropout with x_add / x_mask / s_out is not supported"); return NDCN_EINVAL; }
+    if (!(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags)) {
+        g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
+        return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
+                             nullptr, opt, &d);
+    }
+    if ((rc = rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st))) return rc;
+    return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
 }
 
 }  // namespace ndcn

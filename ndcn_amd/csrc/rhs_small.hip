@@ -13,8 +13,13 @@
 //              consecutive words) and S[h] as an LDS broadcast
 //     epilogue row-local panels at column o: the stage algebra in the reference's operator order (separate mul / add)
 //   => results are bit-identical to the composed path  ndcn_spmm_f32 -> ndcn_linear_f32 -> rk kernel.
+//
+// Dropout (training, 0 < p < 1; the contract is csrc/dropout.h): the factor m multiplies K right after the ReLU, so that K as stored and
+// K as consumed by the stage algebra are both the masked one - the bits of the un-fused launch -> ndcn_dropout_apply_f32 -> rk kernel.
+// These are instantiations of their own (rhs_small_kernel<.., DropArgs>); the p = 0 kernels carry no trace of the generator.
 #include <stdlib.h>
 
+#include "dropout.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -48,9 +53,12 @@ struct SmallEpi {
     float c2[kSmMaxPrev + 1];
 };
 
-// NH = 1: H <= 64 (one column per lane), NH = 2: H <= 128
-template <int NH, bool HALO, int MODE>
-__global__ __launch_bounds__(256) void rhs_small_kernel(SmallArgs a, SmallEpi e) {
+__device__ __forceinline__ const DropArgs &drop_of(const DropArgs &d) { return d; }
+
+// NH = 1: H <= 64 (one column per lane), NH = 2: H <= 128.  DROP... is empty (p = 0: the kernel and its argument block are the ones they
+// always were) or one DropArgs: the dropout factor in the epilogue (no halo panel then)
+template <int NH, bool HALO, int MODE, typename... DROP>
+__global__ __launch_bounds__(256) void rhs_small_kernel(SmallArgs a, SmallEpi e, DROP... drop) {
     extern __shared__ float lds[];
     const int H = a.H;
     const int ldw = H + 1;                                  // W^T rows padded: lane o reads word h * ldw + o
@@ -68,6 +76,15 @@ __global__ __launch_bounds__(256) void rhs_small_kernel(SmallArgs a, SmallEpi e)
     for (int u = 0; u < NH; ++u) bias[u] = (a.bias && lane + 64 * u < H) ? a.bias[lane + 64 * u] : 0.f;
     auto coef = [&](int m) { return (MODE != SM_PLAIN && e.c_dev) ? e.c_dev[m] : e.c[m]; };
     double err_sum = 0.0, err_bad = 0.0;
+    DropArgs dv = {};
+    if constexpr (sizeof...(DROP) != 0) {
+        dv = drop_of(drop...);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // seed and evaluation live in vector registers across the row loop: the COMBINE / ERROR epilogues fill the scalar file with
+        // their coefficients (NH = 2 COMBINE spilled two scalars otherwise), the vector file has room
+        asm volatile("" : "+v"(dv.k0), "+v"(dv.k1), "+v"(dv.e0), "+v"(dv.e1));
+#endif
+    }
     const int np = e.n_prev;
     const int n_waves = gridDim.x * 4;
     for (int r = blockIdx.x * 4 + wave; r < a.n_rows; r += n_waves) {
@@ -120,6 +137,7 @@ __global__ __launch_bounds__(256) void rhs_small_kernel(SmallArgs a, SmallEpi e)
             float kn = k[u] + bias[u];
             if (a.relu) kn = relu_nan(kn);
             const size_t idx = (size_t)r * H + o;
+            if constexpr (sizeof...(DROP) != 0) kn = kn * drop_factor<true>(dv, (int64_t)idx);   // (every lane its own element)
             a.K[idx] = kn;
             if (MODE == SM_PLAIN) continue;
             const float y0 = e.y0[idx];
@@ -201,9 +219,10 @@ int rhs_small_supported(const ndcn_csr *A, int H, uint32_t flags) { return A ? r
 int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                   int H, uint32_t flags, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,
                   float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st, const float *c_dev,
-                  const RkOpt *opt) {
+                  const RkOpt *opt, const DropArgs *drop) {
     const int n_rows = (int)A->n_rows;
     if (n_rows == 0) return NDCN_OK;
+    if (drop && (Xh || !(flags & NDCN_F_RELU))) { set_error("rhs_small: dropout with a halo panel or without the ReLU"); return NDCN_EINVAL; }
     if (n_prev < 0 || n_prev > kSmMaxPrev || (mode == SM_RK4 && n_prev > 3)) { set_error("rhs_small: bad stage count"); return NDCN_EINVAL; }
     SmallArgs a;
     a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val; a.X = X; a.Xh = Xh; a.n_own = (int)n_own; a.n_rows = n_rows;
@@ -225,25 +244,35 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
     double bytes = 8.0 * A->nnz + 4.0 * (n_rows + 1) + 4.0 * H * (double)(A->n_rows + A->n_cols) + 4.0 * H * H;
     if (mode != SM_PLAIN) bytes += P * (n_prev + 2 + (e.y_aux ? 1 : 0));
     ProfScope prof(PROF_RHS_FUSED, st, bytes, 2.0 * A->nnz * H + 2.0 * (double)n_rows * H * H);
-#define NDCN_SM(NH_, HALO_, MODE_)                                                                                    \
+    // (the kernel expression in parentheses: its commas; __VA_ARGS__: the DropArgs of a dropout launch)
+#define NDCN_SM(KERN_, ...)                                                                                           \
     do {                                                                                                              \
-        auto kern = rhs_small_kernel<NH_, HALO_, MODE_>;                                                              \
+        auto kern = KERN_;                                                                                            \
         static std::atomic<unsigned long long> attr_seen{0};                                                                                 \
         if (once_per_device(attr_seen)) {                                                                                              \
             NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,              \
                                          (int)(((size_t)kSmMaxH * (kSmMaxH + 1) + 4 * kSmMaxH) * sizeof(float))));     \
         }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, e);                                               \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, e, ##__VA_ARGS__);                                \
     } while (0)
-#define NDCN_SM_MODE(NH_, HALO_)                                   \
-    do {                                                           \
-        if (mode == SM_PLAIN) NDCN_SM(NH_, HALO_, SM_PLAIN);       \
-        else if (mode == SM_COMBINE) NDCN_SM(NH_, HALO_, SM_COMBINE); \
-        else if (mode == SM_ERROR) NDCN_SM(NH_, HALO_, SM_ERROR);  \
-        else NDCN_SM(NH_, HALO_, SM_RK4);                          \
+#define NDCN_SM_MODE(NH_, HALO_)                                                      \
+    do {                                                                              \
+        if (mode == SM_PLAIN) NDCN_SM((rhs_small_kernel<NH_, HALO_, SM_PLAIN>));      \
+        else if (mode == SM_COMBINE) NDCN_SM((rhs_small_kernel<NH_, HALO_, SM_COMBINE>)); \
+        else if (mode == SM_ERROR) NDCN_SM((rhs_small_kernel<NH_, HALO_, SM_ERROR>)); \
+        else NDCN_SM((rhs_small_kernel<NH_, HALO_, SM_RK4>));                         \
     } while (0)
-    if (H <= 64) { if (Xh) NDCN_SM_MODE(1, true); else NDCN_SM_MODE(1, false); }
+#define NDCN_SM_DROP_MODE(NH_)                                                                        \
+    do {                                                                                              \
+        if (mode == SM_PLAIN) NDCN_SM((rhs_small_kernel<NH_, false, SM_PLAIN, DropArgs>), *drop);     \
+        else if (mode == SM_COMBINE) NDCN_SM((rhs_small_kernel<NH_, false, SM_COMBINE, DropArgs>), *drop); \
+        else if (mode == SM_ERROR) NDCN_SM((rhs_small_kernel<NH_, false, SM_ERROR, DropArgs>), *drop); \
+        else NDCN_SM((rhs_small_kernel<NH_, false, SM_RK4, DropArgs>), *drop);                        \
+    } while (0)
+    if (drop) { if (H <= 64) NDCN_SM_DROP_MODE(1); else NDCN_SM_DROP_MODE(2); }
+    else if (H <= 64) { if (Xh) NDCN_SM_MODE(1, true); else NDCN_SM_MODE(1, false); }
     else { if (Xh) NDCN_SM_MODE(2, true); else NDCN_SM_MODE(2, false); }
+#undef NDCN_SM_DROP_MODE
 #undef NDCN_SM_MODE
 #undef NDCN_SM
     NDCN_LAUNCH_CHECK();

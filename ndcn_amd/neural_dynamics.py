@@ -7,6 +7,7 @@ Out of scope: TemporalGCN (discrete RNN baselines, neural_dynamics.py:179-238).
 import torch
 import torch.nn as nn
 
+from . import dropout as _dropout
 from . import torchdiffeq as ode
 from .ops import hip
 
@@ -39,8 +40,16 @@ class ODEFunc(nn.Module):
         self.no_control = no_control
 
     def forward(self, t, x):
+        if _dropout.is_active(self):
+            # stochastic RHS, 0 < p < 1: the factor is 0 or 1 / (1 - p) > 0, so relu(dropout(z)) = relu(z) * m - one fused launch (and
+            # one autograd node) with the counter-based mask of csrc/dropout.h; ndcn_amd/dropout.py numbers the evaluations
+            triple = _dropout.next_evaluation(self.dropout)
+            if _needs_grad(x, self.wt):
+                from .autograd_ops import rhs
+                return rhs(self.A, x, self.wt.weight, self.wt.bias, self.no_graph, self.no_control, dropout=triple)
+            return hip.rhs(self.A, x, self.wt.weight, self.wt.bias, no_graph=self.no_graph, no_control=self.no_control, dropout=triple)
         if self.dropout > 0 and self.training:
-            # stochastic RHS: un-fused sequence, dropout between Linear and relu as neural_dynamics.py:34
+            # p >= 1: un-fused sequence, dropout between Linear and relu as neural_dynamics.py:34
             from .autograd_ops import spmm, linear
             if not self.no_graph:
                 x = spmm(self.A, x)

@@ -364,10 +364,12 @@ class HipOps:
         return out
 
     @staticmethod
-    def rhs(A, X, W, b, no_graph=False, no_control=False, X_halo=None, out=None, relu=True):
-        """The whole ODEFunc.forward: relu(W (A X) + b)   (neural_dynamics.py:20-39, dropout 0).
+    def rhs(A, X, W, b, no_graph=False, no_control=False, X_halo=None, out=None, relu=True, dropout=None):
+        """The whole ODEFunc.forward: relu(dropout(W (A X) + b))   (neural_dynamics.py:20-39).
         relu=False: the same launch without the activation - the transposed half of the adjoint right-hand side,
-        (A^T gZ) W with the operator / weight pair (A^T, W^T) and no bias (_impl/adjoint_fused.py)."""
+        (A^T gZ) W with the operator / weight pair (A^T, W^T) and no bias (_impl/adjoint_fused.py).
+        dropout: None (p = 0, eval mode) or (p, seed, evaluation) with 0 < p < 1 - the result times the mask of csrc/dropout.h,
+        a function of those three numbers and the element index alone (ndcn_rhs_drop_f32)."""
         X = _panel(X)
         H = X.shape[1]
         flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
@@ -399,14 +401,29 @@ class HipOps:
             else:
                 work = torch.empty(wbytes, dtype=torch.uint8, device=X.device)
         with torch.cuda.device(X.device):
+            if dropout is not None:
+                check(lib.ndcn_rhs_drop_f32(view_ref, ptr(X), ptr(X_halo), X.shape[0], ptr(None if no_control else W),
+                                            ptr(None if no_control else b), ptr(Y), ptr(work), H, flags, stream_ptr(),
+                                            _lib.dropout_desc(dropout)))
+                return Y
             check(lib.ndcn_rhs_f32(view_ref, ptr(X), ptr(X_halo), X.shape[0], ptr(None if no_control else W),
                                    ptr(None if no_control else b), ptr(Y), ptr(work), H, flags, stream_ptr()))
         return Y
 
     @staticmethod
+    def dropout_apply(K, dropout):
+        """K *= mask in place (ndcn_dropout_apply_f32): dropout = (p, seed, evaluation), element index = position in K's memory.
+        K: a contiguous float32 device tensor or view (a misaligned one takes the scalar kernel).  Returns K."""
+        require_device(K, 'panel')
+        assert K.is_contiguous()
+        with torch.cuda.device(K.device):
+            check(_lib.load().ndcn_dropout_apply_f32(ptr(K), K.numel(), _lib.dropout_desc(dropout), stream_ptr()))
+        return K
+
+    @staticmethod
     def rhs_rk(A, X, W, b, mode, y0, kprev, cs, rtol=0.0, atol=0.0, no_graph=False, no_control=False, X_halo=None,
                out_K=None, out_y=None, y1=None, accum=False, fetch=True, aux_cs=None, out_aux=None, record=None, relu=True,
-               x_mask=None, s_out=None):
+               x_mask=None, s_out=None, dropout=None):
         """K = ODEFunc(X) plus, in the same pass, the stage algebra consuming K (ndcn_rhs_rk_f32).
         record (mode 'error'): an ErrorRecord of the caller's that receives / accumulates the result instead of the
         per-device one (split evaluations: new_error_record()).
@@ -419,7 +436,9 @@ class HipOps:
         mode 'combine' only - aux_cs: coefficients of a second linear combination of the same stages (no y0), formed in
         the same pass: returns (K, y_next, sum aux_cs[m] kprev[m] + aux_cs[-1] K) - dopri5's partial error sum E.
         x_mask / s_out (ndcn_rhs_rk_adj_f32, where rhs_adj_supported says so): the input is X (.) [x_mask > 0] formed on the staged
-        rows / S = A X is written into s_out too - the two halves of odeint_adjoint's right-hand side (_impl/adjoint_fused.py)."""
+        rows / S = A X is written into s_out too - the two halves of odeint_adjoint's right-hand side (_impl/adjoint_fused.py).
+        dropout: None or (p, seed, evaluation) as in rhs(): K, as returned and as consumed by the stage algebra, is the masked one
+        (ndcn_rhs_rk_drop_f32; not with x_mask / s_out / a halo panel)."""
         X = _panel(X)
         H = X.shape[1]
         flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
@@ -466,7 +485,7 @@ class HipOps:
         y_next = (out_y if out_y is not None else torch.empty_like(K)) if mode in ('combine', 'rk4') else None
         red = _Reducer.get(X.device)
         if x_mask is not None or s_out is not None:
-            assert X_halo is None and aux_cs is None and not accum
+            assert X_halo is None and aux_cs is None and not accum and dropout is None
             x_mask = _panel(x_mask, 'mask panel') if x_mask is not None else None
             with _REDUCE_LOCK, torch.cuda.device(X.device):
                 check(lib.ndcn_rhs_rk_adj_f32(view_ref, ptr(X), ptr(x_mask), ptr(s_out), ptr(W), ptr(b), ptr(K), ptr(work), H, flags, rk,
@@ -476,10 +495,14 @@ class HipOps:
                     return K, y_next
                 return K, ((record or red).fetch() if fetch else None)
         with _REDUCE_LOCK, torch.cuda.device(X.device):
-            check(lib.ndcn_rhs_rk_f32(view_ref, ptr(X), ptr(X_halo), X.shape[0], ptr(None if no_control else W),
-                                      ptr(None if no_control else b), ptr(K), ptr(work), H, flags, rk, ptr(y0), arr_k,
-                                      arr_c, len(kprev), ptr(y_next), ptr(y1), ptr(y_aux), arr_c2, float(rtol), float(atol),
-                                      ptr((record or red).out), ptr(red.ws), stream_ptr()))
+            args = (view_ref, ptr(X), ptr(X_halo), X.shape[0], ptr(None if no_control else W),
+                    ptr(None if no_control else b), ptr(K), ptr(work), H, flags, rk, ptr(y0), arr_k,
+                    arr_c, len(kprev), ptr(y_next), ptr(y1), ptr(y_aux), arr_c2, float(rtol), float(atol),
+                    ptr((record or red).out), ptr(red.ws), stream_ptr())
+            if dropout is not None:
+                check(lib.ndcn_rhs_rk_drop_f32(*args, _lib.dropout_desc(dropout)))
+            else:
+                check(lib.ndcn_rhs_rk_f32(*args))
             if aux_cs is not None:
                 return K, y_next, y_aux
             if mode in ('combine', 'rk4'):

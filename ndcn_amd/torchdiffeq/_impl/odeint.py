@@ -17,6 +17,7 @@ import weakref
 import torch
 
 from ... import _lib
+from ... import dropout as _dropout
 from ...ops import hip, new_solve_epoch
 from . import core
 
@@ -64,8 +65,9 @@ def _reuse_first_evaluation(func, y0, out):
 
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_log=None):
     """Integrate dy/dt = func(t, y), y(t[0]) = y0; returns y at every t (first dim), y0 first.  (The body is `_odeint`; this frame
-    fetches the time grid to the host once for everything below that asks about it: core.grid_scope.)"""
-    with core.grid_scope(t):
+    fetches the time grid to the host once for everything below that asks about it: core.grid_scope - and opens the solve's dropout
+    stream: one seed, evaluations numbered from 0, ndcn_amd/dropout.py.)"""
+    with core.grid_scope(t), _dropout.solve_scope():
         return _odeint(func, y0, t, rtol, atol, method, options, step_log)
 
 
@@ -116,8 +118,12 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     needs_grad, f0 = _needs_grad(user_func, y0, probe=lambda: func(t[0].to(y0[0].dtype), y0))
     if f0 is not None:
         func = _reuse_first_evaluation(func, y0, f0)
-    if needs_grad and method in ('euler', 'midpoint', 'rk4') and _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        sol = _small_solve_with_grad(user_func, y0[0], t, method, plan)                      # one launch forward, one backward
+    if needs_grad and method in ('euler', 'midpoint', 'rk4') and \
+            _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_dropout=True):
+        # (an active dropout: the one-launch pair declines; the fused launches carry the mask and re-create it in the reverse sweep)
+        sol = None
+        if not _dropout.is_active(user_func):
+            sol = _small_solve_with_grad(user_func, y0[0], t, method, plan)                  # one launch forward, one backward
         if sol is None:
             sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan)   # any size: fused launches forward, closed-form sweep backward
         if sol is not None:
@@ -228,36 +234,49 @@ class _FixedGridSolve(torch.autograd.Function):
                 form - SpMM, the masked Linear backward (g_S, g_W, g_b in one call), SpMM with A^T with the step size folded
                 into its alpha - and the stage recurrences as one linear-combination launch each.
     No autograd graph per operation: the torch `add` / `mul` launches between the kernels are gone (they were 17 % of the
-    kernel time of a 100k-node Euler training step)."""
+    kernel time of a 100k-node Euler training step).
+    Active dropout (drop = (p, seed, first evaluation number of the solve)): evaluation e of the solve - EVALS[method] per step, in the
+    solver's order - runs with the mask of (seed, first + e) in its launch; the reverse pass re-forms the stages with the same
+    numbers, so the K it masks the backward kernels with are the forward's, and the scalar s = 1 / (1 - p) rides in the alphas."""
+
+    EVALS = {'euler': 1, 'midpoint': 2, 'rk4': 4}
 
     @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, dts):
+    def _drop_at(drop, method, step):
+        """the (p, seed, evaluation) of the first evaluation of grid step `step`"""
+        return None if drop is None else (drop[0], drop[1], drop[2] + step * _FixedGridSolve.EVALS[method])
+
+    @staticmethod
+    def forward(ctx, y0, W, b, csr, flags, method, dts, drop=None):
         n_ticks = len(dts)
         out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
         no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
-        ctx.meta = (csr, no_graph, no_control, method, dts)
+        ctx.meta = (csr, no_graph, no_control, method, dts, drop)
         for i, dt in enumerate(dts):
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dt, out[i + 1])
+            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dt, out[i + 1],
+                                  drop=_FixedGridSolve._drop_at(drop, method, i))
         ctx.save_for_backward(out, W, b)
         return out
 
     @staticmethod
-    def _step(csr, y, W, b, no_graph, no_control, method, dt, out_y, keep=None):
-        """one step by fused launches; keep (a list) receives [(stage input, K), ...] for the reverse sweep"""
+    def _step(csr, y, W, b, no_graph, no_control, method, dt, out_y, keep=None, drop=None):
+        """one step by fused launches; keep (a list) receives [(stage input, K), ...] for the reverse sweep; drop: the dropout triple
+        of the step's first evaluation (the following ones count on from it)"""
         kw = dict(no_graph=no_graph, no_control=no_control)
+        ev = lambda j: {} if drop is None else {'dropout': (drop[0], drop[1], drop[2] + j)}
         f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
         if method == 'euler':
-            K, _ = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [dt], out_y=out_y, **kw)              # y + dt k1
+            K, _ = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(0))              # y + dt k1
             stages = [(y, K)]
         elif method == 'midpoint':
-            K1, ym = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [f32(dt / 2.0)], **kw)             # y + k1 dt / 2 (an exact halving)
-            K2, _ = hip.rhs_rk(csr, ym, W, b, 'combine', y, [], [dt], out_y=out_y, **kw)           # y + dt k2
+            K1, ym = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [f32(dt / 2.0)], **kw, **ev(0))             # y + k1 dt / 2 (an exact halving)
+            K2, _ = hip.rhs_rk(csr, ym, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(1))           # y + dt k2
             stages = [(y, K1), (ym, K2)]
         else:
             stages, x, ks = [], y, []
             for i in range(4):
-                K, nxt = hip.rhs_rk(csr, x, W, b, 'rk4', y, ks, [dt], out_y=out_y if i == 3 else None, **kw)
+                K, nxt = hip.rhs_rk(csr, x, W, b, 'rk4', y, ks, [dt], out_y=out_y if i == 3 else None, **kw, **ev(i))
                 stages.append((x, K))
                 ks = ks + [K]
                 x = nxt
@@ -312,25 +331,34 @@ class _FixedGridSolve(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         out, W, b = ctx.saved_tensors
-        csr, no_graph, no_control, method, dts = ctx.meta
+        csr, no_graph, no_control, method, dts, drop = ctx.meta
         g = g.contiguous()
         n_ticks = len(dts)
         H = out.shape[2]
         a = g[n_ticks]
         gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
         gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
-        vj = lambda u, K, gk, alpha: _FixedGridSolve._vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha)
-
-        def acc(gW, gb, scale):
-            if gW is not None:
-                gW_tot.add_(gW, alpha=scale)
-                gb_tot.add_(gb, alpha=scale)
+        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
         for i in range(n_ticks - 1, -1, -1):
             st = []
             scratch = torch.empty_like(out[0])
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st)
+            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st,
+                                  drop=_FixedGridSolve._drop_at(drop, method, i))
             a = _FixedGridSolve._sweep_step(method, dts[i], st, a, vj, acc, [g[i]])
-        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None
+        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None, None
+
+    @staticmethod
+    def _vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot):
+        """the two closures of _sweep_step.  With dropout K is the masked K' = relu(z) * m, m in {0, s}: J^T g = s * (the p = 0 closed
+        form masked by K'), so s multiplies the alpha of the transposed SpMM and the scale of the parameter gradients"""
+        s = 1.0 if drop is None else _dropout.scale(drop[0])
+        vj = lambda u, K, gk, alpha: _FixedGridSolve._vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha * s)
+
+        def acc(gW, gb, scale):
+            if gW is not None:
+                gW_tot.add_(gW, alpha=scale * s)
+                gb_tot.add_(gb, alpha=scale * s)
+        return vj, acc
 
 
 class _SubstepSolve(torch.autograd.Function):
@@ -353,8 +381,9 @@ class _SubstepSolve(torch.autograd.Function):
         return segs
 
     @staticmethod
-    def _run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, last_out, keep=None):
-        """steps lo .. hi from the state y; the last one writes to `last_out`; keep (a list) receives each step's stages"""
+    def _run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, last_out, keep=None, drop=None):
+        """steps lo .. hi from the state y; the last one writes to `last_out`; keep (a list) receives each step's stages; drop: the
+        solve's dropout triple - grid step i evaluates with the numbers it had in the forward pass, whenever it is run"""
         pp = [None, None]
         for i in range(lo, hi + 1):
             if i == hi:
@@ -365,14 +394,15 @@ class _SubstepSolve(torch.autograd.Function):
                     pp[q] = torch.empty_like(last_out)
                 dst = pp[q]
             st = None if keep is None else []
-            _FixedGridSolve._step(csr, y, W, b, no_graph, no_control, method, float(plan.dts[i]), dst, keep=st)
+            _FixedGridSolve._step(csr, y, W, b, no_graph, no_control, method, float(plan.dts[i]), dst, keep=st,
+                                  drop=_FixedGridSolve._drop_at(drop, method, i))
             if keep is not None:
                 keep.append(st)
             y = dst
         return y
 
     @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, plan):
+    def forward(ctx, y0, W, b, csr, flags, method, plan, drop=None):
         n_ticks = len(plan.t)
         out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
@@ -390,14 +420,14 @@ class _SubstepSolve(torch.autograd.Function):
                 y1 = torch.empty_like(out[0])
                 own.append(y1)
                 where = ('own', len(own) - 1)
-            y = _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, y1)
+            y = _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, y1, drop=drop)
             loose = [e for e in em if not e[1]]
             for q in range(0, len(loose), core.MAX_EMIT):
                 part = loose[q:q + core.MAX_EMIT]
                 hip.tick_emit(y, plan.dts[hi], [e[2] for e in part], outs=[out[e[0]] for e in part])
         if own and where[0] == 'own':
             own.pop()                        # nothing starts from the state after the last step
-        ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts)
+        ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts, drop)
         ctx.save_for_backward(out, W, b, *own)
         return out
 
@@ -405,17 +435,12 @@ class _SubstepSolve(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         out, W, b, *own = ctx.saved_tensors
-        csr, no_graph, no_control, method, plan, segs, starts = ctx.meta
+        csr, no_graph, no_control, method, plan, segs, starts, drop = ctx.meta
         g = g.contiguous()
         H = out.shape[2]
         gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
         gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
-        vj = lambda u, K, gk, alpha: _FixedGridSolve._vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha)
-
-        def acc(gW, gb, scale):
-            if gW is not None:
-                gW_tot.add_(gW, alpha=scale)
-                gb_tot.add_(gb, alpha=scale)
+        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
         a = None
         for (lo, hi), (kind, idx) in zip(reversed(segs), reversed(starts)):
             gs = [g[e[0]] for e in plan.emits[hi]]                       # the ticks this interval's last step reported
@@ -425,13 +450,13 @@ class _SubstepSolve(torch.autograd.Function):
                 a = hip.lincomb(gs[q:q + 8], [1.0] * len(gs[q:q + 8]), y0=a)
             y = out[idx] if kind == 'out' else own[idx]
             keep = []
-            _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep)
+            _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep, drop=drop)
             for i in range(hi, lo - 1, -1):
                 a = _FixedGridSolve._sweep_step(method, float(plan.dts[i]), keep.pop(), a, vj, acc, [])
         if a is None:
             a = torch.zeros_like(out[0])
         a = hip.lincomb([g[0]], [1.0], y0=a)                            # the first tick is y0 itself
-        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None
+        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None, None
 
 
 def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None):
@@ -443,17 +468,25 @@ def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None):
         return None
     csr, _, flags = op
     core.assert_increasing(t)
+    drop = None
+    n_steps = len(plan.dts) if plan is not None else t.numel() - 1
+    if _dropout.is_active(odefunc):
+        # the solve's seed and a block of evaluation numbers, one per evaluation in the solver's order - the numbers the per-operation
+        # path hands out one by one (ODEFunc.forward), so both paths apply the same masks
+        stream = _dropout.current() or _dropout.Stream()
+        drop = (float(odefunc.dropout), stream.seed, stream.take(n_steps * _FixedGridSolve.EVALS[method]))
     if plan is not None:                                      # the step_size option: checkpointed per tick interval
         return _SubstepSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
-                                   method, plan)
+                                   method, plan, drop)
     tt = core.host_grid(t).to(y0.dtype)
     dts = (tt[1:] - tt[:-1]).tolist()
-    from . import tape
-    sol = tape.fixed_grid(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags, method, dts)
-    if sol is not None:
-        return sol
+    if drop is None:                                          # (the C++ tape has no dropout form)
+        from . import tape
+        sol = tape.fixed_grid(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags, method, dts)
+        if sol is not None:
+            return sol
     return _FixedGridSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
-                                 method, dts)
+                                 method, dts, drop)
 
 
 def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
@@ -501,14 +534,15 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
 # device-resident path
 # ---------------------------------------------------------------------------------------------------
 
-def _device_resident_ok(user_func, tensor_input, y0, t, method, options):
+def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_dropout=False):
+    """allow_dropout: the caller (the fixed-grid training path) takes an ACTIVE dropout, 0 < p < 1 in training mode, too"""
     from ...neural_dynamics import ODEFunc
     if not (tensor_input and type(user_func) is ODEFunc):
         return False
     y = y0[0]
     if y.dim() != 2 or y.shape[1] != user_func.hidden_size:
         return False
-    if user_func.training and user_func.dropout > 0:
+    if user_func.training and user_func.dropout > 0 and not (allow_dropout and _dropout.is_active(user_func)):
         return False
     if method in core.FIXED_METHODS:
         if set(options) - {'step_size'}:                      # (odeint hands over what core.fixed_options left: nothing, or the step size)

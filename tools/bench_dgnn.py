@@ -8,6 +8,13 @@ the CPU oracle (torch autograd through the restated solver, same model, same box
 seed twice -> are loss values, gradients after step 1 and the final parameters bit-identical?
 
     python tools/bench_dgnn.py [--case cora|pubmed_topology_H256|all] [--epochs 30] [--oracle-epochs 2]
+
+With --dropout P the model trains with an active dropout on the right-hand side (dgnn.py's own default is 0.5); --dgnn-defaults sets
+the rest of that driver's default command (hidden 16, T = 2, 5 ticks, weight decay 5e-4, with the Linear).  --package-root DIR times
+the package of another checkout (built there) with this script - the A/B against a parent commit; the CPU oracle has no dropout, so
+--dropout implies --oracle-epochs 0.
+    python tools/bench_dgnn.py --case cora --dgnn-defaults --dropout 0.5 --det-epochs 0
+    python tools/bench_dgnn.py --case cora --dgnn-defaults --hidden 256 --no-control --dropout 0.5 --det-epochs 0
 """
 import argparse
 import json
@@ -16,7 +23,13 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+PKG_ROOT = ROOT
+for _i, _a in enumerate(sys.argv):                                  # (before the package is imported)
+    if _a == '--package-root':
+        PKG_ROOT = os.path.abspath(sys.argv[_i + 1])
+    elif _a.startswith('--package-root='):
+        PKG_ROOT = os.path.abspath(_a.split('=', 1)[1])
+sys.path.insert(0, PKG_ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 import torch
@@ -48,6 +61,7 @@ def load_case(name):
 
 HID, T_END, TICKS, RTOL, ATOL, LR, WD = 256, 1.2, 16, 0.1, 0.1, 0.01, 0.024          # the README command
 NO_CONTROL = os.environ.get('NDCN_DGNN_CONTROL', '0') != '1'                          # (NDCN_DGNN_CONTROL=1: with the Linear - the determinism probe of W / b)
+DROPOUT = 0.0
 
 
 def build_hip(case, dev, seed=0):
@@ -58,7 +72,7 @@ def build_hip(case, dev, seed=0):
     torch.manual_seed(seed)
     t = torch.linspace(0, T_END, TICKS).float().to(dev)
     model = nn.Sequential(nn.Linear(feats.shape[1], HID), nn.Tanh(),
-                          ODEBlock2(ODEFunc(HID, adj, dropout=0.0, no_control=NO_CONTROL), t, rtol=RTOL, atol=ATOL, method='dopri5', terminal=True),
+                          ODEBlock2(ODEFunc(HID, adj, dropout=DROPOUT, no_control=NO_CONTROL), t, rtol=RTOL, atol=ATOL, method='dopri5', terminal=True),
                           nn.Linear(HID, ncls)).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=LR, weight_decay=WD)
     return model, opt, torch.from_numpy(feats).to(dev), torch.from_numpy(labels).to(dev), torch.from_numpy(itr).to(dev), torch.from_numpy(iva).to(dev)
@@ -175,20 +189,37 @@ def main():
     ap.add_argument('--epochs', type=int, default=30)
     ap.add_argument('--oracle-epochs', type=int, default=2)
     ap.add_argument('--det-epochs', type=int, default=60)
+    ap.add_argument('--dropout', type=float, default=0.0, help='dropout of the right-hand side in training mode')
+    ap.add_argument('--dgnn-defaults', action='store_true', help="dgnn.py's default command: hidden 16, T 2, 5 ticks, weight decay 5e-4, with the Linear")
+    ap.add_argument('--hidden', type=int, default=None)
+    ap.add_argument('--no-control', action='store_true')
+    ap.add_argument('--package-root', default=None, help='time the ndcn_amd package of another checkout')
     a = ap.parse_args()
+    global HID, T_END, TICKS, WD, NO_CONTROL, DROPOUT
+    if a.dgnn_defaults:
+        HID, T_END, TICKS, WD, NO_CONTROL = 16, 2.0, 5, 5e-4, False
+    if a.hidden is not None:
+        HID = a.hidden
+    if a.no_control:
+        NO_CONTROL = True
+    DROPOUT = a.dropout
+    if DROPOUT > 0:
+        a.oracle_epochs = 0
     dev = torch.device('cuda:0')
     torch.set_num_threads(min(32, os.cpu_count() or 1))
     for name in (['cora', 'pubmed_topology_H256'] if a.case == 'all' else [a.case]):
         case = load_case(name)
         tr, ev = time_hip(case, dev, a.epochs)
-        rec = {'case': 'dgnn differential_gcn, ' + name, 'nodes': int(case[0][3][0]), 'hidden': HID, 'ticks': TICKS, 'method': 'dopri5 rtol=atol=0.1 no_control',
+        rec = {'case': 'dgnn differential_gcn, ' + name, 'nodes': int(case[0][3][0]), 'hidden': HID, 'ticks': TICKS,
+               'method': 'dopri5 rtol=atol=0.1' + (' no_control' if NO_CONTROL else ''), 'dropout': DROPOUT, 'package': PKG_ROOT,
                'hip_s_per_epoch': round(tr + ev, 5), 'hip_train_s': round(tr, 5), 'hip_eval_s': round(ev, 5), 'timed_epochs': a.epochs}
         if name == 'cora':
             rec['readme_s_per_epoch'] = 1.544                       # README.md:72: 772 s for 5 x 100 epochs, hardware not named
         if a.oracle_epochs:
             rec['cpu_oracle_s_per_epoch'] = round(time_oracle(case, a.oracle_epochs), 3)
             rec['cpu_threads'] = torch.get_num_threads()
-        rec['determinism'] = [determinism(case, dev, a.det_epochs, False), determinism(case, dev, a.det_epochs, True)]
+        if a.det_epochs:
+            rec['determinism'] = [determinism(case, dev, a.det_epochs, False), determinism(case, dev, a.det_epochs, True)]
         print(json.dumps(rec), flush=True)
 
 
