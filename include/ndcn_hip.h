@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 23
+#define NDCN_ABI_VERSION 24
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -457,9 +457,10 @@ NDCN_API int ndcn_rk_combine_f32(float *out, const float *y0, const float *const
 NDCN_API int ndcn_rk_error_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_c, int n_k,
                       float rtol, float atol, int64_t n_elem, double *d_out, void *d_ws, void *stream);
 
-/* Reductions of ndcn_rk_error_f32 / ndcn_scaled_sumsq_f32 over at most this many elements reproduce ATen's float32 summation order
- * (torch.mean / Tensor.norm: misc.py:71-76,156 - one workgroup, serial: the reference-sized solves, whose accept / reject decisions
- * hang on the last bit); larger ones use the parallel fixed-order fp64 reduction.  Default 2^18 (environment NDCN_ATEN_NORM_MAX).
+/* Reductions of ndcn_rk_error_f32 / ndcn_scaled_sumsq_f32 over at most this many elements reproduce ATen's SINGLE-THREAD float32
+ * summation order (torch.mean / Tensor.norm: misc.py:71-76,156 - one workgroup, serial: the reference-sized solves, whose accept /
+ * reject decisions hang on the last bit; above 32768 elements torch.sum depends on the size of its thread pool, and the threaded sum
+ * is not reproduced by anything here); larger ones use the parallel fixed-order fp64 reduction.  Default 2^18 (environment NDCN_ATEN_NORM_MAX).
  * This call overrides the bound PROCESS-WIDE at run time (n_elem < 0: back to the default) and returns the previous override
  * (-1: none).  odeint_adjoint's fused reverse pass lowers it around its parameter-gradient vector (65 792 elements riding next
  * to 10^5..10^6-row panels: 0.6 ms serial against 10 us parallel).                                                               */
@@ -757,6 +758,41 @@ NDCN_API int ndcn_debug_last_linear_path(void);
 #define NDCN_RKB_PULL        64     /* ndcn_rk_pull_f32                                                                             */
 #define NDCN_RKB_VEC        128     /* ... by 16 bytes per lane (n % 4 == 0, every panel 16-byte aligned); the grid counts float4 items then */
 NDCN_API int ndcn_debug_last_rk_bwd_path(void);
+/* Which kernel of the FORWARD solver panel operations the last call of this thread launched (ABI 24; tests: each case reaches the kernel,
+ * element path, reduction and grid it targets).  Set by ndcn_rk_combine_f32, ndcn_rk_error_f32, ndcn_scaled_sumsq_f32,
+ * ndcn_dopri5_interp_fit_f32, ndcn_interp_eval_f32, ndcn_dopri5_interp_direct_f32, ndcn_dopri5_interp_direct_multi_f32,
+ * ndcn_fixed_stage_f32, ndcn_tick_emit_f32, ndcn_fixed_stage_emit_f32, ndcn_scale_f32, ndcn_copy_f32 and ndcn_relu_bwd_f32 (and by the
+ * solver's own use of the same wrappers).  Each of these calls clears the word on entry and records its LAST launch: 0 before the
+ * first call, after a call that launched nothing (n_elem = 0 of an element-wise kernel, an argument error) - and a call that takes
+ * several launches reports the last one (ndcn_tick_emit_f32 with more than 8 ticks: the launch of the last group;
+ * ndcn_fixed_stage_emit_f32 with more than 8 ticks: the NDCN_RKF_TICK_EMIT launch behind the stage).  64 bits:
+ *   bits  0..7   the kernel, one of the NDCN_RKF_* numbers below (NDCN_RKF_KERNEL_MASK)
+ *   bits  8..11  op of ndcn_fixed_stage_f32 (0..5) / ndcn_fixed_stage_emit_f32 (0 or 5); 0 otherwise
+ *   bit   12     NDCN_RKF_VEC: 16 bytes per lane (n % 4 == 0 and every panel 16-byte aligned; scale and copy: both panels aligned, any n,
+ *                the n % 4 tail by single elements); the grid counts float4 items then
+ *   bit   13     NDCN_RKF_ATEN: a reduction in ATen's single-thread float32 order (one workgroup; NDCN_RKF_VEC is clear)
+ *   bit   14     NDCN_RKF_PAR64: a reduction by the parallel fixed-order fp64 pair (partial sums per workgroup, then reduce_finish)
+ *   bits 32..63  the grid of that launch in workgroups (streaming kernels go up to 2^24; the partial-sum launch of a reduction, <= 2048) */
+#define NDCN_RKF_COMBINE              1   /* ndcn_rk_combine_f32                                                                   */
+#define NDCN_RKF_ERROR                2   /* ndcn_rk_error_f32                                                                     */
+#define NDCN_RKF_SUMSQ                3   /* ndcn_scaled_sumsq_f32                                                                 */
+#define NDCN_RKF_INTERP_FIT           4   /* ndcn_dopri5_interp_fit_f32                                                            */
+#define NDCN_RKF_INTERP_EVAL          5   /* ndcn_interp_eval_f32                                                                  */
+#define NDCN_RKF_INTERP_DIRECT        6   /* ndcn_dopri5_interp_direct_f32                                                         */
+#define NDCN_RKF_INTERP_DIRECT_MULTI  7   /* ndcn_dopri5_interp_direct_multi_f32                                                   */
+#define NDCN_RKF_FIXED_STAGE          8   /* ndcn_fixed_stage_f32                                                                  */
+#define NDCN_RKF_TICK_EMIT            9   /* ndcn_tick_emit_f32                                                                    */
+#define NDCN_RKF_FIXED_STAGE_EMIT    10   /* ndcn_fixed_stage_emit_f32                                                             */
+#define NDCN_RKF_SCALE               11   /* ndcn_scale_f32                                                                        */
+#define NDCN_RKF_COPY                12   /* ndcn_copy_f32                                                                         */
+#define NDCN_RKF_RELU_BWD            13   /* ndcn_relu_bwd_f32 (always by single elements)                                         */
+#define NDCN_RKF_KERNEL_MASK       0xff
+#define NDCN_RKF_OP_SHIFT             8
+#define NDCN_RKF_VEC             0x1000
+#define NDCN_RKF_ATEN            0x2000
+#define NDCN_RKF_PAR64           0x4000
+#define NDCN_RKF_GRID_SHIFT          32
+NDCN_API int64_t ndcn_debug_last_rk_path(void);
 /* Which SpMM kernel the LAST SpMM of this thread launched (ABI 21; tests: each case reaches the route it targets): ndcn_spmm_f32, and the
  * no_control epilogues of ndcn_rhs_rk_f32 (NDCN_PATH_REC / NDCN_PATH_WIDE above).  A family bit | NDCN_SPMM_VEC | NDCN_SPMM_HALO |
  * (LPR or NV) << NDCN_SPMM_LANES_SHIFT | record shape << NDCN_SPMM_REC_SHIFT | mode << NDCN_SPMM_MODE_SHIFT | rows_per_block <<

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
@@ -24,6 +24,11 @@ RKB_COMBINE, RKB_ERROR, RKB_RMS, RKB_DENSE, RKB_DENSE_MULTI, RKB_DOT_DIFF, RKB_P
 # SpMM launch (include/ndcn_hip.h NDCN_SPMM_*)
 SPMM_CSR, SPMM_WIDE, SPMM_REC, SPMM_SWEEP, SPMM_HUB, SPMM_VEC, SPMM_HALO = 1, 2, 4, 8, 16, 32, 64
 SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 20
+# ndcn_debug_last_rk_path (64 bits): kernel | op << 8 | RKF_VEC | RKF_ATEN | RKF_PAR64 | grid << 32 of the last forward panel launch
+# (include/ndcn_hip.h NDCN_RKF_*)
+(RKF_COMBINE, RKF_ERROR, RKF_SUMSQ, RKF_INTERP_FIT, RKF_INTERP_EVAL, RKF_INTERP_DIRECT, RKF_INTERP_DIRECT_MULTI, RKF_FIXED_STAGE,
+ RKF_TICK_EMIT, RKF_FIXED_STAGE_EMIT, RKF_SCALE, RKF_COPY, RKF_RELU_BWD) = range(1, 14)
+RKF_KERNEL_MASK, RKF_OP_SHIFT, RKF_VEC, RKF_ATEN, RKF_PAR64, RKF_GRID_SHIFT = 0xff, 8, 0x1000, 0x2000, 0x4000, 32
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6
@@ -245,6 +250,7 @@ SIGNATURES = {
     'ndcn_debug_last_linear_path': (_I, []),
     'ndcn_debug_last_rk_bwd_path': (_I, []),
     'ndcn_debug_last_spmm_path': (_I, []),
+    'ndcn_debug_last_rk_path': (_L, []),
     'ndcn_set_range_guard': (_I, [_I]),
 }
 

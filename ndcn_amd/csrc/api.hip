@@ -44,6 +44,7 @@ int ndcn_debug_last_rhs_path(void) { return g_last_rhs_path; }
 int ndcn_debug_last_linear_path(void) { return g_last_linear_path; }
 int ndcn_debug_last_rk_bwd_path(void) { return g_last_rk_bwd_path; }
 int ndcn_debug_last_spmm_path(void) { return g_last_spmm_path; }
+int64_t ndcn_debug_last_rk_path(void) { return g_last_rk_path; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
 const char *ndcn_last_error(void) { return g_err; }
 
@@ -231,6 +232,8 @@ int ndcn_dopri5_interp_bwd_f32(const float *g, const float *y0, const float *y1,
 int ndcn_dopri5_interp_direct_multi_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                                         const float *h_xpow, float *const *h_out, int n_t, int64_t n_elem, void *stream) {
     NDCN_CHECK_ARG(n_elem >= 0 && y0 && y1 && h_k && h_cmid && h_xpow && h_out, "bad argument");
+    // the header's contract: n_t <= 7, the ticks its VJP (ndcn_dopri5_interp_bwd_multi_f32) takes; the solver's own launches carry 8
+    if (n_t < 1 || n_t > 7) { g_last_rk_path = 0; set_error("interp_direct_multi: 1..7 ticks per call"); return NDCN_EINVAL; }
     return interp_direct_multi_f32(y0, y1, h_k, h_cmid, dt, h_xpow, h_out, n_t, n_elem, ST(stream));
 }
 

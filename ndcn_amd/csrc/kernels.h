@@ -163,6 +163,7 @@ bool prof_pause(bool on);     // returns the previous state
 extern thread_local int g_last_linear_path;  // ndcn_debug_last_linear_path (linear.hip)
 extern thread_local int g_last_rk_bwd_path;  // ndcn_debug_last_rk_bwd_path (rk_bwd.hip)
 extern thread_local int g_last_spmm_path;    // ndcn_debug_last_spmm_path (spmm.hip)
+extern thread_local int64_t g_last_rk_path;  // ndcn_debug_last_rk_path (rk.hip)
 extern thread_local int g_last_rhs_path;     // ndcn_debug_last_rhs_path     // no launch timing while a stream is being captured
 int scaled_sumsq_f32(const float *a, const float *b, const float *y, float rtol, float atol, int64_t n, double *d_out,
                      void *d_ws, hipStream_t st);

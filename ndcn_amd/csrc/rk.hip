@@ -17,6 +17,12 @@ namespace ndcn {
 constexpr int kMaxTerms = 8;
 constexpr int kRedBlocks = 2048;       // partial sums per reduction (deterministic two-pass)
 
+// ndcn_debug_last_rk_path (include/ndcn_hip.h NDCN_RKF_*): every host wrapper below clears it on entry and records its LAST launch
+thread_local int64_t g_last_rk_path = 0;
+static void record_path(int kernel, bool vec, int64_t grid, int extra = 0) {
+    g_last_rk_path = (int64_t)(kernel | (vec ? NDCN_RKF_VEC : 0) | extra) | (grid << NDCN_RKF_GRID_SHIFT);
+}
+
 struct Terms {
     const float *k[kMaxTerms];
     float c[kMaxTerms];
@@ -37,9 +43,10 @@ __device__ __forceinline__ void apply_dt(Terms &t) {
 __device__ __forceinline__ float4 ld4(const float *p, int64_t i) { return reinterpret_cast<const float4 *>(p)[i]; }
 __device__ __forceinline__ void st4(float *p, int64_t i, float4 v) { reinterpret_cast<float4 *>(p)[i] = v; }
 
-// sum_j c_j * k_j[i], left to right, separate roundings  (misc.py:22-25)
+// sum_j c_j * k_j[i], left to right, separate roundings  (misc.py:22-25).  Python's sum() starts from 0: the first product is
+// added to +0, which turns a -0 product into +0 (contraction is off, so the addition stays)
 __device__ __forceinline__ float wsum1(const Terms &t, int64_t i) {
-    float acc = t.c[0] * t.k[0][i];
+    float acc = 0.f + t.c[0] * t.k[0][i];
 #pragma unroll
     for (int j = 1; j < kMaxTerms; ++j)
         if (j < t.n) acc = acc + t.c[j] * t.k[j][i];
@@ -47,7 +54,7 @@ __device__ __forceinline__ float wsum1(const Terms &t, int64_t i) {
 }
 __device__ __forceinline__ float4 wsum4(const Terms &t, int64_t i) {
     float4 k = ld4(t.k[0], i);
-    float4 acc = make_float4(t.c[0] * k.x, t.c[0] * k.y, t.c[0] * k.z, t.c[0] * k.w);
+    float4 acc = make_float4(0.f + t.c[0] * k.x, 0.f + t.c[0] * k.y, 0.f + t.c[0] * k.z, 0.f + t.c[0] * k.w);
 #pragma unroll
     for (int j = 1; j < kMaxTerms; ++j)
         if (j < t.n) {
@@ -97,10 +104,13 @@ __device__ __forceinline__ void block_sum2(double &a, double &b) {
     }
 }
 
-// Panels up to this many elements are reduced in ATen's float32 order - the order of ONE torch CPU build: torch 2.10.0, x86-64
-// AVX2 kernels (8-lane vectors, 4 interleaved accumulators, the cascade sum of SumKernel.cpp), which is what the reference's
-// Python executed when the fixtures under tests/golden were captured; an AVX-512 dispatch or another torch version sums in
-// another order and these kernels would then match IT no better than any parallel reduction does.  The one-workgroup serial
+// Panels up to this many elements are reduced in ATen's SINGLE-THREAD float32 order - the order of ONE torch CPU build: torch 2.10.0,
+// x86-64 (8-lane vectors, 4 interleaved accumulators, the cascade sum of SumKernel.cpp), which is what the reference's
+// Python executed when the fixtures under tests/golden were captured; another vector width or another torch version sums in
+// another order and these kernels would then match IT no better than any parallel reduction does.  Single-thread: above 32768
+// elements torch.sum hands slices of the row to its thread pool and its result depends on the thread count (norm() did not at 2^18);
+// that threaded sum is reproduced by nothing here.  tests/_aten_order.py states the order in numpy; tests/test_aten_order_host.py
+// compares it with torch under one thread.  The one-workgroup serial
 // form costs ~4 ns per element and lane group (2^18 elements: ~0.13 ms), so it is confined to the sizes where a last-bit
 // difference of the mean can flip an accept / reject decision and a reference run exists to compare with: 2^18 elements
 // covers every reference-sized solve (the README commands: 400 x 20; Cora 2708 x 64).  NDCN_ATEN_NORM_MAX=<elements> moves
@@ -254,7 +264,9 @@ __device__ __forceinline__ float scaled_sq(float a, float b, float y, float rtol
 // The same sum in the order ATen's float32 `norm` forms it (torch 2.x CPU, the build the fixtures were captured with;
 // found by matching torch's result bit for bit on 60 random vectors, tools/micro/aten_norm_order.py): EIGHT running sums -
 // lane j owns elements j, j + 8, j + 16, ... and accumulates acc_j = fma(q, q, acc_j) in index order - added up left to
-// right, then the n % 8 tail elements with fma.  The reference's initial step (misc.py:121-138) takes three such norms; at
+// right, then the n % 8 tail elements: with fma - except that a tail of 4..7 elements has its FIRST FOUR added as separately rounded
+// products (the compiler of that torch build vectorised the tail loop by four with an in-order reduction; found by
+// tests/test_aten_order_host.py, which compares tests/_aten_order.py with torch at every n).  The reference's initial step (misc.py:121-138) takes three such norms; at
 // rtol 1e-7 a 1-ulp difference there reshuffles later accept / reject decisions (the error estimate is then a cancellation
 // of O(1e-9) terms), so for panels up to aten_order_max_elems() elements the sum is formed in exactly that order: one workgroup,
 // q = (a - b) / scale computed by all threads into LDS, then 8 lanes walk their chains.  Larger panels keep the parallel
@@ -314,7 +326,9 @@ __global__ __launch_bounds__(kAtenThreads) void scaled_sumsq_aten_kernel(const f
             const float av = a[i];
             const float scale = atol + fabsf(y[i]) * rtol;
             const float qq = HASB ? (av - b[i]) / scale : av / scale;
-            s = fmaf(qq, qq, s);
+            // torch's build runs a tail of four or more elements as one 4-wide product (each rounded) added in index order, and
+            // only what is left after those four by fma (contraction is off in this file: s + qq * qq keeps both roundings)
+            s = (n - n8 >= 4 && i < n8 + 4) ? s + qq * qq : fmaf(qq, qq, s);
             tb += (int)nonfinite(av);
         }
         out[0] = (double)s;
@@ -413,9 +427,10 @@ __device__ __forceinline__ void fit1(float y0, float y1, float ms, float f0, flo
                                      float &c, float &d) {
     const float ym = y0 + ms;                                                  // dopri5.py:42
     // interp.py:21-35 -- `_dot_product` sums c*x products left to right; -2*dt etc. are fp32 scalars
-    a = ((((-2.f * dt) * f0 + (2.f * dt) * f1) + -8.f * y0) + -8.f * y1) + 16.f * ym;
-    b = ((((5.f * dt) * f0 + (-3.f * dt) * f1) + 18.f * y0) + 14.f * y1) + -32.f * ym;
-    c = ((((-4.f * dt) * f0 + dt * f1) + -11.f * y0) + -5.f * y1) + 16.f * ym;
+    // (sum() starts from 0: 0 + the first product, as in wsum1)
+    a = ((((0.f + (-2.f * dt) * f0) + (2.f * dt) * f1) + -8.f * y0) + -8.f * y1) + 16.f * ym;
+    b = ((((0.f + (5.f * dt) * f0) + (-3.f * dt) * f1) + 18.f * y0) + 14.f * y1) + -32.f * ym;
+    c = ((((0.f + (-4.f * dt) * f0) + dt * f1) + -11.f * y0) + -5.f * y1) + 16.f * ym;
     d = dt * f0;
 }
 
@@ -447,7 +462,7 @@ struct EvalArgs {
 
 __device__ __forceinline__ float eval1(float a, float b, float c, float d, float e, const EvalArgs &p) {
     // interp.py:65: a*x^4 + b*x^3 + c*x^2 + d*x + e*1, left to right
-    return (((a * p.x4 + b * p.x3) + c * p.x2) + d * p.x1) + e * p.x0;
+    return ((((0.f + a * p.x4) + b * p.x3) + c * p.x2) + d * p.x1) + e * p.x0;
 }
 
 template <bool VEC>
@@ -473,7 +488,7 @@ struct DirectArgs {
 __device__ __forceinline__ float direct1(float y0, float y1, float ms, float f0, float f1, const DirectArgs &p) {
     float a, b, c, d;
     fit1(y0, y1, ms, f0, f1, p.f.dt, a, b, c, d);
-    return (((a * p.x4 + b * p.x3) + c * p.x2) + d * p.x1) + y0 * p.x0;     // interp.py:65, e = y0
+    return ((((0.f + a * p.x4) + b * p.x3) + c * p.x2) + d * p.x1) + y0 * p.x0;     // interp.py:65, e = y0
 }
 
 template <bool VEC>
@@ -501,7 +516,7 @@ struct DirectMultiArgs {
 };
 
 __device__ __forceinline__ float poly1(float a, float b, float c, float d, float y0, const float *xp) {
-    return (((a * xp[0] + b * xp[1]) + c * xp[2]) + d * xp[3]) + y0 * xp[4];      // interp.py:65, e = y0
+    return ((((0.f + a * xp[0]) + b * xp[1]) + c * xp[2]) + d * xp[3]) + y0 * xp[4];      // interp.py:65, e = y0
 }
 
 template <bool VEC>
@@ -660,10 +675,13 @@ __global__ __launch_bounds__(256) void fixed_stage_emit_kernel(float *out, const
 }
 
 int copy_f32(float *dst, const float *src, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_STAGE, st, 8.0 * n, 0.0);
     const int64_t n4 = (aligned16(dst) && aligned16(src)) ? n / 4 : 0;
-    hipLaunchKernelGGL(copy_kernel, dim3(stream_grid_full(n4 ? n4 : n, 256)), dim3(256), 0, st, dst, src, n4, n);
+    const int g = stream_grid_full(n4 ? n4 : n, 256);
+    hipLaunchKernelGGL(copy_kernel, dim3(g), dim3(256), 0, st, dst, src, n4, n);
+    record_path(NDCN_RKF_COPY, n4 > 0, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -676,20 +694,26 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(float *__restrict__ out, 
 }
 
 int relu_bwd_f32(float *out, const float *g, const float *y, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_RELU_BWD, st, 12.0 * n, 0.0);
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, g, y, n);
+    const int grid = stream_grid_full(n, 256);
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid), dim3(256), 0, st, out, g, y, n);
+    record_path(NDCN_RKF_RELU_BWD, false, grid);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
 
 int scale_f32(float *out, const float *x, float w, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_STAGE, st, 8.0 * n, 1.0 * n);
     // views at odd element offsets (torch.stack's backward hands out slices of one buffer): scalar path, like the
     // other panel kernels of this file
     const int64_t n4 = (aligned16(out) && aligned16(x)) ? n / 4 : 0;
-    hipLaunchKernelGGL(scale_kernel, dim3(stream_grid_full((n4 ? n4 : n) + 1, 256)), dim3(256), 0, st, out, x, w, n4, n);
+    const int g = stream_grid_full((n4 ? n4 : n) + 1, 256);
+    hipLaunchKernelGGL(scale_kernel, dim3(g), dim3(256), 0, st, out, x, w, n4, n);
+    record_path(NDCN_RKF_SCALE, n4 > 0, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -718,14 +742,17 @@ static bool fill_terms(Terms &t, const float *const *h_k, const float *h_c, int 
 
 int rk_combine_f32(float *out, const float *y0, const float *const *h_k, const float *h_c, int n_k, int64_t n,
                    hipStream_t st, const float *dt_dev) {
+    g_last_rk_path = 0;
     Terms t;
     t.dt_dev = dt_dev;
     bool vec = (n % 4 == 0) && aligned16(out) && (!y0 || aligned16(y0));
     if (!fill_terms(t, h_k, h_c, n_k, vec)) { set_error("rk_combine: need 1..%d non-null terms", kMaxTerms); return NDCN_EINVAL; }
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_COMBINE, st, 4.0 * n * (n_k + 2), 2.0 * n * n_k);
-    if (vec) hipLaunchKernelGGL((combine_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y0, t, n / 4);
-    else hipLaunchKernelGGL((combine_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y0, t, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((combine_kernel<true>), dim3(g), dim3(256), 0, st, out, y0, t, n / 4);
+    else hipLaunchKernelGGL((combine_kernel<false>), dim3(g), dim3(256), 0, st, out, y0, t, n);
+    record_path(NDCN_RKF_COMBINE, vec, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -761,6 +788,7 @@ static int red_grid(int64_t items) {
 
 int rk_error_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_c, int n_k, float rtol,
                  float atol, int64_t n, double *d_out, void *d_ws, hipStream_t st, const float *dt_dev, int accum) {
+    g_last_rk_path = 0;
     Terms t;
     t.dt_dev = dt_dev;
     bool vec = (n % 4 == 0) && aligned16(y0) && aligned16(y1);
@@ -768,6 +796,7 @@ int rk_error_f32(const float *y0, const float *y1, const float *const *h_k, cons
     if (n >= 8 && n <= aten_order_max_elems()) {
         ProfScope prof(PROF_ERROR, st, 4.0 * n * (n_k + 2), 2.0 * n * (n_k + 4));
         hipLaunchKernelGGL(rk_error_aten_kernel, dim3(1), dim3(kAtenThreads), 0, st, y0, y1, t, rtol, atol, n, d_out, accum);
+        record_path(NDCN_RKF_ERROR, false, 1, NDCN_RKF_ATEN);
         NDCN_LAUNCH_CHECK();
         return NDCN_OK;
     }
@@ -778,16 +807,19 @@ int rk_error_f32(const float *y0, const float *y1, const float *const *h_k, cons
     if (vec) hipLaunchKernelGGL((rk_error_kernel<true>), dim3(g), dim3(256), 0, st, y0, y1, t, rtol, atol, items, partial);
     else hipLaunchKernelGGL((rk_error_kernel<false>), dim3(g), dim3(256), 0, st, y0, y1, t, rtol, atol, items, partial);
     hipLaunchKernelGGL(reduce_finish_kernel, dim3(1), dim3(256), 0, st, partial, g, d_out, accum);
+    record_path(NDCN_RKF_ERROR, vec, g, NDCN_RKF_PAR64);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
 
 int scaled_sumsq_f32(const float *a, const float *b, const float *y, float rtol, float atol, int64_t n, double *d_out,
                      void *d_ws, hipStream_t st) {
+    g_last_rk_path = 0;
     if (n > 0 && n <= aten_order_max_elems()) {
         ProfScope prof(PROF_SUMSQ, st, 4.0 * n * (b ? 3 : 2), 6.0 * n);
         if (b) hipLaunchKernelGGL(scaled_sumsq_aten_kernel<true>, dim3(1), dim3(kAtenThreads), 0, st, a, b, y, rtol, atol, n, d_out);
         else hipLaunchKernelGGL(scaled_sumsq_aten_kernel<false>, dim3(1), dim3(kAtenThreads), 0, st, a, b, y, rtol, atol, n, d_out);
+        record_path(NDCN_RKF_SUMSQ, false, 1, NDCN_RKF_ATEN);
         NDCN_LAUNCH_CHECK();
         return NDCN_OK;
     }
@@ -801,6 +833,7 @@ int scaled_sumsq_f32(const float *a, const float *b, const float *y, float rtol,
     else { if (b) NDCN_SS(false, true); else NDCN_SS(false, false); }
 #undef NDCN_SS
     hipLaunchKernelGGL(reduce_finish_kernel, dim3(1), dim3(256), 0, st, partial, g, d_out, 0);
+    record_path(NDCN_RKF_SUMSQ, vec, g, NDCN_RKF_PAR64);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -823,6 +856,7 @@ int scaled_sumsq_pair_f32(const float *f, const float *y, float rtol, float atol
 
 int interp_fit_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, float *a,
                    float *b, float *c, float *d, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     FitArgs p;
     bool vec = (n % 4 == 0) && aligned16(y0) && aligned16(y1) && aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d);
     // drop zero coefficients (c_mid[1] == 0): the product would be an exact zero
@@ -840,14 +874,17 @@ int interp_fit_f32(const float *y0, const float *y1, const float *const *h_k, co
     p.y0 = y0; p.y1 = y1; p.f0 = h_k[0]; p.f1 = h_k[6]; p.dt = dt; p.a = a; p.b = b; p.c = c; p.d = d;
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_FIT, st, 4.0 * n * (2 + m + 4), 2.0 * n * (m + 16));
-    if (vec) hipLaunchKernelGGL((interp_fit_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, p, n / 4);
-    else hipLaunchKernelGGL((interp_fit_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, p, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((interp_fit_kernel<true>), dim3(g), dim3(256), 0, st, p, n / 4);
+    else hipLaunchKernelGGL((interp_fit_kernel<false>), dim3(g), dim3(256), 0, st, p, n);
+    record_path(NDCN_RKF_INTERP_FIT, vec, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
 
 int interp_direct_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                       const float xp[5], float *out, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     DirectArgs p;
     bool vec = (n % 4 == 0) && aligned16(y0) && aligned16(y1) && aligned16(out);
     const float *kk[kMaxTerms];
@@ -867,14 +904,17 @@ int interp_direct_f32(const float *y0, const float *y1, const float *const *h_k,
     p.out = out;
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_EVAL, st, 4.0 * n * (2 + m + 1), 2.0 * n * (m + 24));
-    if (vec) hipLaunchKernelGGL((interp_direct_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, p, n / 4);
-    else hipLaunchKernelGGL((interp_direct_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, p, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((interp_direct_kernel<true>), dim3(g), dim3(256), 0, st, p, n / 4);
+    else hipLaunchKernelGGL((interp_direct_kernel<false>), dim3(g), dim3(256), 0, st, p, n);
+    record_path(NDCN_RKF_INTERP_DIRECT, vec, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
 
 int interp_direct_multi_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                             const float *h_xp /*nt x 5*/, float *const *h_out, int nt, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (nt < 1 || nt > kMaxTicks) { set_error("interp_direct_multi: 1..%d ticks per launch", kMaxTicks); return NDCN_EINVAL; }
     DirectMultiArgs p;
     bool vec = (n % 4 == 0) && aligned16(y0) && aligned16(y1);
@@ -899,20 +939,25 @@ int interp_direct_multi_f32(const float *y0, const float *y1, const float *const
     }
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_EVAL, st, 4.0 * n * (2 + m + nt), 2.0 * n * (m + 16 + 9 * nt));
-    if (vec) hipLaunchKernelGGL((interp_direct_multi_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, p, n / 4);
-    else hipLaunchKernelGGL((interp_direct_multi_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, p, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((interp_direct_multi_kernel<true>), dim3(g), dim3(256), 0, st, p, n / 4);
+    else hipLaunchKernelGGL((interp_direct_multi_kernel<false>), dim3(g), dim3(256), 0, st, p, n);
+    record_path(NDCN_RKF_INTERP_DIRECT_MULTI, vec, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
 
 int interp_eval_f32(const float *a, const float *b, const float *c, const float *d, const float *e, const float xp[5],
                     float *out, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     EvalArgs p{a, b, c, d, e, xp[0], xp[1], xp[2], xp[3], xp[4], out};
     const bool vec = (n % 4 == 0) && aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e) && aligned16(out);
     if (n == 0) return NDCN_OK;
     ProfScope prof(PROF_EVAL, st, 4.0 * n * 6, 9.0 * n);
-    if (vec) hipLaunchKernelGGL((interp_eval_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, p, n / 4);
-    else hipLaunchKernelGGL((interp_eval_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, p, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((interp_eval_kernel<true>), dim3(g), dim3(256), 0, st, p, n / 4);
+    else hipLaunchKernelGGL((interp_eval_kernel<false>), dim3(g), dim3(256), 0, st, p, n);
+    record_path(NDCN_RKF_INTERP_EVAL, vec, g);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }
@@ -920,12 +965,15 @@ int interp_eval_f32(const float *a, const float *b, const float *c, const float 
 template <int OP>
 static void launch_stage(bool vec, float *out, const float *y, const float *k1, const float *k2, const float *k3,
                          const float *k4, float dt, const float *dt_dev, int64_t n, hipStream_t st) {
-    if (vec) hipLaunchKernelGGL((fixed_stage_kernel<OP, true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, dt, dt_dev, n / 4);
-    else hipLaunchKernelGGL((fixed_stage_kernel<OP, false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, dt, dt_dev, n);
+    const int g = stream_grid_full(vec ? n / 4 : n, 256);
+    if (vec) hipLaunchKernelGGL((fixed_stage_kernel<OP, true>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, dt, dt_dev, n / 4);
+    else hipLaunchKernelGGL((fixed_stage_kernel<OP, false>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, dt, dt_dev, n);
+    record_path(NDCN_RKF_FIXED_STAGE, vec, g, OP << NDCN_RKF_OP_SHIFT);
 }
 
 int fixed_stage_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3,
                     const float *k4, float dt, int64_t n, hipStream_t st, const float *dt_dev) {
+    g_last_rk_path = 0;
     const int need = op <= 2 ? 1 : op == 3 ? 2 : op == 4 ? 3 : 4;
     const float *ks[4] = {k1, k2, k3, k4};
     bool vec = (n % 4 == 0) && aligned16(out) && aligned16(y);
@@ -966,6 +1014,7 @@ static bool fill_emit(EmitArgs &e, float dt, const float *h_tm, const int *h_sam
 }
 
 int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (nt < 0 || (nt > 0 && (!y || !h_tm || !h_same || !h_out))) { set_error("tick_emit: null argument"); return NDCN_EINVAL; }
     for (int lo = 0; lo < nt; lo += kMaxTicks) {                // more than kMaxTicks ticks in one step: one launch per kMaxTicks
         const int m = nt - lo < kMaxTicks ? nt - lo : kMaxTicks;
@@ -974,8 +1023,10 @@ int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same
         if (!fill_emit(e, dt, h_tm + lo, h_same + lo, h_out + lo, m, vec)) { set_error("tick_emit: null tick panel"); return NDCN_EINVAL; }
         if (n == 0) continue;
         ProfScope prof(PROF_STAGE, st, 4.0 * n * (1 + m), 3.0 * n * m);
-        if (vec) hipLaunchKernelGGL((tick_emit_kernel<true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, y, e, n / 4);
-        else hipLaunchKernelGGL((tick_emit_kernel<false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, y, e, n);
+        const int g = stream_grid_full(vec ? n / 4 : n, 256);
+        if (vec) hipLaunchKernelGGL((tick_emit_kernel<true>), dim3(g), dim3(256), 0, st, y, e, n / 4);
+        else hipLaunchKernelGGL((tick_emit_kernel<false>), dim3(g), dim3(256), 0, st, y, e, n);
+        record_path(NDCN_RKF_TICK_EMIT, vec, g);
         NDCN_LAUNCH_CHECK();
     }
     return NDCN_OK;
@@ -983,6 +1034,7 @@ int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same
 
 int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3, const float *k4,
                          float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st) {
+    g_last_rk_path = 0;
     if (op != 0 && op != 5) { set_error("fixed_stage_emit: op %d does not end a step (0 or 5)", op); return NDCN_EINVAL; }
     if (nt < 1 || !h_tm || !h_same || !h_out) { set_error("fixed_stage_emit: needs at least one tick"); return NDCN_EINVAL; }
     const int need = op == 0 ? 1 : 4;
@@ -1000,13 +1052,15 @@ int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, co
     if (!fill_emit(e, dt, h_tm, h_same, h_out, m, vec)) { set_error("fixed_stage_emit: null tick panel"); return NDCN_EINVAL; }
     if (n > 0) {
         ProfScope prof(PROF_STAGE, st, 4.0 * n * (need + 2 + m), 2.0 * n * need + 3.0 * n * m);
+        const int g = stream_grid_full(vec ? n / 4 : n, 256);
         if (op == 0) {
-            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<0, true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
-            else hipLaunchKernelGGL((fixed_stage_emit_kernel<0, false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
+            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<0, true>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
+            else hipLaunchKernelGGL((fixed_stage_emit_kernel<0, false>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
         } else {
-            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<5, true>), dim3(stream_grid_full(n / 4, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
-            else hipLaunchKernelGGL((fixed_stage_emit_kernel<5, false>), dim3(stream_grid_full(n, 256)), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
+            if (vec) hipLaunchKernelGGL((fixed_stage_emit_kernel<5, true>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n / 4);
+            else hipLaunchKernelGGL((fixed_stage_emit_kernel<5, false>), dim3(g), dim3(256), 0, st, out, y, k1, k2, k3, k4, e, n);
         }
+        record_path(NDCN_RKF_FIXED_STAGE_EMIT, vec, g, op << NDCN_RKF_OP_SHIFT);
         NDCN_LAUNCH_CHECK();
     }
     if (nt > m) return tick_emit_f32(out, dt, h_tm + m, h_same + m, h_out + m, nt - m, n, st);

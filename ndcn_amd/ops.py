@@ -704,11 +704,11 @@ class HipOps:
 
     @staticmethod
     def interp_direct_multi(y0, y1, ks, cmid, dt, xpows):
-        """len(xpows) <= 8 ticks of one step in one pass: [dense output at each tick] - per tick the arithmetic of interp_direct."""
+        """len(xpows) <= 7 ticks of one step in one pass: [dense output at each tick] - per tick the arithmetic of interp_direct."""
         y0, y1 = _panel(y0), _panel(y1)
         ks = [_panel(k) for k in ks]
         nt = len(xpows)
-        assert len(ks) == 7 and 1 <= nt <= 8
+        assert len(ks) == 7 and 1 <= nt <= 7
         outs = [torch.empty_like(y0) for _ in range(nt)]
         arr_k, arr_c, _ = _terms(ks, cmid)
         xp = (_F * (5 * nt))(*[float(v) for row in xpows for v in row])

@@ -26,6 +26,20 @@ def _bad(x):
     return float((~torch.isfinite(x)).sum())
 
 
+class one_thread:
+    """torch's float32 `sum` depends on the size of its thread pool above 32768 elements; the HIP kernels reproduce the SINGLE-THREAD
+    order (tests/_aten_order.py, pinned by tests/test_aten_order_host.py).  The float32 reductions an assertion compares bit for bit
+    are formed inside this context; the previous thread count comes back whatever happens."""
+    def __enter__(self):
+        self.prev = torch.get_num_threads()
+        torch.set_num_threads(1)
+        return self
+
+    def __exit__(self, *exc):
+        torch.set_num_threads(self.prev)
+        return False
+
+
 class OracleOps:
     name = 'oracle'
     differentiable = True          # plain torch: the sharded training path differentiates straight through it
@@ -113,18 +127,22 @@ class OracleOps:
         err = _wsum(ks, cs)
         tol = atol + rtol * torch.max(torch.abs(y0), torch.abs(y1))
         r = err / tol
-        # the float32 sum ATen forms for torch.mean (what the HIP kernel reproduces in ATen's cascade order for panels
+        # the float32 sum ATen forms for torch.mean ON ONE THREAD (what the HIP kernel reproduces in ATen's cascade order for panels
         # <= 2^20 elements); fp64 above that, like the product
         v = r * r
-        return float(v.sum().double() if 8 <= v.numel() <= (1 << 20) else v.double().sum()), _bad(y1)
+        with one_thread():
+            s = float(v.sum().double() if 8 <= v.numel() <= (1 << 20) else v.double().sum())
+        return s, _bad(y1)
 
     @staticmethod
     def scaled_sumsq(a, b, y, rtol, atol):
         scale = atol + torch.abs(y) * rtol
         q = (a / scale) if b is None else ((a - b) / scale)
-        # the float32 norm ATen forms (what the HIP kernel reproduces in ATen's summation order for panels <= 2^20
+        # the float32 norm ATen forms on one thread (what the HIP kernel reproduces in ATen's summation order for panels <= 2^20
         # elements): returned as the double whose square root is that norm exactly
-        return float(q.norm().double() ** 2), _bad(a)
+        with one_thread():
+            nrm = q.norm().double()
+        return float(nrm ** 2), _bad(a)
 
     @staticmethod
     def interp_fit(y0, y1, ks, cmid, dt):
