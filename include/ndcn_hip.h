@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 24
+#define NDCN_ABI_VERSION 25
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -639,6 +639,30 @@ NDCN_API int ndcn_solver_advance(ndcn_solver *s, double next_t, float *out, int6
  * steps: heat_dynamics.py:35,123; dgnn.py:173-182); same arithmetic per element as ndcn_solver_advance.  Fixed grid:
  * one step per tick.                                                                                     */
 NDCN_API int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, void *stream);
+/* Inference: ndcn_solver_advance_many with the decoder Linear(H, C) of neural_dynamics.py:148-160 applied to every tick as it is
+ * produced, so that the hidden trajectory (n_ticks x n_rows x H) is never stored: out[i] (n_rows x C, panels back to back) =
+ * Wd y(h_ticks[i]) + bd with Wd [C][H] row-major and bd [C] nullable - bit for bit ndcn_linear_f32 of the panel
+ * ndcn_solver_advance_many writes there.  The steps, their launches and the accept / reject log are ndcn_solver_advance_many's.
+ *   dopri5      the ticks of a fresh accepted step are evaluated AND decoded in one pass over the step's panels (<= 8 per launch: a
+ *               wave per row holds the fitted row in registers and dots it with Wd in the lane order of the decoder's row-dot
+ *               kernel); the single-tick paths (a stored fit, a tick without a fresh step) evaluate into `scratch` first
+ *   fixed grid  one step per tick with the state inside the solver (Euler whose update rides in the right-hand side's epilogue
+ *               alternates between the solver's panel and `scratch`), each new state decoded by ndcn_linear_f32
+ *   scratch     caller-owned device memory, room for two n_rows x H panels (the staged ticks and the Euler alternation use the
+ *               first; the second is reserved); free after the call
+ * Declines with NDCN_EINVAL: a sharded solver; H outside 64..512 or C outside 1..15 (the decoder's row-dot route); a fixed-grid
+ * solve that ndcn_solve_small_supported would run as one launch (states of at most 1 MB: decode that trajectory instead).  The
+ * step_size grid has no such form: ndcn_solver_advance_grid writes hidden ticks.  These are decided before anything else, so a call
+ * with n_ticks = 0 (valid before ndcn_solver_begin, touches nothing) asks whether the solver would decline.
+ * ndcn_last_readout_path: what the last call on this thread ran (cleared on its entry, so 0 after a call that declined);
+ * ndcn_clear_readout_path zeroes it - for callers that decide above the library whether to call at all.                       */
+#define NDCN_READOUT_FUSED   1      /* the fused dense-output kernel ran (interp_readout_kernel<ceil(H / 64)>)                       */
+#define NDCN_READOUT_STAGED  2      /* a dopri5 tick was evaluated into `scratch` and decoded from there                            */
+#define NDCN_READOUT_FIXED   4      /* fixed grid: the state decoded after each step                                                */
+NDCN_API int ndcn_solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd,
+                                              int C, float *out, float *scratch, void *stream);
+NDCN_API int ndcn_last_readout_path(void);
+NDCN_API void ndcn_clear_readout_path(void);
 /* Fixed grid only (NDCN_EINVAL for dopri5 and for a sharded solver): FixedGridODESolver.integrate with the step_size option
  * (solvers.py:55-68,79-108) from the solver's current time.  h_grid (HOST, fp32, n_grid points, h_grid[0] = the current time in the
  * state dtype) is the solver's own grid; every one of its n_grid - 1 steps runs with the state INSIDE the solver - eager: the launches

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
@@ -240,6 +240,9 @@ SIGNATURES = {
     'ndcn_solver_begin_borrowed': (_I, [_P, _P, _D, _P]),
     'ndcn_solver_advance': (_I, [_P, _D, _P, _L, _P]),
     'ndcn_solver_advance_many': (_I, [_P, ctypes.POINTER(_D), _L, _P, _P]),
+    'ndcn_solver_advance_many_readout': (_I, [_P, ctypes.POINTER(_D), _L, _P, _P, _I, _P, _P, _P]),
+    'ndcn_last_readout_path': (_I, []),
+    'ndcn_clear_readout_path': (None, []),
     'ndcn_solver_advance_grid': (_I, [_P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_F), _L, _P, _P]),
     'ndcn_solver_stats': (_I, [_P, ctypes.POINTER(_D)]),
     'ndcn_solver_steplog': (_L, [_P, ctypes.POINTER(_D), _L]),

@@ -45,6 +45,8 @@ int ndcn_debug_last_linear_path(void) { return g_last_linear_path; }
 int ndcn_debug_last_rk_bwd_path(void) { return g_last_rk_bwd_path; }
 int ndcn_debug_last_spmm_path(void) { return g_last_spmm_path; }
 int64_t ndcn_debug_last_rk_path(void) { return g_last_rk_path; }
+int ndcn_last_readout_path(void) { return g_last_readout_path; }
+void ndcn_clear_readout_path(void) { g_last_readout_path = 0; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
 const char *ndcn_last_error(void) { return g_err; }
 
@@ -494,6 +496,10 @@ int ndcn_solver_advance(ndcn_solver *s, double next_t, float *out, int64_t step_
 }
 int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, void *stream) {
     return solver_advance_many(s, h_ticks, n_ticks, out, ST(stream));
+}
+int ndcn_solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd, int C,
+                                     float *out, float *scratch, void *stream) {
+    return solver_advance_many_readout(s, h_ticks, n_ticks, Wd, bd, C, out, scratch, ST(stream));
 }
 int ndcn_solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step, const float *h_tick_time,
                              int64_t n_ticks, float *out, void *stream) {

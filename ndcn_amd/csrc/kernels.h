@@ -179,6 +179,11 @@ int interp_direct_f32(const float *y0, const float *y1, const float *const *h_k,
 // fit + evaluate nt <= 8 ticks of ONE accepted step in one pass (h_xp: nt x {x^4, x^3, x^2, x, 1}; h_out: nt panels)
 int interp_direct_multi_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                             const float *h_xp, float *const *h_out, int nt, int64_t n, hipStream_t st);
+// the same pass with the decoder Linear(H, C) applied in registers: h_out holds nt panels of n_rows x C, each bit for bit
+// linear_f32 (row-dot route) of the tick panel interp_direct_multi_f32 would write; 64 <= H <= 512, 1 <= C <= 15
+int interp_readout_supported(int H, int C);
+int interp_readout_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, const float *h_xp,
+                       float *const *h_out, int nt, const float *Wd, const float *bd, int64_t n_rows, int H, int C, hipStream_t st);
 int interp_eval_f32(const float *a, const float *b, const float *c, const float *d, const float *e, const float xp[5],
                     float *out, int64_t n, hipStream_t st);
 int fixed_stage_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3,
@@ -209,6 +214,9 @@ int solver_destroy(ndcn_solver *s);
 int solver_begin(ndcn_solver *s, const float *y0, double t0, hipStream_t st, bool borrow = false);
 int solver_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st);
 int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, hipStream_t st);
+int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd, int C,
+                                float *out, float *scratch, hipStream_t st);
+extern thread_local int g_last_readout_path;  // ndcn_last_readout_path (solver.hip)
 int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, const int64_t *h_tick_step, const float *h_tick_time,
                         int64_t n_ticks, float *out, hipStream_t st);
 int solver_stats(const ndcn_solver *s, double h[6]);

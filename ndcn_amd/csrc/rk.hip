@@ -546,6 +546,59 @@ __global__ __launch_bounds__(256) void interp_direct_multi_kernel(DirectMultiArg
     }
 }
 
+// Dense output decoded in place (inference: the hidden tick panels are never written).  A wave per row: lane l holds the elements
+// l + 64 v of the row's fit, evaluates them at each of the launch's ticks (fit1 / poly1: the arithmetic of the kernel above) and
+// dots them with the decoder's rows while they sit in registers - element-to-lane map, fmaf chain over v and butterfly are
+// linear_rowdot_kernel's (linear.hip), so out[t] is bit for bit ndcn_linear_f32 of the tick panel interp_direct_multi would have
+// written.  (2 + m) P read, nt N C 4 written.
+struct ReadoutArgs {
+    FitArgs f;                      // a, b, c, d unused
+    float xp[kMaxTicks][5];
+    float *out[kMaxTicks];          // n_rows x C each
+    int nt;
+};
+
+template <int NV>          // NV = ceil(H / 64) <= 8
+__global__ __launch_bounds__(256) void interp_readout_kernel(ReadoutArgs p, const float *__restrict__ Wd,
+                                                             const float *__restrict__ bd, int64_t n_rows, int H, int C) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave0; r < n_rows; r += n_waves) {
+        float a[NV], b[NV], c[NV], d[NV], y0[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int k = lane + 64 * v;                            // (NV = ceil(H / 64): only the last v has surplus lanes)
+            const int64_t i = r * H + ((v < NV - 1 || k < H) ? k : H - 1);   // unconditional request; the surplus lanes are zeroed below
+            y0[v] = p.f.y0[i];
+            fit1(y0[v], p.f.y1[i], wsum1(p.f.mid, i), p.f.f0[i], p.f.f1[i], p.f.dt, a[v], b[v], c[v], d[v]);
+        }
+        // (a run-time loop: unrolled, the eight ticks' powers and pointers do not fit the scalar registers)
+#pragma unroll 1
+        for (int t = 0; t < p.nt; ++t) {
+                float h[NV];
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    h[v] = poly1(a[v], b[v], c[v], d[v], y0[v], p.xp[t]);
+                    h[v] = (v < NV - 1 || lane + 64 * v < H) ? h[v] : 0.f;
+                }
+                for (int o = 0; o < C; ++o) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int v = 0; v < NV; ++v) {
+                        const int k = lane + 64 * v;
+                        acc = fmaf(h[v], Wd[(int64_t)o * H + ((v < NV - 1 || k < H) ? k : H - 1)], acc);
+                    }
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+                    if (lane == 0) {
+                        if (bd) acc += bd[o];
+                        p.out[t][r * C + o] = acc;
+                    }
+                }
+            }
+    }
+}
+
 // -------------------------------------------------------------------------------- fixed-grid stages
 template <int OP>
 __device__ __forceinline__ float stage1(float y, float k1, float k2, float k3, float k4, float dt) {
@@ -943,6 +996,53 @@ int interp_direct_multi_f32(const float *y0, const float *y1, const float *const
     if (vec) hipLaunchKernelGGL((interp_direct_multi_kernel<true>), dim3(g), dim3(256), 0, st, p, n / 4);
     else hipLaunchKernelGGL((interp_direct_multi_kernel<false>), dim3(g), dim3(256), 0, st, p, n);
     record_path(NDCN_RKF_INTERP_DIRECT_MULTI, vec, g);
+    NDCN_LAUNCH_CHECK();
+    return NDCN_OK;
+}
+
+int interp_readout_supported(int H, int C) { return H >= 64 && H <= 512 && C >= 1 && C <= 15; }
+
+int interp_readout_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, const float *h_xp,
+                       float *const *h_out, int nt, const float *Wd, const float *bd, int64_t n_rows, int H, int C, hipStream_t st) {
+    g_last_rk_path = 0;
+    if (nt < 1 || nt > kMaxTicks) { set_error("interp_readout: 1..%d ticks per launch", kMaxTicks); return NDCN_EINVAL; }
+    if (!interp_readout_supported(H, C)) { set_error("interp_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C); return NDCN_EINVAL; }
+    if (!y0 || !y1 || !Wd) { set_error("interp_readout: null argument"); return NDCN_EINVAL; }
+    ReadoutArgs p;
+    const float *kk[kMaxTerms];
+    float cc[kMaxTerms];
+    int m = 0;
+    for (int j = 0; j < 7; ++j) {
+        if (!h_k[j]) { set_error("interp_readout: null stage pointer"); return NDCN_EINVAL; }
+        if (h_cmid[j] != 0.f) { kk[m] = h_k[j]; cc[m] = h_cmid[j]; ++m; }
+    }
+    if (m == 0) { kk[0] = h_k[0]; cc[0] = 0.f; m = 1; }
+    bool dummy = true;
+    fill_terms(p.f.mid, kk, cc, m, dummy);
+    p.f.y0 = y0; p.f.y1 = y1; p.f.f0 = h_k[0]; p.f.f1 = h_k[6]; p.f.dt = dt;
+    p.f.a = p.f.b = p.f.c = p.f.d = nullptr;
+    p.nt = nt;
+    for (int t = 0; t < kMaxTicks; ++t) {
+        p.out[t] = h_out[t < nt ? t : 0];
+        if (!p.out[t]) { set_error("interp_readout: null output"); return NDCN_EINVAL; }
+        for (int q = 0; q < 5; ++q) p.xp[t][q] = h_xp[(t < nt ? t : 0) * 5 + q];
+    }
+    if (n_rows == 0) return NDCN_OK;
+    const double P = (double)n_rows * H;
+    ProfScope prof(PROF_EVAL, st, 4.0 * P * (2 + m) + 4.0 * nt * (double)n_rows * C, 2.0 * P * (m + 16 + (9 + C) * nt));
+    const int g = stream_grid(n_rows * 64, 256);
+#define NDCN_RO(NV_) hipLaunchKernelGGL((interp_readout_kernel<NV_>), dim3(g), dim3(256), 0, st, p, Wd, bd, n_rows, H, C)
+    switch ((H + 63) / 64) {
+        case 1: NDCN_RO(1); break;
+        case 2: NDCN_RO(2); break;
+        case 3: NDCN_RO(3); break;
+        case 4: NDCN_RO(4); break;
+        case 5: NDCN_RO(5); break;
+        case 6: NDCN_RO(6); break;
+        case 7: NDCN_RO(7); break;
+        default: NDCN_RO(8); break;
+    }
+#undef NDCN_RO
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
 }

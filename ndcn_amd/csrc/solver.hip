@@ -1303,6 +1303,94 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
     return NDCN_OK;
 }
 
+// ndcn_last_readout_path: cleared on entry of solver_advance_many_readout, NDCN_READOUT_* bits of what it then ran
+thread_local int g_last_readout_path = 0;
+
+// solver_advance_many with the decoder Linear(H, C) applied to every tick as it is produced (inference: neural_dynamics.py:148-160
+// decodes the whole (T, N, H) trajectory afterwards): the same steps, launches and accept / reject log, but out[i] is the n_rows x C
+// readout Wd y(h_ticks[i]) + bd - bit for bit linear_f32 of the panel solver_advance_many writes - and no tick panel is stored.
+//   dopri5: the ticks of a fresh accepted step go through interp_readout_f32 (<= 8 per launch); the single-tick paths (a stored fit,
+//           a tick without a fresh step) evaluate into `scratch` and decode from there.
+//   fixed grid: each step keeps the state inside the solver (Euler with its algebra in the RHS epilogue alternates between the
+//           solver's panel and `scratch`, as solver_advance_grid does with a stage panel), then linear_f32 decodes it.
+int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd, int C,
+                                float *out, float *scratch, hipStream_t st) {
+    g_last_readout_path = 0;
+    NDCN_CHECK_ARG(s && Wd && n_ticks >= 0 && (n_ticks == 0 || (h_ticks && out && scratch)), "null argument");
+    const int H = s->d.H;
+    const bool fixed = s->d.method != NDCN_M_DOPRI5;
+    if (s->sharded) { set_error("ndcn_solver_advance_many_readout: un-sharded solvers only (decode the shard's trajectory instead)"); return NDCN_EINVAL; }
+    if (!interp_readout_supported(H, C)) {
+        set_error("ndcn_solver_advance_many_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C);
+        return NDCN_EINVAL;
+    }
+    if (fixed && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
+        set_error("ndcn_solver_advance_many_readout: this state fits the one-launch solve (ndcn_solve_small_f32); decode its trajectory instead");
+        return NDCN_EINVAL;
+    }
+    if (n_ticks == 0) return NDCN_OK;                               // (also the question "would this solver decline?", before begin)
+    if (!s->begun) { set_error("ndcn_solver_advance_many_readout before ndcn_solver_begin"); return NDCN_ESTATE; }
+    if (overlaps_borrowed(s, scratch, 2)) return NDCN_EINVAL;
+    const int64_t rows = s->n_rows;
+    const size_t ostride = (size_t)rows * (size_t)C;
+    int rc;
+    if (fixed) {
+        const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
+        for (int64_t i = 0; i < n_ticks; ++i) {
+            float *inside = (pingpong && s->ycur == s->ycur_own) ? scratch : nullptr;
+            if ((rc = fixed_advance(s, h_ticks[i], inside, st))) return rc;
+            if ((rc = linear_f32(s->ycur, Wd, bd, out + (size_t)i * ostride, rows, H, C, 0, st))) return rc;
+            g_last_readout_path |= NDCN_READOUT_FIXED;
+        }
+        if (s->ycur == scratch) {                                   // the caller's scratch does not outlive the call
+            NDCN_HIP(hipMemcpyAsync(s->ycur_own, scratch, (size_t)s->n_elem * sizeof(float), hipMemcpyDeviceToDevice, st));
+            s->ycur = s->ycur_own;
+            s->cur_is_borrowed = false;
+        }
+        return NDCN_OK;
+    }
+    int64_t i = 0;
+    while (i < n_ticks) {
+        rc = dopri5_advance(s, h_ticks[i], nullptr, 0, st);               // steps only (no evaluation)
+        if (rc) return rc;
+        if (s->fit_valid || !s->fit_pending) {                           // a stored fit / no fresh step: single-tick path
+            if ((rc = dopri5_advance(s, h_ticks[i], scratch, 0, st))) return rc;
+            if ((rc = linear_f32(scratch, Wd, bd, out + (size_t)i * ostride, rows, H, C, 0, st))) return rc;
+            g_last_readout_path |= NDCN_READOUT_STAGED;
+            ++i;
+            continue;
+        }
+        int64_t j = i;
+        while (j < n_ticks && !(h_ticks[j] > s->t1)) ++j;                // the ticks this accepted step covers
+        const float a0 = (float)s->t0, a1 = (float)s->t1;
+        const float *kk[7];
+        float cm[7];
+        if ((rc = dense_terms(s, kk, cm))) return rc;
+        while (i < j) {
+            const int nt = (int)((j - i) < 8 ? (j - i) : 8);
+            float xp[8][5];
+            float *outs[8];
+            for (int t = 0; t < nt; ++t) {
+                // interp.py:51-65: abscissa and its powers in the state dtype
+                const float at = (float)h_ticks[i + t];
+                if (!(a0 <= at && at <= a1)) {
+                    set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", a0, at, a1);
+                    return NDCN_ESTATE;
+                }
+                const float x = (at - a0) / (a1 - a0);
+                xp[t][4] = 1.f; xp[t][3] = x; xp[t][2] = xp[t][3] * x; xp[t][1] = xp[t][2] * x; xp[t][0] = xp[t][1] * x;
+                outs[t] = out + (size_t)(i + t) * ostride;
+            }
+            rc = interp_readout_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, &xp[0][0], outs, nt, Wd, bd, rows, H, C, st);
+            if (rc) return rc;
+            g_last_readout_path |= NDCN_READOUT_FUSED;
+            s->evals_in_step += nt;
+            i += nt;
+        }
+    }
+    return NDCN_OK;
+}
+
 // FixedGridODESolver.integrate with the step_size option (solvers.py:55-68,79-108): every step of h_grid with the state inside the
 // solver, the ticks written as the steps that report them end.  The step sizes are fixed_advance's own float32 differences, the
 // launches are its launches: bit-identical to solver_advance_many over all of h_grid.

@@ -24,6 +24,10 @@ def _needs_grad(*tensors_and_modules):
     return False
 
 
+def _has_hooks(module):
+    return bool(module._forward_hooks or module._forward_pre_hooks or module._backward_hooks or module._backward_pre_hooks)
+
+
 class ODEFunc(nn.Module):
     """dX/dt = relu(dropout(W (A X) + b))   -- reference neural_dynamics.py:8-39."""
 
@@ -73,7 +77,12 @@ class _OdeBlock(nn.Module):
         self.rtol, self.atol, self.method = rtol, atol, method
         self.adjoint, self.terminal = adjoint, terminal
 
-    def _solve(self, x, vt):
+    def _solve(self, x, vt, readout=None):
+        """readout=(weight, bias): the decoder applied to every tick inside the solve (odeint's keyword; non-adjoint blocks)"""
+        if readout is not None:
+            assert not self.adjoint, 'readout: odeint_adjoint has no such keyword'
+            out = ode.odeint(self.odefunc, x, vt.type_as(x), rtol=self.rtol, atol=self.atol, method=self.method, readout=readout)
+            return out[-1] if self.terminal else out
         solve = ode.odeint_adjoint if self.adjoint else ode.odeint
         out = solve(self.odefunc, x, vt.type_as(x), rtol=self.rtol, atol=self.atol, method=self.method)
         return out[-1] if self.terminal else out
@@ -135,7 +144,14 @@ class NDCN(nn.Module):
 
     def forward(self, vt, x):
         h = x if self.no_embed else self.input_layer(x)
-        return self.output_layer(self.neural_dynamic_layer(vt, h))
+        block, dec = self.neural_dynamic_layer, self.output_layer
+        # inference: the decoder rides inside the solve and the (T, N, H) trajectory is never stored (odeint's `readout`: the same
+        # bits as the two steps below).  Anything that could observe the hidden trajectory keeps the two-step form: a gradient, a
+        # replaced or hooked decoder, hooks on the block, an adjoint block.
+        if not _needs_grad(x, self) and type(dec) is _HipLinear and type(block) is ODEBlock and not block.adjoint and \
+                not _has_hooks(dec) and not _has_hooks(block):
+            return block._solve(h, vt, readout=(dec.weight, dec.bias))
+        return dec(block(vt, h))
 
 
 class GraphConvolution(nn.Module):

@@ -63,22 +63,44 @@ def _reuse_first_evaluation(func, y0, out):
     return wrapped
 
 
-def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_log=None):
+def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_log=None, readout=None):
     """Integrate dy/dt = func(t, y), y(t[0]) = y0; returns y at every t (first dim), y0 first.  (The body is `_odeint`; this frame
     fetches the time grid to the host once for everything below that asks about it: core.grid_scope - and opens the solve's dropout
-    stream: one seed, evaluations numbered from 0, ndcn_amd/dropout.py.)"""
+    stream: one seed, evaluations numbered from 0, ndcn_amd/dropout.py.)
+
+    readout=(weight (C, H), bias (C,) or None): return `linear(odeint(...), weight, bias)`, shape (len(t), N, C), instead of the
+    hidden states (neural_dynamics.py:148-160: NDCN decodes every tick).  Where nothing needs a gradient and the solve is
+    device-resident, the library decodes each tick as the solver produces it (ndcn_solver_advance_many_readout) and the
+    (len(t), N, H) trajectory is never stored; everywhere else the ordinary solve runs and the Linear is applied to its result - the
+    values are the same bits either way, only the memory differs.  A tuple state raises ValueError."""
     with core.grid_scope(t), _dropout.solve_scope():
-        return _odeint(func, y0, t, rtol, atol, method, options, step_log)
+        if readout is None:
+            return _odeint(func, y0, t, rtol, atol, method, options, step_log)[0]
+        if not torch.is_tensor(y0):
+            raise ValueError('`readout` decodes a tensor state; got a tuple')
+        W, b = readout
+        _lib.load().ndcn_clear_readout_path()
+        sol, decoded = _odeint(func, y0, t, rtol, atol, method, options, step_log, readout=(W, b))
+        return sol if decoded else _decode(sol, W, b)
 
 
-def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_log=None):
+def _decode(sol, W, b):
+    """linear(sol, W, b) over the last dimension: the differentiable wrapper where a gradient is asked for"""
+    if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (sol, W, b)):
+        from ...autograd_ops import linear
+        return linear(sol, W, b)
+    return hip.linear(sol, W, b)
+
+
+def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_log=None, readout=None):
     """Integrate dy/dt = func(t, y), y(t[0]) = y0; returns y at every t (first dim), y0 first.
 
     Same signature, defaults, return layout and exceptions as the reference (odeint.py:20-76):
     TypeError for non-float y0 / t, ValueError for `options` without `method`, KeyError for an unknown
     method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / euler / midpoint / rk4 are
     provided (tsit5 / explicit_adams / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
-    `step_log` (a list) optionally receives the dopri5 per-attempt log.
+    `step_log` (a list) optionally receives the dopri5 per-attempt log.  Returns (solution, decoded): decoded is True when
+    `readout` was applied inside the solve (the device-resident inference path), else the solution is the hidden one.
 
     Fixed-grid methods take options={'step_size': h} as the reference's FixedGridODESolver does (solvers.py:39-108): the solver
     integrates on its own float32 grid t[0], t[0] + h, ... (last point clamped to t[-1]; AssertionError where rounding leaves it
@@ -127,7 +149,7 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         if sol is None:
             sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan)   # any size: fused launches forward, closed-form sweep backward
         if sol is not None:
-            return sol
+            return sol, False
     if needs_grad:
         from .autograd_path import odeint_with_grad
         plain = method == 'dopri5' and _device_resident_ok(user_func, tensor_input, y0, t_user, method, options) and \
@@ -136,11 +158,11 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
             # one autograd node per solve: the native tape (csrc/tape.hip) runs the launches below and their reverse pass itself
             from . import tape
             if tape.applicable(user_func, y0[0], t_user):
-                return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log)
+                return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
                                step_log=step_log, odefunc=user_func if plain else None, plan=plan)
     elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan)
+        return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan, readout)
     elif method == 'dopri5':
         sol = core.integrate_dopri5(hip, func, y0, t, rtol, atol, autonomous=_autonomous(user_func),
                                     step_log=step_log, **options)
@@ -150,7 +172,7 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     else:
         sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan)
     out = tuple(torch.stack([s[i] for s in sol]) for i in range(len(y0)))
-    return out[0] if tensor_input else out
+    return (out[0] if tensor_input else out), False
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -629,6 +651,25 @@ class DeviceSolver:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.ndcn_solver_advance_many(self.handle, arr, len(ticks), _lib.ptr(out), _lib.stream_ptr()))
 
+    def advance_many_readout(self, ticks, weight, bias, out, scratch):
+        """advance_many with Linear(weight (C, H), bias (C,) or None) applied to every tick inside the library: out is
+        (len(ticks), n_rows, C) and no hidden tick panel is stored; scratch: room for two n_rows x H panels.  Returns False where the
+        library declines (NDCN_EINVAL: a sharded solver, H outside 64..512, C outside 1..15, a state that the one-launch solve takes)
+        - nothing has been advanced then.  With no ticks (out and scratch may be None, before begin too) it only asks that question."""
+        C = weight.shape[0]
+        assert weight.is_contiguous() and weight.shape[1] == self.shape[1] and (bias is None or bias.is_contiguous())
+        if len(ticks):
+            assert out.is_contiguous() and tuple(out.shape) == (len(ticks), self.shape[0], C)
+            assert scratch.is_contiguous() and scratch.numel() >= 2 * self.shape[0] * self.shape[1]
+        arr = (ctypes.c_double * max(len(ticks), 1))(*[float(v) for v in ticks])
+        with torch.cuda.device(self.device):
+            rc = self.lib.ndcn_solver_advance_many_readout(self.handle, arr, len(ticks), _lib.ptr(weight), _lib.ptr(bias), C,
+                                                           _lib.ptr(out), _lib.ptr(scratch), _lib.stream_ptr())
+        if rc == _lib.EINVAL:
+            return False
+        _lib.check(rc)
+        return True
+
     def advance_grid(self, plan, out):
         """A sub-stepped fixed grid (core.FixedPlan) in one library call: every step of plan.grid with the state inside the solver,
         out: (len(plan.t) - 1, n_rows, H) contiguous - the ticks after the first."""
@@ -764,7 +805,31 @@ def _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph):
     return solver, None                                      # the kept one is busy (another thread): a solver of its own
 
 
-def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan=None):
+def _device_resident_readout(solver, y0, tt, Wd, bd):
+    """The decoded solution (len(tt), N, C) through ndcn_solver_advance_many_readout, or None where the library declines.  The hidden
+    state lives in the solver's workspace and in two scratch panels that are freed on return."""
+    C = Wd.shape[0]
+    if not solver.advance_many_readout([], Wd, bd, None, None):   # asked before begin: a declined solve pays nothing twice
+        return None
+    out = torch.empty((len(tt), y0.shape[0], C), dtype=torch.float32, device=y0.device)
+    scratch = torch.empty((2,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+    y0 = y0.contiguous()
+    solver.begin(y0, tt[0], borrow=True)                     # dopri5 reads the caller's y0 in place; nothing here writes it
+    try:
+        if not solver.advance_many_readout(tt[1:], Wd, bd, out[1:], scratch):
+            return None
+    except _lib.NdcnHipError as e:
+        if e.code in (_lib.ENONFINITE, _lib.EUNDERFLOW, _lib.EMAXSTEPS, _lib.ESTATE):
+            raise AssertionError(str(e)) from None             # the reference raises AssertionError here
+        raise
+    out[0].copy_(hip.linear(y0, Wd, bd))
+    torch.cuda.current_stream().synchronize()                # the scratch is released here, the workspace by the caller
+    return out
+
+
+def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan=None, readout=None):
+    """(solution, decoded).  readout (weight, bias): with no gradient asked of them and no step_size plan the library decodes every
+    tick inside the solve - decoded is True and the solution is (len(t), N, C); where it declines, the hidden solution is returned."""
     core.assert_increasing(t)
     tt = core.host_grid(t).to(torch.float64).tolist()
     if method != 'dopri5':
@@ -773,13 +838,25 @@ def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan
     if method != 'dopri5' and len(tt) > 1:
         out = _small_solve(odefunc, y0, tt, method, plan)       # a state that fits one compute unit: the whole grid in ONE launch
         if out is not None:
-            return out
+            return out, False
+    fuse = False
+    if readout is not None and plan is None and len(tt) > 1:
+        Wd, bd = readout
+        fuse = not (torch.is_grad_enabled() and (Wd.requires_grad or (bd is not None and bd.requires_grad))) and \
+            Wd.dim() == 2 and Wd.shape[1] == y0.shape[1] and Wd.is_cuda and Wd.dtype == torch.float32
     # launch-bound sizes replay ONE captured hipGraph per step - a fixed-grid step, or one attempted dopri5 step - with the
     # step size in device memory (the library declines where a path has no replayable form)
     use_graph = y0.numel() <= GRAPH_MAX_ELEMS
     opt = core.dopri5_options(options, 1) if method == 'dopri5' else dict(options)      # (fixed grid: nothing, or the step size)
     solver, cache_key = _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph)
     try:
+        if fuse:
+            out = _device_resident_readout(solver, y0, tt, Wd.detach().contiguous(), None if bd is None else bd.detach().contiguous())
+            if out is not None:
+                if step_log is not None:
+                    step_log.extend(solver.steplog())
+                    step_log.append(('nfe', int(solver.stats()['nfe'])))
+                return out, True
         out = torch.empty((len(tt),) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
         solver.begin(out[0], tt[0], borrow=True)           # the solution's first panel IS the initial state: read in place
@@ -796,7 +873,7 @@ def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan
             step_log.extend(solver.steplog())
             step_log.append(('nfe', int(solver.stats()['nfe'])))
         torch.cuda.current_stream().synchronize()    # the workspace is released (or handed to the next solve) below
-        return out
+        return out, False
     finally:
         if cache_key is None:
             solver.close()
