@@ -116,6 +116,7 @@ int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t 
 // solve_small.hip: a whole fixed-grid solve (all ticks) in ONE launch for states that fit one CU; h_dt: the n_ticks step sizes in
 // the state dtype; out: n_ticks panels.  Euler also has the reverse sweep (traj / g_out: n_ticks + 1 panels, y_0 first).
 int solve_small_supported(const ndcn_csr *A, int H, uint32_t flags, int method);
+int evals_per_step(int method);   // right-hand sides per fixed-grid step: euler 1, midpoint 2, rk4 4 (solver.hip)
 int solve_small_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method, const float *y0,
                     const float *h_dt, int64_t n_ticks, float *out, hipStream_t st, float *keep = nullptr);
 // ... on a grid finer than the ticks: n_steps steps, tick j (n_ticks of them, h_tick_step non-decreasing) is written after step

@@ -1109,7 +1109,7 @@ static int solve_small_impl(const ndcn_csr *A, const float *W, const float *b, i
         static long long *dbg_buf = nullptr;
         if (dbg_on && !dbg_buf) NDCN_HIP(hipMalloc(&dbg_buf, 4 * sizeof(long long)));
         a.dbg = dbg_on ? dbg_buf : nullptr;
-        const double evals = (method == NDCN_M_EULER ? 1 : method == NDCN_M_MIDPOINT ? 2 : 4) * (double)a.n_ticks;
+        const double evals = evals_per_step(method) * (double)a.n_ticks;
         ProfScope prof(PROF_RHS_FUSED, st, 4.0 * n_elem * (a.n_ticks + 1) + 8.0 * nnz + 4.0 * H * H,
                        evals * (2.0 * nnz * H + 2.0 * (double)A->n_rows * H * H));
 #define NDCN_GO(M_, IT_, C_, HT_)                                                              \

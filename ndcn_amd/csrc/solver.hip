@@ -198,22 +198,16 @@ int rhs_epi(ndcn_solver *s, const float *x, float *K, int mode, const float *y0,
                           y_next, rtol, atol, d_out, d_ws, st, opt);
 }
 
-// wait for the reduction record enqueued last on `st`
-int fetch_record(ndcn_solver *s, hipStream_t st, double &sum, double &bad) {
+// wait for the n-double reduction record enqueued last on `st`: s->h_red[0..n)
+int fetch_record(ndcn_solver *s, hipStream_t st, int n = 2) {
     if (s->sharded) {                                   // every rank sees the same record: identical controller decisions
-        int rc = comm_allreduce_sum_f64(s->shard.comm, s->d_red, 2, st);
+        int rc = comm_allreduce_sum_f64(s->shard.comm, s->d_red, n, st);
         if (rc) return rc;
     }
-    if (s->poll) {
-        int rc = rec_wait(s->h_red, 2, st);
-        if (rc) return rc;
-    } else {
-        NDCN_HIP(hipMemcpyAsync(s->h_red, s->d_red, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        NDCN_HIP(hipEventRecord(s->ev, st));
-        NDCN_HIP(hipEventSynchronize(s->ev));
-    }
-    sum = s->h_red[0];
-    bad = s->h_red[1];
+    if (s->poll) return rec_wait(s->h_red, n, st);
+    NDCN_HIP(hipMemcpyAsync(s->h_red, s->d_red, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    NDCN_HIP(hipEventRecord(s->ev, st));
+    NDCN_HIP(hipEventSynchronize(s->ev));
     return NDCN_OK;
 }
 
@@ -227,11 +221,11 @@ int rms_scaled(ndcn_solver *s, const float *a, const float *b, const float *y, f
     arm(s);
     int rc = scaled_sumsq_f32(a, b, y, rtol, atol, s->n_elem, s->d_red, s->d_ws, st);
     if (rc) return rc;
-    double sum;
-    rc = fetch_record(s, st, sum, bad);
+    rc = fetch_record(s, st);
     if (rc) return rc;
+    bad = s->h_red[1];
     // misc.py:71-76: x.norm() / numel ** 0.5, a float32 0-d tensor divided by a python float
-    const float nrm = (float)sqrt(sum);
+    const float nrm = (float)sqrt(s->h_red[0]);
     rms = nrm / (float)sqrt(s->n_mean);
     return NDCN_OK;
 }
@@ -249,17 +243,7 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
         arm(s, 4);
         rc = scaled_sumsq_pair_f32(s->k[0], s->ycur, rtol, atol, s->n_elem, s->d_red, s->d_ws, s->d_ws2, st);
         if (rc) return rc;
-        if (s->sharded) {
-            rc = comm_allreduce_sum_f64(s->shard.comm, s->d_red, 4, st);
-            if (rc) return rc;
-        }
-        if (s->poll) {
-            if ((rc = rec_wait(s->h_red, 4, st))) return rc;
-        } else {
-            NDCN_HIP(hipMemcpyAsync(s->h_red, s->d_red, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-            NDCN_HIP(hipEventRecord(s->ev, st));
-            NDCN_HIP(hipEventSynchronize(s->ev));
-        }
+        if ((rc = fetch_record(s, st, 4))) return rc;
         bad0 = s->h_red[1];
         d0 = (float)sqrt(s->h_red[0]) / (float)sqrt(s->n_mean);
         d1 = (float)sqrt(s->h_red[2]) / (float)sqrt(s->n_mean);
@@ -271,9 +255,7 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
         rc = rms_scaled(s, s->k[0], nullptr, s->ycur, rtol, atol, st, d1, bad);
         if (rc) return rc;
     }
-    float h0;
-    if (d0 < 1e-5 || d1 < 1e-5) h0 = 1e-6f;
-    else h0 = 0.01f * (d0 / d1);
+    const float h0 = initial_h0(d0, d1);
     // y1 = y0 + h0 * f0 ; f1 = f(t0 + h0, y1)
     const float *kp[1] = {s->k[0]};
     const float cp[1] = {h0};
@@ -296,32 +278,16 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
         rc = rhs_epi(s, xadd ? s->ycur : s->ytmp, s->k[1], 2, s->ycur, kq, cq, 1, nullptr, rtol, atol, s->d_red, s->d_ws2, st, nullptr,
                      &opt);
         if (rc) return rc;
-        double sum;
-        rc = fetch_record(s, st, sum, bad);
+        rc = fetch_record(s, st);
         if (rc) return rc;
-        d2 = (float)sqrt(sum) / (float)sqrt(s->n_mean);
+        d2 = (float)sqrt(s->h_red[0]) / (float)sqrt(s->n_mean);
     } else {
         rc = rhs(s, s->ytmp, s->k[1], st);
         if (rc) return rc;
         rc = rms_scaled(s, s->k[1], s->k[0], s->ycur, rtol, atol, st, d2, bad);
         if (rc) return rc;
     }
-    d2 = d2 / h0;
-    float h1;
-    if (d1 <= 1e-15 && d2 <= 1e-15) {
-        const float a = 1e-6f, b = h0 * 1e-3f;
-        h1 = a > b ? a : b;
-    } else {
-        // `(0.01 / m) ** (1 / 5)` as torch evaluates it on a float32 0-d tensor (misc.py:141): python_scalar / tensor is
-        // tensor.reciprocal() * scalar - two float32 roundings - and tensor ** python_float runs std::pow in double with
-        // the exponent at full double precision, rounded to float32 once
-        const float m = d1 > d2 ? d1 : d2;
-        const float a = (1.0f / m) * 0.01f;
-        h1 = (float)pow((double)a, 1. / 5.);
-    }
-    const float h100 = 100.f * h0;
-    h_out = (double)(h100 < h1 ? h100 : h1);
-    if (isnan(h100) || isnan(h1)) h_out = NAN;
+    h_out = initial_dt(h0, initial_h1(d1, d2 / h0, h0));
     return NDCN_OK;
 }
 
@@ -385,18 +351,6 @@ int rhs_sharded(ndcn_solver *s, const float *x, float *K, int mode, const float 
     return launch(&s->d.A, x, s->halo, 0, true, x);
 }
 
-void dt_coeffs(float dt32, const double *beta, int n, const float *const *kall, const float **kp, float *cp, int &m) {
-    // (scale * x) of misc.py:25 in float32; exact-zero tableau entries are dropped (their product is 0)
-    m = 0;
-    for (int j = 0; j < n; ++j) {
-        const float bj = (float)beta[j];
-        if (bj == 0.f) continue;
-        kp[m] = kall[j];
-        cp[m] = dt32 * bj;
-        ++m;
-    }
-}
-
 // The launches of one attempted step (rk_common.py:41-61): six stage inputs / evaluations and the error record.
 // dt_dev == nullptr: dt32 is the step size and rides in the kernel arguments.  dt_dev != nullptr (hipGraph capture):
 // dt32 must be 1 - the coefficients passed are the bare tableau entries and every kernel forms fl(dt * c) from the
@@ -414,7 +368,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         // form it on the rows it stages (RkOpt::xadd: the lattice plan of rhs_fused3.hip, one more gather instead)
         const bool xadd = !dt_dev && !s->rec_epi && !s->exact32 &&
                           (s->sharded ? s->xadd_block >= 0 : rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 1, 1));
-        dt_coeffs(dt32, kBeta[0], 1, s->k, kp, cp, m);
+        m = dt_terms(dt32, kBeta[0], 1, s->k, kp, cp);
         const float xadd_c = cp[0];
         if (!xadd) {
             rc = rk_combine_f32(s->ytmp, s->ycur, kp, cp, m, s->n_elem, st, dt_dev);
@@ -523,7 +477,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
             } else if (split_error) {
                 rc = rhs(s, in, s->k[6], st);
                 if (rc) return rc;
-                dt_coeffs(dt32, kCErr, 7, s->k, kp, cp, m);
+                m = dt_terms(dt32, kCErr, 7, s->k, kp, cp);
                 rc = rk_error_f32(s->ycur, s->ynext, kp, cp, m, (float)s->d.rtol, (float)s->d.atol, s->n_elem, s->d_red, s->d_ws, st,
                                   dt_dev);
                 if (rc) return rc;
@@ -552,19 +506,96 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         return NDCN_OK;
     }
     for (int i = 0; i < 6; ++i) {
-        dt_coeffs(dt32, kBeta[i], i + 1, s->k, kp, cp, m);
+        m = dt_terms(dt32, kBeta[i], i + 1, s->k, kp, cp);
         float *dst = (i == 5) ? s->ynext : s->ytmp;          // the 6th stage input IS y1 (rk_common.py:54-58)
         rc = rk_combine_f32(dst, s->ycur, kp, cp, m, s->n_elem, st, dt_dev);
         if (rc) return rc;
         rc = rhs(s, dst, s->k[i + 1], st);
         if (rc) return rc;
     }
-    dt_coeffs(dt32, kCErr, 7, s->k, kp, cp, m);
+    m = dt_terms(dt32, kCErr, 7, s->k, kp, cp);
     return rk_error_f32(s->ycur, s->ynext, kp, cp, m, (float)s->d.rtol, (float)s->d.atol, s->n_elem, s->d_red, s->d_ws, st,
                         dt_dev);
 }
 
-int graph_setup_dopri5(ndcn_solver *s);
+// the ticks one step of a sub-stepped grid reports (solver_advance_grid): tm[q] = t_q - t0, same[q]: the tick is an end of the step
+struct StepEmit {
+    const float *tm;
+    const int *same;
+    float *const *out;
+    int nt;
+};
+
+// The un-fused kernel sequence of one fixed-grid step src -> dst (solvers.py:81-97, rk_common.py:72-78: rk4 by the 3/8 rule), the
+// step size by value, or - dt_dev, hipGraph capture: dt is 0 - read from device memory.  emit (nullable, eager steps): the stage
+// that ends the step writes the new state AND these ticks in one pass (fixed_stage_emit_f32).
+int enqueue_fixed_stages(ndcn_solver *s, const float *src, float *dst, float dt, const float *dt_dev, const StepEmit *emit,
+                         hipStream_t st) {
+    const int64_t n = s->n_elem;
+    float *const *k = s->k;
+    auto last = [&](int op, const float *k2, const float *k3, const float *k4) {
+        if (emit) return fixed_stage_emit_f32(op, dst, src, k[0], k2, k3, k4, dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
+        return fixed_stage_f32(op, dst, src, k[0], k2, k3, k4, dt, n, st, dt_dev);
+    };
+    int rc;
+    if ((rc = rhs(s, src, k[0], st))) return rc;
+    switch (s->d.method) {
+        case NDCN_M_EULER:
+            return last(0, nullptr, nullptr, nullptr);
+        case NDCN_M_MIDPOINT:
+            if ((rc = fixed_stage_f32(1, s->ytmp, src, k[0], nullptr, nullptr, nullptr, dt, n, st, dt_dev))) return rc;
+            if ((rc = rhs(s, s->ytmp, k[0], st))) return rc;
+            return last(0, nullptr, nullptr, nullptr);
+        default:
+            if ((rc = fixed_stage_f32(2, s->ytmp, src, k[0], nullptr, nullptr, nullptr, dt, n, st, dt_dev))) return rc;
+            if ((rc = rhs(s, s->ytmp, k[1], st))) return rc;
+            if ((rc = fixed_stage_f32(3, s->ytmp, src, k[0], k[1], nullptr, nullptr, dt, n, st, dt_dev))) return rc;
+            if ((rc = rhs(s, s->ytmp, k[2], st))) return rc;
+            if ((rc = fixed_stage_f32(4, s->ytmp, src, k[0], k[1], k[2], nullptr, dt, n, st, dt_dev))) return rc;
+            if ((rc = rhs(s, s->ytmp, k[3], st))) return rc;
+            return last(5, k[1], k[2], k[3]);
+    }
+}
+
+// One step's launches, as `enqueue(stream)` issues them on the replay stream, captured into s->gexec; the step size of every replay
+// travels through the pinned ring s->h_dt into s->d_dt.
+template <class Enqueue>
+int capture_step(ndcn_solver *s, Enqueue enqueue) {
+    NDCN_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_dt), kDtRing * sizeof(float), hipHostMallocDefault));
+    hipGraph_t graph = nullptr;
+    prof_pause(true);
+    hipError_t e = hipStreamBeginCapture(s->gstream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) { prof_pause(false); set_error("hipStreamBeginCapture: %s", hipGetErrorString(e)); return NDCN_EHIP; }
+    const int64_t rhs_before = s->n_rhs;
+    const int rc = enqueue(s->gstream);
+    s->n_rhs = rhs_before;                                      // capturing is not evaluating
+    e = hipStreamEndCapture(s->gstream, &graph);
+    prof_pause(false);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return NDCN_EHIP; }
+    e = hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) { set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return NDCN_EHIP; }
+    return NDCN_OK;
+}
+
+// one fixed-grid step on the solver's own panel (y updated in place), dt from d_dt
+int graph_setup(ndcn_solver *s) {
+    return capture_step(s, [s](hipStream_t st) { return enqueue_fixed_stages(s, s->ycur_own, s->ycur_own, 0.f, s->d_dt, nullptr, st); });
+}
+
+// one attempted dopri5 step: the first node forms the fl(dt * beta) table the captured launches read
+int graph_setup_dopri5(ndcn_solver *s) {
+    s->n_coef = 0;
+    int rc = capture_step(s, [s](hipStream_t st) {
+        const int rc = scale_coef_f32(s->d_coef, s->d_beta, s->d_dt, kCoefCap, st);
+        return rc ? rc : enqueue_attempt(s, st, 1.f, s->d_dt);
+    });
+    if (rc) return rc;
+    // the tableau entries the captured launches refer to (constant for the life of the graph)
+    NDCN_HIP(hipMemcpy(s->d_beta, s->h_beta, sizeof(s->h_beta), hipMemcpyHostToDevice));
+    return NDCN_OK;
+}
 
 // dopri5.py:94-122
 int dopri5_step(ndcn_solver *s, hipStream_t st, const StepWant *want) {
@@ -594,26 +625,17 @@ int dopri5_step(ndcn_solver *s, hipStream_t st, const StepWant *want) {
         rc = enqueue_attempt(s, st, dt32, nullptr, &keep);
         if (rc) return rc;
     }
-    double sum, bad;
-    rc = fetch_record(s, st, sum, bad);
+    rc = fetch_record(s, st);
     if (rc) return rc;
+    const double bad = s->h_red[1];
     // misc.py:156 mean in the state dtype; dopri5.py:109
-    const float ratio = (float)(sum / s->n_mean);
+    const float ratio = (float)(s->h_red[0] / s->n_mean);
     const bool accept = ratio <= 1.f;
     // misc.py:160-170.  safety / dfactor passed through a float32 tensor in the reference (dopri5.py:72-74)
     const double safety = s->d.safety > 0 ? s->d.safety : (double)0.9f;
     const double ifactor = s->d.ifactor > 0 ? s->d.ifactor : 10.0;
     const double dfactor = s->d.dfactor > 0 ? s->d.dfactor : (double)0.2f;
-    double dt_next;
-    if (ratio == 0.f) {
-        dt_next = dt * ifactor;
-    } else {
-        const double dfac = ratio < 1.f ? 1.0 : dfactor;
-        const double er = (double)sqrtf(ratio);
-        const double expo = (double)0.2f;
-        const double factor = nan_max(1.0 / ifactor, nan_min(pow(er, expo) / safety, 1.0 / dfac));
-        dt_next = dt / factor;
-    }
+    const double dt_next = ratio == 0.f ? dt * ifactor : dt / step_factor(ratio, safety, ifactor, dfactor).factor;
     s->n_attempt++;
     s->last_ratio = ratio;
     const double row[5] = {t_start, dt, accept ? 1.0 : 0.0, (double)ratio, dt_next};
@@ -953,76 +975,22 @@ int solver_begin(ndcn_solver *s, const float *y0, double t0, hipStream_t st, boo
     return NDCN_OK;
 }
 
-// the kernel sequence of one fixed-grid step on the solver's own buffers (y updated in place), dt from d_dt
-static int enqueue_fixed_step(ndcn_solver *s, hipStream_t st) {
-    const int64_t n = s->n_elem;
-    float *y = s->ycur_own;
-    const float *dtp = s->d_dt;
-    int rc;
-    if ((rc = rhs(s, y, s->k[0], st))) return rc;
-    switch (s->d.method) {
-        case NDCN_M_EULER:
-            return fixed_stage_f32(0, y, y, s->k[0], nullptr, nullptr, nullptr, 0.f, n, st, dtp);
-        case NDCN_M_MIDPOINT:
-            if ((rc = fixed_stage_f32(1, s->ytmp, y, s->k[0], nullptr, nullptr, nullptr, 0.f, n, st, dtp))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[0], st))) return rc;
-            return fixed_stage_f32(0, y, y, s->k[0], nullptr, nullptr, nullptr, 0.f, n, st, dtp);
-        default:
-            if ((rc = fixed_stage_f32(2, s->ytmp, y, s->k[0], nullptr, nullptr, nullptr, 0.f, n, st, dtp))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[1], st))) return rc;
-            if ((rc = fixed_stage_f32(3, s->ytmp, y, s->k[0], s->k[1], nullptr, nullptr, 0.f, n, st, dtp))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[2], st))) return rc;
-            if ((rc = fixed_stage_f32(4, s->ytmp, y, s->k[0], s->k[1], s->k[2], nullptr, 0.f, n, st, dtp))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[3], st))) return rc;
-            return fixed_stage_f32(5, y, y, s->k[0], s->k[1], s->k[2], s->k[3], 0.f, n, st, dtp);
+int evals_per_step(int method) { return method == NDCN_M_EULER ? 1 : method == NDCN_M_MIDPOINT ? 2 : 4; }
+
+// The clock, the counters and the state's whereabouts after n_steps fixed-grid steps.  dst: where the last one wrote the state
+// (nullptr: in place); tf: the time in the state dtype; [t0, t1]: the last step.  Evaluations are counted where they are
+// enqueued (rhs / rhs_epi), or by the caller where one launch or a replay stands for several.
+static void finish_steps(ndcn_solver *s, float *dst, float tf, double t0, double t1, int64_t n_steps) {
+    if (dst) {                         // the next step reads the state from where it was written
+        s->ycur = dst;
+        s->cur_is_borrowed = (dst != s->ycur_own);
     }
+    s->tf = tf;
+    s->t0 = t0;
+    s->t1 = t1;
+    s->n_attempt += n_steps;
+    s->n_accept += n_steps;
 }
-
-static int graph_setup(ndcn_solver *s) {
-    NDCN_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_dt), kDtRing * sizeof(float), hipHostMallocDefault));
-    hipGraph_t graph = nullptr;
-    prof_pause(true);
-    hipError_t eb = hipStreamBeginCapture(s->gstream, hipStreamCaptureModeThreadLocal);
-    if (eb != hipSuccess) { prof_pause(false); set_error("hipStreamBeginCapture: %s", hipGetErrorString(eb)); return NDCN_EHIP; }
-    const int64_t rhs_before = s->n_rhs;
-    const int rc = enqueue_fixed_step(s, s->gstream);
-    s->n_rhs = rhs_before;                                      // capturing is not evaluating
-    hipError_t e = hipStreamEndCapture(s->gstream, &graph);
-    prof_pause(false);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return NDCN_EHIP; }
-    e = hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return NDCN_EHIP; }
-    return NDCN_OK;
-}
-
-}  // namespace ndcn
-namespace {
-int graph_setup_dopri5(ndcn_solver *s) {
-    NDCN_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_dt), kDtRing * sizeof(float), hipHostMallocDefault));
-    hipGraph_t graph = nullptr;
-    prof_pause(true);
-    hipError_t e = hipStreamBeginCapture(s->gstream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) { prof_pause(false); set_error("hipStreamBeginCapture: %s", hipGetErrorString(e)); return NDCN_EHIP; }
-    const int64_t rhs_before = s->n_rhs;
-    s->n_coef = 0;
-    int rc = scale_coef_f32(s->d_coef, s->d_beta, s->d_dt, kCoefCap, s->gstream);    // first node: fl(dt * beta) table
-    if (!rc) rc = enqueue_attempt(s, s->gstream, 1.f, s->d_dt);
-    s->n_rhs = rhs_before;                                      // capturing is not evaluating
-    e = hipStreamEndCapture(s->gstream, &graph);
-    prof_pause(false);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return NDCN_EHIP; }
-    // the tableau entries the captured launches refer to (constant for the life of the graph)
-    NDCN_HIP(hipMemcpy(s->d_beta, s->h_beta, sizeof(s->h_beta), hipMemcpyHostToDevice));
-    e = hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return NDCN_EHIP; }
-    return NDCN_OK;
-}
-}  // namespace
-namespace ndcn {
 
 static int graph_advance(ndcn_solver *s, double next_t, float *out, hipStream_t st) {
     const float t1 = (float)next_t;
@@ -1041,23 +1009,10 @@ static int graph_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
     if (out) NDCN_HIP(hipMemcpyAsync(out, s->ycur_own, (size_t)s->n_elem * sizeof(float), hipMemcpyDeviceToDevice, s->gstream));
     NDCN_HIP(hipEventRecord(s->gev_out, s->gstream));
     NDCN_HIP(hipStreamWaitEvent(st, s->gev_out, 0));            // the caller's stream sees the result
-    const int per = s->d.method == NDCN_M_EULER ? 1 : s->d.method == NDCN_M_MIDPOINT ? 2 : 4;
-    s->n_rhs += per;
-    s->tf = t1;
-    s->t0 = s->t1;
-    s->t1 = next_t;
-    s->n_attempt++;
-    s->n_accept++;
+    s->n_rhs += evals_per_step(s->d.method);
+    finish_steps(s, nullptr, t1, s->t1, next_t, 1);
     return NDCN_OK;
 }
-
-// the ticks one step of a sub-stepped grid reports (solver_advance_grid): tm[q] = t_q - t0, same[q]: the tick is an end of the step
-struct StepEmit {
-    const float *tm;
-    const int *same;
-    float *const *out;
-    int nt;
-};
 
 // emit (nullable): the stage that ends the step writes the new state AND these ticks in one pass (fixed_stage_emit_f32) where the
 // step ends in a stage kernel; `emitted` then says so - where it ends in a fused RHS epilogue the caller emits from the new state
@@ -1067,7 +1022,6 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
     // solvers.py:81-97 with grid == t: one step of size t1 - t0 formed in the state dtype
     const float t1 = (float)next_t;
     const float dt = t1 - s->tf;
-    const int64_t n = s->n_elem;
     float *dst = out ? out : s->ycur_own;
     int rc;
     if (s->fused2 && s->d.method == NDCN_M_EULER && dst != s->ycur) {
@@ -1077,16 +1031,7 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
         opt.no_k = 1;                                        // nothing reads an Euler step's K
         rc = rhs_epi(s, s->ycur, s->k[0], 1, s->ycur, nullptr, c1, 0, dst, 0.f, 0.f, nullptr, nullptr, st, nullptr, &opt);
         if (rc) return rc;
-        s->ycur = dst;
-        s->cur_is_borrowed = (dst != s->ycur_own);
-        s->tf = t1;
-        s->t0 = s->t1;
-        s->t1 = next_t;
-        s->n_attempt++;
-        s->n_accept++;
-        return NDCN_OK;
-    }
-    if (s->fused2 && s->d.method == NDCN_M_RK4) {
+    } else if (s->fused2 && s->d.method == NDCN_M_RK4) {
         // the 3/8-rule stage algebra in the RHS epilogues (rk_common.py:72-78): 4 launches instead of 8, each stage
         // input written by the launch that produced the stage it needs last
         const float c1[1] = {dt};
@@ -1100,51 +1045,20 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
             if (rc) return rc;
             in = nxt;
         }
-        s->ycur = dst;
-        s->cur_is_borrowed = (dst != s->ycur_own);
-        s->tf = t1;
-        s->t0 = s->t1;
-        s->t1 = next_t;
-        s->n_attempt++;
-        s->n_accept++;
-        return NDCN_OK;
+    } else {
+        if ((rc = enqueue_fixed_stages(s, s->ycur, dst, dt, nullptr, emit, st))) return rc;
+        if (emit && emitted) *emitted = true;
     }
-    if ((rc = rhs(s, s->ycur, s->k[0], st))) return rc;
-    switch (s->d.method) {
-        case NDCN_M_EULER:
-            if (emit) rc = fixed_stage_emit_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
-            else rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
-            break;
-        case NDCN_M_MIDPOINT:
-            if ((rc = fixed_stage_f32(1, s->ytmp, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[0], st))) return rc;
-            if (emit) rc = fixed_stage_emit_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
-            else rc = fixed_stage_f32(0, dst, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st);
-            break;
-        default:  // rk4, 3/8 rule
-            if ((rc = fixed_stage_f32(2, s->ytmp, s->ycur, s->k[0], nullptr, nullptr, nullptr, dt, n, st))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[1], st))) return rc;
-            if ((rc = fixed_stage_f32(3, s->ytmp, s->ycur, s->k[0], s->k[1], nullptr, nullptr, dt, n, st))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[2], st))) return rc;
-            if ((rc = fixed_stage_f32(4, s->ytmp, s->ycur, s->k[0], s->k[1], s->k[2], nullptr, dt, n, st))) return rc;
-            if ((rc = rhs(s, s->ytmp, s->k[3], st))) return rc;
-            if (emit) rc = fixed_stage_emit_f32(5, dst, s->ycur, s->k[0], s->k[1], s->k[2], s->k[3], dt, emit->tm, emit->same, emit->out, emit->nt, n, st);
-            else rc = fixed_stage_f32(5, dst, s->ycur, s->k[0], s->k[1], s->k[2], s->k[3], dt, n, st);
-            break;
-    }
-    if (rc) return rc;
-    if (emit && emitted) *emitted = true;
-    s->ycur = dst;                 // the next step reads the state from where it was written
-    s->cur_is_borrowed = (dst != s->ycur_own);
-    s->tf = t1;
-    s->t0 = s->t1;
-    s->t1 = next_t;
-    s->n_attempt++;
-    s->n_accept++;
+    finish_steps(s, dst, t1, s->t1, next_t, 1);
     return NDCN_OK;
 }
 
-static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st);
+// An Euler step whose stage algebra rides in the RHS epilogue cannot update the panel it reads: with the state inside the solver such
+// steps alternate between its own panel and `alt`.  The `out` of the next fixed_advance: `alt`, or nullptr (the solver's panel).
+static float *euler_pingpong(const ndcn_solver *s, float *alt) {
+    const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
+    return (pingpong && s->ycur == s->ycur_own) ? alt : nullptr;
+}
 
 // ndcn_solver_begin_borrowed: results must not land in the initial state the solver still reads
 static bool overlaps_borrowed(const ndcn_solver *s, const float *out, int64_t n_panels) {
@@ -1157,14 +1071,9 @@ static bool overlaps_borrowed(const ndcn_solver *s, const float *out, int64_t n_
     return false;
 }
 
-int solver_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st) {
-    NDCN_CHECK_ARG(s, "null solver");
-    if (!s->begun) { set_error("ndcn_solver_advance before ndcn_solver_begin"); return NDCN_ESTATE; }
-    if (overlaps_borrowed(s, out, 1)) return NDCN_EINVAL;
-    if (s->d.method != NDCN_M_DOPRI5) return fixed_advance(s, next_t, out, st);
-    // replay mode: the captured attempt is launched into the caller's stream like any other work (capture needed a
-    // stream of its own, replay does not)
-    return dopri5_advance(s, next_t, out, budget, st);
+static int bad_abscissa(float a0, float at, float a1) {
+    set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", a0, at, a1);
+    return NDCN_ESTATE;
 }
 
 static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st) {
@@ -1189,15 +1098,9 @@ static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t bud
         ++n_here;
     }
     if (!out) return NDCN_OK;
-    // interp.py:51-65: abscissa and its powers in the state dtype
     const float a0 = (float)s->t0, a1 = (float)s->t1, at = (float)next_t;
-    if (!(a0 <= at && at <= a1)) {
-        set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", a0, at, a1);
-        return NDCN_ESTATE;
-    }
-    const float x = (at - a0) / (a1 - a0);
     float xp[5];
-    xp[4] = 1.f; xp[3] = x; xp[2] = xp[3] * x; xp[1] = xp[2] * x; xp[0] = xp[1] * x;
+    if (!interp_abscissa(a0, a1, at, xp)) return bad_abscissa(a0, at, a1);
     if (!s->fit_valid) {
         if (!s->fit_pending) { set_error("no accepted step covers t=%g", next_t); return NDCN_ESTATE; }
         if (s->evals_in_step++ == 0) {
@@ -1217,59 +1120,30 @@ static int dopri5_advance(ndcn_solver *s, double next_t, float *out, int64_t bud
     return interp_eval_f32(s->ca, s->cb, s->cc, s->cd, s->ce, xp, out, s->n_elem, st);
 }
 
-// dopri5: all of `h_ticks` (increasing) in one call; out[i] = y(h_ticks[i]), panels back to back.  Ticks that fall
-// into the same accepted step are evaluated together: the step's panels are read once per <= 8 ticks
-// (interp_direct_multi_f32) instead of once per tick - the reference's drivers sample 16-120 ticks over a handful of
-// steps, where the dense output is most of the solve (dgnn.py:173-182: 15 ticks in 2 steps).  Same arithmetic per
-// element as the single-tick path (bit-identical).  Fixed-grid methods: one step per tick, as ndcn_solver_advance.
-int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, hipStream_t st) {
-    NDCN_CHECK_ARG(s && (n_ticks == 0 || (h_ticks && out)), "null argument");
-    if (!s->begun) { set_error("ndcn_solver_advance_many before ndcn_solver_begin"); return NDCN_ESTATE; }
-    if (overlaps_borrowed(s, out, n_ticks)) return NDCN_EINVAL;
-    const size_t stride = (size_t)s->n_elem;
+int solver_advance(ndcn_solver *s, double next_t, float *out, int64_t budget, hipStream_t st) {
+    NDCN_CHECK_ARG(s, "null solver");
+    if (!s->begun) { set_error("ndcn_solver_advance before ndcn_solver_begin"); return NDCN_ESTATE; }
+    if (overlaps_borrowed(s, out, 1)) return NDCN_EINVAL;
+    if (s->d.method != NDCN_M_DOPRI5) return fixed_advance(s, next_t, out, st);
+    // replay mode: the captured attempt is launched into the caller's stream like any other work (capture needed a
+    // stream of its own, replay does not)
+    return dopri5_advance(s, next_t, out, budget, st);
+}
+
+// dopri5 over all of `h_ticks` (increasing).  Ticks that fall into the same accepted step are evaluated together: the step's panels
+// are read once per <= 8 ticks instead of once per tick - the reference's drivers sample 16-120 ticks over a handful of steps, where
+// the dense output is most of the solve (dgnn.py:173-182: 15 ticks in 2 steps).  Same arithmetic per element as the single-tick path
+// (bit-identical).  The caller supplies where the ticks go:
+//   single(i)                         tick i through dopri5_advance (a stored fit, or no fresh step)
+//   batch(kk, cm, xp, first, nt)      ticks [first, first + nt) of the fresh accepted step: its dense_terms, 5 powers per tick
+template <class Single, class Batch>
+static int dopri5_ticks(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, Single single, Batch batch, hipStream_t st) {
     int64_t i = 0;
-    // Fixed grid on a state that fits one compute unit: the whole time vector in ONE launch (solve_small.hip) - bit-identical
-    // to the per-step kernels below, without their launch latency.
-    if (s->d.method != NDCN_M_DOPRI5 && n_ticks > 0 && !s->sharded && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
-        std::vector<float> dts((size_t)n_ticks);
-        float tf = s->tf;
-        for (int64_t q = 0; q < n_ticks; ++q) {            // solvers.py:81-97 with grid == t: step sizes formed in the state dtype
-            const float t1 = (float)h_ticks[q];
-            dts[(size_t)q] = t1 - tf;
-            tf = t1;
-        }
-        int rc = solve_small_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_ticks, out, st);
-        if (rc) return rc;
-        float *last = out + (size_t)(n_ticks - 1) * stride;
-        if (s->graph_on) {                                 // replayed steps keep the state inside the solver
-            NDCN_HIP(hipMemcpyAsync(s->ycur_own, last, stride * sizeof(float), hipMemcpyDeviceToDevice, st));
-            s->ycur = s->ycur_own;
-            s->cur_is_borrowed = false;
-        } else {
-            s->ycur = last;
-            s->cur_is_borrowed = true;
-        }
-        const int per = s->d.method == NDCN_M_EULER ? 1 : s->d.method == NDCN_M_MIDPOINT ? 2 : 4;
-        s->n_rhs += per * n_ticks;
-        s->tf = tf;
-        s->t0 = n_ticks > 1 ? h_ticks[n_ticks - 2] : s->t1;
-        s->t1 = h_ticks[n_ticks - 1];
-        s->n_attempt += n_ticks;
-        s->n_accept += n_ticks;
-        return NDCN_OK;
-    }
     while (i < n_ticks) {
-        if (s->d.method != NDCN_M_DOPRI5) {
-            int rc = fixed_advance(s, h_ticks[i], out + i * stride, st);
-            if (rc) return rc;
-            ++i;
-            continue;
-        }
         int rc = dopri5_advance(s, h_ticks[i], nullptr, 0, st);          // steps only (no evaluation)
         if (rc) return rc;
         if (s->fit_valid || !s->fit_pending) {                           // a stored fit / no fresh step: single-tick path
-            rc = dopri5_advance(s, h_ticks[i], out + i * stride, 0, st);
-            if (rc) return rc;
+            if ((rc = single(i))) return rc;
             ++i;
             continue;
         }
@@ -1282,24 +1156,58 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
         while (i < j) {
             const int nt = (int)((j - i) < 8 ? (j - i) : 8);
             float xp[8][5];
-            float *outs[8];
             for (int t = 0; t < nt; ++t) {
-                // interp.py:51-65: abscissa and its powers in the state dtype
                 const float at = (float)h_ticks[i + t];
-                if (!(a0 <= at && at <= a1)) {
-                    set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", a0, at, a1);
-                    return NDCN_ESTATE;
-                }
-                const float x = (at - a0) / (a1 - a0);
-                xp[t][4] = 1.f; xp[t][3] = x; xp[t][2] = xp[t][3] * x; xp[t][1] = xp[t][2] * x; xp[t][0] = xp[t][1] * x;
-                outs[t] = out + (i + t) * stride;
+                if (!interp_abscissa(a0, a1, at, xp[t])) return bad_abscissa(a0, at, a1);
             }
-            rc = interp_direct_multi_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, &xp[0][0], outs, nt, s->n_elem, st);
-            if (rc) return rc;
+            if ((rc = batch(kk, cm, &xp[0][0], i, nt))) return rc;
             s->evals_in_step += nt;
             i += nt;
         }
     }
+    return NDCN_OK;
+}
+
+// All of `h_ticks` (increasing) in one call; out[i] = y(h_ticks[i]), panels back to back.  dopri5: dopri5_ticks, a step's ticks
+// through interp_direct_multi_f32.  Fixed-grid methods: one step per tick, as ndcn_solver_advance.
+int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, float *out, hipStream_t st) {
+    NDCN_CHECK_ARG(s && (n_ticks == 0 || (h_ticks && out)), "null argument");
+    if (!s->begun) { set_error("ndcn_solver_advance_many before ndcn_solver_begin"); return NDCN_ESTATE; }
+    if (overlaps_borrowed(s, out, n_ticks)) return NDCN_EINVAL;
+    const size_t stride = (size_t)s->n_elem;
+    int rc;
+    if (s->d.method == NDCN_M_DOPRI5)
+        return dopri5_ticks(
+            s, h_ticks, n_ticks, [&](int64_t i) { return dopri5_advance(s, h_ticks[i], out + i * stride, 0, st); },
+            [&](const float *const *kk, const float *cm, const float *xp, int64_t first, int nt) {
+                float *outs[8];
+                for (int t = 0; t < nt; ++t) outs[t] = out + (first + t) * stride;
+                return interp_direct_multi_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, xp, outs, nt, s->n_elem, st);
+            },
+            st);
+    // Fixed grid on a state that fits one compute unit: the whole time vector in ONE launch (solve_small.hip) - bit-identical
+    // to the per-step kernels below, without their launch latency.
+    if (n_ticks > 0 && !s->sharded && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+        std::vector<float> dts((size_t)n_ticks);
+        float tf = s->tf;
+        for (int64_t q = 0; q < n_ticks; ++q) {            // solvers.py:81-97 with grid == t: step sizes formed in the state dtype
+            const float t1 = (float)h_ticks[q];
+            dts[(size_t)q] = t1 - tf;
+            tf = t1;
+        }
+        rc = solve_small_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_ticks, out, st);
+        if (rc) return rc;
+        float *last = out + (size_t)(n_ticks - 1) * stride;
+        if (s->graph_on) {                                 // replayed steps keep the state inside the solver
+            NDCN_HIP(hipMemcpyAsync(s->ycur_own, last, stride * sizeof(float), hipMemcpyDeviceToDevice, st));
+            last = s->ycur_own;
+        }
+        s->n_rhs += evals_per_step(s->d.method) * n_ticks;
+        finish_steps(s, last, tf, n_ticks > 1 ? h_ticks[n_ticks - 2] : s->t1, h_ticks[n_ticks - 1], n_ticks);
+        return NDCN_OK;
+    }
+    for (int64_t i = 0; i < n_ticks; ++i)
+        if ((rc = fixed_advance(s, h_ticks[i], out + i * stride, st))) return rc;
     return NDCN_OK;
 }
 
@@ -1335,10 +1243,8 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
     const size_t ostride = (size_t)rows * (size_t)C;
     int rc;
     if (fixed) {
-        const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
         for (int64_t i = 0; i < n_ticks; ++i) {
-            float *inside = (pingpong && s->ycur == s->ycur_own) ? scratch : nullptr;
-            if ((rc = fixed_advance(s, h_ticks[i], inside, st))) return rc;
+            if ((rc = fixed_advance(s, h_ticks[i], euler_pingpong(s, scratch), st))) return rc;
             if ((rc = linear_f32(s->ycur, Wd, bd, out + (size_t)i * ostride, rows, H, C, 0, st))) return rc;
             g_last_readout_path |= NDCN_READOUT_FIXED;
         }
@@ -1349,46 +1255,22 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
         }
         return NDCN_OK;
     }
-    int64_t i = 0;
-    while (i < n_ticks) {
-        rc = dopri5_advance(s, h_ticks[i], nullptr, 0, st);               // steps only (no evaluation)
-        if (rc) return rc;
-        if (s->fit_valid || !s->fit_pending) {                           // a stored fit / no fresh step: single-tick path
-            if ((rc = dopri5_advance(s, h_ticks[i], scratch, 0, st))) return rc;
-            if ((rc = linear_f32(scratch, Wd, bd, out + (size_t)i * ostride, rows, H, C, 0, st))) return rc;
-            g_last_readout_path |= NDCN_READOUT_STAGED;
-            ++i;
-            continue;
-        }
-        int64_t j = i;
-        while (j < n_ticks && !(h_ticks[j] > s->t1)) ++j;                // the ticks this accepted step covers
-        const float a0 = (float)s->t0, a1 = (float)s->t1;
-        const float *kk[7];
-        float cm[7];
-        if ((rc = dense_terms(s, kk, cm))) return rc;
-        while (i < j) {
-            const int nt = (int)((j - i) < 8 ? (j - i) : 8);
-            float xp[8][5];
+    return dopri5_ticks(
+        s, h_ticks, n_ticks,
+        [&](int64_t i) {
+            int rc1 = dopri5_advance(s, h_ticks[i], scratch, 0, st);
+            if (!rc1) rc1 = linear_f32(scratch, Wd, bd, out + (size_t)i * ostride, rows, H, C, 0, st);
+            if (!rc1) g_last_readout_path |= NDCN_READOUT_STAGED;
+            return rc1;
+        },
+        [&](const float *const *kk, const float *cm, const float *xp, int64_t first, int nt) {
             float *outs[8];
-            for (int t = 0; t < nt; ++t) {
-                // interp.py:51-65: abscissa and its powers in the state dtype
-                const float at = (float)h_ticks[i + t];
-                if (!(a0 <= at && at <= a1)) {
-                    set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", a0, at, a1);
-                    return NDCN_ESTATE;
-                }
-                const float x = (at - a0) / (a1 - a0);
-                xp[t][4] = 1.f; xp[t][3] = x; xp[t][2] = xp[t][3] * x; xp[t][1] = xp[t][2] * x; xp[t][0] = xp[t][1] * x;
-                outs[t] = out + (size_t)(i + t) * ostride;
-            }
-            rc = interp_readout_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, &xp[0][0], outs, nt, Wd, bd, rows, H, C, st);
-            if (rc) return rc;
-            g_last_readout_path |= NDCN_READOUT_FUSED;
-            s->evals_in_step += nt;
-            i += nt;
-        }
-    }
-    return NDCN_OK;
+            for (int t = 0; t < nt; ++t) outs[t] = out + (size_t)(first + t) * ostride;
+            const int rc1 = interp_readout_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, xp, outs, nt, Wd, bd, rows, H, C, st);
+            if (!rc1) g_last_readout_path |= NDCN_READOUT_FUSED;
+            return rc1;
+        },
+        st);
 }
 
 // FixedGridODESolver.integrate with the step_size option (solvers.py:55-68,79-108): every step of h_grid with the state inside the
@@ -1408,7 +1290,6 @@ int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, con
             return NDCN_EINVAL;
         }
     const size_t stride = (size_t)s->n_elem;
-    const int per = s->d.method == NDCN_M_EULER ? 1 : s->d.method == NDCN_M_MIDPOINT ? 2 : 4;
     std::vector<float> tm((size_t)n_ticks);
     std::vector<int> same((size_t)n_ticks);
     std::vector<float *> outs((size_t)n_ticks);
@@ -1426,22 +1307,14 @@ int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, con
         int rc = solve_small_grid_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_steps,
                                       h_tick_step, same.data(), n_ticks, out, s->ycur_own, st);
         if (rc) return rc;
-        s->ycur = s->ycur_own;
-        s->cur_is_borrowed = false;
-        s->n_rhs += per * n_steps;
-        s->tf = h_grid[n_steps];
-        s->t0 = (double)h_grid[n_steps - 1];
-        s->t1 = (double)h_grid[n_steps];
-        s->n_attempt += n_steps;
-        s->n_accept += n_steps;
+        s->n_rhs += evals_per_step(s->d.method) * n_steps;
+        finish_steps(s, s->ycur_own, h_grid[n_steps], (double)h_grid[n_steps - 1], (double)h_grid[n_steps], n_steps);
         return NDCN_OK;
     }
-    // an Euler step whose stage algebra rides in the RHS epilogue cannot update the panel it reads: with the state inside the solver
-    // such steps alternate between its own panel and a stage panel Euler leaves idle (the launches of a step that writes a tick)
-    const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
     int64_t j = 0;
     for (int64_t i = 0; i < n_steps; ++i) {
-        float *inside = (pingpong && s->ycur == s->ycur_own) ? s->ytmp2 : nullptr;
+        // (Euler in the RHS epilogue: a stage panel Euler leaves idle is the alternate - the launches of a step that writes a tick)
+        float *inside = euler_pingpong(s, s->ytmp2);
         int64_t j1 = j;
         while (j1 < n_ticks && h_tick_step[j1] == i) ++j1;
         const int nt = (int)(j1 - j);

@@ -205,8 +205,7 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
     if (rc) return rc;
     t->d0 = rms_value(t->s0, (double)t->n);
     t->d1 = rms_value(t->s1, (double)t->n);
-    t->h0_const = t->d0 < 1e-5 || t->d1 < 1e-5;
-    t->h0 = t->h0_const ? 1e-6f : 0.01f * (t->d0 / t->d1);
+    t->h0 = initial_h0(t->d0, t->d1, &t->h0_const);
     float *yh, *f1;
     if ((rc = panel(t, &yh)) || (rc = panel(t, &f1))) return rc;
     const float *kp[1] = {t->f0};
@@ -221,33 +220,9 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
     if (rc) return rc;
     t->d2r = rms_value(t->s2, (double)t->n);
     t->d2 = t->d2r / t->h0;
-    t->h1_alt = t->d1 <= 1e-15 && t->d2 <= 1e-15;
-    if (t->h1_alt) {
-        const float a = 1e-6f, b = t->h0 * 1e-3f;
-        t->h1 = a > b ? a : b;
-    } else {
-        const float m = t->d1 >= t->d2 ? t->d1 : t->d2;       // python max([d1, d2]): the first maximum
-        const float a = (1.0f / m) * 0.01f;                   // solver.hip initial_step: the same two float32 roundings
-        t->h1 = (float)pow((double)a, 1. / 5.);
-    }
-    const float h100 = 100.f * t->h0;
-    t->dt_init = (double)(h100 < t->h1 ? h100 : t->h1);
-    if (isnan(h100) || isnan(t->h1)) t->dt_init = NAN;
+    t->h1 = initial_h1(t->d1, t->d2, t->h0, &t->h1_alt);
+    t->dt_init = initial_dt(t->h0, t->h1);
     return NDCN_OK;
-}
-
-// the non-zero terms of row `beta` scaled by the step size (misc.py:25 in float32), k indices kept
-int terms(float dts, const double *beta, int n, const float *const *kall, const float **kp, float *cp, int *idx) {
-    int m = 0;
-    for (int j = 0; j < n; ++j) {
-        const float bj = (float)beta[j];
-        if (bj == 0.f) continue;
-        kp[m] = kall[j];
-        cp[m] = dts * bj;
-        if (idx) idx[m] = j;
-        ++m;
-    }
-    return m;
 }
 
 int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, double &bad_out) {
@@ -265,20 +240,13 @@ int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, d
     const float *kp[8];
     float cp[8];
     const float dts = a.dts;
-    int m = terms(dts, kBeta[0], 1, kall, kp, cp, nullptr);
+    int m = dt_terms(dts, kBeta[0], 1, kall, kp, cp);
     rc = rk_combine_f32(u[2], a.y0, kp, cp, m, t->n, st);
     if (rc) return rc;
     const uint32_t fl = t->flags;
     for (int i = 0; i < 5; ++i) {
         // evaluation i + 2: k[i + 1] = f(u[i + 2]); its epilogue forms u[i + 3] from row i + 1 of the tableau
-        int mp = 0;
-        for (int j = 0; j <= i; ++j) {
-            const float bj = (float)kBeta[i + 1][j];
-            if (bj == 0.f) continue;
-            kp[mp] = kall[j];
-            cp[mp] = dts * bj;
-            ++mp;
-        }
+        const int mp = dt_terms(dts, kBeta[i + 1], i + 1, kall, kp, cp);
         cp[mp] = dts * (float)kBeta[i + 1][i + 1];
         t->nfe++;
         RkOpt opt = {};
@@ -292,14 +260,7 @@ int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, d
     }
     a.fused_err = t->n > aten_order_max_elems();
     if (a.fused_err) {
-        int mp = 0;
-        for (int j = 0; j < 6; ++j) {
-            const float cj = (float)kCErr[j];
-            if (cj == 0.f) continue;
-            kp[mp] = kall[j];
-            cp[mp] = dts * cj;
-            ++mp;
-        }
+        const int mp = dt_terms(dts, kCErr, 6, kall, kp, cp);
         cp[mp] = dts * (float)kCErr[6];
         t->nfe++;
         RkOpt opt = {};
@@ -314,7 +275,7 @@ int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, d
     } else {
         rc = rhs_plain(t, u[7], k[6], st);
         if (rc) return rc;
-        m = terms(dts, kCErr, 7, kall, kp, cp, nullptr);
+        m = dt_terms(dts, kCErr, 7, kall, kp, cp);
         rc = rk_error_f32(a.y0, u[7], kp, cp, m, (float)t->rtol, (float)t->atol, t->n, t->d_red, t->d_ws, st);
         if (rc) return rc;
     }
@@ -524,10 +485,7 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
                 dt_next = dt * t->ifactor;
                 a.factor = 0;
             } else {
-                const double dfac = ratio < 1.f ? 1.0 : t->dfactor;
-                const double er = (double)sqrtf(ratio);
-                const double expo = (double)0.2f;
-                a.factor = nan_max(1.0 / t->ifactor, nan_min(pow(er, expo) / t->safety, 1.0 / dfac));
+                a.factor = step_factor(ratio, t->safety, t->ifactor, t->dfactor).factor;
                 dt_next = dt / a.factor;
             }
             a.dt_next = dt_next;
@@ -557,14 +515,11 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
         float *outs[7];
         for (;;) {
             const float at = (float)ticks[i];
-            if (!(g.a0 <= at && at <= g.a1)) { set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", (double)g.a0, (double)at, (double)g.a1); return NDCN_EINVAL; }
-            const float x = (at - g.a0) / (g.a1 - g.a0);
-            const float x2 = x * x, x3 = x2 * x, x4 = x3 * x;
             float *q = xp + 5 * g.nt;
-            q[0] = x4; q[1] = x3; q[2] = x2; q[3] = x; q[4] = 1.f;
+            if (!interp_abscissa(g.a0, g.a1, at, q)) { set_error("invalid interpolation, fails `t0 <= t <= t1`: %g, %g, %g", (double)g.a0, (double)at, (double)g.a1); return NDCN_EINVAL; }
             outs[g.nt] = out + (size_t)i * t->n;
             g.tick[g.nt] = (int)i;
-            g.x[g.nt] = x;
+            g.x[g.nt] = q[3];
             ++g.nt;
             if (i + 1 < n_t && g.nt < 7 && !(ticks[i + 1] > t_hi)) ++i;
             else break;
@@ -658,9 +613,8 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
         } else {
             g_dt += g_dt_next / a.factor;
             const double g_factor = -g_dt_next * a.dt / (a.factor * a.factor);
-            const double dfac = a.ratio < 1.f ? 1.0 : t->dfactor;
-            const double er = (double)sqrtf(a.ratio), expo = (double)0.2f;
-            const double Bv = pow(er, expo) / t->safety, Cv = 1.0 / dfac, Av = 1.0 / t->ifactor;
+            const StepFactor sf = step_factor(a.ratio, t->safety, t->ifactor, t->dfactor);
+            const double er = sf.er, expo = kStepExpo, Bv = sf.b, Cv = sf.c, Av = sf.a;
             const double inner = nan_min(Bv, Cv);
             // torch.max(A, min(B, C)): maximum / minimum split the gradient evenly on ties
             const double share_inner = half_on_tie_gt(inner, Av);
@@ -726,7 +680,7 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
             const float *kp[8];
             float *hgk[8];
             const float *hacc[8];
-            err_m = terms(a.dts, kCErr, 7, a.k, kp, err_c, err_idx);
+            err_m = dt_terms(a.dts, kCErr, 7, a.k, kp, err_c, err_idx);
             for (int q = 0; q < err_m; ++q) {
                 hgk[q] = own_gk[err_idx[q]];
                 hacc[q] = cur_gk[err_idx[q]];
@@ -869,8 +823,8 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
             const float b1 = t->h0 * 1e-3f;
             g_h0 += 1e-3f * g_h1 * (float)half_on_tie_gt((double)b1, (double)1e-6f);
         } else {
-            const float m = t->d1 >= t->d2 ? t->d1 : t->d2;
-            const float av = (1.0f / m) * 0.01f;
+            float m;
+            const float av = initial_h1_base(t->d1, t->d2, &m);
             const float g_av = g_h1 * (float)(0.2 * pow((double)av, 0.2 - 1.0));
             const float g_m = -g_av * 0.01f / (m * m);
             if (t->d1 >= t->d2) g_d1 += g_m;

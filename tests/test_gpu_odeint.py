@@ -428,6 +428,89 @@ def test_borrowed_initial_state_equals_the_copied_one(dev):
     assert torch.equal(res[True][1][0], res[True][2][0])
 
 
+@pytest.mark.parametrize('state', ['one_launch_20x20_H20', 'lattice_33x33_H64'])
+@pytest.mark.parametrize('method', ['euler', 'midpoint', 'rk4', 'dopri5'])
+def test_clock_and_counters_do_not_depend_on_the_entry_point(dev, method, state):
+    """The same ticks through ndcn_solver_advance in a loop, ndcn_solver_advance_many, ndcn_solver_advance_many_readout (where it does
+    not decline) and, fixed grids, ndcn_solver_advance_grid with a plan whose grid IS the ticks; hipGraph replay asked for and not.
+    Every route leaves the same stats() - attempts, accepts, evaluations, t1, dt, last ratio - and the same steplog(), writes the
+    same panels (the readout: their decoded image), and - the float32 clock of the fixed grids and the state's whereabouts are not
+    in stats() - takes the same step to one more tick afterwards.
+    States: the 20 x 20 lattice at H = 20 (fixed grids: the one-launch branches; the readout declines there - H < 64, or the
+    one-launch state - which test_gpu_readout.py covers) and test_gpu_readout.py's 33 x 33 lattice at its smallest width, H = 64
+    (beyond the one-launch solve: per-step launches, every route applies).  The ticks are float32 values, as odeint passes them."""
+    from test_gpu_readout import DOPRI5_CASES, make_decoder, make_func as lattice_func
+    from ndcn_amd import hip
+    from ndcn_amd.torchdiffeq._impl import core
+    from ndcn_amd.torchdiffeq._impl.odeint import DeviceSolver
+    S, H = (20, 20) if state.startswith('one_launch') else (33, min(c[0] for c in DOPRI5_CASES))
+    assert (S, H) in ((20, 20), (33, 64))
+    f, x0 = lattice_func(S, H, dev)
+    n = S * S
+    C = 3
+    Wd, bd = make_decoder(H, C, True, dev)
+    if method == 'dopri5':                                   # 22 ticks over a few accepted steps: more than 8 in one, none in others
+        t32 = np.linspace(0., 5., 23).astype(np.float32)
+        kw = dict(rtol=.01, atol=.001)
+    else:
+        t32 = np.array([0., .05, .3, .35, .8, 1., 1.5], dtype=np.float32)
+        kw = {}
+    ticks, extra = t32[1:-1].tolist(), float(t32[-1])
+    plan = core.fixed_plan(t32[:-1])
+    assert plan.default and plan.tick_step[1:].tolist() == list(range(len(ticks)))
+    routes = ['advance', 'advance_many', 'advance_many_readout'] + (['advance_grid'] if method != 'dopri5' else [])
+    res = {}
+    for use_graph in (False, True):
+        for route in routes:
+            s = DeviceSolver(f, n, method, use_graph=use_graph, **kw)
+            try:
+                hidden = torch.empty((len(ticks), n, H), device=dev)
+                decoded = None
+                if route == 'advance_many_readout' and not s.advance_many_readout([], Wd, bd, None, None):
+                    assert state.startswith('one_launch')
+                    continue
+                s.begin(x0, 0.)
+                if route == 'advance':
+                    for i, ti in enumerate(ticks):
+                        assert s.advance(ti, hidden[i])
+                elif route == 'advance_many':
+                    s.advance_many(ticks, hidden)
+                elif route == 'advance_grid':
+                    s.advance_grid(plan, hidden)
+                else:
+                    decoded = torch.empty((len(ticks), n, C), device=dev)
+                    assert s.advance_many_readout(ticks, Wd, bd, decoded, torch.empty((2, n, H), device=dev))
+                torch.cuda.synchronize()
+                stats, log = s.stats(), s.steplog()
+                after = torch.empty((n, H), device=dev)
+                assert s.advance(extra, after)
+                torch.cuda.synchronize()
+                res[(use_graph, route)] = (stats, log, None if decoded is not None else hidden, decoded, after, s.stats(), s.steplog())
+            finally:
+                s.close()
+    for key, r in res.items():
+        print(key, r[0], len(r[1]), r[5], len(r[6]))
+    assert state.startswith('one_launch') or len(res) == 2 * len(routes)
+    base = res[(False, 'advance')]
+    per = {'euler': 1, 'midpoint': 2, 'rk4': 4}
+    if method != 'dopri5':
+        assert base[0] == dict(steps=len(ticks), accepted=len(ticks), nfe=per[method] * len(ticks), t1=ticks[-1], dt_next=0.,
+                               last_ratio=0.) and base[1] == []
+    else:
+        acc = [r for r in base[1] if r[2]]
+        assert len(acc) >= 1 and base[0]['steps'] == len(base[1]) and base[0]['accepted'] == len(acc)
+        assert base[0]['nfe'] == 2 + 6 * len(base[1]) and acc[-1][0] + acc[-1][1] == base[0]['t1']
+    ref_decoded = hip.linear(base[2], Wd, bd)
+    for key, r in res.items():
+        assert r[0] == base[0] and r[1] == base[1], key
+        assert r[5] == base[5] and r[6] == base[6], key
+        assert torch.equal(r[4], base[4]), key
+        if r[3] is None:
+            assert torch.equal(r[2], base[2]), key
+        else:
+            assert torch.equal(r[3], ref_decoded), key
+
+
 @pytest.mark.parametrize('side', [48, 55, 64])       # 48: some workgroups of the persistent grid get no tile
 def test_fused_epilogue_solver_equals_generic_path(dev, side):
     """H = 256: the device-resident solver runs the stage algebra / error norm inside the fused RHS epilogue
