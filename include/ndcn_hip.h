@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 25
+#define NDCN_ABI_VERSION 26
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -526,6 +526,26 @@ NDCN_API int ndcn_gene_rhs_f32(const ndcn_csr *A, const float *x, float *out, fl
 NDCN_API int ndcn_mutual_rhs_f32(const ndcn_csr *A, const float *x, float *out, float b, float k, float c, float d,
                         float e, float h, void *stream);
 
+/* The same three right-hand sides with the Runge-Kutta algebra that consumes K in the launch's epilogue: ndcn_rhs_rk_f32's
+ * contract (rk_mode, y0, h_kprev, h_c, n_prev <= 5, y_next, y1, y_aux / h_c_aux, the error record) on an N x 1 state - the
+ * launches of the device-resident truth solve (ndcn_solver_desc::dyn), exported so that they can be driven alone.
+ *   dyn->kind  NDCN_DYN_HEAT: K = -p[0] (A x), A = L;  NDCN_DYN_GENE: p = {b, f, h};  NDCN_DYN_MUTUAL: p = {b, k, c, d, e, h}
+ *   K          bit for bit what ndcn_spmm_f32 (H = 1, alpha = -p[0]) / ndcn_gene_rhs_f32 / ndcn_mutual_rhs_f32 write
+ *   c_dev      (nullable) the coefficients in DEVICE memory instead of h_c (a replayed step reads fl(dt * c) from there; RK4: dt);
+ *              not together with y_aux
+ * Everything after K in the reference's operator order with contraction off, as ndcn_rhs_rk_f32.  d_ws: ndcn_reduce_ws_bytes(). */
+#define NDCN_DYN_HEAT   0
+#define NDCN_DYN_GENE   1
+#define NDCN_DYN_MUTUAL 2
+typedef struct ndcn_dynamics {
+    int   kind;               /* NDCN_DYN_*                                                          */
+    float p[6];               /* the kind's scalar parameters in the order above, the rest unused    */
+} ndcn_dynamics;
+NDCN_API int ndcn_dyn_rk_f32(const ndcn_dynamics *dyn, const ndcn_csr *A, const float *x, float *K, int rk_mode, const float *y0,
+                             const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, const float *y1,
+                             float *y_aux, const float *h_c_aux, float rtol, float atol, double *d_out, void *d_ws,
+                             const float *c_dev, void *stream);
+
 /* Row-wise L1 normalisation: Y[r,:] = X[r,:] / max(sum_j |X[r,j]|, 1e-12), infinities zeroed.  Replaces
  * `row_normalization` / `RowNorm.forward` (ode_gcn.py:9-26; used by ResBlock(normalize=True) ode_gcn.py:50-57 and the
  * odeGCN input stack dgnn.py:152).  Y may alias X.                                                                   */
@@ -614,6 +634,9 @@ typedef struct ndcn_solver_desc {
                                             Values <= 0 select those defaults.                                  */
     const ndcn_shard *shard;  /* NULL: the whole graph on this device.  Otherwise this rank's shard of a node-range
                                  sharded graph: A.n_rows = own rows, A.n_cols = own + halo columns (see ndcn_shard) */
+    const ndcn_dynamics *dyn; /* NULL: the ODEFunc right-hand side above.  Otherwise one of the drivers' ground-truth dynamics on
+                                 an N x 1 state (ndcn_dyn_rk_f32; read at ndcn_solver_create): H must be 1 and shard NULL; W, b
+                                 and rhs_flags are ignored; A is L for heat, the adjacency for gene and mutual               */
 } ndcn_solver_desc;
 
 NDCN_API int64_t ndcn_solver_workspace_bytes(const ndcn_solver_desc *desc);
@@ -747,6 +770,7 @@ NDCN_API int ndcn_prof_kinds(void);
 #define NDCN_PATH_RANGE  512 /* such weights on a launch that exists only fused (x_add / x_mask / s_out): split product, warned once */
 #define NDCN_PATH_DROP_EPI 1024 /* ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the dropout factor was applied inside the launch (clear: by
                                  * the streaming pass ndcn_dropout_apply_f32 behind it)                                              */
+#define NDCN_PATH_DYN 2048   /* a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; ndcn_solver_desc::dyn)       */
 NDCN_API int ndcn_debug_last_rhs_path(void);
 /* Which kernels the LAST ndcn_linear_f32 / ndcn_linear_bwd_f32 call of this thread launched (tests: every dispatch route of the dense
  * Linear is reached on purpose, not merely some correct one); each call replaces the set, 0 for n = 0 and before the first call.

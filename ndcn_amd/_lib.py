@@ -11,9 +11,11 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
+PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
+DYN_HEAT, DYN_GENE, DYN_MUTUAL = 0, 1, 2
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
 LIN_GS_SMALL, LIN_GS_FP32, LIN_GS_RES, LIN_GS_RES_MASK, LIN_GS_SPLIT32, LIN_GS_SPLIT64 = 256, 512, 1024, 2048, 4096, 8192
@@ -127,13 +129,26 @@ class ShardView(ctypes.Structure):
                 ('n_blocks', ctypes.c_int32), ('blocks', ShardBlock * 4), ('A_own', CsrView), ('X_halo', ctypes.c_void_p)]
 
 
+class Dynamics(ctypes.Structure):
+    """struct ndcn_dynamics: kind DYN_* and its scalar parameters (heat: k; gene: b, f, h; mutual: b, k, c, d, e, h)"""
+    _fields_ = [('kind', ctypes.c_int), ('p', ctypes.c_float * 6)]
+
+
+def dynamics(kind, params):
+    d = Dynamics()
+    d.kind = int(kind)
+    for i, v in enumerate(params):
+        d.p[i] = float(v)
+    return d
+
+
 class SolverDesc(ctypes.Structure):
     """struct ndcn_solver_desc"""
     _fields_ = [('method', ctypes.c_int), ('H', ctypes.c_int), ('rhs_flags', ctypes.c_uint32),
                 ('use_graph', ctypes.c_int), ('A', CsrView), ('W', ctypes.c_void_p), ('b', ctypes.c_void_p),
                 ('rtol', ctypes.c_double), ('atol', ctypes.c_double), ('max_num_steps', ctypes.c_int64),
                 ('safety', ctypes.c_double), ('ifactor', ctypes.c_double), ('dfactor', ctypes.c_double),
-                ('shard', ctypes.POINTER(ShardView))]
+                ('shard', ctypes.POINTER(ShardView)), ('dyn', ctypes.POINTER(Dynamics))]
 
 
 _P, _I, _L, _F, _D, _U = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_uint32
@@ -224,6 +239,8 @@ SIGNATURES = {
     'ndcn_row_l1_normalize_bwd_f32': (_I, [_P, _P, _P, _L, _I, _P]),
     'ndcn_gene_rhs_f32': (_I, [_CSR, _P, _P, _F, _F, _F, _P]),
     'ndcn_mutual_rhs_f32': (_I, [_CSR, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
+    'ndcn_dyn_rk_f32': (_I, [ctypes.POINTER(Dynamics), _CSR, _P, _P, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _P, _P, _P,
+                        ctypes.POINTER(_F), _F, _F, _P, _P, _P, _P]),
     'ndcn_comm_unique_id': (_I, [ctypes.c_char_p]),
     'ndcn_comm_create': (_I, [ctypes.c_char_p, _I, _I, ctypes.POINTER(_P)]),
     'ndcn_comm_adopt': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),

@@ -484,6 +484,31 @@ int ndcn_mutual_rhs_f32(const ndcn_csr *A, const float *x, float *out, float b, 
     return mutual_rhs_f32(A, x, out, b, k, c, d, e, h, ST(stream));
 }
 
+int ndcn_dyn_rk_f32(const ndcn_dynamics *dyn, const ndcn_csr *A, const float *x, float *K, int rk_mode, const float *y0,
+                    const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, const float *y1, float *y_aux,
+                    const float *h_c_aux, float rtol, float atol, double *d_out, void *d_ws, const float *c_dev, void *stream) {
+    NDCN_CHECK_ARG(dyn, "null dynamics descriptor");
+    int rc = check_csr(A, __func__);
+    if (rc) return rc;
+    NDCN_CHECK_ARG(A->n_rows == A->n_cols, "the truth dynamics need a square operator");
+    NDCN_CHECK_ARG(rk_mode >= 0 && rk_mode <= 3, "rk_mode must be 0, NDCN_RK_COMBINE, NDCN_RK_ERROR or NDCN_RK_RK4");
+    NDCN_CHECK_ARG(A->n_rows == 0 || (x && K), "null vector");
+    NDCN_CHECK_ARG(x != K, "K must not alias x");
+    if (rk_mode != 0) {
+        NDCN_CHECK_ARG(y0 && (h_c || c_dev) && (n_prev == 0 || h_kprev), "rk arguments missing");
+        NDCN_CHECK_ARG(rk_mode == NDCN_RK_ERROR || (y_next && y_next != x && y_next != K), "y_next missing or aliased");
+        NDCN_CHECK_ARG(rk_mode != NDCN_RK_ERROR || (d_out && d_ws), "error record / scratch missing");
+    }
+    NDCN_CHECK_ARG(!y_aux || (rk_mode == NDCN_RK_COMBINE && h_c_aux && h_c && y_aux != y_next && y_aux != K && y_aux != x),
+                   "y_aux: NDCN_RK_COMBINE only, with h_c and h_c_aux, not aliasing x / K / y_next");
+    RkOpt opt = {};
+    opt.y1 = rk_mode == NDCN_RK_ERROR ? y1 : nullptr;
+    opt.y_aux = y_aux;
+    opt.c_aux = h_c_aux;
+    return dyn_rk_f32(dyn->kind, dyn->p, A, x, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, ST(stream), c_dev,
+                      &opt);
+}
+
 int64_t ndcn_solver_workspace_bytes(const ndcn_solver_desc *desc) { return solver_workspace_bytes(desc); }
 int ndcn_solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t workspace_bytes, ndcn_solver **out) {
     return solver_create(desc, workspace, workspace_bytes, out);

@@ -200,6 +200,11 @@ int row_l1_normalize_bwd_f32(const float *G, const float *X, float *GX, int64_t 
 int gene_rhs_f32(const ndcn_csr *A, const float *x, float *out, float b, float f, float h, hipStream_t st);
 int mutual_rhs_f32(const ndcn_csr *A, const float *x, float *out, float b, float k, float c, float d, float e, float h,
                    hipStream_t st);
+// dynamics.hip: the three truth dynamics (kind NDCN_DYN_*, p: ndcn_dynamics::p) on an N x 1 state with the RK epilogue - modes, stage
+// arguments, c_dev and the error record as rhs_small_f32 at H = 1; of RkOpt: y1 and y_aux / c_aux, NDCN_EINVAL for any other field
+int dyn_rk_f32(int kind, const float *p, const ndcn_csr *A, const float *x, float *K, int mode, const float *y0,
+               const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out,
+               void *d_ws, hipStream_t st, const float *c_dev = nullptr, const RkOpt *opt = nullptr);
 
 // comm.hip
 int comm_world(const ndcn_comm *c);

@@ -47,6 +47,9 @@ struct ndcn_solver {
     bool rec_epi = false;          // ... of an SpMM kernel (no_control RHS) instead of the fused MFMA kernel:
     bool wide_epi = false;         //     the group-record kernel, or (no plan) the row kernel
     bool small_epi = false;        // ... of the narrow-panel kernel (H <= 128, rhs_small.hip)
+    bool dyn_rhs = false;          // the right-hand side is one of the truth dynamics (ndcn_solver_desc::dyn, dynamics.hip) ...
+    bool dyn_epi = false;          // ... and (dopri5) the RK algebra rides in its epilogue, as with small_epi
+    ndcn_dynamics dyn = {};
     float *ytmp2 = nullptr;        // second stage-input panel (fused2: a stage's input must outlive its epilogue)
     double t0 = 0, t1 = 0, dt = 0; // dopri5: last interval [t0, t1], next step size
     float tf = 0;                  // fixed grid: current time in the state dtype
@@ -117,7 +120,7 @@ int n_panels(const ndcn_solver_desc *d) {
 
 size_t workspace_bytes(const ndcn_solver_desc *d) {
     const size_t panel = align_up((size_t)d->A.n_rows * (size_t)d->H * sizeof(float) + 16);
-    const size_t work = align_up((size_t)rhs_work_bytes(d->A.n_rows, d->H, d->rhs_flags) + 16);
+    const size_t work = d->dyn ? 0 : align_up((size_t)rhs_work_bytes(d->A.n_rows, d->H, d->rhs_flags) + 16);
     size_t shard = 0;
     if (d->shard) {
         const size_t rows = (size_t)halo_plan_n_halo(d->shard->halo) + (size_t)halo_plan_n_send(d->shard->halo) +
@@ -152,6 +155,8 @@ int rhs_sharded(ndcn_solver *s, const float *x, float *K, int mode, const float 
 int rhs(ndcn_solver *s, const float *x, float *out, hipStream_t st) {
     if (s->sharded) return rhs_sharded(s, x, out, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st, nullptr);
     s->n_rhs++;
+    if (s->dyn_rhs)
+        return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, out, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
     if (s->fused2 && !s->rec_epi && !s->exact32)
         return rhs_fused2_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, 0, nullptr,
                               nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
@@ -181,6 +186,9 @@ int rhs_epi(ndcn_solver *s, const float *x, float *K, int mode, const float *y0,
             c_dev = s->d_coef + s->n_coef;
             s->n_coef += 8;                                   // slices stay 32-byte aligned
         }
+        if (s->dyn_epi)                                       // (reports NDCN_PATH_DYN itself)
+            return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, K, mode, y0, kp, cp, n_prev, y_next, rtol, atol, d_out, d_ws, st, c_dev,
+                              opt);
         g_last_rhs_path = s->small_epi ? NDCN_PATH_SMALL : (s->wide_epi ? NDCN_PATH_WIDE : NDCN_PATH_REC);
         if (s->small_epi)
             return rhs_small_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, K, s->d.H, s->d.rhs_flags, mode, y0, kp, cp,
@@ -730,10 +738,25 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
     NDCN_CHECK_ARG(desc->H > 0, "H must be positive");
     const bool no_graph = desc->rhs_flags & NDCN_F_NO_GRAPH, no_ctl = desc->rhs_flags & NDCN_F_NO_CONTROL;
     NDCN_CHECK_ARG(no_graph || (desc->A.rowptr && (desc->A.nnz == 0 || (desc->A.colidx && desc->A.val))), "operator missing");
-    NDCN_CHECK_ARG(no_ctl || desc->W, "weight missing");
+    NDCN_CHECK_ARG(desc->dyn || no_ctl || desc->W, "weight missing");
+    if (desc->dyn) {
+        const int kind = desc->dyn->kind;
+        NDCN_CHECK_ARG(kind == NDCN_DYN_HEAT || kind == NDCN_DYN_GENE || kind == NDCN_DYN_MUTUAL, "unknown dynamics kind");
+        NDCN_CHECK_ARG(desc->H == 1, "the truth dynamics act on an N x 1 state: H must be 1");
+        NDCN_CHECK_ARG(!desc->shard, "the truth dynamics have no sharded form");
+        NDCN_CHECK_ARG(desc->A.rowptr && (desc->A.nnz == 0 || (desc->A.colidx && desc->A.val)) && desc->A.n_rows == desc->A.n_cols,
+                       "the truth dynamics need a square operator");
+    }
     ndcn_solver *s = new (std::nothrow) ndcn_solver();
     if (!s) { set_error("out of host memory"); return NDCN_EINVAL; }
     s->d = *desc;
+    if (desc->dyn) {                                          // W, b and rhs_flags are ignored
+        s->dyn = *desc->dyn;
+        s->d.dyn = &s->dyn;
+        s->d.W = s->d.b = nullptr;
+        s->d.rhs_flags = 0;
+        s->dyn_rhs = true;
+    }
     s->n_rows = desc->A.n_rows;
     s->n_elem = s->n_rows * (int64_t)desc->H;
     s->n_mean = (double)s->n_elem;
@@ -815,7 +838,11 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
     s->ycur_own = s->ycur;
     if ((rc = alloc_panel(s, &s->ytmp))) return fail(rc);
     if ((rc = alloc_panel(s, &s->ytmp2))) return fail(rc);
-    {
+    if (s->dyn_rhs) {
+        // dopri5: 1 combine + 6 launches per attempt, as on the narrow-panel route; fixed-grid methods keep their replayed step,
+        // whose right-hand sides are the same kernel in plain mode (rhs)
+        s->fused2 = s->rec_epi = s->dyn_epi = desc->method == NDCN_M_DOPRI5;
+    } else {
         const int64_t wb = rhs_work_bytes(s->n_rows, desc->H, desc->rhs_flags);
         if (wb > 0) {
             void *wq = nullptr;
@@ -1187,7 +1214,7 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
             st);
     // Fixed grid on a state that fits one compute unit: the whole time vector in ONE launch (solve_small.hip) - bit-identical
     // to the per-step kernels below, without their launch latency.
-    if (n_ticks > 0 && !s->sharded && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+    if (n_ticks > 0 && !s->sharded && !s->dyn_rhs && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
         std::vector<float> dts((size_t)n_ticks);
         float tf = s->tf;
         for (int64_t q = 0; q < n_ticks; ++q) {            // solvers.py:81-97 with grid == t: step sizes formed in the state dtype
@@ -1232,7 +1259,7 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
         set_error("ndcn_solver_advance_many_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C);
         return NDCN_EINVAL;
     }
-    if (fixed && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
+    if (fixed && !s->dyn_rhs && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
         set_error("ndcn_solver_advance_many_readout: this state fits the one-launch solve (ndcn_solve_small_f32); decode its trajectory instead");
         return NDCN_EINVAL;
     }
@@ -1301,7 +1328,7 @@ int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, con
     }
     if (n_steps == 0) return NDCN_OK;
     // a state that fits one compute unit: the whole grid in one launch per 128 steps, only the ticks written (solve_small.hip)
-    if (solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+    if (!s->dyn_rhs && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
         std::vector<float> dts((size_t)n_steps);
         for (int64_t i = 0; i < n_steps; ++i) dts[(size_t)i] = h_grid[i + 1] - h_grid[i];
         int rc = solve_small_grid_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_steps,

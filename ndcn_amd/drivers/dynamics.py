@@ -25,7 +25,7 @@ import torch.optim as optim
 from .. import graphs
 from .. import torchdiffeq as ode
 from ..neural_dynamics import NDCN
-from ..ops import hip
+from ..truth import HeatDiffusion, GeneDynamics, MutualDynamics
 
 TITLES = {'heat': 'Heat Diffusion Dynamic Case', 'gene': 'Gene Regulatory Dynamic Case',
           'mutualistic': 'Mutualistic Interaction Dynamic Case'}
@@ -78,12 +78,13 @@ def time_split(args, rng):
 
 
 def truth_rhs(kind, A_op, L_op):
-    """The three ground-truth right-hand sides as O(nnz) HIP kernels."""
+    """The three ground-truth right-hand sides as O(nnz) HIP kernels: the modules of ndcn_amd.truth, whose solve
+    without a gradient runs inside the device solver."""
     if kind == 'heat':
-        return lambda t, x: hip.spmm(L_op, x, alpha=-1.0)             # heat_dynamics.py:189-204, k = 1
+        return HeatDiffusion(L_op, 1)                                 # heat_dynamics.py:189-204, k = 1
     if kind == 'gene':
-        return lambda t, x: hip.gene_rhs(A_op, x, b=1.0, f=1.0, h=2.0)  # gene_dynamics.py:186-205
-    return lambda t, x: hip.mutual_rhs(A_op, x)                       # mutualistic_dynamics.py:186-216
+        return GeneDynamics(A_op, 1.0, 1.0, 2.0)                      # gene_dynamics.py:186-205
+    return MutualDynamics(A_op)                                       # mutualistic_dynamics.py:186-216
 
 
 def main(kind, argv=None):

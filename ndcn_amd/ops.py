@@ -853,6 +853,43 @@ class HipOps:
                                                   float(e), float(h), stream_ptr()))
         return out
 
+    @staticmethod
+    def dyn_rk(kind, params, A, x, mode='plain', y0=None, kprev=(), cs=(), rtol=0.0, atol=0.0, y1=None, aux_cs=None, c_dev=None):
+        """One of the truth dynamics on an N x 1 state plus, in the same launch, the stage algebra consuming K (ndcn_dyn_rk_f32):
+        rhs_rk's contract.  kind: 'heat' (params (k,); A = L), 'gene' (b, f, h) or 'mutual' (b, k, c, d, e, h).
+        mode 'plain': returns K; 'combine': (K, y0 + sum cs[m] kprev[m] + cs[-1] K), with aux_cs also the second combination
+        (K, y_next, y_aux); 'rk4': stage len(kprev) of the 3/8-rule step, cs = [dt]: (K, next stage input / step result);
+        'error': (K, (sum of squared error ratios, non-finite count of y1)), y1 defaulting to x.
+        c_dev: a float32 device tensor holding the coefficients in place of cs (what a replayed step reads)."""
+        A = as_csr(A)
+        x = _panel(x)
+        assert x.numel() == A.shape[0] == A.shape[1]
+        dyn = _lib.dynamics({'heat': _lib.DYN_HEAT, 'gene': _lib.DYN_GENE, 'mutual': _lib.DYN_MUTUAL}.get(kind, kind), params)
+        rk = {'plain': _lib.RK_NONE, 'combine': _lib.RK_COMBINE, 'error': _lib.RK_ERROR, 'rk4': _lib.RK_RK4}[mode]
+        kprev = [_panel(k) for k in kprev]
+        y0 = _panel(y0) if y0 is not None else None
+        y1 = _panel(y1, 'y1') if y1 is not None else None
+        K = torch.empty_like(x)
+        y_next = torch.empty_like(x) if mode in ('combine', 'rk4') else None
+        arr_k = (_P * max(len(kprev), 1))(*[k.data_ptr() for k in kprev])
+        arr_c = (_F * len(cs))(*[float(c) for c in cs]) if len(cs) else None
+        y_aux = arr_c2 = None
+        if aux_cs is not None:
+            arr_c2 = (_F * len(aux_cs))(*[float(c) for c in aux_cs])
+            y_aux = torch.empty_like(x)
+        if c_dev is not None:
+            c_dev = _panel(c_dev, 'coefficients')
+        red = _Reducer.get(x.device)
+        with _REDUCE_LOCK, torch.cuda.device(x.device):
+            check(_lib.load().ndcn_dyn_rk_f32(ctypes.byref(dyn), A.view_ref(), ptr(x), ptr(K), rk, ptr(y0), arr_k, arr_c, len(kprev),
+                                              ptr(y_next), ptr(y1), ptr(y_aux), arr_c2, float(rtol), float(atol), ptr(red.out),
+                                              ptr(red.ws), ptr(c_dev), stream_ptr()))
+            if mode == 'error':
+                return K, red.fetch()
+        if mode == 'plain':
+            return K
+        return (K, y_next, y_aux) if aux_cs is not None else (K, y_next)
+
 
 hip = HipOps()
 

@@ -2,7 +2,8 @@
 torchdiffeq entry point (torchdiffeq/_impl/odeint.py:20-76), computed by HIP kernels.
 
 Two execution paths, both on the GPU:
-  * device-resident: `func` is this package's ODEFunc acting on one N x H fp32 panel -> the whole solve
+  * device-resident: `func` is this package's ODEFunc acting on one N x H fp32 panel - or one of the drivers' ground-truth
+    dynamics (ndcn_amd.truth) on an N x 1 state - -> the whole solve
     runs inside libndcn_hip.so (`ndcn_solver_*`): state, stages and dense-output coefficients never
     leave HBM and the host sees one 16-byte record per adaptive step;
   * generic: any callable / tuple state -> the reference's solver control flow (core.py) with one fused
@@ -19,6 +20,7 @@ import torch
 from ... import _lib
 from ... import dropout as _dropout
 from ...ops import hip, new_solve_epoch
+from ...truth import TRUTH_CLASSES
 from . import core
 
 SOLVERS = {m: m for m in core.METHODS}      # the in-scope subset of odeint.py:8-17
@@ -161,7 +163,7 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
                 return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
                                step_log=step_log, odefunc=user_func if plain else None, plan=plan)
-    elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
+    elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_truth=True):
         return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan, readout)
     elif method == 'dopri5':
         sol = core.integrate_dopri5(hip, func, y0, t, rtol, atol, autonomous=_autonomous(user_func),
@@ -556,15 +558,28 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
 # device-resident path
 # ---------------------------------------------------------------------------------------------------
 
-def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_dropout=False):
-    """allow_dropout: the caller (the fixed-grid training path) takes an ACTIVE dropout, 0 < p < 1 in training mode, too"""
+def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_dropout=False, allow_truth=False):
+    """allow_dropout: the caller (the fixed-grid training path) takes an ACTIVE dropout, 0 < p < 1 in training mode, too.
+    allow_truth: the caller (the solve without a gradient) takes the ground-truth dynamics of ndcn_amd.truth, too - exactly those
+    classes, on a float32 (N, 1) state that lives with the operator."""
     from ...neural_dynamics import ODEFunc
-    if not (tensor_input and type(user_func) is ODEFunc):
+    if not tensor_input:
         return False
     y = y0[0]
-    if y.dim() != 2 or y.shape[1] != user_func.hidden_size:
+    if allow_truth and type(user_func) in TRUTH_CLASSES:
+        from ...csr import as_csr
+        op = user_func.ndcn_dynamics()[0]
+        if torch.is_grad_enabled() and torch.is_tensor(op) and op.requires_grad:     # (a gradient is asked of the operator)
+            return False
+        csr = as_csr(op)
+        if y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 1 or csr.device != y.device or \
+                tuple(csr.shape) != (y.shape[0], y.shape[0]):
+            return False
+    elif type(user_func) is not ODEFunc:
         return False
-    if user_func.training and user_func.dropout > 0 and not (allow_dropout and _dropout.is_active(user_func)):
+    elif y.dim() != 2 or y.shape[1] != user_func.hidden_size:
+        return False
+    elif user_func.training and user_func.dropout > 0 and not (allow_dropout and _dropout.is_active(user_func)):
         return False
     if method in core.FIXED_METHODS:
         if set(options) - {'step_size'}:                      # (odeint hands over what core.fixed_options left: nothing, or the step size)
@@ -580,7 +595,8 @@ def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_d
 
 
 class DeviceSolver:
-    """RAII wrapper of ndcn_solver_* for one (ODEFunc, method) pair; the workspace is a torch allocation."""
+    """RAII wrapper of ndcn_solver_* for one (ODEFunc, method) pair - or one of the ground-truth dynamics of ndcn_amd.truth in
+    ODEFunc's place (an N x 1 state: the descriptor's `dyn` field) -; the workspace is a torch allocation."""
 
     def __init__(self, odefunc, n_rows, method, rtol=1e-7, atol=1e-9, max_num_steps=2 ** 31 - 1, use_graph=False,
                  safety=core.SAFETY, ifactor=core.IFACTOR, dfactor=core.DFACTOR, shard=None):
@@ -588,6 +604,9 @@ class DeviceSolver:
         the shard's (own rows, [own | halo] columns) and `odefunc.A` is ignored."""
         from ...csr import as_csr
         self.lib = _lib.load()
+        if type(odefunc) in TRUTH_CLASSES:
+            self._init_truth(odefunc, n_rows, method, rtol, atol, max_num_steps, use_graph, safety, ifactor, dfactor, shard)
+            return
         H = odefunc.hidden_size
         flags = _lib.F_RELU | (_lib.F_NO_GRAPH if odefunc.no_graph else 0) | (_lib.F_NO_CONTROL if odefunc.no_control else 0)
         dev = odefunc.wt.weight.device
@@ -617,8 +636,25 @@ class DeviceSolver:
                                     W.data_ptr(), b.data_ptr() if b is not None else None,
                                     float(rtol), float(atol), int(max_num_steps), float(safety), float(ifactor),
                                     float(dfactor), shard.view_ptr(H) if shard is not None else None)
+        self._create(dev, (n_rows, H))
+
+    def _init_truth(self, module, n_rows, method, rtol, atol, max_num_steps, use_graph, safety, ifactor, dfactor, shard):
+        """the descriptor of a truth solve: H = 1, no weights, the module's operator, kind and scalars in `dyn`"""
+        from ...csr import as_csr
+        assert shard is None, 'the truth dynamics have no sharded form'
+        op, kind, params = module.ndcn_dynamics()
+        csr = as_csr(op)
+        assert csr.shape[0] == n_rows, 'operator has %d rows, state has %d' % (csr.shape[0], n_rows)
+        self.csr = csr
+        self._dyn = _lib.dynamics(kind, params)
+        self._keep = (csr, self._dyn)
+        self.desc = _lib.SolverDesc(_lib.METHODS[method], 1, 0, 1 if use_graph else 0, csr.view(), None, None, float(rtol), float(atol),
+                                    int(max_num_steps), float(safety), float(ifactor), float(dfactor), None, ctypes.pointer(self._dyn))
+        self._create(csr.device, (n_rows, 1))
+
+    def _create(self, dev, shape):
         self.device = dev
-        self.shape = (n_rows, H)
+        self.shape = shape
         nbytes = int(self.lib.ndcn_solver_workspace_bytes(ctypes.byref(self.desc)))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.handle = ctypes.c_void_p()
@@ -724,6 +760,8 @@ def _small_solve(odefunc, y0, tt, method, plan=None):
     _SmallEulerSolve.  tt: the time grid as Python floats ALREADY rounded to the state dtype (solvers.py:81).  plan (the step_size
     option): ndcn_solve_small_grid_f32 - the steps of plan.grid, still one launch per 128 steps, only the ticks written."""
     import numpy as np
+    if type(odefunc) in TRUTH_CLASSES:                        # (the one-launch solve is ODEFunc's)
+        return None
     op = _small_operator(odefunc, y0)
     if op is None:
         return None
@@ -774,29 +812,41 @@ def _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph):
                             dfactor=opt.get('dfactor', core.DFACTOR))
     if not use_graph or y0.numel() > _SOLVER_CACHE_MAX_ELEMS:
         return make(), None
-    W, b = odefunc.wt.weight, odefunc.wt.bias
-    key = (id(odefunc), W.data_ptr(), None if b is None else b.data_ptr(), id(getattr(odefunc, 'A', None)), tuple(y0.shape), method,
-           float(rtol), float(atol), tuple(sorted((k, v) for k, v in opt.items() if v is not None)), y0.device.index,
-           torch.cuda.current_stream(y0.device).cuda_stream, bool(odefunc.no_graph), bool(odefunc.no_control))
+    from ...csr import as_csr
+    solve = (tuple(y0.shape), method, float(rtol), float(atol), tuple(sorted((k, v) for k, v in opt.items() if v is not None)),
+             y0.device.index, torch.cuda.current_stream(y0.device).cuda_stream)
+    truth = type(odefunc) in TRUTH_CLASSES
+    if truth:
+        # everything the descriptor is built from: the class, its scalars and the operator the module's attribute converts to NOW
+        # (a module is made per solve - drivers/dynamics.py - so the kept solver belongs to the operator, not to the module)
+        op, _, params = odefunc.ndcn_dynamics()
+        owner = current = as_csr(op)
+        key = (type(odefunc), params, id(owner)) + solve
+    else:
+        W, b = odefunc.wt.weight, odefunc.wt.bias
+        owner = odefunc
+        key = (id(odefunc), W.data_ptr(), None if b is None else b.data_ptr(), id(getattr(odefunc, 'A', None))) + solve + \
+            (bool(odefunc.no_graph), bool(odefunc.no_control))
     hit = _SOLVERS.get(key)
-    if hit is not None and not odefunc.no_graph:
+    if hit is not None and (truth or not odefunc.no_graph):
         # id(A) names an object, not its contents: an in-place write to A re-converts (csr.as_csr keys on A._version), and a new
         # tensor may re-use a freed one's id - the kept solver's captured graph would go on reading the OLD operator arrays that
         # its _keep holds alive.  The CsrOperator the solver was built on must be the one the operator converts to now.
-        from ...csr import as_csr
-        if getattr(hit[1], 'csr', None) is not as_csr(odefunc.A):
+        if not truth:
+            current = as_csr(odefunc.A)
+        if getattr(hit[1], 'csr', None) is not current:
             del _SOLVERS[key]
             if not getattr(hit[1], '_in_use', False):
                 hit[1].close()
             hit = None
-    if hit is not None and hit[0]() is odefunc and not getattr(hit[1], '_in_use', False) and hit[1].handle:
+    if hit is not None and hit[0]() is owner and not getattr(hit[1], '_in_use', False) and hit[1].handle:
         _SOLVERS.move_to_end(key)
         hit[1]._in_use = True
         return hit[1], key
     solver = make()
     solver._in_use = True
     if hit is None:
-        _SOLVERS[key] = (weakref.ref(odefunc), solver)
+        _SOLVERS[key] = (weakref.ref(owner), solver)
         while len(_SOLVERS) > _SOLVER_CACHE_SIZE:
             _, (_, old) = _SOLVERS.popitem(last=False)
             if not getattr(old, '_in_use', False):
@@ -840,7 +890,7 @@ def _device_resident(odefunc, y0, t, rtol, atol, method, options, step_log, plan
         if out is not None:
             return out, False
     fuse = False
-    if readout is not None and plan is None and len(tt) > 1:
+    if readout is not None and plan is None and len(tt) > 1 and type(odefunc) not in TRUTH_CLASSES:
         Wd, bd = readout
         fuse = not (torch.is_grad_enabled() and (Wd.requires_grad or (bd is not None and bd.requires_grad))) and \
             Wd.dim() == 2 and Wd.shape[1] == y0.shape[1] and Wd.is_cuda and Wd.dtype == torch.float32
