@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 26
+#define NDCN_ABI_VERSION 27
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -899,6 +899,27 @@ NDCN_API int ndcn_fixed_grid_train_f32(const ndcn_csr *A, const float *W, const 
 NDCN_API int ndcn_fixed_grid_backward_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
                                           int method, const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks,
                                           float *g_y0, float *g_W, float *g_b, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream);
+/* ---- the decoder inside the fixed-grid reverse sweep (ABI 27) ------------------------------------------------------------------
+ * NDCN decodes every tick (neural_dynamics.py:148-160: output_layer over the whole trajectory); trained through odeint's `readout`
+ * the solve's autograd node receives the gradient of the DECODED ticks, g_dec (n_ticks + 1, N, C), and the (n_ticks + 1, N, H) tensor
+ * g_dec . Wd that the Linear's own backward would write is never formed.
+ * ndcn_readout_bwd_f32, one tick:  gi[n,h] = the fp32 fma chain over c = 0 .. C-1 of gd[n,c] * Wd[c,h] from +0;
+ *   out = a + ((((0 + h_add[0]) + h_add[1]) + ...) + gi), every sum rounded on its own - what ndcn_rk_combine_f32(out, a, {h_add..., gi},
+ *   {1, ..}) gives - and out = gi when a is NULL and n_add is 0 (a NULL with addends: the sum without the base);  n_add <= 5;
+ *   acc (nullable: then y and ws may be NULL): C*H + C doubles, acc[c*H + h] += sum_n gd[n,c] y[n,h] and acc[C*H + c] += sum_n gd[n,c]
+ *   in fp64 in a fixed order (no atomics: the same inputs give the same bits); the caller zeroes it before the first tick and rounds
+ *   it to fp32 after the last.  ws: ndcn_readout_bwd_ws_bytes(n_rows, H, C) bytes of scratch.  1 <= C <= 15, any H >= 1: NDCN_EINVAL
+ *   otherwise.  Panels whose base is 16-byte aligned with H % 4 == 0 take 16-byte lanes.
+ * ndcn_fixed_grid_backward_readout_f32: ndcn_fixed_grid_backward_f32 with (g_dec, Wd (C, H), C) in place of g_out and the decoder's
+ *   gradients g_Wd (C, H) / g_bd (C) as further outputs (both nullable; g_bd alone nullable): bit for bit the gradients that
+ *   ndcn_fixed_grid_backward_f32 gives for g_out[i] = the chain above of g_dec[i].                                                 */
+NDCN_API int64_t ndcn_readout_bwd_ws_bytes(int64_t n_rows, int H, int C);
+NDCN_API int ndcn_readout_bwd_f32(float *out, const float *a, const float *const *h_add, int n_add, const float *gd, const float *Wd,
+                                  const float *y, int64_t n_rows, int H, int C, double *acc, void *ws, void *stream);
+NDCN_API int ndcn_fixed_grid_backward_readout_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H,
+                                                  uint32_t flags, int method, const float *traj, const float *g_dec, const float *Wd,
+                                                  int C, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W, float *g_b,
+                                                  float *g_Wd, float *g_bd, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
@@ -191,6 +191,10 @@ SIGNATURES = {
     'ndcn_tape_destroy': (None, [_P]),
     'ndcn_fixed_grid_train_f32': (_I, [_P, _P, _P, _I, ctypes.c_uint32, _I, _P, ctypes.POINTER(_F), _L, _P, _P, _P, _P]),
     'ndcn_fixed_grid_backward_f32': (_I, [_P, _P, _P, _P, _I, ctypes.c_uint32, _I, _P, _P, ctypes.POINTER(_F), _L, _P, _P, _P, _P, _P, _P]),
+    'ndcn_fixed_grid_backward_readout_f32': (_I, [_P, _P, _P, _P, _I, ctypes.c_uint32, _I, _P, _P, _P, _I, ctypes.POINTER(_F), _L, _P, _P, _P,
+                                             _P, _P, _P, _P, _P]),
+    'ndcn_readout_bwd_ws_bytes': (_L, [_L, _I, _I]),
+    'ndcn_readout_bwd_f32': (_I, [_P, _P, ctypes.POINTER(_P), _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     'ndcn_rk_dot_diff_f32': (_I, [_P, _P, _P, _P, _P, _L, _P]),
     'ndcn_rk_pull_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _P, _P, _P, _P, _P, _L, _P]),
     'ndcn_rk_error_bwd_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _F, _F, _F, _D, _P, _P,

@@ -399,6 +399,14 @@ int ndcn_rk_combine_f32(float *out, const float *y0, const float *const *h_k, co
     return rk_combine_f32(out, y0, h_k, h_c, n_k, n_elem, ST(stream));
 }
 
+int64_t ndcn_readout_bwd_ws_bytes(int64_t n_rows, int H, int C) { return readout_bwd_ws_bytes(n_rows, H, C); }
+
+int ndcn_readout_bwd_f32(float *out, const float *a, const float *const *h_add, int n_add, const float *gd, const float *Wd,
+                         const float *y, int64_t n_rows, int H, int C, double *acc, void *ws, void *stream) {
+    NDCN_CHECK_ARG(n_rows >= 0 && n_rows * (int64_t)(H > 0 ? H : 1) < (1ll << 40), "bad shape");
+    return readout_bwd_f32(out, a, h_add, n_add, gd, Wd, y, n_rows, H, C, acc, ws, ST(stream));
+}
+
 int ndcn_rk_error_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_c, int n_k, float rtol,
                       float atol, int64_t n_elem, double *d_out, void *d_ws, void *stream) {
     NDCN_CHECK_ARG(n_elem >= 0 && h_k && h_c && d_out && d_ws, "bad argument");

@@ -142,6 +142,15 @@ int rk_combine_f32(float *out, const float *y0, const float *const *h_k, const f
                    hipStream_t st, const float *dt_dev = nullptr);
 int rk_error_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_c, int n_k, float rtol,
                  float atol, int64_t n, double *d_out, void *d_ws, hipStream_t st, const float *dt_dev = nullptr, int accum = 0);
+// readout_bwd.hip: the decoder's backward for one tick of a fixed-grid reverse sweep.  gi = fma chain over c of gd[:, c] Wd[c, :] from +0;
+// out = a + ((((0 + add_0) + ...) + add_k) + gi) - rk_combine_f32's order for unit coefficients - or gi alone without a and addends;
+// acc (nullable; C H + C doubles, zeroed by the caller before the first tick) += {gd^T y, column sums of gd}, deterministic; ws:
+// readout_bwd_ws_bytes() bytes.  1 <= C <= 15, any H >= 1 (NDCN_EINVAL otherwise); n_add <= 5.  finish: acc -> fp32 g_Wd / g_bd (nullable)
+int readout_bwd_supported(int H, int C);
+int64_t readout_bwd_ws_bytes(int64_t n_rows, int H, int C);
+int readout_bwd_f32(float *out, const float *a, const float *const *h_add, int n_add, const float *gd, const float *Wd, const float *y,
+                    int64_t n_rows, int H, int C, double *acc, void *ws, hipStream_t st);
+int readout_bwd_finish_f32(const double *acc, float *g_Wd, float *g_bd, int H, int C, hipStream_t st);
 // VJPs of the dopri5 panel operations (rk_bwd.hip); d_dots receives 8 doubles, d_ws: rk_bwd_ws_bytes() bytes
 int64_t rk_bwd_ws_bytes();
 int rk_pull_f32(float *out, const float *base, const float *const *h_p, const float *h_c, int n_p, const float *mask, const float *ua,

@@ -987,10 +987,24 @@ int ndcn_fixed_grid_train_f32(const ndcn_csr *A, const float *W, const float *b,
     return NDCN_OK;
 }
 
-int ndcn_fixed_grid_backward_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, int method,
-                                 const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W,
-                                 float *g_b, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream) {
-    NDCN_CHECK_ARG(A && traj && g_out && h_dt && n_ticks >= 1 && g_y0 && alloc && H > 0, "bad argument");
+}  // extern "C"
+
+namespace {
+
+// Where the reverse sweep takes a tick's gradient from: the (n_ticks + 1, N, H) tensor g_out itself, or - the decoder inside the
+// sweep - the (n_ticks + 1, N, C) gradient of the decoded ticks, turned into g_dec[i] . Wd where the sweep adds it (readout_bwd.hip)
+struct TickGrad {
+    const float *g_out = nullptr;
+    const float *g_dec = nullptr, *Wd = nullptr;
+    int C = 0;
+    float *g_Wd = nullptr, *g_bd = nullptr;       // both nullable: the decoder's own gradients are not wanted
+};
+
+int fixed_backward(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, int method,
+                   const float *traj, const TickGrad &tg, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W,
+                   float *g_b, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream) {
+    const float *g_out = tg.g_out;
+    NDCN_CHECK_ARG(A && traj && h_dt && n_ticks >= 1 && g_y0 && alloc && H > 0, "bad argument");
     NDCN_CHECK_ARG(method == NDCN_M_EULER || method == NDCN_M_MIDPOINT || method == NDCN_M_RK4, "method must be euler, midpoint or rk4");
     const bool no_graph = flags & NDCN_F_NO_GRAPH, no_control = flags & NDCN_F_NO_CONTROL;
     NDCN_CHECK_ARG(no_graph || At, "the transposed operator is required");
@@ -1049,22 +1063,55 @@ int ndcn_fixed_grid_backward_f32(const ndcn_csr *A, const ndcn_csr *At, const fl
         for (float c : cs) cp[m++] = c;
         return rk_combine_f32(out, y0p, kp, cp, m, n, st);
     };
-    const float *a = g_out + (size_t)n_ticks * n;
+    // the tick gradient source: tick(out, a, addends, i) = a + sum(addends) + (gradient of tick i), the sweep's last combination
+    double *dacc = nullptr;
+    void *dws = nullptr;
+    const int64_t n_dec = (int64_t)t->n_rows * tg.C;
+    if (tg.g_dec) {
+        if (tg.g_Wd) {
+            if ((rc = arena(t, (size_t)((int64_t)tg.C * H + tg.C) * sizeof(double), &p))) return rc;
+            dacc = static_cast<double *>(p);
+            NDCN_HIP(hipMemsetAsync(dacc, 0, (size_t)((int64_t)tg.C * H + tg.C) * sizeof(double), st));
+            if ((rc = arena(t, (size_t)readout_bwd_ws_bytes(t->n_rows, H, tg.C), &dws))) return rc;
+        }
+    }
+    auto tick = [&](float *out, const float *base, std::initializer_list<const float *> adds, int64_t i) -> int {
+        if (!tg.g_dec) {
+            const float *kp[8];
+            float cp[8];
+            int m = 0;
+            for (const float *k : adds) { kp[m] = k; cp[m++] = 1.f; }
+            kp[m] = g_out + (size_t)i * n;
+            cp[m++] = 1.f;
+            return rk_combine_f32(out, base, kp, cp, m, n, st);
+        }
+        const float *ap[5];
+        int m = 0;
+        for (const float *k : adds) ap[m++] = k;
+        return readout_bwd_f32(out, base, ap, m, tg.g_dec + (size_t)i * n_dec, tg.Wd, traj + (size_t)i * n, t->n_rows, H, tg.C, dacc, dws, st);
+    };
+    const float *a;
     int pp = 0;
+    if (tg.g_dec) {                                           // the seed: the last tick's gradient by the kernel into a panel
+        if ((rc = tick(a2[1], nullptr, {}, n_ticks))) return rc;
+        a = a2[1];
+    } else {
+        a = g_out + (size_t)n_ticks * n;
+    }
     for (int64_t i = n_ticks - 1; i >= 0; --i) {
         const float dt = h_dt[i];
-        const float *y = traj + (size_t)i * n, *gi = g_out + (size_t)i * n;
+        const float *y = traj + (size_t)i * n;
         u[0] = const_cast<float *>(y);
         if ((rc = fixed_step(F, y, dt, scratch, u, K))) return rc;
         float *a_new = a2[pp];
         if (method == NDCN_M_EULER) {                         // y1 = y + dt k1
             if ((rc = vjp(y, K[0], a, dt, dt, gu[0]))) return rc;
-            rc = lincomb(a_new, a, {gu[0], gi}, {1.f, 1.f});
+            rc = tick(a_new, a, {gu[0]}, i);
         } else if (method == NDCN_M_MIDPOINT) {               // ym = y + (dt / 2) k1 ; y1 = y + dt k2
             const float h = (float)((double)dt / 2.0);
             if ((rc = vjp(u[1], K[1], a, dt, dt, gu[1]))) return rc;          // dL / d ym
             if ((rc = vjp(y, K[0], gu[1], h, h, gu[0]))) return rc;
-            rc = lincomb(a_new, a, {gu[1], gu[0], gi}, {1.f, 1.f, 1.f});
+            rc = tick(a_new, a, {gu[1], gu[0]}, i);
         } else {                                              // the 3/8 rule, rk_common.py:72-78
             const float c8 = (float)((double)dt / 8.0), c38 = (float)(3.0 * (double)c8), d3 = (float)((double)dt / 3.0);
             if ((rc = vjp(u[3], K[3], a, c8, c8, gu[3]))) return rc;          // J4^T (c8 a)
@@ -1074,14 +1121,43 @@ int ndcn_fixed_grid_backward_f32(const ndcn_csr *A, const ndcn_csr *At, const fl
             if ((rc = vjp(u[1], K[1], gk, 1.f, 1.f, gu[1]))) return rc;
             if ((rc = lincomb(gk, nullptr, {a, gu[3], gu[2], gu[1]}, {c8, dt, -d3, d3}))) return rc;
             if ((rc = vjp(y, K[0], gk, 1.f, 1.f, gu[0]))) return rc;
-            rc = lincomb(a_new, a, {gu[3], gu[2], gu[1], gu[0], gi}, {1.f, 1.f, 1.f, 1.f, 1.f});
+            rc = tick(a_new, a, {gu[3], gu[2], gu[1], gu[0]}, i);
         }
         if (rc) return rc;
         a = a_new;
         pp = 1 - pp;
     }
     NDCN_HIP(hipMemcpyAsync(g_y0, a, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (dacc) return readout_bwd_finish_f32(dacc, tg.g_Wd, tg.g_bd, H, tg.C, st);
     return NDCN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndcn_fixed_grid_backward_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, int method,
+                                 const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W,
+                                 float *g_b, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream) {
+    NDCN_CHECK_ARG(g_out, "bad argument");
+    TickGrad tg;
+    tg.g_out = g_out;
+    return fixed_backward(A, At, W, b, H, flags, method, traj, tg, h_dt, n_ticks, g_y0, g_W, g_b, alloc, alloc_ctx, stream);
+}
+
+int ndcn_fixed_grid_backward_readout_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
+                                         int method, const float *traj, const float *g_dec, const float *Wd, int C, const float *h_dt,
+                                         int64_t n_ticks, float *g_y0, float *g_W, float *g_b, float *g_Wd, float *g_bd,
+                                         ndcn_alloc_fn alloc, void *alloc_ctx, void *stream) {
+    NDCN_CHECK_ARG(g_dec && Wd && (g_Wd || !g_bd), "bad argument");
+    if (!readout_bwd_supported(H, C)) { set_error("%s: 1 <= C <= 15 is supported (C = %d)", __func__, C); return NDCN_EINVAL; }
+    TickGrad tg;
+    tg.g_dec = g_dec;
+    tg.Wd = Wd;
+    tg.C = C;
+    tg.g_Wd = g_Wd;
+    tg.g_bd = g_bd;
+    return fixed_backward(A, At, W, b, H, flags, method, traj, tg, h_dt, n_ticks, g_y0, g_W, g_b, alloc, alloc_ctx, stream);
 }
 
 }  // extern "C"

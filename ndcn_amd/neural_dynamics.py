@@ -145,10 +145,11 @@ class NDCN(nn.Module):
     def forward(self, vt, x):
         h = x if self.no_embed else self.input_layer(x)
         block, dec = self.neural_dynamic_layer, self.output_layer
-        # inference: the decoder rides inside the solve and the (T, N, H) trajectory is never stored (odeint's `readout`: the same
-        # bits as the two steps below).  Anything that could observe the hidden trajectory keeps the two-step form: a gradient, a
-        # replaced or hooked decoder, hooks on the block, an adjoint block.
-        if not _needs_grad(x, self) and type(dec) is _HipLinear and type(block) is ODEBlock and not block.adjoint and \
+        # the decoder rides inside the solve (odeint's `readout`: the same bits as the two steps below): in inference the (T, N, H)
+        # trajectory is never stored, in training its (T, N, H) gradient is not (the fixed-grid reverse sweep takes the decoded
+        # ticks' gradient; odeint decodes in a step of its own wherever the solve does not take the decoder).  Anything that could
+        # observe the hidden trajectory keeps the two-step form: a replaced or hooked decoder, hooks on the block, an adjoint block.
+        if type(dec) is _HipLinear and type(block) is ODEBlock and not block.adjoint and \
                 not _has_hooks(dec) and not _has_hooks(block):
             return block._solve(h, vt, readout=(dec.weight, dec.bias))
         return dec(block(vt, h))

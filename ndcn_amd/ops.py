@@ -579,6 +579,33 @@ class HipOps:
                                                   stream_ptr()))
         return out
 
+    READOUT_BWD_MAX_C = 15
+
+    @staticmethod
+    def readout_bwd(gd, Wd, y=None, base=None, addends=(), acc=None):
+        """One tick of the decoder's backward inside a fixed-grid reverse sweep (ndcn_readout_bwd_f32): with gi = gd (N, C) . Wd (C, H)
+        as the fp32 fma chain over c, returns base + (sum of the addends, left to right from +0, + gi) - lincomb(addends + [gi], ones,
+        y0=base) without gi ever stored - or gi itself without base and addends.  acc (C * H + C float64, zeroed by the caller): += the
+        decoder's gradients gd^T y and the column sums of gd for this tick, in a fixed order."""
+        gd, Wd = _panel(gd, 'tick gradient'), _panel(Wd, 'decoder weight')
+        N, C = gd.shape
+        H = Wd.shape[1]
+        assert Wd.shape[0] == C and len(addends) <= 5
+        adds = [_panel(k) for k in addends]
+        base = _panel(base) if base is not None else None
+        out = torch.empty((N, H), dtype=torch.float32, device=gd.device)
+        lib = _lib.load()
+        ws = None
+        if acc is not None:
+            y = _panel(y, 'tick state')
+            assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == C * H + C and tuple(y.shape) == (N, H)
+            ws = torch.empty(max(int(lib.ndcn_readout_bwd_ws_bytes(N, H, C)), 8), dtype=torch.uint8, device=gd.device)
+        arr = (_P * max(len(adds), 1))(*[k.data_ptr() for k in adds])
+        with torch.cuda.device(gd.device):
+            check(lib.ndcn_readout_bwd_f32(ptr(out), ptr(base), arr, len(adds), ptr(gd), ptr(Wd), ptr(y) if acc is not None else None, N, H, C,
+                                           ptr(acc), ptr(ws), stream_ptr()))
+        return out
+
     @staticmethod
     def error(y0, y1, ks, cs, rtol, atol):
         """(sum of squared error ratios, non-finite count of y1) as host floats; one 16-byte read-back."""

@@ -73,7 +73,10 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_lo
     readout=(weight (C, H), bias (C,) or None): return `linear(odeint(...), weight, bias)`, shape (len(t), N, C), instead of the
     hidden states (neural_dynamics.py:148-160: NDCN decodes every tick).  Where nothing needs a gradient and the solve is
     device-resident, the library decodes each tick as the solver produces it (ndcn_solver_advance_many_readout) and the
-    (len(t), N, H) trajectory is never stored; everywhere else the ordinary solve runs and the Linear is applied to its result - the
+    (len(t), N, H) trajectory is never stored; under a gradient, euler / midpoint / rk4 over ODEFunc on the fused-launch training
+    path hold the decoder inside the solve's autograd node: the trajectory is stored once (the reverse sweep needs it) but the
+    (len(t), N, H) gradient of it, which the Linear's own backward would write, is not - the sweep forms each tick's g . W where it
+    adds it (ndcn_readout_bwd_f32); everywhere else the ordinary solve runs and the Linear is applied to its result - the
     values are the same bits either way, only the memory differs.  A tuple state raises ValueError."""
     with core.grid_scope(t), _dropout.solve_scope():
         if readout is None:
@@ -102,7 +105,8 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / euler / midpoint / rk4 are
     provided (tsit5 / explicit_adams / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
     `step_log` (a list) optionally receives the dopri5 per-attempt log.  Returns (solution, decoded): decoded is True when
-    `readout` was applied inside the solve (the device-resident inference path), else the solution is the hidden one.
+    `readout` was applied inside the solve (the device-resident inference path; the fixed-grid training nodes), else the solution
+    is the hidden one.
 
     Fixed-grid methods take options={'step_size': h} as the reference's FixedGridODESolver does (solvers.py:39-108): the solver
     integrates on its own float32 grid t[0], t[0] + h, ... (last point clamped to t[-1]; AssertionError where rounding leaves it
@@ -149,7 +153,11 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         if not _dropout.is_active(user_func):
             sol = _small_solve_with_grad(user_func, y0[0], t, method, plan)                  # one launch forward, one backward
         if sol is None:
-            sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan)   # any size: fused launches forward, closed-form sweep backward
+            # any size: fused launches forward, closed-form sweep backward - with `readout` the decoder inside the same node
+            dec = _readout_for_grad(readout, y0[0])
+            sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan, readout=dec)
+            if sol is not None:
+                return sol, dec is not None
         if sol is not None:
             return sol, False
     if needs_grad:
@@ -271,7 +279,8 @@ class _FixedGridSolve(torch.autograd.Function):
         return None if drop is None else (drop[0], drop[1], drop[2] + step * _FixedGridSolve.EVALS[method])
 
     @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, dts, drop=None):
+    def _solve(ctx, y0, W, b, csr, flags, method, dts, drop):
+        """the forward launches -> the trajectory; ctx.meta set"""
         n_ticks = len(dts)
         out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
@@ -280,6 +289,11 @@ class _FixedGridSolve(torch.autograd.Function):
         for i, dt in enumerate(dts):
             _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dt, out[i + 1],
                                   drop=_FixedGridSolve._drop_at(drop, method, i))
+        return out
+
+    @staticmethod
+    def forward(ctx, y0, W, b, csr, flags, method, dts, drop=None):
+        out = _FixedGridSolve._solve(ctx, y0, W, b, csr, flags, method, dts, drop)
         ctx.save_for_backward(out, W, b)
         return out
 
@@ -322,20 +336,24 @@ class _FixedGridSolve(torch.autograd.Function):
     @staticmethod
     def _sweep_step(method, dt, st, a, vj, acc, extra):
         """the adjoint before one step from the adjoint `a` after it: st = the step's [(stage input, K), ...], vj / acc as in backward;
-        extra: gradients that enter at the state the step starts from, added in the same pass"""
-        ones = [1.0] * len(extra)
+        extra: gradients that enter at the state the step starts from, added in the same pass - a list of panels, or a callable
+        extra(a, [gu, ...]) that makes the pass itself (the readout form: the entering gradient is formed inside hip.readout_bwd)"""
+        if callable(extra):
+            close = lambda gus: extra(a, gus)
+        else:
+            close = lambda gus: hip.lincomb(gus + extra, [1.0] * (len(gus) + len(extra)), y0=a)
         if method == 'euler':                                   # y1 = y + dt k1
             (u1, K1), = st
             gu1, gW, gb = vj(u1, K1, a, dt)
             acc(gW, gb, dt)
-            return hip.lincomb([gu1] + extra, [1.0] + ones, y0=a)
+            return close([gu1])
         if method == 'midpoint':                                # ym = y + (dt / 2) k1 ; y1 = y + dt k2
             (u1, K1), (u2, K2) = st
             gu2, gW, gb = vj(u2, K2, a, dt)                     # dL/d ym
             acc(gW, gb, dt)
             gu1, gW, gb = vj(u1, K1, gu2, dt / 2.0)
             acc(gW, gb, dt / 2.0)
-            return hip.lincomb([gu2, gu1] + extra, [1.0, 1.0] + ones, y0=a)
+            return close([gu2, gu1])
         (u1, K1), (u2, K2), (u3, K3), (u4, K4) = st             # the 3/8 rule, rk_common.py:72-78
         c8 = dt / 8.0
         gu4, gW, gb = vj(u4, K4, a, c8)                         # J4^T (c8 a)
@@ -349,7 +367,7 @@ class _FixedGridSolve(torch.autograd.Function):
         gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
         gu1, gW, gb = vj(u1, K1, gk1, 1.0)
         acc(gW, gb, 1.0)
-        return hip.lincomb([gu4, gu3, gu2, gu1] + extra, [1.0] * 4 + ones, y0=a)
+        return close([gu4, gu3, gu2, gu1])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -383,6 +401,60 @@ class _FixedGridSolve(torch.autograd.Function):
                 gW_tot.add_(gW, alpha=scale * s)
                 gb_tot.add_(gb, alpha=scale * s)
         return vj, acc
+
+
+def _decoder_acc(Wd, needs_W, needs_b):
+    """the fp64 accumulator of the decoder's gradients over a reverse sweep (hip.readout_bwd), or None when neither is wanted"""
+    if not (needs_W or needs_b):
+        return None
+    C, H = Wd.shape
+    return torch.zeros(C * H + C, dtype=torch.float64, device=Wd.device)
+
+
+def _decoder_grads(acc, Wd, needs_W, needs_b):
+    """(g_Wd, g_bd): the accumulator rounded to float32 once, after the last tick"""
+    if acc is None:
+        return None, None
+    C, H = Wd.shape
+    f = acc.to(torch.float32)
+    return (f[:C * H].view(C, H) if needs_W else None), (f[C * H:] if needs_b else None)
+
+
+class _FixedGridSolveReadout(torch.autograd.Function):
+    """_FixedGridSolve with the decoder Linear(Wd, bd) of every tick inside the node (odeint's `readout` under a gradient): the output
+    is the decoded solution (T, N, C), hip.linear of the trajectory; the reverse sweep takes the (T, N, C) gradient and forms tick i's
+    g[i] . Wd inside the pass that adds it (hip.readout_bwd in _sweep_step's last combination) - the (T, N, H) gradient of the
+    trajectory is never written - and accumulates the decoder's own gradients from the stored states on the way."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, dts, drop=None):
+        out = _FixedGridSolve._solve(ctx, y0, W, b, csr, flags, method, dts, drop)
+        ctx.save_for_backward(out, W, b, Wd)
+        return hip.linear(out, Wd, bd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        out, W, b, Wd = ctx.saved_tensors
+        csr, no_graph, no_control, method, dts, drop = ctx.meta
+        g = g.contiguous()
+        n_ticks = len(dts)
+        H = out.shape[2]
+        needs = ctx.needs_input_grad
+        dacc = _decoder_acc(Wd, needs[3], needs[4])
+        a = hip.readout_bwd(g[n_ticks], Wd, y=out[n_ticks], acc=dacc)
+        gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
+        gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
+        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
+        for i in range(n_ticks - 1, -1, -1):
+            st = []
+            scratch = torch.empty_like(out[0])
+            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st,
+                                  drop=_FixedGridSolve._drop_at(drop, method, i))
+            a = _FixedGridSolve._sweep_step(method, dts[i], st, a, vj, acc,
+                                            lambda base, gus, i=i: hip.readout_bwd(g[i], Wd, y=out[i], base=base, addends=gus, acc=dacc))
+        gWd, gbd = _decoder_grads(dacc, Wd, needs[3], needs[4])
+        return a, gW_tot, (gb_tot if b is not None else None), gWd, gbd, None, None, None, None, None
 
 
 class _SubstepSolve(torch.autograd.Function):
@@ -426,7 +498,8 @@ class _SubstepSolve(torch.autograd.Function):
         return y
 
     @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, plan, drop=None):
+    def _solve(ctx, y0, W, b, csr, flags, method, plan, drop):
+        """the forward launches -> (the ticks, the interval starts that are no tick); ctx.meta set"""
         n_ticks = len(plan.t)
         out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
         out[0].copy_(y0)
@@ -452,6 +525,11 @@ class _SubstepSolve(torch.autograd.Function):
         if own and where[0] == 'own':
             own.pop()                        # nothing starts from the state after the last step
         ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts, drop)
+        return out, own
+
+    @staticmethod
+    def forward(ctx, y0, W, b, csr, flags, method, plan, drop=None):
+        out, own = _SubstepSolve._solve(ctx, y0, W, b, csr, flags, method, plan, drop)
         ctx.save_for_backward(out, W, b, *own)
         return out
 
@@ -459,19 +537,29 @@ class _SubstepSolve(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         out, W, b, *own = ctx.saved_tensors
-        csr, no_graph, no_control, method, plan, segs, starts, drop = ctx.meta
         g = g.contiguous()
+
+        def enter(a, ticks):
+            """the adjoint `a` (None: nothing yet) plus the gradients of the ticks reported at this state"""
+            gs = [g[j] for j in ticks]
+            if a is None:
+                a, gs = gs[0], gs[1:]
+            for q in range(0, len(gs), 8):
+                a = hip.lincomb(gs[q:q + 8], [1.0] * len(gs[q:q + 8]), y0=a)
+            return a
+        return _SubstepSolve._reverse(ctx, out, W, b, own, enter) + (None, None, None, None, None)
+
+    @staticmethod
+    def _reverse(ctx, out, W, b, own, enter):
+        """(g_y0, g_W, g_b): the tick intervals last first; enter(a, ticks) adds the gradients of the listed ticks to the adjoint"""
+        csr, no_graph, no_control, method, plan, segs, starts, drop = ctx.meta
         H = out.shape[2]
         gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
         gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
         vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
         a = None
         for (lo, hi), (kind, idx) in zip(reversed(segs), reversed(starts)):
-            gs = [g[e[0]] for e in plan.emits[hi]]                       # the ticks this interval's last step reported
-            if a is None:
-                a, gs = gs[0], gs[1:]
-            for q in range(0, len(gs), 8):
-                a = hip.lincomb(gs[q:q + 8], [1.0] * len(gs[q:q + 8]), y0=a)
+            a = enter(a, [e[0] for e in plan.emits[hi]])                 # the ticks this interval's last step reported
             y = out[idx] if kind == 'out' else own[idx]
             keep = []
             _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep, drop=drop)
@@ -479,12 +567,53 @@ class _SubstepSolve(torch.autograd.Function):
                 a = _FixedGridSolve._sweep_step(method, float(plan.dts[i]), keep.pop(), a, vj, acc, [])
         if a is None:
             a = torch.zeros_like(out[0])
-        a = hip.lincomb([g[0]], [1.0], y0=a)                            # the first tick is y0 itself
-        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None, None
+        a = enter(a, [0])                                               # the first tick is y0 itself
+        return a, gW_tot, (gb_tot if b is not None else None)
 
 
-def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None):
-    """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size)."""
+class _SubstepSolveReadout(torch.autograd.Function):
+    """_SubstepSolve with the decoder of every tick inside the node, as _FixedGridSolveReadout: a tick's gradient enters the adjoint
+    at the end of the step that reported it, one hip.readout_bwd call per tick (an interval's last step may report several)."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, plan, drop=None):
+        out, own = _SubstepSolve._solve(ctx, y0, W, b, csr, flags, method, plan, drop)
+        ctx.save_for_backward(out, W, b, Wd, *own)
+        return hip.linear(out, Wd, bd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        out, W, b, Wd, *own = ctx.saved_tensors
+        g = g.contiguous()
+        needs = ctx.needs_input_grad
+        dacc = _decoder_acc(Wd, needs[3], needs[4])
+
+        def enter(a, ticks):
+            for j in ticks:
+                a = hip.readout_bwd(g[j], Wd, y=out[j], base=a, acc=dacc)
+            return a
+        ga, gW, gb = _SubstepSolve._reverse(ctx, out, W, b, own, enter)
+        gWd, gbd = _decoder_grads(dacc, Wd, needs[3], needs[4])
+        return ga, gW, gb, gWd, gbd, None, None, None, None, None
+
+
+def _readout_for_grad(readout, y0):
+    """(Wd, bd) when the fixed-grid training nodes can hold this decoder (hip.readout_bwd: float32 on the state's device, (C, H) with
+    1 <= C <= 15), else None - odeint then decodes the hidden solution in a step of its own"""
+    if readout is None:
+        return None
+    Wd, bd = readout
+    ok = torch.is_tensor(Wd) and Wd.dim() == 2 and Wd.dtype == torch.float32 and Wd.device == y0.device and Wd.shape[1] == y0.shape[1] and \
+        1 <= Wd.shape[0] <= hip.READOUT_BWD_MAX_C
+    if ok and bd is not None:
+        ok = torch.is_tensor(bd) and bd.dtype == torch.float32 and bd.device == y0.device and tuple(bd.shape) == (Wd.shape[0],)
+    return (Wd, bd) if ok else None
+
+
+def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None, readout=None):
+    """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size).
+    readout = (Wd, bd) (checked by _readout_for_grad): the DECODED solution, the decoder's Linear inside the solve's autograd node."""
     if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
         return None
     op = _small_operator(odefunc, y0)
@@ -499,18 +628,22 @@ def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None):
         # path hands out one by one (ODEFunc.forward), so both paths apply the same masks
         stream = _dropout.current() or _dropout.Stream()
         drop = (float(odefunc.dropout), stream.seed, stream.take(n_steps * _FixedGridSolve.EVALS[method]))
+    y0 = _lib.require_device(y0, 'state y0').contiguous()
+    W, b = odefunc.wt.weight, odefunc.wt.bias
     if plan is not None:                                      # the step_size option: checkpointed per tick interval
-        return _SubstepSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
-                                   method, plan, drop)
+        if readout is not None:
+            return _SubstepSolveReadout.apply(y0, W, b, readout[0], readout[1], csr, flags, method, plan, drop)
+        return _SubstepSolve.apply(y0, W, b, csr, flags, method, plan, drop)
     tt = core.host_grid(t).to(y0.dtype)
     dts = (tt[1:] - tt[:-1]).tolist()
     if drop is None:                                          # (the C++ tape has no dropout form)
         from . import tape
-        sol = tape.fixed_grid(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags, method, dts)
+        sol = tape.fixed_grid(y0, W, b, csr, flags, method, dts, readout=readout)
         if sol is not None:
             return sol
-    return _FixedGridSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
-                                 method, dts, drop)
+    if readout is not None:
+        return _FixedGridSolveReadout.apply(y0, W, b, readout[0], readout[1], csr, flags, method, dts, drop)
+    return _FixedGridSolve.apply(y0, W, b, csr, flags, method, dts, drop)
 
 
 def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
