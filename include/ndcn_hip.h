@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 27
+#define NDCN_ABI_VERSION 28
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -876,14 +876,31 @@ NDCN_API int ndcn_set_range_guard(int on);
  * opts: {first_step given (0 / 1), safety, ifactor, dfactor, max_num_steps, keep S (0 / 1: evaluations that can - ndcn_rhs_adj_supported -
  * also store S = A u on the tape, one panel more per evaluation, instead of one SpMM per evaluation in the reverse pass)}.
  * At: the transposed operator (unused with NDCN_F_NO_GRAPH).
- * alloc: device memory for the tape (12 panels per attempted step; ~24 more during a reverse pass), owned by the caller; what
- * ndcn_tape_dopri5_f32 asked for is kept until ndcn_tape_destroy.  y0, W, b and the operators must stay valid and unchanged until then.
- * Errors as the solver's: NDCN_EMAXSTEPS, NDCN_EUNDERFLOW, NDCN_ENONFINITE; the tape handle is set on every path - destroy it.     */
+ * alloc: device memory for the tape (12 panels per attempted step, 18 where S is kept; ~24 more during a reverse pass), owned by the
+ * caller; what ndcn_tape_dopri5_f32 asked for is kept until ndcn_tape_destroy.  y0, W, b and the operators must stay valid and
+ * unchanged until then.
+ * Errors as the solver's: NDCN_EMAXSTEPS, NDCN_EUNDERFLOW, NDCN_ENONFINITE; the tape handle is set on every path - destroy it.
+ * ndcn_tape_dopri5_budget_f32 (ABI 28) bounds that record: record_budget_bytes < 0 is ndcn_tape_dopri5_f32 (which calls it with -1);
+ * otherwise an attempt is recorded in full while (panels held by full attempts) * panel bytes + (12 + (keep S ? 6 : 0)) * panel bytes
+ * fits the budget - ndcn_tape_attempt_is_full, asked before the attempt starts - and is THIN from the first one that does not fit on
+ * (0: every attempt).  A thin attempt forms its stage inputs, derivatives and S panels in a ring of <= 10 + 6 panels all thin attempts
+ * share and keeps y1 and k7 alone - the next attempt's y0 and k1; a rejected one hands those two panels on.  The reverse pass re-forms
+ * a thin attempt's ring panels from (y0, k1, dt) by the forward pass's own launches before it processes the attempt: the gradients
+ * are the same bits, for six more right-hand-side evaluations per thin attempt and pass; ndcn_tape_nfe does not count them.
+ * ndcn_tape_record: out = {panels held by full attempts, panels kept for thin attempts (2 per accepted one + 2 spare), ring panels,
+ * thin attempts}.                                                                                                                  */
 typedef struct ndcn_tape ndcn_tape;
 typedef void *(*ndcn_alloc_fn)(void *ctx, int64_t bytes);
 NDCN_API int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
                                   const float *y0, const double *ticks, int64_t n_t, double rtol, double atol, const double *opts,
                                   float *out, ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape, void *stream);
+NDCN_API int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
+                                         const float *y0, const double *ticks, int64_t n_t, double rtol, double atol,
+                                         const double *opts, float *out, ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape,
+                                         void *stream, int64_t record_budget_bytes);
+NDCN_API int ndcn_tape_attempt_is_full(int64_t record_budget_bytes, int64_t full_panels, int64_t panel_bytes, int keep_s,
+                                       int thin_already);             /* 1: recorded in full, 0: thin (no device call) */
+NDCN_API int ndcn_tape_record(const ndcn_tape *tape, int64_t out[4]);
 NDCN_API int ndcn_tape_backward_f32(ndcn_tape *tape, const float *g_out, float *g_y0, float *g_W, float *g_b, void *stream);
 NDCN_API int64_t ndcn_tape_steplog(const ndcn_tape *tape, double *rows, int64_t cap);   /* 5 doubles per attempt, as ndcn_solver_steplog */
 NDCN_API int64_t ndcn_tape_nfe(const ndcn_tape *tape);

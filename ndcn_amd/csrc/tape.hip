@@ -19,7 +19,13 @@
 // in one device array and come back in ONE read: the only host synchronisation per attempted step, as in the forward pass.
 //
 // Memory: panels come from the caller's allocator (ndcn_alloc_fn: torch's caching allocator through the binding) and live until
-// ndcn_tape_destroy: 12 panels per attempted step (stage inputs and derivatives) + ~24 of scratch in the reverse pass.
+// ndcn_tape_destroy: 12 panels per attempted step (stage inputs and derivatives; + up to 6 of S = A u with keep_s) + ~24 of scratch in
+// the reverse pass.  Under a record budget (ndcn_tape_dopri5_budget_f32) the attempts past the budget are THIN: everything an attempt
+// computes is a function of (y0, k1, dts) and the operator, y0 is the previous accepted attempt's u[7] and k1 its k[6] (FSAL), so a thin
+// attempt keeps those two panels alone (when it is accepted; a rejected one leaves them to the next attempt) and forms the rest in a ring
+// of <= 10 + 6 panels that every thin attempt shares.  The reverse pass re-forms a thin attempt's ring panels by the forward's own launch
+// sequence (attempt_launches: same modes, coefficients, S decisions, packed weights - the same bits) before it processes the attempt:
+// 2 accepted + 2 + 16 panels instead of 12 A (+ 6 A), for six more right-hand-side evaluations per thin attempt and pass.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,6 +43,7 @@ namespace {
 
 struct Attempt {
     bool accept = false, fused_err = false;
+    bool thin = false;                 // u[2..6], k[1..5], S live in the tape's ring: the reverse pass re-forms them first
     double t0 = 0, dt = 0, dt_next = 0, factor = 0;
     float dts = 0, ratio = 0;
     const float *y0 = nullptr;
@@ -58,6 +65,12 @@ struct HostScratch {                   // per host thread: pinned mirror of the 
     double *rec = nullptr;             // ... + 8 (a reduction record), same allocation
     double *h_dev = nullptr, *rec_dev = nullptr;      // their device aliases (polling mode: hostrec.h), else null
     hipEvent_t ev = nullptr;
+};
+
+// the panels one attempt's launches write; S[e]: in - the panel evaluation e stores S = A u in where its launch can (null: one from the
+// arena), out - that panel, or untouched where the launch cannot
+struct StagePanels {
+    float *u[8] = {}, *k[7] = {}, *S[8] = {};
 };
 
 constexpr int kDotSlots = 40;          // 8 doubles each
@@ -115,6 +128,13 @@ struct ndcn_tape {
     bool packed = false;
     void *bwork = nullptr;             // linear_bwd scratch
     bool bpacked = false;
+    // record budget (ndcn_tape_dopri5_budget_f32): < 0 unlimited
+    int64_t budget = -1;
+    bool thin_mode = false;            // an attempt did not fit: it and all later ones are thin
+    int64_t full_panels = 0, thin_kept = 0, ring_panels = 0, thin_attempts = 0;
+    StagePanels ring;                  // u[2..6], k[1..5], S[2..7]: shared by the thin attempts; u[7] / k[6]: the spare pair (the kept pair of
+                                       // the next accepted thin attempt; at the end of the forward pass, where a re-run's y1 / k7 land)
+    double *d_red_rerun = nullptr;     // the error record of a re-run attempt (nobody reads it)
     bool bwd_marked = false;           // arena position behind the forward record: every reverse pass starts its scratch there
     char *mark_chunk = nullptr;
     size_t mark_left = 0;
@@ -146,8 +166,8 @@ int panel(ndcn_tape *t, float **p) {
     return rc;
 }
 
-int rhs_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st) {
-    t->nfe++;
+int rhs_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st, bool count = true) {
+    if (count) t->nfe++;
     uint32_t fl = t->flags | (t->packed ? NDCN_F_PACKED : 0u);
     int rc = rhs_rk_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, fl, 0, nullptr, nullptr, nullptr, 0, nullptr,
                         0.f, 0.f, nullptr, nullptr, st, nullptr);
@@ -225,66 +245,116 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
     return NDCN_OK;
 }
 
-int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, double &bad_out) {
+// The launches of one attempted step from (y0, k0 = f(y0), dts) into the panels of P: the forward pass, and the reverse pass where it
+// re-forms a thin attempt (rerun: the evaluations are not counted, the error record goes to `d_red`, which nobody reads).  S_used[e]:
+// the panel evaluation e's launch wrote S = A u to, else null.
+int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, StagePanels &P, const float **S_used, bool *fused_err,
+                     double *d_red, bool rerun, hipStream_t st) {
     int rc;
-    arm_record(t, hs);
-    float *u[8] = {}, *k[7] = {}, *S[8] = {};
-    for (int e = 2; e <= 7; ++e)
-        if ((rc = panel(t, &u[e]))) return rc;
+    float *const *u = P.u, *const *k = P.k;
     const bool both = !(t->flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL));
     // (the narrow-panel kernel - rhs_small.hip: what rhs_rk_f32 picks for H <= 128 at launch-bound sizes - writes S on the side too)
     const bool small_s = both && !rhs_fused2_supported(&t->A, t->H, t->flags) && rhs_small_supported(&t->A, t->H, t->flags);
-    for (int j = 1; j < 7; ++j)
-        if ((rc = panel(t, &k[j]))) return rc;
-    const float *kall[7] = {a.k[0], k[1], k[2], k[3], k[4], k[5], k[6]};
+    const float *kall[7] = {k0, k[1], k[2], k[3], k[4], k[5], k[6]};
     const float *kp[8];
     float cp[8];
-    const float dts = a.dts;
+    for (int e = 0; e < 8; ++e) S_used[e] = nullptr;
+    auto s_panel = [&](int e, float **out) -> int {
+        if (!P.S[e]) {
+            if (rerun) { set_error("tape: a re-formed attempt asks for an S panel its forward pass did not"); return NDCN_EINVAL; }
+            int r = panel(t, &P.S[e]);
+            if (r) return r;
+        }
+        S_used[e] = *out = P.S[e];
+        return NDCN_OK;
+    };
     int m = dt_terms(dts, kBeta[0], 1, kall, kp, cp);
-    rc = rk_combine_f32(u[2], a.y0, kp, cp, m, t->n, st);
+    rc = rk_combine_f32(u[2], y0, kp, cp, m, t->n, st);
     if (rc) return rc;
     const uint32_t fl = t->flags;
     for (int i = 0; i < 5; ++i) {
         // evaluation i + 2: k[i + 1] = f(u[i + 2]); its epilogue forms u[i + 3] from row i + 1 of the tableau
         const int mp = dt_terms(dts, kBeta[i + 1], i + 1, kall, kp, cp);
         cp[mp] = dts * (float)kBeta[i + 1][i + 1];
-        t->nfe++;
+        if (!rerun) t->nfe++;
         RkOpt opt = {};
         if (t->keep_s && both && (rhs_adj_supported(&t->A, t->H, fl, NDCN_RK_COMBINE, mp) || small_s)) {
-            if ((rc = panel(t, &S[i + 2]))) return rc;
-            opt.s_out = S[i + 2];
+            if ((rc = s_panel(i + 2, &opt.s_out))) return rc;
         }
         rc = rhs_rk_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
-                        NDCN_RK_COMBINE, a.y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr);
+                        NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr);
         if (rc) return rc;
     }
-    a.fused_err = t->n > aten_order_max_elems();
-    if (a.fused_err) {
+    *fused_err = t->n > aten_order_max_elems();
+    if (*fused_err) {
         const int mp = dt_terms(dts, kCErr, 6, kall, kp, cp);
         cp[mp] = dts * (float)kCErr[6];
-        t->nfe++;
+        if (!rerun) t->nfe++;
         RkOpt opt = {};
         if (t->keep_s && both && rhs_adj_supported(&t->A, t->H, fl, NDCN_RK_ERROR, mp)) {
-            if ((rc = panel(t, &S[7]))) return rc;
-            opt.s_out = S[7];
+            if ((rc = s_panel(7, &opt.s_out))) return rc;
         }
         rc = rhs_rk_f32(&t->A, u[7], nullptr, t->A.n_cols, t->W, t->b, k[6], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
-                        NDCN_RK_ERROR, a.y0, kp, cp, mp, nullptr, (float)t->rtol, (float)t->atol, t->d_red, t->d_ws2, st,
+                        NDCN_RK_ERROR, y0, kp, cp, mp, nullptr, (float)t->rtol, (float)t->atol, d_red, t->d_ws2, st,
                         opt.s_out ? &opt : nullptr);
         if (rc) return rc;
     } else {
-        rc = rhs_plain(t, u[7], k[6], st);
+        rc = rhs_plain(t, u[7], k[6], st, !rerun);
         if (rc) return rc;
         m = dt_terms(dts, kCErr, 7, kall, kp, cp);
-        rc = rk_error_f32(a.y0, u[7], kp, cp, m, (float)t->rtol, (float)t->atol, t->n, t->d_red, t->d_ws, st);
+        rc = rk_error_f32(y0, u[7], kp, cp, m, (float)t->rtol, (float)t->atol, t->n, d_red, t->d_ws, st);
         if (rc) return rc;
     }
+    return NDCN_OK;
+}
+
+// a thin attempt's panels: the ring (allocated at the first thin attempt) and the spare pair for y1 / k7
+int thin_panels(ndcn_tape *t, StagePanels &P) {
+    int rc;
+    if (!t->ring.u[2]) {
+        for (int e = 2; e <= 6; ++e)
+            if ((rc = panel(t, &t->ring.u[e]))) return rc;
+        for (int j = 1; j <= 5; ++j)
+            if ((rc = panel(t, &t->ring.k[j]))) return rc;
+        t->ring_panels = 10;
+        void *p;
+        if ((rc = arena(t, 2 * sizeof(double) + 256, &p))) return rc;
+        t->d_red_rerun = static_cast<double *>(p);
+    }
+    if (!t->ring.u[7]) {
+        if ((rc = panel(t, &t->ring.u[7])) || (rc = panel(t, &t->ring.k[6]))) return rc;
+        t->thin_kept += 2;
+    }
+    P = t->ring;
+    return NDCN_OK;
+}
+
+int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, double &bad_out) {
+    int rc;
+    arm_record(t, hs);
+    StagePanels P;
+    a.thin = t->thin_mode = !ndcn_tape_attempt_is_full(t->budget, t->full_panels, (int64_t)t->panel_bytes, t->keep_s, t->thin_mode);
+    if (a.thin) {
+        if ((rc = thin_panels(t, P))) return rc;
+        t->thin_attempts++;
+    } else {
+        for (int e = 2; e <= 7; ++e)
+            if ((rc = panel(t, &P.u[e]))) return rc;
+        for (int j = 1; j < 7; ++j)
+            if ((rc = panel(t, &P.k[j]))) return rc;
+        t->full_panels += 12;
+    }
+    rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, a.S, &a.fused_err, t->d_red, false, st);
+    for (int e = 2; e <= 7; ++e)                   // (S panels the launches took from the arena)
+        if (a.thin && P.S[e] && !t->ring.S[e]) t->ring.S[e] = P.S[e], t->ring_panels++;
+        else if (!a.thin && P.S[e]) t->full_panels++;
+    if (rc) return rc;
     rc = fetch_record(t, st, hs);
     if (rc) return rc;
     a.ratio = (float)(hs->h[0] / (double)t->n);
     bad_out = hs->h[1];
-    for (int e = 2; e <= 7; ++e) a.u[e] = u[e], a.S[e] = S[e];
-    for (int j = 1; j < 7; ++j) a.k[j] = k[j];
+    for (int e = 2; e <= 7; ++e) a.u[e] = P.u[e];
+    for (int j = 1; j < 7; ++j) a.k[j] = P.k[j];
     return NDCN_OK;
 }
 
@@ -383,9 +453,22 @@ inline double half_on_tie_gt(double a, double b) { return a > b ? 1.0 : (a == b 
 // ====================================================================================================== C ABI
 extern "C" {
 
+int ndcn_tape_attempt_is_full(int64_t record_budget_bytes, int64_t full_panels, int64_t panel_bytes, int keep_s, int thin_already) {
+    if (record_budget_bytes < 0) return 1;
+    if (thin_already) return 0;
+    const int64_t cost = (12 + (keep_s ? 6 : 0)) * panel_bytes;       // the upper bound for one full attempt
+    return full_panels * panel_bytes + cost <= record_budget_bytes ? 1 : 0;
+}
+
 int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, const float *y0,
                          const double *ticks, int64_t n_t, double rtol, double atol, const double *opts, float *out, ndcn_alloc_fn alloc,
                          void *alloc_ctx, ndcn_tape **tape, void *stream) {
+    return ndcn_tape_dopri5_budget_f32(A, At, W, b, H, flags, y0, ticks, n_t, rtol, atol, opts, out, alloc, alloc_ctx, tape, stream, -1);
+}
+
+int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
+                                const float *y0, const double *ticks, int64_t n_t, double rtol, double atol, const double *opts, float *out,
+                                ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape, void *stream, int64_t record_budget_bytes) {
     NDCN_CHECK_ARG(A && y0 && ticks && n_t >= 1 && out && alloc && tape && opts && H > 0, "bad argument");
     const bool no_graph = flags & NDCN_F_NO_GRAPH, no_control = flags & NDCN_F_NO_CONTROL;
     NDCN_CHECK_ARG(no_graph || (At && A->n_rows == A->n_cols), "a square operator and its transpose are required");
@@ -416,6 +499,7 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
     t->keep_s = opts[5] != 0.0;
     t->alloc = alloc;
     t->alloc_ctx = alloc_ctx;
+    t->budget = record_budget_bytes;
     t->panel_bytes = (size_t)t->n * sizeof(float) + 16;
     t->ticks.assign(ticks, ticks + n_t);
     void *p;
@@ -494,6 +578,7 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
             if (a.accept) {
                 y_cur = a.u[7];
                 f_cur = a.k[6];
+                if (a.thin) t->ring.u[7] = t->ring.k[6] = nullptr;    // the spare pair is this step's kept pair now
                 t_lo = t0;
                 t_hi = t0 + dt;
                 pending_bad = (int64_t)bad;
@@ -531,6 +616,23 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
         t->attempts[(size_t)last_acc].dense.push_back((int)t->groups.size());
         t->groups.push_back(g);
     }
+    if (t->thin_attempts > 0) {
+        // where a re-run's y1 / k7 land: the spare pair (part of the forward record - the reverse pass may run again).  The rejected
+        // thin attempts wrote theirs into panels later attempts took over: their reverse pass reads the re-run's
+        StagePanels P;
+        if ((rc = thin_panels(t, P))) return rc;
+        for (Attempt &a : t->attempts)
+            if (a.thin && !a.accept) a.u[7] = P.u[7], a.k[6] = P.k[6];
+    }
+    return NDCN_OK;
+}
+
+int ndcn_tape_record(const ndcn_tape *t, int64_t out[4]) {
+    NDCN_CHECK_ARG(t && out, "bad argument");
+    out[0] = t->full_panels;
+    out[1] = t->thin_kept;
+    out[2] = t->ring_panels;
+    out[3] = t->thin_attempts;
     return NDCN_OK;
 }
 
@@ -602,6 +704,15 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
 
     for (int s = (int)t->attempts.size() - 1; s >= 0; --s) {
         const Attempt &a = t->attempts[(size_t)s];
+        if (a.thin) {
+            // re-form u[2..6], k[1..5] and the S panels in the ring (where `a` points) by the forward's launches; y1 / k7 land in the
+            // spare pair - an accepted attempt's kept pair, which the next attempt read in the forward pass, is what `a` points to
+            StagePanels P = t->ring;
+            const float *S_used[8];
+            bool fused_err;
+            rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, S_used, &fused_err, t->d_red_rerun, true, st);
+            if (rc) return rc;
+        }
         int slot = 0;
         if (hs->h_dev) rec_arm(hs->h, kDotSlots * 8);
         auto dots_at = [&](int sl) { return t->d_dots + 8 * sl; };

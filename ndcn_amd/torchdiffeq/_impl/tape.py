@@ -5,8 +5,14 @@ solve with the per-operation path's own launches and keeps every attempted step;
 VJP kernels of the panel operations plus the hand-written adjoint of the step-size controller's scalar chain (which the reference
 differentiates: dt, the initial step, the interpolation abscissa are tensors with history).  One autograd node per solve instead of
 ~130 (`autograd_path.integrate_dopri5_grad`, which stays the path of tuple states, plain callables, `t` with gradient and the A/B:
-NDCN_GRAD_TAPE=0)."""
+NDCN_GRAD_TAPE=0).
+
+The forward record grows with the number of attempted steps (12 to 18 panels each).  NDCN_TAPE_BUDGET_MB bounds it: attempts past
+the budget keep two panels each and the reverse pass re-forms the rest by the forward pass's launches (`ndcn_tape_dopri5_budget_f32`:
+the same gradients bit for bit, six more evaluations per such attempt); unset, a solve whose record does not fit the device runs once
+more with budget 0.  `last_record` says what the last solve kept."""
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -16,6 +22,11 @@ from ... import _lib
 from ..._lib import check, ptr, stream_ptr
 
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64)
+
+
+# what the last tape solve recorded (ndcn_tape_record) and whether it was the second run after the record did not fit
+last_record = {'full_panels': 0, 'thin_kept_panels': 0, 'ring_panels': 0, 'thin_attempts': 0, 'retried': False}
+_retry_warned = False
 
 
 def enabled():
@@ -30,16 +41,19 @@ class Tape:
         self.blocks = []
         self.error = None
         self.handle = ctypes.c_void_p()
-        self.cb = ALLOC_FN(self._alloc)             # (kept: the library calls it until the reverse pass has run)
+        self.cb = ALLOC_FN(self._alloc_cb)          # (kept: the library calls it until the reverse pass has run)
 
     def _alloc(self, ctx, nbytes):
+        blk = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        self.blocks.append(blk)
+        return blk.data_ptr()
+
+    def _alloc_cb(self, ctx, nbytes):
         try:
-            blk = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            return self._alloc(ctx, nbytes)
         except Exception as e:                      # an exception cannot cross the C frames: the call fails with "no memory", then re-raised
             self.error = e
             return None
-        self.blocks.append(blk)
-        return blk.data_ptr()
 
     def close(self):
         if self.handle:
@@ -56,7 +70,7 @@ class Tape:
 
 class _TapeDopri5(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y0, W, b, op, ticks, rtol, atol, opts, step_log):
+    def forward(ctx, y0, W, b, op, ticks, rtol, atol, opts, step_log, budget):
         csr, csr_t, flags, H = op
         lib = _lib.load()
         y0c = y0.detach().contiguous()
@@ -64,14 +78,31 @@ class _TapeDopri5(torch.autograd.Function):
         bc = b.detach().contiguous() if b is not None else None
         n_t = len(ticks)
         out = torch.empty((n_t,) + tuple(y0c.shape), dtype=torch.float32, device=y0c.device)
-        tape = Tape(y0c.device)
         tk = (ctypes.c_double * n_t)(*ticks)
         op_arr = (ctypes.c_double * 6)(*opts)
         view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(y0c.shape[0]))
         view_t = csr_t.view_ref() if csr_t is not None else None
-        with torch.cuda.device(y0c.device):
-            rc = lib.ndcn_tape_dopri5_f32(view, view_t, ptr(Wc), ptr(bc), H, flags, ptr(y0c), tk, n_t, float(rtol), float(atol), op_arr,
-                                          ptr(out), ctypes.cast(tape.cb, ctypes.c_void_p), None, ctypes.byref(tape.handle), stream_ptr())
+        retried = False
+        while True:
+            tape = Tape(y0c.device)
+            with torch.cuda.device(y0c.device):
+                rc = lib.ndcn_tape_dopri5_budget_f32(view, view_t, ptr(Wc), ptr(bc), H, flags, ptr(y0c), tk, n_t, float(rtol), float(atol),
+                                                     op_arr, ptr(out), ctypes.cast(tape.cb, ctypes.c_void_p), None,
+                                                     ctypes.byref(tape.handle), stream_ptr(), budget)
+            if rc < 0 and budget < 0 and not retried and isinstance(tape.error, torch.cuda.OutOfMemoryError):
+                # the unlimited record did not fit: its blocks go back to the allocator and the solve runs once more with every attempt
+                # thin (a failure of that run is raised as it is)
+                tape.close()
+                del tape
+                _warn_retry()
+                retried, budget = True, 0
+                continue
+            break
+        if tape.handle:
+            rec = (ctypes.c_int64 * 4)()
+            lib.ndcn_tape_record(tape.handle, rec)
+            last_record.update(full_panels=int(rec[0]), thin_kept_panels=int(rec[1]), ring_panels=int(rec[2]), thin_attempts=int(rec[3]),
+                               retried=retried)
         if step_log is not None and tape.handle:
             n = int(lib.ndcn_tape_steplog(tape.handle, None, 0))
             rows = (ctypes.c_double * (5 * max(n, 1)))()
@@ -123,7 +154,16 @@ class _TapeDopri5(torch.autograd.Function):
             del record
         needs = ctx.needs_input_grad
         return (gy if needs[0] else None, gW if (needs[1] and ctx.has[0]) else None, gb if (needs[2] and ctx.has[1]) else None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
+
+
+def _warn_retry():
+    global _retry_warned
+    if not _retry_warned:
+        _retry_warned = True
+        warnings.warn('the dopri5 training tape did not fit the device memory: solving again with every attempted step re-formed in the '
+                      'reverse pass (set NDCN_TAPE_BUDGET_MB to bound the record from the start; 0 keeps two panels per accepted step)',
+                      RuntimeWarning, stacklevel=2)
 
 
 def applicable(odefunc, y0, t_user):
@@ -160,7 +200,9 @@ def solve(odefunc, y0, t, rtol, atol, options, step_log):
     keep_s = (not odefunc.no_graph) and (not odefunc.no_control) and _keep_s_enabled(y0)      # (the library keeps S where a kernel writes it)
     opts = (0.0 if opt['first_step'] is None else 1.0, opt['safety'], opt['ifactor'], opt['dfactor'], float(min(opt['max_num_steps'], 2 ** 53)),
             1.0 if keep_s else 0.0)
-    return _TapeDopri5.apply(y0, W, b, (csr, csr_t, flags, odefunc.hidden_size), ticks, rt, at, opts, step_log)
+    budget_mb = _lib.env_int('NDCN_TAPE_BUDGET_MB', -1)
+    budget = budget_mb * (1 << 20) if budget_mb >= 0 else -1         # bytes of forward record kept in full; < 0: no bound
+    return _TapeDopri5.apply(y0, W, b, (csr, csr_t, flags, odefunc.hidden_size), ticks, rt, at, opts, step_log, budget)
 
 
 # ---- fixed grids ---------------------------------------------------------------------------------------------------------------
