@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NDCN_ABI_VERSION 28
+#define NDCN_ABI_VERSION 29
 #define NDCN_API __attribute__((visibility("default")))
 
 #define NDCN_OK          0
@@ -420,13 +420,23 @@ NDCN_API int ndcn_rhs_rk_adj_f32(const ndcn_csr *A, const float *X, const float 
  * those calls).  H <= 128 on the one-launch route: the factor is applied in the launch's epilogue (NDCN_PATH_DROP_EPI); every other
  * route runs its launch without a stage epilogue, ndcn_dropout_apply_f32 and the un-fused stage kernel.  NDCN_EINVAL: p outside
  * (0, 1), a halo panel, NDCN_F_RELU off.
- * ndcn_dropout_apply_f32: K[i] *= m(i) in place for i < n_elem (16 bytes per lane where K is 16-byte aligned; any n_elem).     */
+ * ndcn_dropout_apply_f32: K[i] *= m(i) in place for i < n_elem (16 bytes per lane where K is 16-byte aligned; any n_elem).
+ * ndcn_dropout_combine_f32 (ABI 29): that pass and the stage sum that consumes its result, in ONE pass -
+ *   K[i] = K[i] * m(i), stored;  out[i] = y0[i] + (((0 + h_c[0] h_kprev[0][i]) + ...) + h_c[n_prev] K'[i])   (y0 NULL: the sum alone)
+ * - the bits of ndcn_dropout_apply_f32(K) followed by ndcn_rk_combine_f32(out, y0, {h_kprev..., K}, h_c, n_prev + 1): (n_prev + 2)
+ * panel reads and two writes instead of (n_prev + 3) and two launches.  n_prev = 0..5; the mask index is the position in K; 16-byte
+ * lanes where every pointer is 16-byte aligned, scalar lanes otherwise; out, y0 and the h_kprev must not overlap K.  It is what
+ * ndcn_rhs_rk_drop_f32 runs behind the launch in NDCN_RK_COMBINE mode (without y_aux) on every route that has no dropout epilogue:
+ * the stage input of the masked derivative - dropout(...) of neural_dynamics.py:34 feeding y0 + sum_j dt beta_ij k_j of
+ * rk_common.py:51.                                                                                                              */
 typedef struct ndcn_dropout {
     float p;
     uint64_t seed;
     uint64_t evaluation;
 } ndcn_dropout;
 NDCN_API int ndcn_dropout_apply_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, void *stream);
+NDCN_API int ndcn_dropout_combine_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, float *out, const float *y0,
+                                      const float *const *h_kprev, const float *h_c, int n_prev, void *stream);
 NDCN_API int ndcn_rhs_drop_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own,
                                const float *W, const float *b, float *Y, float *work, int H, uint32_t flags, void *stream,
                                const ndcn_dropout *desc);
@@ -888,7 +898,17 @@ NDCN_API int ndcn_set_range_guard(int on);
  * a thin attempt's ring panels from (y0, k1, dt) by the forward pass's own launches before it processes the attempt: the gradients
  * are the same bits, for six more right-hand-side evaluations per thin attempt and pass; ndcn_tape_nfe does not count them.
  * ndcn_tape_record: out = {panels held by full attempts, panels kept for thin attempts (2 per accepted one + 2 spare), ring panels,
- * thin attempts}.                                                                                                                  */
+ * thin attempts}.
+ * ndcn_tape_dopri5_drop_f32 (ABI 29): the budgeted call plus a dropout descriptor - training through dopri5 with ODEFunc's dropout
+ * active (dgnn.py:192-222 at its default --dropout 0.5; heat_dynamics.py:313-334 with --dropout p).  desc NULL: exactly
+ * ndcn_tape_dopri5_budget_f32 (which calls it so).  Otherwise every evaluation's launch carries the mask of (desc->p, desc->seed) and
+ * a number of its own: desc->evaluation is the number of the solve's FIRST evaluation f0, the initial step's f1 follows when it is
+ * evaluated (first_step not given), then six per attempted step, accepted or rejected, in stage order -
+ * ndcn_tape_attempt_evaluation(first, probe evaluated, attempt index) is the first number of an attempt (no device call), and
+ * ndcn_tape_evaluations how many numbers the solve consumed.  An attempt keeps its numbers: re-formed in the reverse pass (budget) it
+ * re-creates its masks and consumes none.  The record holds K' = relu(z) * m; the reverse pass is the p = 0 one with every J^T g times
+ * s = 1 / (1 - p) (no mask stored or re-created).  S = A u is not kept (opts[5] is ignored: 12 panels per full attempt) and the error
+ * record always comes from ndcn_rk_error_f32's kernel, as on the per-operation path with dropout.                                  */
 typedef struct ndcn_tape ndcn_tape;
 typedef void *(*ndcn_alloc_fn)(void *ctx, int64_t bytes);
 NDCN_API int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
@@ -898,6 +918,12 @@ NDCN_API int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, 
                                          const float *y0, const double *ticks, int64_t n_t, double rtol, double atol,
                                          const double *opts, float *out, ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape,
                                          void *stream, int64_t record_budget_bytes);
+NDCN_API int ndcn_tape_dopri5_drop_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
+                                       const float *y0, const double *ticks, int64_t n_t, double rtol, double atol,
+                                       const double *opts, float *out, ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape,
+                                       void *stream, int64_t record_budget_bytes, const ndcn_dropout *desc);
+NDCN_API int64_t ndcn_tape_attempt_evaluation(int64_t first, int probe_evaluated, int64_t attempt);
+NDCN_API int64_t ndcn_tape_evaluations(const ndcn_tape *tape);
 NDCN_API int ndcn_tape_attempt_is_full(int64_t record_budget_bytes, int64_t full_panels, int64_t panel_bytes, int keep_s,
                                        int thin_already);             /* 1: recorded in full, 0: thin (no device call) */
 NDCN_API int ndcn_tape_record(const ndcn_tape *tape, int64_t out[4]);

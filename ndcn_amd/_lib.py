@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- must come first: the library binds to the HIP run
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libndcn_hip.so')
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
@@ -187,7 +187,11 @@ SIGNATURES = {
                              ctypes.POINTER(_P), _P]),
     'ndcn_tape_dopri5_budget_f32': (_I, [_P, _P, _P, _P, _I, ctypes.c_uint32, _P, ctypes.POINTER(_D), _L, _D, _D, ctypes.POINTER(_D), _P, _P,
                                     _P, ctypes.POINTER(_P), _P, _L]),
+    'ndcn_tape_dopri5_drop_f32': (_I, [_P, _P, _P, _P, _I, ctypes.c_uint32, _P, ctypes.POINTER(_D), _L, _D, _D, ctypes.POINTER(_D), _P, _P,
+                                  _P, ctypes.POINTER(_P), _P, _L, ctypes.POINTER(DropoutDesc)]),
     'ndcn_tape_attempt_is_full': (_I, [_L, _L, _L, _I, _I]),
+    'ndcn_tape_attempt_evaluation': (_L, [_L, _I, _L]),
+    'ndcn_tape_evaluations': (_L, [_P]),
     'ndcn_tape_record': (_I, [_P, ctypes.POINTER(_L)]),
     'ndcn_tape_backward_f32': (_I, [_P, _P, _P, _P, _P, _P]),
     'ndcn_tape_steplog': (_L, [_P, ctypes.POINTER(_D), _L]),
@@ -217,6 +221,7 @@ SIGNATURES = {
     'ndcn_rhs_rk_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I,
                         _P, _P, _P, ctypes.POINTER(_F), _F, _F, _P, _P, _P]),
     'ndcn_dropout_apply_f32': (_I, [_P, _L, ctypes.POINTER(DropoutDesc), _P]),
+    'ndcn_dropout_combine_f32': (_I, [_P, _L, ctypes.POINTER(DropoutDesc), _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _P]),
     'ndcn_rhs_drop_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _P, ctypes.POINTER(DropoutDesc)]),
     'ndcn_rhs_rk_drop_f32': (_I, [_CSR, _P, _P, _L, _P, _P, _P, _P, _I, _U, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I,
                              _P, _P, _P, ctypes.POINTER(_F), _F, _F, _P, _P, _P, ctypes.POINTER(DropoutDesc)]),

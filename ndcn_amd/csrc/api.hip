@@ -361,6 +361,17 @@ int ndcn_dropout_apply_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, v
     return dropout_apply_f32(K, n_elem, d, ST(stream));
 }
 
+int ndcn_dropout_combine_f32(float *K, int64_t n_elem, const ndcn_dropout *desc, float *out, const float *y0, const float *const *h_kprev,
+                             const float *h_c, int n_prev, void *stream) {
+    NDCN_CHECK_ARG(n_elem >= 0 && desc && h_c && n_prev >= 0 && n_prev <= 5 && (n_prev == 0 || h_kprev), "bad argument");
+    NDCN_CHECK_ARG(n_elem == 0 || (K && out && out != K && y0 != K), "null panel, or out / y0 aliasing K");
+    for (int j = 0; j < n_prev; ++j) NDCN_CHECK_ARG(h_kprev[j] && h_kprev[j] != K && h_kprev[j] != out, "null stage panel, or one aliasing K / out");
+    DropArgs d;
+    int rc = drop_args(desc, &d);
+    if (rc) return rc;
+    return dropout_combine_f32(K, n_elem, d, out, y0, h_kprev, h_c, n_prev, ST(stream));
+}
+
 int ndcn_rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int rk_mode, int n_prev) {
     return A ? rhs_adj_supported(A, H, flags, rk_mode, n_prev) : 0;
 }

@@ -107,6 +107,9 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
 // rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch, by the streaming pass behind every other route
 int drop_args(const ndcn_dropout *desc, DropArgs *out);
 int dropout_apply_f32(float *K, int64_t n, const DropArgs &d, hipStream_t st);
+// dropout_apply_f32(K) and rk_combine_f32(out, y0, {h_kprev..., K}, h_c, n_prev + 1) as one pass (h_c[n_prev]: K's coefficient): the same bits
+int dropout_combine_f32(float *K, int64_t n, const DropArgs &d, float *out, const float *y0, const float *const *h_kprev, const float *h_c,
+                        int n_prev, hipStream_t st);
 int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
                  float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st);
 int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,

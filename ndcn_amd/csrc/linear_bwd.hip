@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void chunk_sum_kernel(const float *__restrict_
         for (int u = 0; u < 8; ++u) s += v[u];
     }
     for (; c < n_chunks; ++c) s += part[(size_t)c * n_elem + e];
-    out[e] = acc ? __fadd_rn(out[e], __fmul_rn(scale, s)) : s;
+    out[e] = acc ? __fadd_rn(out[e], __fmul_rn(scale, s)) : __fmul_rn(scale, s);      // (scale = 1: s itself)
 }
 
 // g_W and g_b in ONE launch (a training step makes ~30 Linear backwards: one small launch less each)
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256) void chunk_sum2_kernel(const float *__restrict
         for (int u = 0; u < 8; ++u) s += v[u];
     }
     for (; c < n_chunks; ++c) s += part[(size_t)c * n_elem + e];
-    out[e] = acc ? __fadd_rn(out[e], __fmul_rn(scale, s)) : s;
+    out[e] = acc ? __fadd_rn(out[e], __fmul_rn(scale, s)) : __fmul_rn(scale, s);      // (scale = 1: s itself)
 }
 
 // ---------------------------------------------------------------------------------------------------- gS
@@ -658,7 +658,7 @@ int64_t linear_bwd_work_bytes(int64_t n, int Hi, int Ho) {
 int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *W, float *gS, float *gW, float *gb, void *work,
                    int64_t n, int Hi, int Ho, hipStream_t st, uint32_t flags, float acc_scale, bool accumulate) {
     // accumulate: gW / gb hold a running total: total + acc_scale * (this call's), each rounded on its own (the native reverse passes
-    // of tape.hip: one small launch per evaluation instead of three)
+    // of tape.hip: one small launch per evaluation instead of three); else they become acc_scale * (this call's)
     g_last_linear_path = 0;
     if (n == 0 && accumulate) return NDCN_OK;
     if (n == 0) {

@@ -173,7 +173,8 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
 // ---------------------------------------------------------------------------------------------------- dropout
 // K' = relu(z) * m (csrc/dropout.h).  Narrow panels: the factor in the epilogue of the one launch (NDCN_PATH_DROP_EPI).  Every other
 // route: the launch without a stage epilogue, the streaming pass K *= m, then the un-fused stage kernel - the composition rhs_rk_f32
-// itself falls back to, hence the same bits as the fused epilogues would give on the masked K.
+// itself falls back to, hence the same bits as the fused epilogues would give on the masked K.  NDCN_RK_COMBINE without y_aux: the
+// last two as ONE pass (dropout_combine_f32), the same bits again.
 static int drop_check(const float *Xh, uint32_t flags) {
     if (Xh) { set_error("dropout with a halo panel (sharded graphs) is not supported"); return NDCN_EINVAL; }
     if (!(flags & NDCN_F_RELU)) { set_error("dropout without NDCN_F_RELU is not supported"); return NDCN_EINVAL; }
@@ -207,6 +208,12 @@ int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t 
         g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
         return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                              nullptr, opt, &d);
+    }
+    if (rk_mode == 1 && !(opt && opt->y_aux)) {
+        // the stage sum consumes the masked K in the pass that forms it (dropout.hip): one launch and one panel read fewer
+        g_last_rhs_path = 0;
+        if ((rc = rhs_f32(A, X, Xh, n_own, W, b, K, work, H, flags, st))) return rc;
+        return dropout_combine_f32(K, A->n_rows * (int64_t)H, d, y_next, y0, h_kprev, h_c, n_prev, st);
     }
     if ((rc = rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st))) return rc;
     return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);

@@ -26,6 +26,14 @@
 // of <= 10 + 6 panels that every thin attempt shares.  The reverse pass re-forms a thin attempt's ring panels by the forward's own launch
 // sequence (attempt_launches: same modes, coefficients, S decisions, packed weights - the same bits) before it processes the attempt:
 // 2 accepted + 2 + 16 panels instead of 12 A (+ 6 A), for six more right-hand-side evaluations per thin attempt and pass.
+//
+// Dropout (ndcn_tape_dopri5_drop_f32): every evaluation's launch carries the counter-based mask of csrc/dropout.h - (p, seed) of the solve
+// and a number of its own, in the order autograd_path.integrate_dopri5_grad evaluates: f0, the initial step's f1, then six per attempted
+// step (ndcn_tape_attempt_evaluation).  An attempt records its first number: re-forming it in the reverse pass re-creates its masks and
+// consumes none.  The stored derivatives are K' = relu(z) * m with m in {0, s}: [K' > 0] is the mask of ReLU and dropout together, so the
+// reverse pass is the p = 0 one with J^T g scaled by s (rhs_vjp) - no mask stored, none re-created there.  The error record is never
+// taken in evaluation 7's epilogue (the per-operation path with dropout runs the stand-alone kernel at every size) and S = A u is not
+// kept (the dropout launches do not write it).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,6 +52,7 @@ namespace {
 struct Attempt {
     bool accept = false, fused_err = false;
     bool thin = false;                 // u[2..6], k[1..5], S live in the tape's ring: the reverse pass re-forms them first
+    int64_t ev0 = 0;                   // dropout: the solve-relative number of evaluation 2 of this attempt (3 .. 7: the five after it)
     double t0 = 0, dt = 0, dt_next = 0, factor = 0;
     float dts = 0, ratio = 0;
     const float *y0 = nullptr;
@@ -128,6 +137,11 @@ struct ndcn_tape {
     bool packed = false;
     void *bwork = nullptr;             // linear_bwd scratch
     bool bpacked = false;
+    // dropout (ndcn_tape_dopri5_drop_f32): (p, seed) in the kernels' form, the number of the solve's first evaluation, numbers consumed
+    bool drop = false;
+    DropArgs dargs = {};
+    uint64_t ev_first = 0;
+    int64_t evals = 0;
     // record budget (ndcn_tape_dopri5_budget_f32): < 0 unlimited
     int64_t budget = -1;
     bool thin_mode = false;            // an attempt did not fit: it and all later ones are thin
@@ -166,9 +180,20 @@ int panel(ndcn_tape *t, float **p) {
     return rc;
 }
 
-int rhs_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st, bool count = true) {
+// the descriptor of the solve's evaluation number `ev`
+DropArgs drop_at(const ndcn_tape *t, int64_t ev) {
+    DropArgs d = t->dargs;
+    const uint64_t e = t->ev_first + (uint64_t)ev;
+    d.e0 = (uint32_t)(e & 0xffffffffu);
+    d.e1 = (uint32_t)(e >> 32);
+    return d;
+}
+
+// ev: the evaluation's number within the solve (read with dropout only)
+int rhs_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st, int64_t ev, bool count = true) {
     if (count) t->nfe++;
     uint32_t fl = t->flags | (t->packed ? NDCN_F_PACKED : 0u);
+    if (t->drop) return rhs_drop_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, fl, drop_at(t, ev), st);
     int rc = rhs_rk_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, fl, 0, nullptr, nullptr, nullptr, 0, nullptr,
                         0.f, 0.f, nullptr, nullptr, st, nullptr);
     return rc;
@@ -232,7 +257,7 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
     const float cp[1] = {t->h0};
     rc = rk_combine_f32(yh, t->y_in, kp, cp, 1, t->n, st);
     if (rc) return rc;
-    rc = rhs_plain(t, yh, f1, st);
+    rc = rhs_plain(t, yh, f1, st, 1);
     if (rc) return rc;
     t->yh = yh;
     t->f1 = f1;
@@ -247,9 +272,9 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
 
 // The launches of one attempted step from (y0, k0 = f(y0), dts) into the panels of P: the forward pass, and the reverse pass where it
 // re-forms a thin attempt (rerun: the evaluations are not counted, the error record goes to `d_red`, which nobody reads).  S_used[e]:
-// the panel evaluation e's launch wrote S = A u to, else null.
+// the panel evaluation e's launch wrote S = A u to, else null.  ev0: the number of the attempt's first evaluation (dropout).
 int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, StagePanels &P, const float **S_used, bool *fused_err,
-                     double *d_red, bool rerun, hipStream_t st) {
+                     double *d_red, bool rerun, int64_t ev0, hipStream_t st) {
     int rc;
     float *const *u = P.u, *const *k = P.k;
     const bool both = !(t->flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL));
@@ -281,11 +306,15 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
         if (t->keep_s && both && (rhs_adj_supported(&t->A, t->H, fl, NDCN_RK_COMBINE, mp) || small_s)) {
             if ((rc = s_panel(i + 2, &opt.s_out))) return rc;
         }
-        rc = rhs_rk_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
-                        NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr);
+        if (t->drop)
+            rc = rhs_rk_drop_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
+                                 NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, nullptr, drop_at(t, ev0 + i));
+        else
+            rc = rhs_rk_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
+                            NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr);
         if (rc) return rc;
     }
-    *fused_err = t->n > aten_order_max_elems();
+    *fused_err = !t->drop && t->n > aten_order_max_elems();
     if (*fused_err) {
         const int mp = dt_terms(dts, kCErr, 6, kall, kp, cp);
         cp[mp] = dts * (float)kCErr[6];
@@ -299,7 +328,7 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
                         opt.s_out ? &opt : nullptr);
         if (rc) return rc;
     } else {
-        rc = rhs_plain(t, u[7], k[6], st, !rerun);
+        rc = rhs_plain(t, u[7], k[6], st, ev0 + 5, !rerun);
         if (rc) return rc;
         m = dt_terms(dts, kCErr, 7, kall, kp, cp);
         rc = rk_error_f32(y0, u[7], kp, cp, m, (float)t->rtol, (float)t->atol, t->n, d_red, t->d_ws, st);
@@ -344,7 +373,9 @@ int forward_attempt(ndcn_tape *t, Attempt &a, hipStream_t st, HostScratch *hs, d
             if ((rc = panel(t, &P.k[j]))) return rc;
         t->full_panels += 12;
     }
-    rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, a.S, &a.fused_err, t->d_red, false, st);
+    a.ev0 = ndcn_tape_attempt_evaluation(0, t->first_given ? 0 : 1, (int64_t)t->attempts.size() - 1);
+    t->evals = a.ev0 + 6;
+    rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, a.S, &a.fused_err, t->d_red, false, a.ev0, st);
     for (int e = 2; e <= 7; ++e)                   // (S panels the launches took from the arena)
         if (a.thin && P.S[e] && !t->ring.S[e]) t->ring.S[e] = P.S[e], t->ring_panels++;
         else if (!a.thin && P.S[e]) t->full_panels++;
@@ -375,10 +406,14 @@ int add_into(float *acc, const float *x, int64_t n, hipStream_t st) {
 
 // (g_X into gx (nullable: not wanted); g_W, g_b accumulated) of K = f(X) for the upstream gradient g: autograd_ops.rhs_vjp
 // premasked: g already IS gZ = g (.) [K > 0] (rk_pull_f32 applied the mask where it formed g)
+// dropout: K is K' = relu(z) * m, m in {0, s}, and J^T g = s * (this closed form masked by K') - s rides in the scalars below: the
+// accumulation scale of g_W / g_b, the alpha of the transposed SpMM, and without a graph one scaling pass (autograd_ops.rhs_vjp)
 int rhs_vjp(Bwd &B, const float *X, const float *K, const float *g, float *gx, const float *S_kept = nullptr, bool premasked = false) {
     ndcn_tape *t = B.t;
     const bool no_graph = t->flags & NDCN_F_NO_GRAPH, no_control = t->flags & NDCN_F_NO_CONTROL;
     const float *mask = ((t->flags & NDCN_F_RELU) && !premasked) ? K : nullptr;
+    const float s = t->drop ? t->dargs.s : 1.f;
+    const bool rescale = no_graph && s != 1.f;     // no SpMM to carry s: g_X = s * g_S by a pass from the scratch panel
     int rc;
     const float *gS = nullptr;
     if (!no_control) {
@@ -390,21 +425,21 @@ int rhs_vjp(Bwd &B, const float *X, const float *K, const float *g, float *gx, c
             if (rc) return rc;
             S = B.tmpS;
         }
-        float *gs_out = gx ? (no_graph ? gx : B.tmpG) : nullptr;
+        float *gs_out = gx ? ((no_graph && !rescale) ? gx : B.tmpG) : nullptr;
         // g_W / g_b: this evaluation's + what the later evaluations sent (autograd_path._add_carried), in the launch that sums the chunks
         rc = linear_bwd_f32(g, mask, S, t->W, gs_out, B.gW_acc, t->b ? B.gb_acc : nullptr, t->bwork, t->n_rows, t->H, t->H, B.st,
-                            t->bpacked ? NDCN_F_PACKED : 0u, 1.f, B.have_w);
+                            t->bpacked ? NDCN_F_PACKED : 0u, s, B.have_w);
         if (rc) return rc;
         if (gs_out && t->H == 256) t->bpacked = true;
         B.have_w = true;
         gS = gs_out;
     } else if (gx) {
-        float *gs_out = no_graph ? gx : B.tmpG;
+        float *gs_out = (no_graph && !rescale) ? gx : B.tmpG;
         if (mask) {
             rc = relu_bwd_f32(gs_out, g, mask, t->n, B.st);
             if (rc) return rc;
             gS = gs_out;
-        } else if (no_graph) {
+        } else if (no_graph && !rescale) {
             rc = copy_f32(gx, g, t->n, B.st);
             if (rc) return rc;
             gS = gx;
@@ -413,7 +448,10 @@ int rhs_vjp(Bwd &B, const float *X, const float *K, const float *g, float *gx, c
         }
     }
     if (gx && !no_graph) {
-        rc = spmm_f32(&t->At, gS, nullptr, t->At.n_cols, gx, t->H, 1.f, 0, B.st);
+        rc = spmm_f32(&t->At, gS, nullptr, t->At.n_cols, gx, t->H, s, 0, B.st);
+        if (rc) return rc;
+    } else if (gx && rescale) {
+        rc = scale_f32(gx, gS, s, t->n, B.st);
         if (rc) return rc;
     }
     return NDCN_OK;
@@ -460,6 +498,10 @@ int ndcn_tape_attempt_is_full(int64_t record_budget_bytes, int64_t full_panels, 
     return full_panels * panel_bytes + cost <= record_budget_bytes ? 1 : 0;
 }
 
+int64_t ndcn_tape_attempt_evaluation(int64_t first, int probe_evaluated, int64_t attempt) {
+    return first + 1 + (probe_evaluated ? 1 : 0) + 6 * attempt;       // f0, the initial step's f1, six per attempted step before this one
+}
+
 int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, const float *y0,
                          const double *ticks, int64_t n_t, double rtol, double atol, const double *opts, float *out, ndcn_alloc_fn alloc,
                          void *alloc_ctx, ndcn_tape **tape, void *stream) {
@@ -469,6 +511,14 @@ int ndcn_tape_dopri5_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, 
 int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags,
                                 const float *y0, const double *ticks, int64_t n_t, double rtol, double atol, const double *opts, float *out,
                                 ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape, void *stream, int64_t record_budget_bytes) {
+    return ndcn_tape_dopri5_drop_f32(A, At, W, b, H, flags, y0, ticks, n_t, rtol, atol, opts, out, alloc, alloc_ctx, tape, stream,
+                                     record_budget_bytes, nullptr);
+}
+
+int ndcn_tape_dopri5_drop_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                              const double *ticks, int64_t n_t, double rtol, double atol, const double *opts, float *out,
+                              ndcn_alloc_fn alloc, void *alloc_ctx, ndcn_tape **tape, void *stream, int64_t record_budget_bytes,
+                              const ndcn_dropout *desc) {
     NDCN_CHECK_ARG(A && y0 && ticks && n_t >= 1 && out && alloc && tape && opts && H > 0, "bad argument");
     const bool no_graph = flags & NDCN_F_NO_GRAPH, no_control = flags & NDCN_F_NO_CONTROL;
     NDCN_CHECK_ARG(no_graph || (At && A->n_rows == A->n_cols), "a square operator and its transpose are required");
@@ -497,6 +547,13 @@ int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, const flo
     t->dfactor = opts[3];
     t->max_steps = (int64_t)opts[4];
     t->keep_s = opts[5] != 0.0;
+    if (desc) {
+        NDCN_CHECK_ARG(flags & NDCN_F_RELU, "dropout without NDCN_F_RELU is not supported");
+        if ((rc = drop_args(desc, &t->dargs))) return rc;
+        t->drop = true;
+        t->ev_first = desc->evaluation;
+        t->keep_s = false;                         // (the dropout launches write no S: the reverse pass forms it by its SpMM)
+    }
     t->alloc = alloc;
     t->alloc_ctx = alloc_ctx;
     t->budget = record_budget_bytes;
@@ -527,8 +584,9 @@ int ndcn_tape_dopri5_budget_f32(const ndcn_csr *A, const ndcn_csr *At, const flo
     NDCN_HIP(hipMemcpyAsync(out, y0, (size_t)t->n * sizeof(float), hipMemcpyDeviceToDevice, st));
     float *f0;
     if ((rc = panel(t, &f0))) return rc;
-    if ((rc = rhs_plain(t, y0, f0, st))) return rc;
+    if ((rc = rhs_plain(t, y0, f0, st, 0))) return rc;
     t->f0 = f0;
+    t->evals = ndcn_tape_attempt_evaluation(0, t->first_given ? 0 : 1, 0);       // (what the solve consumes before its first attempt)
     t->nfe = 2;                                    // (the count the python path reports: autograd_path.py nfe = 2)
     int64_t pending_bad = 0;
     double dt;
@@ -646,6 +704,8 @@ int64_t ndcn_tape_steplog(const ndcn_tape *t, double *rows, int64_t cap) {
 
 int64_t ndcn_tape_nfe(const ndcn_tape *t) { return t ? t->nfe : NDCN_EINVAL; }
 
+int64_t ndcn_tape_evaluations(const ndcn_tape *t) { return t ? t->evals : NDCN_EINVAL; }
+
 void ndcn_tape_destroy(ndcn_tape *t) { delete t; }
 
 int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float *g_W, float *g_b, void *stream) {
@@ -710,7 +770,7 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
             StagePanels P = t->ring;
             const float *S_used[8];
             bool fused_err;
-            rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, S_used, &fused_err, t->d_red_rerun, true, st);
+            rc = attempt_launches(t, a.y0, a.k[0], a.dts, P, S_used, &fused_err, t->d_red_rerun, true, a.ev0, st);
             if (rc) return rc;
         }
         int slot = 0;

@@ -421,6 +421,23 @@ class HipOps:
         return K
 
     @staticmethod
+    def dropout_combine(K, dropout, kprev, cs, y0=None, out=None):
+        """K *= mask in place and, in the same pass, out = y0 + sum_j cs[j] kprev[j] + cs[-1] K (ndcn_dropout_combine_f32): the bits of
+        dropout_apply(K, dropout) followed by combine(y0, kprev + [K], cs).  y0 None: the sum alone.  Contiguous float32 device
+        tensors or views (misaligned ones take the scalar lanes); out must not overlap K.  Returns (K, out)."""
+        require_device(K, 'panel')
+        assert K.is_contiguous() and len(cs) == len(kprev) + 1 and all(k.is_contiguous() and k.numel() == K.numel() for k in kprev)
+        if out is None:
+            out = torch.empty_like(K)
+        n = len(kprev)
+        arr_k = (_P * max(n, 1))(*[k.data_ptr() for k in kprev])
+        arr_c = (_F * (n + 1))(*[float(c) for c in cs])
+        with torch.cuda.device(K.device):
+            check(_lib.load().ndcn_dropout_combine_f32(ptr(K), K.numel(), _lib.dropout_desc(dropout), ptr(out), ptr(y0), arr_k, arr_c, n,
+                                                       stream_ptr()))
+        return K, out
+
+    @staticmethod
     def rhs_rk(A, X, W, b, mode, y0, kprev, cs, rtol=0.0, atol=0.0, no_graph=False, no_control=False, X_halo=None,
                out_K=None, out_y=None, y1=None, accum=False, fetch=True, aux_cs=None, out_aux=None, record=None, relu=True,
                x_mask=None, s_out=None, dropout=None):

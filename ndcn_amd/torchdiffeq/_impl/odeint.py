@@ -162,13 +162,11 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
             return sol, False
     if needs_grad:
         from .autograd_path import odeint_with_grad
-        plain = method == 'dopri5' and _device_resident_ok(user_func, tensor_input, y0, t_user, method, options) and \
-            _small_operator(user_func, y0[0]) is not None
-        if plain:
+        plain, taped = _dopri5_tape_route(user_func, tensor_input, y0, t_user, method, options)
+        if taped:
             # one autograd node per solve: the native tape (csrc/tape.hip) runs the launches below and their reverse pass itself
             from . import tape
-            if tape.applicable(user_func, y0[0], t_user):
-                return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
+            return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
                                step_log=step_log, odefunc=user_func if plain else None, plan=plan)
     elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_truth=True):
@@ -691,8 +689,23 @@ def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
 # device-resident path
 # ---------------------------------------------------------------------------------------------------
 
+def _dopri5_tape_route(user_func, tensor_input, y0, t_user, method, options):
+    """(plain, taped) of a solve that needs a gradient.  plain: dopri5 over a plain ODEFunc whose evaluations are deterministic - the
+    per-operation graph may fuse its stage algebra into them; taped: the solve runs on the native tape (csrc/tape.hip) - a plain one
+    where the tape applies, and with NDCN_TAPE_DROPOUT=1 also one with an ACTIVE dropout (training mode, 0 < p < 1: the tape's launches
+    carry the mask, ndcn_tape_dopri5_drop_f32; the fused per-operation nodes do not, so `plain` stays False there)."""
+    if method != 'dopri5':
+        return False, False
+    from . import tape
+    plain = _device_resident_ok(user_func, tensor_input, y0, t_user, method, options) and _small_operator(user_func, y0[0]) is not None
+    ok = plain or (tape.dropout_enabled() and _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_dropout=True)
+                   and _small_operator(user_func, y0[0]) is not None)
+    return plain, bool(ok and tape.applicable(user_func, y0[0], t_user))
+
+
 def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_dropout=False, allow_truth=False):
-    """allow_dropout: the caller (the fixed-grid training path) takes an ACTIVE dropout, 0 < p < 1 in training mode, too.
+    """allow_dropout: the caller (the fixed-grid training path; the dopri5 tape under NDCN_TAPE_DROPOUT=1) takes an ACTIVE dropout,
+    0 < p < 1 in training mode, too.
     allow_truth: the caller (the solve without a gradient) takes the ground-truth dynamics of ndcn_amd.truth, too - exactly those
     classes, on a float32 (N, 1) state that lives with the operator."""
     from ...neural_dynamics import ODEFunc

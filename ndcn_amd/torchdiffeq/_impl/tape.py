@@ -10,7 +10,11 @@ NDCN_GRAD_TAPE=0).
 The forward record grows with the number of attempted steps (12 to 18 panels each).  NDCN_TAPE_BUDGET_MB bounds it: attempts past
 the budget keep two panels each and the reverse pass re-forms the rest by the forward pass's launches (`ndcn_tape_dopri5_budget_f32`:
 the same gradients bit for bit, six more evaluations per such attempt); unset, a solve whose record does not fit the device runs once
-more with budget 0.  `last_record` says what the last solve kept."""
+more with budget 0.  `last_record` says what the last solve kept.
+
+An active dropout (training mode, 0 < p < 1) takes the tape under NDCN_TAPE_DROPOUT=1 (`ndcn_tape_dopri5_drop_f32`): the solve's
+stream (ndcn_amd/dropout.py) gives the seed and the number of the first evaluation, the library numbers the evaluations as the
+per-operation path makes them - the same masks, trajectory and step log bit for bit - and reports how many it consumed."""
 import ctypes
 import warnings
 
@@ -19,6 +23,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ... import _lib
+from ... import dropout as _dropout
 from ..._lib import check, ptr, stream_ptr
 
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64)
@@ -31,6 +36,11 @@ _retry_warned = False
 
 def enabled():
     return _lib.env_on('NDCN_GRAD_TAPE') and _lib.env_str('NDCN_VJP', 'hip') != 'torch'
+
+
+def dropout_enabled():
+    """NDCN_TAPE_DROPOUT=1: a solve with an active dropout takes the tape too (default: the per-operation graph)"""
+    return _lib.env_str('NDCN_TAPE_DROPOUT', '0') == '1'
 
 
 class Tape:
@@ -70,7 +80,8 @@ class Tape:
 
 class _TapeDopri5(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y0, W, b, op, ticks, rtol, atol, opts, step_log, budget):
+    def forward(ctx, y0, W, b, op, ticks, rtol, atol, opts, step_log, budget, drop=None):
+        """drop: None or (p, seed, number of the solve's first evaluation, the dropout stream to advance by what the solve consumed)"""
         csr, csr_t, flags, H = op
         lib = _lib.load()
         y0c = y0.detach().contiguous()
@@ -82,13 +93,14 @@ class _TapeDopri5(torch.autograd.Function):
         op_arr = (ctypes.c_double * 6)(*opts)
         view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(y0c.shape[0]))
         view_t = csr_t.view_ref() if csr_t is not None else None
+        desc = _lib.dropout_desc(None if drop is None else drop[:3])       # (a retry runs with the SAME seed and first number)
         retried = False
         while True:
             tape = Tape(y0c.device)
             with torch.cuda.device(y0c.device):
-                rc = lib.ndcn_tape_dopri5_budget_f32(view, view_t, ptr(Wc), ptr(bc), H, flags, ptr(y0c), tk, n_t, float(rtol), float(atol),
-                                                     op_arr, ptr(out), ctypes.cast(tape.cb, ctypes.c_void_p), None,
-                                                     ctypes.byref(tape.handle), stream_ptr(), budget)
+                rc = lib.ndcn_tape_dopri5_drop_f32(view, view_t, ptr(Wc), ptr(bc), H, flags, ptr(y0c), tk, n_t, float(rtol), float(atol),
+                                                   op_arr, ptr(out), ctypes.cast(tape.cb, ctypes.c_void_p), None,
+                                                   ctypes.byref(tape.handle), stream_ptr(), budget, desc)
             if rc < 0 and budget < 0 and not retried and isinstance(tape.error, torch.cuda.OutOfMemoryError):
                 # the unlimited record did not fit: its blocks go back to the allocator and the solve runs once more with every attempt
                 # thin (a failure of that run is raised as it is)
@@ -103,6 +115,8 @@ class _TapeDopri5(torch.autograd.Function):
             lib.ndcn_tape_record(tape.handle, rec)
             last_record.update(full_panels=int(rec[0]), thin_kept_panels=int(rec[1]), ring_panels=int(rec[2]), thin_attempts=int(rec[3]),
                                retried=retried)
+        if drop is not None and tape.handle:
+            drop[3].take(max(int(lib.ndcn_tape_evaluations(tape.handle)), 0))
         if step_log is not None and tape.handle:
             n = int(lib.ndcn_tape_steplog(tape.handle, None, 0))
             rows = (ctypes.c_double * (5 * max(n, 1)))()
@@ -154,7 +168,7 @@ class _TapeDopri5(torch.autograd.Function):
             del record
         needs = ctx.needs_input_grad
         return (gy if needs[0] else None, gW if (needs[1] and ctx.has[0]) else None, gb if (needs[2] and ctx.has[1]) else None,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 def _warn_retry():
@@ -202,7 +216,11 @@ def solve(odefunc, y0, t, rtol, atol, options, step_log):
             1.0 if keep_s else 0.0)
     budget_mb = _lib.env_int('NDCN_TAPE_BUDGET_MB', -1)
     budget = budget_mb * (1 << 20) if budget_mb >= 0 else -1         # bytes of forward record kept in full; < 0: no bound
-    return _TapeDopri5.apply(y0, W, b, (csr, csr_t, flags, odefunc.hidden_size), ticks, rt, at, opts, step_log, budget)
+    drop = None
+    if _dropout.is_active(odefunc):
+        stream = _dropout.current() or _dropout.Stream()
+        drop = (float(odefunc.dropout), stream.seed, stream.evaluations, stream)
+    return _TapeDopri5.apply(y0, W, b, (csr, csr_t, flags, odefunc.hidden_size), ticks, rt, at, opts, step_log, budget, drop)
 
 
 # ---- fixed grids ---------------------------------------------------------------------------------------------------------------
