@@ -21,6 +21,7 @@ import torch
 
 from _fma_chain import U, chain, chain_hub, row_terms
 from _oracle_ops import OracleOps
+from _rk_epilogue import error_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -612,19 +613,8 @@ def test_no_control_epilogues(dev, route, halo):
     def err_ref(npv, y1, rows=slice(None)):
         """the fp32 z * z terms (z = the stage sum / (atol + rtol max_nan(|y0|, |y1|))) and the count of non-finite y1"""
         kk = [_np(k)[rows].numpy() for k in ks[:npv]] + [Kc[rows].numpy()]
-        c = cs[:npv] + [cs[5]]
-        s = kk[-1] * c[-1]
-        if npv:
-            u = kk[0] * c[0]
-            for j in range(1, npv):
-                u = (u + kk[j] * c[j]).astype(np.float32)
-            s = (u + s).astype(np.float32)
-        a0, a1 = np.abs(_np(y0)[rows].numpy()), np.abs(_np(y1)[rows].numpy())
-        tol = (atol + rtol * np.where((a0 > a1) | np.isnan(a0), a0, a1)).astype(np.float32)
-        with np.errstate(invalid='ignore', divide='ignore'):
-            z = (s / tol).astype(np.float32)
-            zz = (z * z).astype(np.float32).astype(np.float64)
-        return zz, float((~np.isfinite(a1)).sum())
+        zz, bad = error_terms(_np(y0)[rows].numpy(), _np(y1)[rows].numpy(), kk, cs[:npv] + [cs[5]], rtol, atol)
+        return zz, float(bad)
 
     for npv in range(6):
         Ke, (s1, b1) = hip.rhs_rk(A, Xo, None, None, 'error', y0, ks[:npv], cs[:npv] + [cs[5]], rtol=rtol, atol=atol,
