@@ -781,6 +781,9 @@ NDCN_API int ndcn_prof_kinds(void);
 #define NDCN_PATH_DROP_EPI 1024 /* ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the dropout factor was applied inside the launch (clear: by
                                  * the streaming pass ndcn_dropout_apply_f32 behind it)                                              */
 #define NDCN_PATH_DYN 2048   /* a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; ndcn_solver_desc::dyn)       */
+#define NDCN_PATH_MID 4096   /* 16 <= H <= 128, H % 4 == 0, any number of rows: gather, fp32 MFMA Linear, ReLU and the COMBINE / RK4
+                              * epilogue in one launch (rhs_mid.hip; ndcn_set_rhs_mid below).  An NDCN_RK_ERROR launch reports it for
+                              * its K, the record is rk_error_f32's                                                                */
 NDCN_API int ndcn_debug_last_rhs_path(void);
 /* Which kernels the LAST ndcn_linear_f32 / ndcn_linear_bwd_f32 call of this thread launched (tests: every dispatch route of the dense
  * Linear is reached on purpose, not merely some correct one); each call replaces the set, 0 for n = 0 and before the first call.
@@ -872,6 +875,24 @@ NDCN_API int ndcn_debug_last_spmm_path(void);
  * split fp16 product whatever its range, and packing does not read back.  Images packed while the guard was off are judged when
  * they are packed next.                                                                                                            */
 NDCN_API int ndcn_set_range_guard(int on);
+/* The one-launch right-hand side for hidden widths 16..128 at any size (NDCN_PATH_MID above, csrc/rhs_mid.hip; the two calls are additions to ABI 29:
+ * no existing declaration changes, and tests/test_gpu_tape_dropout.py and tests/test_gpu_dropout_combine.py pin that number).   Without it
+ * those widths run composed once n_rows * H exceeds 2^18: row SpMM into a scratch panel, MFMA Linear, stand-alone stage kernel.  Every
+ * panel it writes - K, y_next, y_aux - equals the composed path's bit for bit, so the switch is invisible in the results.
+ * ndcn_set_rhs_mid switches it PROCESS-WIDE at run time and returns the previous mode; mode < 0 returns to the environment's
+ * (NDCN_RHS_MID, default 0):
+ *   0  off
+ *   1  on wherever the narrow-panel kernel (NDCN_PATH_SMALL) does not take the shape, for H <= 96 (wider, the launch holds one
+ *      workgroup per compute unit and measured slower than the composed kernels: those widths stay composed)
+ *   2  on for every supported shape, ahead of that kernel (tests, measuring the crossover; the narrow-panel kernel's stage sums
+ *      start from the new stage's product, so the sign of an all-zero sum can differ from this route's there)
+ * ndcn_rhs_f32 / ndcn_rhs_rk_f32 (plain, NDCN_RK_COMBINE with or without y_aux, NDCN_RK_RK4; NDCN_RK_ERROR as the plain launch plus the
+ * stand-alone error kernel) take the route; it declines - the launch runs as without it - a halo panel, dropout, NDCN_F_NO_GRAPH /
+ * NDCN_F_NO_CONTROL, x_add / x_mask / s_out and panels that are not 16-byte aligned.  ndcn_rhs_work_bytes does not depend on the mode.
+ * ndcn_rhs_mid_supported: the shape part of that decision for `mode` - H a multiple of 4 in 16..128, n_rows >= 1, neither NO_ flag,
+ * and in mode 1 H <= 96 and n_rows * H beyond the narrow-panel kernel's bound; a host predicate, no device needed.                          */
+NDCN_API int ndcn_set_rhs_mid(int mode);
+NDCN_API int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);
 
 /* ---- training through the adaptive solver: the solve that keeps its tape, and its reverse pass ---------------------------------
  * Replaces, for a plain ODEFunc on one state tensor, what the reference's drivers do by autograd through odeint

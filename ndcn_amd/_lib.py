@@ -15,6 +15,7 @@ ABI_VERSION = 29
 PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, PATH_SMALL, PATH_EXACT32, PATH_RANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
+PATH_MID = 4096           # 16 <= H <= 128 at any size: the whole right-hand side + COMBINE / RK4 epilogue in one launch (csrc/rhs_mid.hip)
 DYN_HEAT, DYN_GENE, DYN_MUTUAL = 0, 1, 2
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
@@ -285,6 +286,8 @@ SIGNATURES = {
     'ndcn_debug_last_spmm_path': (_I, []),
     'ndcn_debug_last_rk_path': (_L, []),
     'ndcn_set_range_guard': (_I, [_I]),
+    'ndcn_set_rhs_mid': (_I, [_I]),
+    'ndcn_rhs_mid_supported': (_I, [_L, _I, _U, _I]),
 }
 
 _lib = None

@@ -48,6 +48,8 @@ int64_t ndcn_debug_last_rk_path(void) { return g_last_rk_path; }
 int ndcn_last_readout_path(void) { return g_last_readout_path; }
 void ndcn_clear_readout_path(void) { g_last_readout_path = 0; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
+int ndcn_set_rhs_mid(int mode) { return set_rhs_mid(mode); }
+int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_supported(n_rows, H, flags, mode); }
 const char *ndcn_last_error(void) { return g_err; }
 
 int64_t ndcn_adjoint_rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) { return adjoint_rhs_work_bytes(n_rows, H, flags); }

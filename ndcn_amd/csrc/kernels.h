@@ -103,6 +103,15 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
                   int H, uint32_t flags, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,
                   float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st, const float *c_dev = nullptr,
                   const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);     // drop: the factor of csrc/dropout.h in the epilogue
+// rhs_mid.hip: the whole ODEFunc in one launch for 16 <= H <= 128 (H % 4 == 0) at any number of rows - mode 0 (plain), NDCN_RK_COMBINE
+// (with RkOpt::y_aux / c_aux) or NDCN_RK_RK4; every panel 16-byte aligned, no halo panel; the bits of the composed path.  The switch
+// (ndcn_set_rhs_mid / NDCN_RHS_MID): 0 off, 1 wherever rhs_small.hip does not take the shape, 2 every supported shape
+int rhs_mid_mode();
+int set_rhs_mid(int mode);                    // ndcn_set_rhs_mid: returns the previous mode; < 0: back to the environment's
+int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // from the sizes alone, no device
+int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
+                const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
+                const RkOpt *opt = nullptr);
 // dropout (csrc/dropout.h; rhs.hip): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1), the streaming pass K *= m, and
 // rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch, by the streaming pass behind every other route
 int drop_args(const ndcn_dropout *desc, DropArgs *out);

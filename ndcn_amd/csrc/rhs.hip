@@ -43,8 +43,15 @@ int64_t rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) {
     return n_rows * (int64_t)H * (int64_t)sizeof(float);                        // S = A X between the two kernels
 }
 
-int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-            float *work, int H, uint32_t flags, hipStream_t st) {
+// rhs_mid.hip takes the launch: the switch is on for this shape, no halo panel, 16-byte aligned panels
+static bool mid_takes(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags) {
+    const int mode = rhs_mid_mode();
+    return mode != 0 && !Xh && rhs_mid_supported(A->n_rows, H, flags, mode) && aligned16(X) && aligned16(W) && aligned16(K);
+}
+
+// allow_mid = false: the callers whose launch rhs_mid.hip declines (dropout; RkOpt fields of the H = 256 launches)
+static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
+                     float *work, int H, uint32_t flags, hipStream_t st, bool allow_mid) {
     const bool graph = !(flags & NDCN_F_NO_GRAPH), ctl = !(flags & NDCN_F_NO_CONTROL);
     const uint32_t act = flags & NDCN_F_RELU;
     const int64_t n = A->n_rows;
@@ -67,6 +74,11 @@ int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, c
                                       0.f, nullptr, nullptr, st);
             }
             return rhs_fused_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, st);
+        }
+        g_last_rhs_path &= ~NDCN_PATH_MID;
+        if (allow_mid && mid_takes(A, X, Xh, W, Y, H, flags)) {   // 16 <= H <= 128 at any size: gather, MFMA Linear, ReLU in one launch
+            g_last_rhs_path = NDCN_PATH_MID;
+            return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st);
         }
         if (rhs_small_supported(A, H, flags))                     // narrow panels: SpMM -> Linear -> ReLU in one launch
             return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr,
@@ -93,6 +105,11 @@ int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, c
     hipLaunchKernelGGL(relu_copy_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, st, X, Y, total, act ? 1 : 0);
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;
+}
+
+int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
+            float *work, int H, uint32_t flags, hipStream_t st) {
+    return rhs_plain(A, X, Xh, n_own, W, b, Y, work, H, flags, st, true);
 }
 
 // the stage algebra over {kprev..., K} by the un-fused kernels, in the term order of the fused epilogues (K is the last term)
@@ -144,7 +161,19 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
         return rhs_fused2_exact_f32(A, X, Xh, n_own, work, b, K, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws,
                                     st, opt);
     }
-    else if (both && rhs_small_supported(A, H, flags)) {
+    // rhs_mid.hip: COMBINE and RK4 in its epilogue; an ERROR launch is its plain launch (rhs_plain below) and rk_error_f32, which keeps
+    // the record's summation.  It declines the RkOpt fields that exist only inside the H = 256 launches and misaligned panels.
+    const bool mid_opt = !(opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid || opt->no_k));
+    bool mid = both && mid_opt && mid_takes(A, X, Xh, W, K, H, flags);
+    if (mid && rk_mode != 2) {
+        mid = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
+        for (int m = 0; m < n_prev; ++m) mid = mid && h_kprev && aligned16(h_kprev[m]);
+        if (mid) {
+            g_last_rhs_path = NDCN_PATH_MID;
+            return rhs_mid_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt);
+        }
+    }
+    if (!mid && both && rhs_small_supported(A, H, flags)) {
         g_last_rhs_path = NDCN_PATH_SMALL;
         return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws,
                              st, nullptr, opt);
@@ -165,7 +194,7 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
     }
     g_last_rhs_path = 0;
     // composition with the same term order: K first, then the algebra over {kprev..., K}
-    int rc = rhs_f32(A, X, Xh, n_own, W, b, K, work, H, flags, st);
+    int rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st, mid_opt);
     if (rc) return rc;
     return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
 }
@@ -191,7 +220,7 @@ int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_o
                              nullptr, nullptr, &d);
     }
     g_last_rhs_path = 0;
-    if ((rc = rhs_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, st))) return rc;
+    if ((rc = rhs_plain(A, X, Xh, n_own, W, b, Y, work, H, flags, st, false))) return rc;
     return dropout_apply_f32(Y, A->n_rows * (int64_t)H, d, st);
 }
 
@@ -212,7 +241,7 @@ int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t 
     if (rk_mode == 1 && !(opt && opt->y_aux)) {
         // the stage sum consumes the masked K in the pass that forms it (dropout.hip): one launch and one panel read fewer
         g_last_rhs_path = 0;
-        if ((rc = rhs_f32(A, X, Xh, n_own, W, b, K, work, H, flags, st))) return rc;
+        if ((rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st, false))) return rc;
         return dropout_combine_f32(K, A->n_rows * (int64_t)H, d, y_next, y0, h_kprev, h_c, n_prev, st);
     }
     if ((rc = rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st))) return rc;

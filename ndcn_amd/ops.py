@@ -536,6 +536,13 @@ class HipOps:
         return bool(_lib.load().ndcn_rhs_adj_supported(A.view_ref(), H, flags, rk, n_prev))
 
     @staticmethod
+    def set_rhs_mid(mode):
+        """The one-launch right-hand side for hidden widths 16..128 at any size (ndcn_set_rhs_mid, csrc/rhs_mid.hip): 0 off, 1 on
+        wherever the narrow-panel kernel does not take the shape, 2 on for every supported shape; < 0: the environment's
+        (NDCN_RHS_MID).  Process-wide; returns the previous mode."""
+        return int(_lib.load().ndcn_set_rhs_mid(int(mode)))
+
+    @staticmethod
     def new_error_record(device):
         return ErrorRecord(device)
 
