@@ -893,6 +893,39 @@ NDCN_API int ndcn_set_range_guard(int on);
  * and in mode 1 H <= 96 and n_rows * H beyond the narrow-panel kernel's bound; a host predicate, no device needed.                          */
 NDCN_API int ndcn_set_rhs_mid(int mode);
 NDCN_API int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);
+/* The reverse of ONE right-hand-side evaluation K = relu(W (A X) + b) as a call (csrc/rhs_mid_bwd.hip; five calls added to ABI 29: no
+ * existing declaration changes) - what autograd executes for ODEFunc.forward (neural_dynamics.py:27-36) under the drivers' training
+ * step, and what the two native tapes run per evaluation:
+ *   gZ = g (.) [K > 0]   (NDCN_F_RELU in flags and premasked = 0; otherwise gZ = g: the caller masked it already, or there is no ReLU)
+ *   gX = acc_scale * A^T (gZ W)                    gX nullable: not wanted
+ *   gW = acc_scale * gZ^T S,  gb = acc_scale * colsum gZ,  S = A X;  accumulate != 0: added to what gW / gb hold (product and sum
+ *        rounded separately).  gb nullable.  With dropout K is the stored K' and acc_scale the kept elements' factor s (ndcn_dropout).
+ *   S    nullable: A X as the forward launch wrote it; it is re-formed (gathered) when absent
+ *   work ndcn_rhs_vjp_work_bytes(n_rows, H, flags) bytes, 256-byte aligned: [S panel | gS panel | ndcn_linear_bwd_f32's scratch], each part
+ *        rounded up to 256 bytes; after a call with gX the n_rows x H panel gS = gZ W stands at byte offset
+ *        ndcn_rhs_vjp_work_bytes(n_rows, H, NDCN_F_NO_CONTROL) / 2 (tests read it there)
+ * A square, A_t its transpose (both ignored under NDCN_F_NO_GRAPH except A->n_rows); no halo panel.  Composed, the call is five launches:
+ * SpMM, ndcn_linear_bwd_f32's three, transposed SpMM.  For 16 <= H <= 128 (H a multiple of 4) at any number of rows ONE launch can form
+ * gS and the row-chunk partials of gW / gb - S never leaves the compute unit, gZ is formed once: three launches - with the raw 32-bit
+ * words of the composed launches in gS, gX, gW and gb, signs of zero and NaN positions included.  ndcn_set_rhs_mid_bwd switches that route
+ * PROCESS-WIDE at run time and returns the previous mode; mode < 0 returns to the environment's (NDCN_RHS_MID_BWD, default 0):
+ *   0  off
+ *   1  on for the widths at which it measured not slower than the composed launches
+ *   2  on for every supported shape
+ * The native tapes (ndcn_tape_backward_f32, ndcn_fixed_backward_f32 and their variants) follow the same switch.  The route declines - the
+ * call runs composed - NDCN_F_NO_GRAPH / NDCN_F_NO_CONTROL, other widths (H = 256 included) and panels that are not 16-byte aligned.
+ * ndcn_rhs_mid_bwd_supported: the shape part of that decision for `mode` (mode < 0: the switch's current mode); a host predicate, no
+ * device needed.  ndcn_debug_last_rhs_vjp_path: the route of the LAST reverse evaluation of this PROCESS (a reverse pass runs on
+ * autograd's thread), whoever ran it; 0 before the first.                                                                          */
+#define NDCN_VJP_COMPOSED 1   /* SpMM (unless S was given), ndcn_linear_bwd_f32's launches, transposed SpMM                           */
+#define NDCN_VJP_MID      2   /* gS and the partials of gW / gb in one launch (rhs_mid_bwd.hip), chunk sum, transposed SpMM           */
+NDCN_API int ndcn_rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *A_t, const float *X, const float *K, const float *g, const float *W,
+                              const float *S, float *gX, float *gW, float *gb, void *work, int H, uint32_t flags, int premasked,
+                              float acc_scale, int accumulate, void *stream);
+NDCN_API int64_t ndcn_rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
+NDCN_API int ndcn_set_rhs_mid_bwd(int mode);
+NDCN_API int ndcn_rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode);
+NDCN_API int ndcn_debug_last_rhs_vjp_path(void);
 
 /* ---- training through the adaptive solver: the solve that keeps its tape, and its reverse pass ---------------------------------
  * Replaces, for a plain ODEFunc on one state tensor, what the reference's drivers do by autograd through odeint

@@ -16,6 +16,8 @@ PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, 
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
 PATH_MID = 4096           # 16 <= H <= 128 at any size: the whole right-hand side + COMBINE / RK4 epilogue in one launch (csrc/rhs_mid.hip)
+# ndcn_debug_last_rhs_vjp_path: the route of the process's last reverse evaluation (include/ndcn_hip.h NDCN_VJP_*)
+VJP_COMPOSED, VJP_MID = 1, 2
 DYN_HEAT, DYN_GENE, DYN_MUTUAL = 0, 1, 2
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
@@ -288,6 +290,11 @@ SIGNATURES = {
     'ndcn_set_range_guard': (_I, [_I]),
     'ndcn_set_rhs_mid': (_I, [_I]),
     'ndcn_rhs_mid_supported': (_I, [_L, _I, _U, _I]),
+    'ndcn_rhs_vjp_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U, _I, _F, _I, _P]),
+    'ndcn_rhs_vjp_work_bytes': (_L, [_L, _I, _U]),
+    'ndcn_set_rhs_mid_bwd': (_I, [_I]),
+    'ndcn_rhs_mid_bwd_supported': (_I, [_L, _I, _U, _I]),
+    'ndcn_debug_last_rhs_vjp_path': (_I, []),
 }
 
 _lib = None

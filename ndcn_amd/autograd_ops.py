@@ -13,6 +13,7 @@ solvers, whose step sizes are data-independent.
 import numpy as np
 import torch
 
+from . import _lib
 from . import dropout as _dropout
 from .csr import as_csr
 from .ops import hip
@@ -73,6 +74,10 @@ def rhs_vjp(A, no_graph, no_control, X, W, Y, g, need_x, need_w, need_b, S=None,
     scale: Y is the dropout-masked K' = relu(z) * m with m in {0, s}, scale = s.  [K' > 0] = [z > 0 and kept], so the gradient is
     gZ = s * g * [K' > 0]: the same kernels masked by the stored K', and the scalar folded into the alpha of the transposed SpMM
     and into the two small parameter gradients - no mask is re-created, no panel pass is added while the graph is on."""
+    if (need_w and not no_graph and not no_control and
+            _lib.load().ndcn_rhs_mid_bwd_supported(X.shape[0], X.shape[1], _lib.F_RELU, -1)):
+        # the switch is on for this shape (csrc/rhs_mid_bwd.hip): the whole reverse as one call, the same bits in three launches
+        return hip.rhs_vjp(A, X.detach(), W, Y, g, S=S, need_x=need_x, need_b=need_b, acc_scale=scale)
     gW = gb = None
     if not no_control:
         if not need_w:

@@ -50,6 +50,35 @@ void ndcn_clear_readout_path(void) { g_last_readout_path = 0; }
 int ndcn_set_range_guard(int on) { return set_range_guard(on); }
 int ndcn_set_rhs_mid(int mode) { return set_rhs_mid(mode); }
 int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_supported(n_rows, H, flags, mode); }
+int ndcn_set_rhs_mid_bwd(int mode) { return set_rhs_mid_bwd(mode); }
+int ndcn_rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_bwd_supported(n_rows, H, flags, mode); }
+int ndcn_debug_last_rhs_vjp_path(void) { return last_rhs_vjp_path(); }
+int64_t ndcn_rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags) { return rhs_vjp_work_bytes(n_rows, H, flags); }
+
+int ndcn_rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *A_t, const float *X, const float *K, const float *g, const float *W, const float *S,
+                     float *gX, float *gW, float *gb, void *work, int H, uint32_t flags, int premasked, float acc_scale, int accumulate,
+                     void *stream) {
+    NDCN_CHECK_ARG(A && H > 0, "null operator descriptor (n_rows is read from it even under NO_GRAPH)");
+    const bool graph = !(flags & NDCN_F_NO_GRAPH), ctl = !(flags & NDCN_F_NO_CONTROL);
+    if (graph) {
+        int rc = check_csr(A, __func__);
+        if (rc) return rc;
+        if ((rc = check_csr(A_t, __func__))) return rc;
+        NDCN_CHECK_ARG(A->n_rows == A->n_cols && A_t->n_rows == A->n_cols && A_t->n_cols == A->n_rows && A_t->nnz == A->nnz,
+                       "a square operator and its transpose are required");
+    }
+    if (A->n_rows == 0 && accumulate) return NDCN_OK;
+    NDCN_CHECK_ARG(A->n_rows == 0 || (X && g && work), "null panel / scratch");
+    NDCN_CHECK_ARG(!((flags & NDCN_F_RELU) && !premasked) || K || A->n_rows == 0, "the ReLU mask needs K");
+    NDCN_CHECK_ARG(!ctl || (W && gW), "weight / g_W missing");
+    NDCN_CHECK_ARG(gX != g && gX != X, "gX must not alias g or X");
+    NDCN_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 255) == 0, "the scratch must be 256-byte aligned");
+    char *w = static_cast<char *>(work);
+    const int64_t off = rhs_vjp_gs_offset(A->n_rows, H);
+    return rhs_vjp_f32(A, A_t, X, K, g, W, S, gX, ctl ? gW : nullptr, ctl ? gb : nullptr, reinterpret_cast<float *>(w),
+                       reinterpret_cast<float *>(w + off), ctl ? w + 2 * off : nullptr, H, flags, premasked != 0, acc_scale, acc_scale,
+                       accumulate != 0, true, nullptr, ST(stream));
+}
 const char *ndcn_last_error(void) { return g_err; }
 
 int64_t ndcn_adjoint_rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) { return adjoint_rhs_work_bytes(n_rows, H, flags); }

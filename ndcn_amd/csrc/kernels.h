@@ -112,6 +112,23 @@ int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // 
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
                 const RkOpt *opt = nullptr);
+// linear_bwd.hip: the row chunks linear_bwd_f32 cuts the weight gradient into (`used` chunks of rpc rows) and the fixed-order sum of
+// their partial blocks into gW / gb (one of them nullable)
+void wgrad_chunking(int64_t n, int Hi, int Ho, int64_t *rpc, int64_t *used);
+int wgrad_chunk_sum(const float *part_w, const float *part_b, float *gW, float *gb, int Hi, int Ho, int64_t used, float acc_scale,
+                    bool accumulate, hipStream_t st);
+// rhs_mid_bwd.hip: the reverse of one evaluation (autograd_ops.rhs_vjp) - the one implementation behind ndcn_rhs_vjp_f32 and the two
+// native tapes - and its one-launch gS / gW / gb kernel for 16 <= H <= 128 (H % 4 == 0) at any number of rows: the bits of the composed
+// launches.  The switch (ndcn_set_rhs_mid_bwd / NDCN_RHS_MID_BWD): 0 off, 1 the widths that measured not slower, 2 every supported shape
+int rhs_mid_bwd_mode();
+int set_rhs_mid_bwd(int mode);                // returns the previous mode; < 0: back to the environment's
+int rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // from the sizes alone; mode < 0: the current mode
+int last_rhs_vjp_path();                      // ndcn_debug_last_rhs_vjp_path
+int rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *At, const float *X, const float *K, const float *g, const float *W,
+                const float *S_kept, float *gx, float *gW, float *gb, float *tmpS, float *tmpG, void *bwork, int H, uint32_t flags,
+                bool premasked, float acc_scale, float alpha, bool accumulate, bool direct, bool *packed, hipStream_t st);
+int64_t rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
+int64_t rhs_vjp_gs_offset(int64_t n_rows, int H);
 // dropout (csrc/dropout.h; rhs.hip): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1), the streaming pass K *= m, and
 // rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch, by the streaming pass behind every other route
 int drop_args(const ndcn_dropout *desc, DropArgs *out);

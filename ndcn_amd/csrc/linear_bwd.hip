@@ -651,6 +651,29 @@ static int64_t wgrad_work_bytes(int64_t n, int Hi, int Ho) {
 }
 
 // partial gW / gb blocks, then (Hi = Ho = 256) the packed fp16 planes of W^T for the gS product
+// the row chunks linear_bwd_f32 cuts n rows into: `used` chunks of rpc rows (whole rounds of 8), the last one shorter
+void wgrad_chunking(int64_t n, int Hi, int Ho, int64_t *rpc_out, int64_t *used_out) {
+    const int64_t chunks = wgrad_chunks(n, Hi < 16 || Ho < 16);
+    const int64_t rpc0 = (n + chunks - 1) / chunks;
+    const int64_t rpc = (rpc0 + 7) / 8 * 8;                    // whole rounds of 8 rows
+    *rpc_out = rpc;
+    *used_out = (n + rpc - 1) / rpc;
+}
+
+// gW / gb (one of them nullable) from the `used` partial blocks, in chunk order; acc_scale / accumulate as linear_bwd_f32
+int wgrad_chunk_sum(const float *part_w, const float *part_b, float *gW, float *gb, int Hi, int Ho, int64_t used, float acc_scale,
+                    bool accumulate, hipStream_t st) {
+    if (gW && gb)
+        hipLaunchKernelGGL(chunk_sum2_kernel, dim3((unsigned)((Ho * Hi + Ho + 255) / 256)), dim3(256), 0, st, part_w, gW, Ho * Hi, part_b, gb,
+                           Ho, (int)used, acc_scale, accumulate ? 1 : 0);
+    else if (gW) hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((Ho * Hi + 255) / 256)), dim3(256), 0, st, part_w, gW, Ho * Hi, (int)used,
+                                    acc_scale, accumulate ? 1 : 0);
+    else hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((Ho + 255) / 256)), dim3(256), 0, st, part_b, gb, Ho, (int)used, acc_scale,
+                            accumulate ? 1 : 0);
+    NDCN_LAUNCH_CHECK();
+    return NDCN_OK;
+}
+
 int64_t linear_bwd_work_bytes(int64_t n, int Hi, int Ho) {
     return wgrad_work_bytes(n, Hi, Ho) + ((Hi == 256 && Ho == 256) ? (int64_t)kS16Bytes + kS16TailBytes + kS16GuardBytes : 0);
 }
@@ -709,10 +732,8 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
     }
     if (gW || gb) {
         if (!work || !S) { set_error("linear_bwd: scratch of ndcn_linear_bwd_work_bytes() bytes and the forward input are required for gW / gb"); return NDCN_EINVAL; }
-        const int64_t chunks = wgrad_chunks(n, small);
-        const int64_t rpc0 = (n + chunks - 1) / chunks;
-        const int64_t rpc = (rpc0 + 7) / 8 * 8;                    // whole rounds of 8 rows
-        const int64_t used = (n + rpc - 1) / rpc;
+        int64_t rpc, used;
+        wgrad_chunking(n, Hi, Ho, &rpc, &used);
         float *part_w = static_cast<float *>(work);
         float *part_b = part_w + (size_t)used * Ho * Hi;
         ProfScope prof(PROF_LINEAR_WGRAD, st, 4.0 * n * (double)(Hi + Ho * (Y ? 2 : 1)) + 4.0 * (used + 1) * (double)Hi * Ho, 2.0 * n * (double)Hi * Ho);
@@ -745,14 +766,7 @@ int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *
         }
         NDCN_LAUNCH_CHECK();
         if (gW && gb) g_last_linear_path |= NDCN_LIN_GW_SUM2;
-        if (gW && gb)
-            hipLaunchKernelGGL(chunk_sum2_kernel, dim3((unsigned)((Ho * Hi + Ho + 255) / 256)), dim3(256), 0, st, part_w, gW, Ho * Hi, part_b, gb,
-                               Ho, (int)used, acc_scale, accumulate ? 1 : 0);
-        else if (gW) hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((Ho * Hi + 255) / 256)), dim3(256), 0, st, part_w, gW, Ho * Hi, (int)used,
-                                        acc_scale, accumulate ? 1 : 0);
-        else hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((Ho + 255) / 256)), dim3(256), 0, st, part_b, gb, Ho, (int)used, acc_scale,
-                                accumulate ? 1 : 0);
-        NDCN_LAUNCH_CHECK();
+        return wgrad_chunk_sum(part_w, part_b, gW, gb, Hi, Ho, used, acc_scale, accumulate, st);
     }
     return NDCN_OK;
 }

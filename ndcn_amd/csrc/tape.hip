@@ -410,50 +410,12 @@ int add_into(float *acc, const float *x, int64_t n, hipStream_t st) {
 // accumulation scale of g_W / g_b, the alpha of the transposed SpMM, and without a graph one scaling pass (autograd_ops.rhs_vjp)
 int rhs_vjp(Bwd &B, const float *X, const float *K, const float *g, float *gx, const float *S_kept = nullptr, bool premasked = false) {
     ndcn_tape *t = B.t;
-    const bool no_graph = t->flags & NDCN_F_NO_GRAPH, no_control = t->flags & NDCN_F_NO_CONTROL;
-    const float *mask = ((t->flags & NDCN_F_RELU) && !premasked) ? K : nullptr;
     const float s = t->drop ? t->dargs.s : 1.f;
-    const bool rescale = no_graph && s != 1.f;     // no SpMM to carry s: g_X = s * g_S by a pass from the scratch panel
-    int rc;
-    const float *gS = nullptr;
-    if (!no_control) {
-        const float *S = X;
-        if (!no_graph && S_kept) {
-            S = S_kept;
-        } else if (!no_graph) {
-            rc = spmm_f32(&t->A, X, nullptr, t->A.n_cols, B.tmpS, t->H, 1.f, 0, B.st);
-            if (rc) return rc;
-            S = B.tmpS;
-        }
-        float *gs_out = gx ? ((no_graph && !rescale) ? gx : B.tmpG) : nullptr;
-        // g_W / g_b: this evaluation's + what the later evaluations sent (autograd_path._add_carried), in the launch that sums the chunks
-        rc = linear_bwd_f32(g, mask, S, t->W, gs_out, B.gW_acc, t->b ? B.gb_acc : nullptr, t->bwork, t->n_rows, t->H, t->H, B.st,
-                            t->bpacked ? NDCN_F_PACKED : 0u, s, B.have_w);
-        if (rc) return rc;
-        if (gs_out && t->H == 256) t->bpacked = true;
-        B.have_w = true;
-        gS = gs_out;
-    } else if (gx) {
-        float *gs_out = (no_graph && !rescale) ? gx : B.tmpG;
-        if (mask) {
-            rc = relu_bwd_f32(gs_out, g, mask, t->n, B.st);
-            if (rc) return rc;
-            gS = gs_out;
-        } else if (no_graph && !rescale) {
-            rc = copy_f32(gx, g, t->n, B.st);
-            if (rc) return rc;
-            gS = gx;
-        } else {
-            gS = g;
-        }
-    }
-    if (gx && !no_graph) {
-        rc = spmm_f32(&t->At, gS, nullptr, t->At.n_cols, gx, t->H, s, 0, B.st);
-        if (rc) return rc;
-    } else if (gx && rescale) {
-        rc = scale_f32(gx, gS, s, t->n, B.st);
-        if (rc) return rc;
-    }
+    // g_W / g_b: this evaluation's + what the later evaluations sent (autograd_path._add_carried), in the launch that sums the chunks
+    int rc = rhs_vjp_f32(&t->A, &t->At, X, K, g, t->W, S_kept, gx, B.gW_acc, t->b ? B.gb_acc : nullptr, B.tmpS, B.tmpG, t->bwork, t->H,
+                         t->flags, premasked, s, s, B.have_w, true, &t->bpacked, B.st);
+    if (rc) return rc;
+    if (!(t->flags & NDCN_F_NO_CONTROL)) B.have_w = true;
     return NDCN_OK;
 }
 
@@ -1200,30 +1162,8 @@ int fixed_backward(const ndcn_csr *A, const ndcn_csr *At, const float *W, const 
         return rc;
     // alpha J(x)^T g for K = relu(W (A x) + b) into out (_FixedGridSolve._vjp); g_W / g_b += scale * (this evaluation's)
     auto vjp = [&](const float *x, const float *Kx, const float *g, float alpha, float scale, float *out) -> int {
-        const float *mask = (flags & NDCN_F_RELU) ? Kx : nullptr;
-        const float *gS;
-        int r;
-        if (no_control) {
-            if (mask) {
-                if ((r = relu_bwd_f32(tmpG, g, mask, n, st))) return r;
-                gS = tmpG;
-            } else {
-                gS = g;
-            }
-        } else {
-            const float *S = x;
-            if (!no_graph) {
-                if ((r = spmm_f32(&t->A, x, nullptr, t->A.n_cols, tmpS, H, 1.f, 0, st))) return r;
-                S = tmpS;
-            }
-            r = linear_bwd_f32(g, mask, S, t->W, tmpG, g_W, t->b ? g_b : nullptr, t->bwork, t->n_rows, H, H, st,
-                               t->bpacked ? NDCN_F_PACKED : 0u, scale, true);                // gW_tot.add_(gW, alpha = scale)
-            if (r) return r;
-            if (H == 256) t->bpacked = true;
-            gS = tmpG;
-        }
-        if (no_graph) return scale_f32(out, gS, alpha, n, st);
-        return spmm_f32(&t->At, gS, nullptr, t->At.n_cols, out, H, alpha, 0, st);
+        return rhs_vjp_f32(&t->A, &t->At, x, Kx, g, t->W, nullptr, out, g_W, t->b ? g_b : nullptr, tmpS, tmpG, t->bwork, H, flags, false,
+                           scale, alpha, true, false, &t->bpacked, st);                       // gW_tot.add_(gW, alpha = scale)
     };
     auto lincomb = [&](float *out, const float *y0p, std::initializer_list<const float *> ks, std::initializer_list<float> cs) -> int {
         const float *kp[8];

@@ -543,6 +543,56 @@ class HipOps:
         return int(_lib.load().ndcn_set_rhs_mid(int(mode)))
 
     @staticmethod
+    def set_rhs_mid_bwd(mode):
+        """The one-launch reverse of the right-hand side for hidden widths 16..128 at any size (ndcn_set_rhs_mid_bwd,
+        csrc/rhs_mid_bwd.hip): 0 off, 1 on for the widths that measured not slower than the composed launches, 2 on for every
+        supported shape; < 0: the environment's (NDCN_RHS_MID_BWD).  Process-wide; returns the previous mode."""
+        return int(_lib.load().ndcn_set_rhs_mid_bwd(int(mode)))
+
+    @staticmethod
+    def rhs_vjp(A, X, W, K, g, S=None, need_x=True, need_b=True, relu=True, premasked=False, acc_scale=1.0, gW=None, gb=None,
+                no_graph=False, no_control=False, return_gs=False):
+        """The reverse of one evaluation K = relu(W (A X) + b) (ndcn_rhs_vjp_f32): (gX, gW, gb) for the upstream gradient g, None
+        where not requested.  S: A X as the forward wrote it (re-formed when None).  gW / gb given: the call ACCUMULATES
+        acc_scale * (this evaluation's) into them and returns them; otherwise they are new tensors.  return_gs: a fourth result, the
+        panel gS = gZ W as it stands in the call's scratch (need_x only)."""
+        X, g = _panel(X), _panel(g)
+        K = _panel(K) if K is not None else None
+        S = _panel(S) if S is not None else None
+        H = X.shape[1]
+        n = X.shape[0]
+        lib = _lib.load()
+        flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
+        if no_graph:
+            view = view_t = ctypes.byref(_lib.empty_csr(n))
+        else:
+            A = as_csr(A)
+            A.ensure_plans(H)
+            At = A.transpose()
+            At.ensure_plans(H)
+            view, view_t = A.view_ref(), At.view_ref()
+        accumulate = gW is not None
+        if no_control:
+            gW = gb = None
+        else:
+            W = _panel(W, 'weight')
+            if gW is None:
+                gW = torch.empty((H, H), dtype=torch.float32, device=X.device)
+                gb = torch.empty((H,), dtype=torch.float32, device=X.device) if need_b else None
+            elif not need_b:
+                gb = None
+        gX = torch.empty_like(X) if need_x else None
+        work = torch.empty(int(lib.ndcn_rhs_vjp_work_bytes(n, H, flags)), dtype=torch.uint8, device=X.device)
+        with torch.cuda.device(X.device):
+            check(lib.ndcn_rhs_vjp_f32(view, view_t, ptr(X), ptr(K), ptr(g), ptr(W), ptr(S), ptr(gX), ptr(gW), ptr(gb), ptr(work), H, flags,
+                                       1 if premasked else 0, float(acc_scale), 1 if accumulate else 0, stream_ptr()))
+        if not return_gs:
+            return gX, gW, gb
+        off = int(lib.ndcn_rhs_vjp_work_bytes(n, H, _lib.F_NO_CONTROL)) // 2
+        gS = work[off:off + n * H * 4].view(torch.float32).view(n, H) if need_x else None
+        return gX, gW, gb, gS
+
+    @staticmethod
     def new_error_record(device):
         return ErrorRecord(device)
 
