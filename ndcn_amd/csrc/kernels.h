@@ -74,6 +74,8 @@ int rhs_fused3_supported(const ndcn_csr *A);
 int rhs_xadd_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev);   // RkOpt::xadd can be honoured
 int rhs_adj_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev);    // RkOpt::xmask / s_out can be honoured
 int rhs_dense_supported(const ndcn_csr *A, int H, uint32_t flags);                         // RkOpt::c_mid can be honoured
+// RkOpt::s_out can be honoured by the launch rhs_rk_f32 picks: rhs_adj_supported, or the narrow-panel kernel of rhs_small.hip (rhs.hip)
+int rhs_s_out_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev);
 int rhs_fused3_variant(int mode, int n_prev);
 int rhs_fused3_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const void *Wq, const float *b, float *K,
                    uint32_t flags, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev,

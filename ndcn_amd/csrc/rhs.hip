@@ -49,6 +49,16 @@ static bool mid_takes(const ndcn_csr *A, const float *X, const float *Xh, const 
     return mode != 0 && !Xh && rhs_mid_supported(A->n_rows, H, flags, mode) && aligned16(X) && aligned16(W) && aligned16(K);
 }
 
+// rhs_small.hip takes the launch (and, alone among the routes below H = 256, carries dropout and RkOpt::s_out in it)
+static bool small_takes(const ndcn_csr *A, int H, uint32_t flags) {
+    return !(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags);
+}
+
+// RkOpt::s_out can be honoured: the lattice-plan kernel (rhs_adj_supported), or the narrow-panel one
+int rhs_s_out_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int n_prev) {
+    return rhs_adj_supported(A, H, flags, mode, n_prev) || small_takes(A, H, flags);
+}
+
 // allow_mid = false: the callers whose launch rhs_mid.hip declines (dropout; RkOpt fields of the H = 256 launches)
 static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
                      float *work, int H, uint32_t flags, hipStream_t st, bool allow_mid) {
@@ -75,11 +85,12 @@ static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t
             }
             return rhs_fused_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, st);
         }
-        g_last_rhs_path &= ~NDCN_PATH_MID;
-        if (allow_mid && mid_takes(A, X, Xh, W, Y, H, flags)) {   // 16 <= H <= 128 at any size: gather, MFMA Linear, ReLU in one launch
-            g_last_rhs_path = NDCN_PATH_MID;
-            return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st);
-        }
+        // 16 <= H <= 128 at any size: gather, MFMA Linear, ReLU in one launch.  The report's MID bit is this branch's own; its other bits
+        // belong to the launches with a stage epilogue and stay as the last of them left them (rhs_rk_f32 and the dropout forms zero them
+        // before they come here; after a plain ndcn_rhs_f32 they still name the thread's previous such launch)
+        const bool mid = allow_mid && mid_takes(A, X, Xh, W, Y, H, flags);
+        g_last_rhs_path = mid ? NDCN_PATH_MID : (g_last_rhs_path & ~NDCN_PATH_MID);
+        if (mid) return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st);
         if (rhs_small_supported(A, H, flags))                     // narrow panels: SpMM -> Linear -> ReLU in one launch
             return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr,
                                  nullptr, st);
@@ -214,7 +225,7 @@ int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_o
                  float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st) {
     int rc = drop_check(Xh, flags);
     if (rc) return rc;
-    if (!(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags)) {
+    if (small_takes(A, H, flags)) {
         g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
         return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st,
                              nullptr, nullptr, &d);
@@ -233,7 +244,7 @@ int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t 
     if (rc) return rc;
     if (n_prev < 0 || n_prev > 5) { set_error("rhs_rk: n_prev must be 0..5"); return NDCN_EINVAL; }
     if (opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid)) { set_error("dropout with x_add / x_mask / s_out is not supported"); return NDCN_EINVAL; }
-    if (!(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags)) {
+    if (small_takes(A, H, flags)) {
         g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
         return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                              nullptr, opt, &d);

@@ -23,6 +23,20 @@
 
 using namespace ndcn;
 
+// Which launch evaluates f for this solve, decided once in solver_create (exact32, the range guard's verdict, follows in solver_begin):
+//   kind      epi                 chosen when                                                       the launch
+//   Dyn       method == DOPRI5    ndcn_solver_desc::dyn                                             dyn_rk_f32 (dynamics.hip)
+//   Mfma      true                un-sharded, H = 256 with graph and control, rhs_fused2_supported  rhs_fused2_f32 / rhs_fused2_exact_f32
+//   Fused1    false               un-sharded, the same without rhs_fused2_supported                 rhs_fused_packed_f32
+//   Rec       true                un-sharded, no_control, spmm_rec_supported, rows * 1 KiB < 4 GiB  spmm_rec_f32
+//   Wide      true                un-sharded, no_control, spmm_wide_rk_supported                    spmm_wide_rk_f32
+//   Small     true                un-sharded, graph and control, not H = 256, DOPRI5,               rhs_small_f32
+//                                 rhs_small_supported (fixed-grid methods: Composed)
+//   Composed  false               everything else                                                   rhs_f32 picks the kernel, rk.hip the algebra
+// A shard (ndcn_solver::sharded) is orthogonal: every launch of it dispatches through rhs_rk_f32 (rhs_sharded), with epi = true;
+// its kind says only whether the weights get packed - Fused1 at H = 256 with graph and control, else Composed.
+enum class Rhs { Composed, Fused1, Mfma, Rec, Wide, Small, Dyn };
+
 struct ndcn_solver {
     ndcn_solver_desc d;
     int64_t n_rows = 0, n_elem = 0;
@@ -36,21 +50,16 @@ struct ndcn_solver {
     bool slab_owned = false;
     double *d_red = nullptr;       // device {sum, nonfinite}
     void *d_ws = nullptr;
-    void *d_ws2 = nullptr;         // fused2 error partials
+    void *d_ws2 = nullptr;         // error partials of the RHS epilogues
     double *h_red = nullptr;       // pinned host mirror
     bool poll = false;             // d_red IS the device alias of h_red: the kernels store the record into host memory, the host polls (hostrec.h)
     hipEvent_t ev = nullptr;
     // scalar state
     bool begun = false;
-    bool fused = false;            // H = 256 fused RHS: `work` holds the packed weights
-    bool fused2 = false;           // the RK algebra rides in the epilogue of the RHS launches (rhs_epi)
-    bool rec_epi = false;          // ... of an SpMM kernel (no_control RHS) instead of the fused MFMA kernel:
-    bool wide_epi = false;         //     the group-record kernel, or (no plan) the row kernel
-    bool small_epi = false;        // ... of the narrow-panel kernel (H <= 128, rhs_small.hip)
-    bool dyn_rhs = false;          // the right-hand side is one of the truth dynamics (ndcn_solver_desc::dyn, dynamics.hip) ...
-    bool dyn_epi = false;          // ... and (dopri5) the RK algebra rides in its epilogue, as with small_epi
+    Rhs kind = Rhs::Composed;
+    bool epi = false;              // the RK stage algebra rides in that launch's epilogue (rhs_epi)
     ndcn_dynamics dyn = {};
-    float *ytmp2 = nullptr;        // second stage-input panel (fused2: a stage's input must outlive its epilogue)
+    float *ytmp2 = nullptr;        // second stage-input panel (epi: a stage's input must outlive its epilogue)
     double t0 = 0, t1 = 0, dt = 0; // dopri5: last interval [t0, t1], next step size
     float tf = 0;                  // fixed grid: current time in the state dtype
     bool fit_pending = false;      // last accepted step not yet fitted
@@ -111,6 +120,18 @@ constexpr int kCoefCap = 64;
 
 inline size_t align_up(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
+// `work` holds the packed weights of the H = 256 kernels (packed in solver_begin)
+inline bool packs_weights(const ndcn_solver *s) { return s->kind == Rhs::Mfma || s->kind == Rhs::Fused1; }
+// the epilogue launch is not the MFMA kernel: it can read its coefficients from device memory (c_dev), i.e. be replayed
+inline bool takes_c_dev(const ndcn_solver *s) { return s->kind == Rhs::Rec || s->kind == Rhs::Wide || s->kind == Rhs::Small || (s->kind == Rhs::Dyn && s->epi); }
+// the launch has the options only the split-product MFMA kernel carries (RkOpt::xadd, c_mid with no_k: dense output).  Never true for a
+// shard - whose launches may still be that kernel: a site that serves shards asks for them by its own condition
+inline bool mfma_options(const ndcn_solver *s) { return s->kind == Rhs::Mfma && !s->exact32; }
+// hipGraph replay pays off where the step is launch-bound.  The MFMA kernel takes dt by value (large panels: never launch-bound);
+// every other launch reads it from device memory when replayed - the epilogue launches in the adaptive step only (fixed-grid steps
+// pass them their coefficients by value).  Decided before exact32 is known: it does not enter.
+inline bool replayable(const ndcn_solver *s) { return !s->sharded && s->d.use_graph && s->kind != Rhs::Mfma && !(takes_c_dev(s) && s->d.method != NDCN_M_DOPRI5); }
+
 int n_panels(const ndcn_solver_desc *d) {
     const int nk = d->method == NDCN_M_DOPRI5 ? 7 : d->method == NDCN_M_RK4 ? 4 : 1;
     int n = 3 + nk;                                       // ycur, ytmp, ytmp2, k[]
@@ -152,58 +173,57 @@ int alloc_panel(ndcn_solver *s, float **p) {
 int rhs_sharded(ndcn_solver *s, const float *x, float *K, int mode, const float *y0, const float *const *kp, const float *cp,
                 int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st, const RkOpt *opt);
 
+// Rhs::Mfma: the split-product launch, or - exact32, the range guard's verdict - the same launch with the fp32 matrix cores as its consumer
+inline decltype(&rhs_fused2_f32) mfma_launch(const ndcn_solver *s) { return s->exact32 ? rhs_fused2_exact_f32 : rhs_fused2_f32; }
+
 int rhs(ndcn_solver *s, const float *x, float *out, hipStream_t st) {
     if (s->sharded) return rhs_sharded(s, x, out, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st, nullptr);
     s->n_rhs++;
-    if (s->dyn_rhs)
-        return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, out, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
-    if (s->fused2 && !s->rec_epi && !s->exact32)
-        return rhs_fused2_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, 0, nullptr,
-                              nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
-    if (s->fused2 && !s->rec_epi)       // exact32: the range guard's route - the same launch on the fp32 matrix cores
-        return rhs_fused2_exact_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, 0, nullptr,
-                                    nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
-    if (s->fused) {     // weights were packed once in solver_begin
-        return rhs_fused_packed_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, st);
+    switch (s->kind) {
+        case Rhs::Dyn:
+            return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, out, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st);
+        case Rhs::Mfma:
+            return mfma_launch(s)(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, 0, nullptr, nullptr, nullptr, 0,
+                                  nullptr, 0.f, 0.f, nullptr, nullptr, st, nullptr);
+        case Rhs::Fused1:   // weights were packed once in solver_begin
+            return rhs_fused_packed_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, st);
+        default:            // Composed, and the plain evaluations of Rec / Wide / Small: rhs_f32 picks the kernel
+            return rhs_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, out, s->work, s->d.H, s->d.rhs_flags, st);
     }
-    return rhs_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, out, s->work, s->d.H, s->d.rhs_flags, st);
 }
 
-// right-hand side whose epilogue carries the stage algebra: the fused MFMA kernel (default RHS, H = 256) or the
-// group-record SpMM (no_control RHS)
+// right-hand side whose epilogue carries the stage algebra (s->epi)
 int rhs_epi(ndcn_solver *s, const float *x, float *K, int mode, const float *y0, const float *const *kp, const float *cp,
             int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws, hipStream_t st,
             const float *dt_dev = nullptr, const RkOpt *opt = nullptr) {
     if (s->sharded) return rhs_sharded(s, x, K, mode, y0, kp, cp, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
     s->n_rhs++;
-    if (s->rec_epi) {
-        // replay: cp holds the bare tableau entries; they join the solver's coefficient table, whose scaled image
-        // (fl(dt * beta), written by the graph's first kernel) the launch reads instead of by-value coefficients
-        const float *c_dev = nullptr;
-        if (dt_dev) {
-            if (s->n_coef + n_prev + 1 > kCoefCap) { set_error("coefficient table full"); return NDCN_EINVAL; }
-            for (int m = 0; m <= n_prev; ++m) s->h_beta[s->n_coef + m] = cp[m];
-            c_dev = s->d_coef + s->n_coef;
-            s->n_coef += 8;                                   // slices stay 32-byte aligned
-        }
-        if (s->dyn_epi)                                       // (reports NDCN_PATH_DYN itself)
-            return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, K, mode, y0, kp, cp, n_prev, y_next, rtol, atol, d_out, d_ws, st, c_dev,
-                              opt);
-        g_last_rhs_path = s->small_epi ? NDCN_PATH_SMALL : (s->wide_epi ? NDCN_PATH_WIDE : NDCN_PATH_REC);
-        if (s->small_epi)
+    // replay: cp holds the bare tableau entries; they join the solver's coefficient table, whose scaled image
+    // (fl(dt * beta), written by the graph's first kernel) the launch reads instead of by-value coefficients
+    const float *c_dev = nullptr;
+    if (dt_dev && takes_c_dev(s)) {
+        if (s->n_coef + n_prev + 1 > kCoefCap) { set_error("coefficient table full"); return NDCN_EINVAL; }
+        for (int m = 0; m <= n_prev; ++m) s->h_beta[s->n_coef + m] = cp[m];
+        c_dev = s->d_coef + s->n_coef;
+        s->n_coef += 8;                                       // slices stay 32-byte aligned
+    }
+    switch (s->kind) {
+        case Rhs::Dyn:                                        // (reports NDCN_PATH_DYN itself)
+            return dyn_rk_f32(s->dyn.kind, s->dyn.p, &s->d.A, x, K, mode, y0, kp, cp, n_prev, y_next, rtol, atol, d_out, d_ws, st, c_dev, opt);
+        case Rhs::Small: g_last_rhs_path = NDCN_PATH_SMALL;
             return rhs_small_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, K, s->d.H, s->d.rhs_flags, mode, y0, kp, cp,
                                  n_prev, y_next, rtol, atol, d_out, d_ws, st, c_dev, opt);
-        if (s->wide_epi)
+        case Rhs::Wide: g_last_rhs_path = NDCN_PATH_WIDE;
             return spmm_wide_rk_f32(&s->d.A, x, nullptr, s->d.A.n_cols, K, s->d.rhs_flags, mode, y0, kp, cp, n_prev, y_next,
                                     rtol, atol, d_out, d_ws, st, c_dev, opt);
-        return spmm_rec_f32(&s->d.A, x, nullptr, s->d.A.n_cols, K, 1.f, s->d.rhs_flags, mode, y0, kp, cp, n_prev, y_next, rtol,
-                            atol, d_out, d_ws, st, c_dev, opt);
+        case Rhs::Rec: g_last_rhs_path = NDCN_PATH_REC;
+            return spmm_rec_f32(&s->d.A, x, nullptr, s->d.A.n_cols, K, 1.f, s->d.rhs_flags, mode, y0, kp, cp, n_prev, y_next, rtol,
+                                atol, d_out, d_ws, st, c_dev, opt);
+        case Rhs::Mfma:
+            return mfma_launch(s)(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, K, s->d.rhs_flags, mode, y0, kp, cp, n_prev, y_next,
+                                  rtol, atol, d_out, d_ws, st, opt);
+        default: set_error("solver: this right-hand side carries no stage epilogue"); return NDCN_ESTATE;
     }
-    if (s->exact32)     // range guard: the same launch with the fp32 matrix cores as its consumer (rhs_fused2_exact.hip)
-        return rhs_fused2_exact_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, K, s->d.rhs_flags, mode, y0, kp, cp, n_prev,
-                                    y_next, rtol, atol, d_out, d_ws, st, opt);
-    return rhs_fused2_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, K, s->d.rhs_flags, mode, y0, kp, cp, n_prev,
-                          y_next, rtol, atol, d_out, d_ws, st, opt);
 }
 
 // wait for the n-double reduction record enqueued last on `st`: s->h_red[0..n)
@@ -268,8 +288,8 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
     const float *kp[1] = {s->k[0]};
     const float cp[1] = {h0};
     // (on the lattice plan the launch that produces f1 forms y0 + h0 f0 on the rows it stages: RkOpt::xadd)
-    const bool fuse_d2 = big && s->fused2;
-    const bool xadd = fuse_d2 && !s->sharded && !s->rec_epi && !s->exact32 && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 2, 1);
+    const bool fuse_d2 = big && s->epi;
+    const bool xadd = fuse_d2 && !s->sharded && mfma_options(s) && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 2, 1);
     if (!xadd) {
         rc = rk_combine_f32(s->ytmp, s->ycur, kp, cp, 1, s->n_elem, st);
         if (rc) return rc;
@@ -369,13 +389,15 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
     float cp[8];
     int m, rc;
     s->att_dense = kDenseAll;
-    if (s->fused2) {
+    if (s->epi) {
         // Stage algebra rides in the RHS epilogues: the evaluation that produces k[i+1] also forms the NEXT stage
         // input y0 + dt * sum_m beta[i+1][m] k[m] (its own K as the last term), the last one the error record.
         // The first stage input y0 + dt beta_21 k1 is a kernel of its own (3 panels) - unless the launch that produces k2 can
         // form it on the rows it stages (RkOpt::xadd: the lattice plan of rhs_fused3.hip, one more gather instead)
-        const bool xadd = !dt_dev && !s->rec_epi && !s->exact32 &&
-                          (s->sharded ? s->xadd_block >= 0 : rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 1, 1));
+        // (a shard asks by its own condition - mfma_options is never true for it: an interior block on the XADD kernel, found in
+        // solver_create, and packed weights inside the split product's guarantee)
+        const bool xadd = !dt_dev && (s->sharded ? !s->exact32 && s->xadd_block >= 0
+                                                 : mfma_options(s) && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 1, 1));
         m = dt_terms(dt32, kBeta[0], 1, s->k, kp, cp);
         const float xadd_c = cp[0];
         if (!xadd) {
@@ -412,8 +434,7 @@ int enqueue_attempt(ndcn_solver *s, hipStream_t st, float dt32, const float *dt_
         // k4, k5, k6 - writes M (the same stages in the same order as interp_direct's terms) into k6's panel, or, when the step covers
         // no tick, stores nothing there (1 P less); the dense output then reads {y0, y1, k1, M, k7} instead of nine panels.
         static const bool mid_on = env_on("NDCN_DENSE_MID");
-        bool dense = mid_on && keep_mid_p && use_aux && !s->sharded && !s->rec_epi && !s->exact32 &&
-                     rhs_dense_supported(&s->d.A, s->d.H, s->d.rhs_flags);
+        bool dense = mid_on && keep_mid_p && use_aux && !s->sharded && mfma_options(s) && rhs_dense_supported(&s->d.A, s->d.H, s->d.rhs_flags);
         float c3[8];
         {
             int m3 = 0;
@@ -755,7 +776,7 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
         s->d.dyn = &s->dyn;
         s->d.W = s->d.b = nullptr;
         s->d.rhs_flags = 0;
-        s->dyn_rhs = true;
+        s->kind = Rhs::Dyn;
     }
     s->n_rows = desc->A.n_rows;
     s->n_elem = s->n_rows * (int64_t)desc->H;
@@ -838,10 +859,10 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
     s->ycur_own = s->ycur;
     if ((rc = alloc_panel(s, &s->ytmp))) return fail(rc);
     if ((rc = alloc_panel(s, &s->ytmp2))) return fail(rc);
-    if (s->dyn_rhs) {
+    if (s->kind == Rhs::Dyn) {
         // dopri5: 1 combine + 6 launches per attempt, as on the narrow-panel route; fixed-grid methods keep their replayed step,
         // whose right-hand sides are the same kernel in plain mode (rhs)
-        s->fused2 = s->rec_epi = s->dyn_epi = desc->method == NDCN_M_DOPRI5;
+        s->epi = desc->method == NDCN_M_DOPRI5;
     } else {
         const int64_t wb = rhs_work_bytes(s->n_rows, desc->H, desc->rhs_flags);
         if (wb > 0) {
@@ -850,10 +871,11 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
             s->work = static_cast<float *>(wq);
         }
         const bool both = !(desc->rhs_flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL));
+        const bool h256 = both && rhs_fused_supported(desc->H, desc->rhs_flags);
         if (s->sharded) {
             // the stage algebra rides in the epilogues of whatever kernel ndcn_rhs_rk_f32 selects per launch
-            s->fused = both && rhs_fused_supported(desc->H, desc->rhs_flags);
-            s->fused2 = true;
+            s->kind = h256 ? Rhs::Fused1 : Rhs::Composed;
+            s->epi = true;
             void *q2 = nullptr;
             if (s->shard.X_halo) {
                 s->halo = s->shard.X_halo;
@@ -873,20 +895,18 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
                 set_error("creating the exchange stream failed");
                 return fail(NDCN_EHIP);
             }
-        } else {
-        s->fused = both && rhs_fused_supported(desc->H, desc->rhs_flags);
-        s->fused2 = s->fused && rhs_fused2_supported(&desc->A, desc->H, desc->rhs_flags);
-        if (!no_graph && no_ctl && spmm_rec_supported(&desc->A, desc->H) && s->n_rows * (int64_t)1024 < (1ll << 32)) {
-            s->fused2 = true;                                   // same stepping, different launch (rhs_epi)
-            s->rec_epi = true;
+        } else if (h256) {
+            s->kind = rhs_fused2_supported(&desc->A, desc->H, desc->rhs_flags) ? Rhs::Mfma : Rhs::Fused1;
+        } else if (!no_graph && no_ctl && spmm_rec_supported(&desc->A, desc->H) && s->n_rows * (int64_t)1024 < (1ll << 32)) {
+            s->kind = Rhs::Rec;                                 // same stepping, different launch (rhs_epi)
         } else if (!no_graph && no_ctl && spmm_wide_rk_supported(&desc->A, desc->H)) {
-            s->fused2 = s->rec_epi = s->wide_epi = true;
-        } else if (both && !s->fused && desc->method == NDCN_M_DOPRI5 && rhs_small_supported(&desc->A, desc->H, desc->rhs_flags)) {
+            s->kind = Rhs::Wide;
+        } else if (both && desc->method == NDCN_M_DOPRI5 && rhs_small_supported(&desc->A, desc->H, desc->rhs_flags)) {
             // narrow panels: the adaptive step runs 1 combine + 6 launches; fixed-grid methods keep their replayed step,
             // whose right-hand sides go through the same kernel in plain mode (rhs_f32)
-            s->fused2 = s->rec_epi = s->small_epi = true;
+            s->kind = Rhs::Small;
         }
-        }
+        if (!s->sharded) s->epi = s->kind != Rhs::Composed && s->kind != Rhs::Fused1;      // the launches named above but the first-generation kernel
     }
     const int nk = desc->method == NDCN_M_DOPRI5 ? 7 : desc->method == NDCN_M_RK4 ? 4 : 1;
     for (int j = 0; j < nk; ++j)
@@ -923,10 +943,7 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
     s->d_dt = static_cast<float *>(q);
     s->d_coef = s->d_dt + 64;
     s->d_beta = s->d_coef + kCoefCap;
-    // hipGraph replay pays off where the step is launch-bound.  The fused MFMA kernel takes dt by value (large
-    // panels: never launch-bound); every other path reads it from device memory when replayed.
-    s->graph_on = !s->sharded && desc->use_graph && !(s->fused2 && !s->rec_epi) &&
-                  !(s->rec_epi && desc->method != NDCN_M_DOPRI5);
+    s->graph_on = replayable(s);
     if (s->graph_on) {
         if (hipStreamCreateWithFlags(&s->gstream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&s->gev_in, hipEventDisableTiming) != hipSuccess ||
@@ -983,7 +1000,7 @@ int solver_begin(ndcn_solver *s, const float *y0, double t0, hipStream_t st, boo
     s->last_ratio = 0;
     s->t0 = s->t1 = t0;
     s->tf = (float)t0;
-    if (s->fused) {
+    if (packs_weights(s)) {
         int rcp = pack_weight_256(s->d.W, s->work, st);
         if (rcp) return rcp;
         s->packed = true;
@@ -1051,14 +1068,14 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
     const float dt = t1 - s->tf;
     float *dst = out ? out : s->ycur_own;
     int rc;
-    if (s->fused2 && s->d.method == NDCN_M_EULER && dst != s->ycur) {
+    if (s->epi && s->d.method == NDCN_M_EULER && dst != s->ycur) {
         // y + dt * f in the RHS epilogue (one term: identical rounding to fixed_stage op 0)
         const float c1[1] = {dt};
         RkOpt opt = {};
         opt.no_k = 1;                                        // nothing reads an Euler step's K
         rc = rhs_epi(s, s->ycur, s->k[0], 1, s->ycur, nullptr, c1, 0, dst, 0.f, 0.f, nullptr, nullptr, st, nullptr, &opt);
         if (rc) return rc;
-    } else if (s->fused2 && s->d.method == NDCN_M_RK4) {
+    } else if (s->epi && s->d.method == NDCN_M_RK4) {
         // the 3/8-rule stage algebra in the RHS epilogues (rk_common.py:72-78): 4 launches instead of 8, each stage
         // input written by the launch that produced the stage it needs last
         const float c1[1] = {dt};
@@ -1083,7 +1100,7 @@ static int fixed_advance(ndcn_solver *s, double next_t, float *out, hipStream_t 
 // An Euler step whose stage algebra rides in the RHS epilogue cannot update the panel it reads: with the state inside the solver such
 // steps alternate between its own panel and `alt`.  The `out` of the next fixed_advance: `alt`, or nullptr (the solver's panel).
 static float *euler_pingpong(const ndcn_solver *s, float *alt) {
-    const bool pingpong = !s->graph_on && s->fused2 && s->d.method == NDCN_M_EULER;
+    const bool pingpong = !s->graph_on && s->epi && s->d.method == NDCN_M_EULER;
     return (pingpong && s->ycur == s->ycur_own) ? alt : nullptr;
 }
 
@@ -1214,7 +1231,7 @@ int solver_advance_many(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, 
             st);
     // Fixed grid on a state that fits one compute unit: the whole time vector in ONE launch (solve_small.hip) - bit-identical
     // to the per-step kernels below, without their launch latency.
-    if (n_ticks > 0 && !s->sharded && !s->dyn_rhs && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+    if (n_ticks > 0 && !s->sharded && s->kind != Rhs::Dyn && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
         std::vector<float> dts((size_t)n_ticks);
         float tf = s->tf;
         for (int64_t q = 0; q < n_ticks; ++q) {            // solvers.py:81-97 with grid == t: step sizes formed in the state dtype
@@ -1259,7 +1276,7 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
         set_error("ndcn_solver_advance_many_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C);
         return NDCN_EINVAL;
     }
-    if (fixed && !s->dyn_rhs && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
+    if (fixed && s->kind != Rhs::Dyn && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
         set_error("ndcn_solver_advance_many_readout: this state fits the one-launch solve (ndcn_solve_small_f32); decode its trajectory instead");
         return NDCN_EINVAL;
     }
@@ -1328,7 +1345,7 @@ int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, con
     }
     if (n_steps == 0) return NDCN_OK;
     // a state that fits one compute unit: the whole grid in one launch per 128 steps, only the ticks written (solve_small.hip)
-    if (!s->dyn_rhs && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
+    if (s->kind != Rhs::Dyn && solve_small_supported(&s->d.A, s->d.H, s->d.rhs_flags, s->d.method)) {
         std::vector<float> dts((size_t)n_steps);
         for (int64_t i = 0; i < n_steps; ++i) dts[(size_t)i] = h_grid[i + 1] - h_grid[i];
         int rc = solve_small_grid_f32(&s->d.A, s->d.W, s->d.b, s->d.H, s->d.rhs_flags, s->d.method, s->ycur, dts.data(), n_steps,

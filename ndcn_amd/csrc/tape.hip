@@ -278,8 +278,6 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
     int rc;
     float *const *u = P.u, *const *k = P.k;
     const bool both = !(t->flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL));
-    // (the narrow-panel kernel - rhs_small.hip: what rhs_rk_f32 picks for H <= 128 at launch-bound sizes - writes S on the side too)
-    const bool small_s = both && !rhs_fused2_supported(&t->A, t->H, t->flags) && rhs_small_supported(&t->A, t->H, t->flags);
     const float *kall[7] = {k0, k[1], k[2], k[3], k[4], k[5], k[6]};
     const float *kp[8];
     float cp[8];
@@ -303,7 +301,8 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
         cp[mp] = dts * (float)kBeta[i + 1][i + 1];
         if (!rerun) t->nfe++;
         RkOpt opt = {};
-        if (t->keep_s && both && (rhs_adj_supported(&t->A, t->H, fl, NDCN_RK_COMBINE, mp) || small_s)) {
+        // (the lattice-plan kernel, or the narrow-panel one - what rhs_rk_f32 picks for H <= 128 at launch-bound sizes -: both write S on the side)
+        if (t->keep_s && both && rhs_s_out_supported(&t->A, t->H, fl, NDCN_RK_COMBINE, mp)) {
             if ((rc = s_panel(i + 2, &opt.s_out))) return rc;
         }
         if (t->drop)
