@@ -778,7 +778,8 @@ NDCN_API int ndcn_prof_kinds(void);
                                * nn.Linear in fp32, neural_dynamics.py:33; csrc/rhs_fused2_exact.hip).  NDCN_RANGE_GUARD=0
                                * switches the guard (and the 32-byte read-back per packed image) off                              */
 #define NDCN_PATH_RANGE  512 /* such weights on a launch that exists only fused (x_add / x_mask / s_out): split product, warned once */
-#define NDCN_PATH_DROP_EPI 1024 /* ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the dropout factor was applied inside the launch (clear: by
+#define NDCN_PATH_DROP_EPI 1024 /* ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: the dropout factor was applied inside the launch - with
+                                 * NDCN_PATH_SMALL, or with NDCN_PATH_MID under ndcn_set_rhs_mid_drop (clear: by
                                  * the streaming pass ndcn_dropout_apply_f32 behind it)                                              */
 #define NDCN_PATH_DYN 2048   /* a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; ndcn_solver_desc::dyn)       */
 #define NDCN_PATH_MID 4096   /* 16 <= H <= 128, H % 4 == 0, any number of rows: gather, fp32 MFMA Linear, ReLU and the COMBINE / RK4
@@ -875,7 +876,7 @@ NDCN_API int ndcn_debug_last_spmm_path(void);
  * split fp16 product whatever its range, and packing does not read back.  Images packed while the guard was off are judged when
  * they are packed next.                                                                                                            */
 NDCN_API int ndcn_set_range_guard(int on);
-/* The one-launch right-hand side for hidden widths 16..128 at any size (NDCN_PATH_MID above, csrc/rhs_mid.hip; the two calls are additions to ABI 29:
+/* The one-launch right-hand side for hidden widths 16..128 at any size (NDCN_PATH_MID above, csrc/rhs_mid.hip; the three calls are additions to ABI 29:
  * no existing declaration changes, and tests/test_gpu_tape_dropout.py and tests/test_gpu_dropout_combine.py pin that number).   Without it
  * those widths run composed once n_rows * H exceeds 2^18: row SpMM into a scratch panel, MFMA Linear, stand-alone stage kernel.  Every
  * panel it writes - K, y_next, y_aux - equals the composed path's bit for bit, so the switch is invisible in the results.
@@ -887,11 +888,20 @@ NDCN_API int ndcn_set_range_guard(int on);
  *   2  on for every supported shape, ahead of that kernel (tests, measuring the crossover; the narrow-panel kernel's stage sums
  *      start from the new stage's product, so the sign of an all-zero sum can differ from this route's there)
  * ndcn_rhs_f32 / ndcn_rhs_rk_f32 (plain, NDCN_RK_COMBINE with or without y_aux, NDCN_RK_RK4; NDCN_RK_ERROR as the plain launch plus the
- * stand-alone error kernel) take the route; it declines - the launch runs as without it - a halo panel, dropout, NDCN_F_NO_GRAPH /
- * NDCN_F_NO_CONTROL, x_add / x_mask / s_out and panels that are not 16-byte aligned.  ndcn_rhs_work_bytes does not depend on the mode.
+ * stand-alone error kernel) take the route; it declines - the launch runs as without it - a halo panel, NDCN_F_NO_GRAPH /
+ * NDCN_F_NO_CONTROL, x_add / x_mask / s_out and panels that are not 16-byte aligned, and it declines dropout unless
+ * ndcn_set_rhs_mid_drop is on.  ndcn_rhs_work_bytes does not depend on the mode.
+ * ndcn_set_rhs_mid_drop (NDCN_RHS_MID_DROP, default 0): on = 1 lets ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32 take the route too, wherever
+ * the mode above takes the shape and under the same conditions - the dropout factor of ndcn_dropout is applied in the launch's epilogue
+ * (K' = K * m, one Philox call per 16-byte lane) and K' is what the launch stores and what its stage algebra consumes: plain, NDCN_RK_COMBINE
+ * with or without y_aux, NDCN_RK_RK4; NDCN_RK_ERROR as the plain dropout launch plus the stand-alone error kernel.  The launch reports
+ * NDCN_PATH_MID | NDCN_PATH_DROP_EPI and writes the bits of the composed form (composed launches, ndcn_dropout_apply_f32 or
+ * ndcn_dropout_combine_f32, stand-alone stage kernel).  PROCESS-WIDE; returns the previous value (1 / 0); on < 0 returns to the
+ * environment's.  Without effect while the mode is 0 or does not take the shape; a halo panel with dropout stays NDCN_EINVAL.
  * ndcn_rhs_mid_supported: the shape part of that decision for `mode` - H a multiple of 4 in 16..128, n_rows >= 1, neither NO_ flag,
  * and in mode 1 H <= 96 and n_rows * H beyond the narrow-panel kernel's bound; a host predicate, no device needed.                          */
 NDCN_API int ndcn_set_rhs_mid(int mode);
+NDCN_API int ndcn_set_rhs_mid_drop(int on);
 NDCN_API int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);
 /* The reverse of ONE right-hand-side evaluation K = relu(W (A X) + b) as a call (csrc/rhs_mid_bwd.hip; five calls added to ABI 29: no
  * existing declaration changes) - what autograd executes for ODEFunc.forward (neural_dynamics.py:27-36) under the drivers' training

@@ -289,6 +289,7 @@ SIGNATURES = {
     'ndcn_debug_last_rk_path': (_L, []),
     'ndcn_set_range_guard': (_I, [_I]),
     'ndcn_set_rhs_mid': (_I, [_I]),
+    'ndcn_set_rhs_mid_drop': (_I, [_I]),
     'ndcn_rhs_mid_supported': (_I, [_L, _I, _U, _I]),
     'ndcn_rhs_vjp_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U, _I, _F, _I, _P]),
     'ndcn_rhs_vjp_work_bytes': (_L, [_L, _I, _U]),

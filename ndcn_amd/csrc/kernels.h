@@ -107,13 +107,17 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
                   const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);     // drop: the factor of csrc/dropout.h in the epilogue
 // rhs_mid.hip: the whole ODEFunc in one launch for 16 <= H <= 128 (H % 4 == 0) at any number of rows - mode 0 (plain), NDCN_RK_COMBINE
 // (with RkOpt::y_aux / c_aux) or NDCN_RK_RK4; every panel 16-byte aligned, no halo panel; the bits of the composed path.  The switch
-// (ndcn_set_rhs_mid / NDCN_RHS_MID): 0 off, 1 wherever rhs_small.hip does not take the shape, 2 every supported shape
+// (ndcn_set_rhs_mid / NDCN_RHS_MID): 0 off, 1 wherever rhs_small.hip does not take the shape, 2 every supported shape.  drop: the factor
+// of csrc/dropout.h in the epilogue (NDCN_F_RELU required) - K as stored and as consumed by the stage algebra is the masked one; the
+// dropout calls of rhs.hip come here only under a switch of their own (ndcn_set_rhs_mid_drop / NDCN_RHS_MID_DROP: 0 off, 1 on)
 int rhs_mid_mode();
 int set_rhs_mid(int mode);                    // ndcn_set_rhs_mid: returns the previous mode; < 0: back to the environment's
+int rhs_mid_drop_on();
+int set_rhs_mid_drop(int on);                 // ndcn_set_rhs_mid_drop: returns the previous value; < 0: back to the environment's
 int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // from the sizes alone, no device
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt = nullptr);
+                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
 // linear_bwd.hip: the row chunks linear_bwd_f32 cuts the weight gradient into (`used` chunks of rpc rows) and the fixed-order sum of
 // their partial blocks into gW / gb (one of them nullable)
 void wgrad_chunking(int64_t n, int Hi, int Ho, int64_t *rpc, int64_t *used);
@@ -132,7 +136,8 @@ int rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *At, const float *X, const flo
 int64_t rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
 int64_t rhs_vjp_gs_offset(int64_t n_rows, int H);
 // dropout (csrc/dropout.h; rhs.hip): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1), the streaming pass K *= m, and
-// rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch, by the streaming pass behind every other route
+// rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch and (under ndcn_set_rhs_mid_drop) of the rhs_mid.hip
+// launch, by the streaming pass behind every other route
 int drop_args(const ndcn_dropout *desc, DropArgs *out);
 int dropout_apply_f32(float *K, int64_t n, const DropArgs &d, hipStream_t st);
 // dropout_apply_f32(K) and rk_combine_f32(out, y0, {h_kprev..., K}, h_c, n_prev + 1) as one pass (h_c[n_prev]: K's coefficient): the same bits

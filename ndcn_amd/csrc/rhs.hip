@@ -1,7 +1,8 @@
 // ODEFunc.forward as one entry point: Y = relu(W (A X) + b)   (neural_dynamics.py:20-39).
 // H = 256 runs the fused kernel (rhs_fused.hip); other widths compose the SpMM and the MFMA Linear through a
 // scratch panel.  rhs_f32 / rhs_rk_f32 are the p = 0 (and eval-mode) forms; rhs_drop_f32 / rhs_rk_drop_f32 at the end of the file
-// add the dropout factor of csrc/dropout.h - inside the narrow-panel launch, as a streaming pass behind every other route.
+// add the dropout factor of csrc/dropout.h - inside the narrow-panel launch and, under its own switch, inside the rhs_mid.hip launch,
+// as a streaming pass behind every other route.
 #include <stdio.h>
 
 #include <atomic>
@@ -59,7 +60,8 @@ int rhs_s_out_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int 
     return rhs_adj_supported(A, H, flags, mode, n_prev) || small_takes(A, H, flags);
 }
 
-// allow_mid = false: the callers whose launch rhs_mid.hip declines (dropout; RkOpt fields of the H = 256 launches)
+// allow_mid = false: the callers whose launch rhs_mid.hip declines (the composed dropout forms, which mask K behind this launch; RkOpt
+// fields of the H = 256 launches)
 static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
                      float *work, int H, uint32_t flags, hipStream_t st, bool allow_mid) {
     const bool graph = !(flags & NDCN_F_NO_GRAPH), ctl = !(flags & NDCN_F_NO_CONTROL);
@@ -215,6 +217,15 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
 // route: the launch without a stage epilogue, the streaming pass K *= m, then the un-fused stage kernel - the composition rhs_rk_f32
 // itself falls back to, hence the same bits as the fused epilogues would give on the masked K.  NDCN_RK_COMBINE without y_aux: the
 // last two as ONE pass (dropout_combine_f32), the same bits again.
+// Widths 16..128 with ndcn_set_rhs_mid_drop on: where rhs_rk_f32 would hand the p = 0 launch to rhs_mid.hip (mid_takes, no RkOpt field
+// of the H = 256 launches, aligned panels) the factor rides in that launch's epilogue (NDCN_PATH_MID | NDCN_PATH_DROP_EPI) - plain,
+// COMBINE with or without y_aux, RK4; ERROR as the plain dropout launch and rk_error_f32.  The bits of the composed forms above, and,
+// as for p = 0, ahead of the narrow-panel kernel where the mode takes the shape.
+// the dropout form of rhs_mid.hip takes the launch: its own switch on top of mid_takes (neither NO_ flag: rhs_mid_supported)
+static bool mid_drop_takes(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags) {
+    return rhs_mid_drop_on() && mid_takes(A, X, Xh, W, K, H, flags);
+}
+
 static int drop_check(const float *Xh, uint32_t flags) {
     if (Xh) { set_error("dropout with a halo panel (sharded graphs) is not supported"); return NDCN_EINVAL; }
     if (!(flags & NDCN_F_RELU)) { set_error("dropout without NDCN_F_RELU is not supported"); return NDCN_EINVAL; }
@@ -225,6 +236,10 @@ int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_o
                  float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st) {
     int rc = drop_check(Xh, flags);
     if (rc) return rc;
+    if (mid_drop_takes(A, X, Xh, W, Y, H, flags)) {
+        g_last_rhs_path = NDCN_PATH_MID | NDCN_PATH_DROP_EPI;
+        return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st, nullptr, &d);
+    }
     if (small_takes(A, H, flags)) {
         g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
         return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st,
@@ -244,7 +259,18 @@ int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t 
     if (rc) return rc;
     if (n_prev < 0 || n_prev > 5) { set_error("rhs_rk: n_prev must be 0..5"); return NDCN_EINVAL; }
     if (opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid)) { set_error("dropout with x_add / x_mask / s_out is not supported"); return NDCN_EINVAL; }
-    if (small_takes(A, H, flags)) {
+    // the predicate and precedence of rhs_rk_f32: COMBINE and RK4 in the launch's epilogue; an ERROR launch is the plain dropout launch
+    // (rhs_drop_f32 at the end) and rk_error_f32, not the narrow-panel kernel's
+    bool mid = !(opt && opt->no_k) && mid_drop_takes(A, X, Xh, W, K, H, flags);
+    if (mid && rk_mode != 2) {
+        mid = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
+        for (int m = 0; m < n_prev; ++m) mid = mid && h_kprev && aligned16(h_kprev[m]);
+        if (mid) {
+            g_last_rhs_path = NDCN_PATH_MID | NDCN_PATH_DROP_EPI;
+            return rhs_mid_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt, &d);
+        }
+    }
+    if (!mid && small_takes(A, H, flags)) {
         g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
         return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                              nullptr, opt, &d);

@@ -17,10 +17,19 @@
 //   => every panel the launch writes equals the composed path's bit for bit, signs of zero and NaN positions included; the switch
 //   (ndcn_set_rhs_mid / NDCN_RHS_MID, off by default) is invisible in the results.
 //
+// Dropout (DROP; the contract is csrc/dropout.h): a lane of the epilogue owns the four consecutive elements idx = gr H + 4 q, and H is a
+// multiple of 4, so idx >> 2 is exactly one Philox group - ONE drop_words call per lane (the rolled form: the round keys are formed as
+// the loop goes, not held in registers), both counter words from the 64-bit index.  K' = K * (w >= T ? s : 0), one rounded product per
+// element behind the ReLU (NaN * 0 and Inf * 0 stay NaN), is what the launch stores as K and what the unchanged stage algebra - y_aux
+// included - consumes: the bits of the composed launches followed by dropout_apply_f32 / dropout_combine_f32 and the stand-alone stage
+// kernel.  The DROP = false instantiations are the kernels they were.  A switch of its own (ndcn_set_rhs_mid_drop /
+// NDCN_RHS_MID_DROP, off by default) lets the dropout calls take the route where the mode above takes the shape.
+//
 // The error record is not formed here: an ERROR launch is this kernel in PLAIN mode followed by rk_error_f32 (rhs.hip), which keeps
-// the record's summation order.  No halo panel, no dropout, none of the RkOpt fields of the H = 256 launches: rhs.hip declines those.
+// the record's summation order.  No halo panel, none of the RkOpt fields of the H = 256 launches: rhs.hip declines those.
 #include <atomic>
 
+#include "dropout.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -35,7 +44,9 @@ constexpr int kMidMaxPrev = 5;
 constexpr int kMidMinH = 16, kMidMaxH = 128;
 // Mode 1 stops here.  Beyond it P = 128: 99 072 bytes of LDS, ONE workgroup per CU, so a tile's gather, MFMA and epilogue phases run
 // one after the other with nothing to overlap them - measured slower than the composed path (tools/micro/rhs_mid_time.py, 99 856 rows,
-// H = 128: plain 0.107 ms against 0.080 ms, COMBINE 5 0.185 against 0.160).  Mode 2 still takes those widths.
+// H = 128: plain 0.107 ms against 0.080 ms, COMBINE 5 0.185 against 0.160).  Mode 2 still takes those widths.  The dropout form follows
+// the same bound: with --dropout 0.5 there H = 128 ran plain 0.119 ms against 0.095 composed and COMBINE 5 0.188 against 0.164, while
+// H = 96 was not slower (plain 0.076 against 0.076, COMBINE 5 0.120 against 0.131).
 constexpr int kMidMode1MaxH = 96;
 constexpr int kLdsPerCu = 160 * 1024;
 enum { MID_PLAIN = 0, MID_COMBINE = 1, MID_RK4 = 3 };
@@ -91,8 +102,8 @@ __device__ __forceinline__ float mid_rk4(float y, const float (&km)[kMidMaxPrev]
     return y + (km[0] + 3.f * km[1] + 3.f * km[2] + kn) * (dt / 8.f);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi e) {
+template <int MODE, bool DROP>
+__global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi e, DropArgs d) {
     extern __shared__ __align__(16) float mid_lds[];
     const int H = a.H, n = a.n_rows;
     const int P = (H + 31) & ~31;                            // H padded to the MFMA tile: k steps and output columns
@@ -172,8 +183,15 @@ __global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi 
             const int row = i / H4, q = i - row * H4;
             const int gr = r0 + row;
             if (gr >= n) continue;
-            const float4 kn = mid_ld4(s_T + row * P + 4 * q);
+            float4 kn = mid_ld4(s_T + row * P + 4 * q);
             const size_t idx = (size_t)gr * H + 4 * q;
+            if (DROP) {                                      // K' = K * m: stored, and the K of everything below
+                const Philox4 o = drop_words<true>(d, (int64_t)(idx >> 2));
+                kn.x = kn.x * (o.w[0] >= d.thresh ? d.s : 0.f);
+                kn.y = kn.y * (o.w[1] >= d.thresh ? d.s : 0.f);
+                kn.z = kn.z * (o.w[2] >= d.thresh ? d.s : 0.f);
+                kn.w = kn.w * (o.w[3] >= d.thresh ? d.s : 0.f);
+            }
             mid_st4(a.K + idx, kn);
             if (MODE == MID_PLAIN) continue;
             const float4 y = mid_ld4(e.y0 + idx);
@@ -216,6 +234,22 @@ int set_rhs_mid(int mode) {
     return prev;
 }
 
+// the dropout form's own switch (ndcn_set_rhs_mid_drop / NDCN_RHS_MID_DROP): effective only where rhs_mid_mode() takes the shape
+static std::atomic<int> g_mid_drop_override{-1};           // -1 = the environment's value
+
+int rhs_mid_drop_on() {
+    const int ov = g_mid_drop_override.load(std::memory_order_relaxed);
+    if (ov >= 0) return ov;
+    static const int env_on_ = env_int("NDCN_RHS_MID_DROP", 0) > 0 ? 1 : 0;
+    return env_on_;
+}
+
+int set_rhs_mid_drop(int on) {
+    const int prev = rhs_mid_drop_on();
+    g_mid_drop_override.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return prev;
+}
+
 // From the sizes alone.  Mode 1 leaves to rhs_small.hip what that kernel takes and to the composed path the widths above
 // kMidMode1MaxH; mode 2 takes every supported shape.
 int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode) {
@@ -233,12 +267,13 @@ static size_t mid_lds_bytes(int H) {
 
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt) {
+                const RkOpt *opt, const DropArgs *drop) {
     const int n_rows = (int)A->n_rows;
     if (n_rows == 0) return NDCN_OK;
     if (H < kMidMinH || H > kMidMaxH || (H & 3)) { set_error("rhs_mid: H must be a multiple of 4 in 16..128"); return NDCN_EINVAL; }
     if (mode != MID_PLAIN && mode != MID_COMBINE && mode != MID_RK4) { set_error("rhs_mid: bad mode"); return NDCN_EINVAL; }
     if (n_prev < 0 || n_prev > kMidMaxPrev || (mode == MID_RK4 && n_prev > 3)) { set_error("rhs_mid: bad stage count"); return NDCN_EINVAL; }
+    if (drop && !(flags & NDCN_F_RELU)) { set_error("rhs_mid: dropout without the ReLU"); return NDCN_EINVAL; }
     MidArgs a;
     a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val; a.X = X; a.W = W; a.bias = b; a.K = K;
     a.n_rows = n_rows; a.H = H; a.relu = (flags & NDCN_F_RELU) ? 1 : 0;
@@ -261,17 +296,22 @@ int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *
     double bytes = 8.0 * A->nnz + 4.0 * (n_rows + 1) + 4.0 * H * (double)(A->n_rows + A->n_cols) + 4.0 * H * H;
     if (mode != MID_PLAIN) bytes += Pn * (n_prev + 2 + (e.y_aux ? 1 : 0));
     ProfScope prof(PROF_RHS_FUSED, st, bytes, 2.0 * A->nnz * H + 2.0 * (double)n_rows * H * H);
-#define NDCN_MID(MODE_)                                                                                                   \
+    const DropArgs dv = drop ? *drop : DropArgs{};
+#define NDCN_MID(MODE_, DROP_)                                                                                            \
     do {                                                                                                                  \
-        auto kern = rhs_mid_kernel<MODE_>;                                                                                \
+        auto kern = rhs_mid_kernel<MODE_, DROP_>;                                                                         \
         static std::atomic<unsigned long long> attr_seen{0};                                                              \
         if (once_per_device(attr_seen))                                                                                   \
             NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds_bytes(kMidMaxH))); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e);                                            \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e, dv);                                       \
     } while (0)
-    if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN);
-    else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE);
-    else NDCN_MID(MID_RK4);
+    if (drop) {
+        if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, true);
+        else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, true);
+        else NDCN_MID(MID_RK4, true);
+    } else if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, false);
+    else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, false);
+    else NDCN_MID(MID_RK4, false);
 #undef NDCN_MID
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;

@@ -543,6 +543,13 @@ class HipOps:
         return int(_lib.load().ndcn_set_rhs_mid(int(mode)))
 
     @staticmethod
+    def set_rhs_mid_drop(on):
+        """Dropout inside the one-launch right-hand side for hidden widths 16..128 (ndcn_set_rhs_mid_drop, csrc/rhs_mid.hip): 0 off -
+        launches with a dropout descriptor run as without set_rhs_mid -, 1 on wherever the set_rhs_mid mode takes the shape; < 0: the
+        environment's (NDCN_RHS_MID_DROP).  Process-wide; returns the previous value."""
+        return int(_lib.load().ndcn_set_rhs_mid_drop(int(on)))
+
+    @staticmethod
     def set_rhs_mid_bwd(mode):
         """The one-launch reverse of the right-hand side for hidden widths 16..128 at any size (ndcn_set_rhs_mid_bwd,
         csrc/rhs_mid_bwd.hip): 0 off, 1 on for the widths that measured not slower than the composed launches, 2 on for every

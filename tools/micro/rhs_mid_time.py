@@ -3,7 +3,12 @@
 solves (rtol 0.01, atol 0.001, two ticks), and a mode-2 sweep over n against the narrow-panel kernel (rhs_small.hip) to place the
 crossover.  Prints one JSON line per measurement (median, min and max over the rounds, in ms) and, with --out FILE, writes them there too.
 
-    python tools/micro/rhs_mid_time.py [--rounds 7] [--iters 30] [--out profiles/NAME.jsonl] [--quick]"""
+--dropout P times the dropout launches instead (ndcn_rhs_drop_f32 / ndcn_rhs_rk_drop_f32: plain, COMBINE with 0 and with 5 earlier stages,
+RK4 stage 3) in mode 2 with ndcn_set_rhs_mid_drop off and on, alternating in the same way: off is the composed form (SpMM, MFMA Linear,
+dropout_combine / dropout_apply + stage kernel) above 2^18 elements, on the factor in the one launch's epilogue.  The rows carry
+"dropout": P and "drop_switch": 0 / 1.
+
+    python tools/micro/rhs_mid_time.py [--rounds 7] [--iters 30] [--out profiles/NAME.jsonl] [--quick] [--dropout P]"""
 import argparse
 import json
 import os
@@ -42,11 +47,13 @@ def timed(fn, iters):
     return a.elapsed_time(e) / iters
 
 
-def alternate(fns, modes, rounds, iters):
-    """fns: name -> callable; per round every mode in turn, every callable inside it.  Returns {(name, mode): [ms per round]}, paths"""
+def alternate(fns, modes, rounds, iters, switch=None):
+    """fns: name -> callable; per round every mode in turn, every callable inside it.  Returns {(name, mode): [ms per round]}, paths.
+    switch: the setter the modes go to (default hip.set_rhs_mid)"""
+    switch = switch or hip.set_rhs_mid
     out, paths = {}, {}
     for mode in modes:                                         # warm every shape in every mode
-        prev = hip.set_rhs_mid(mode)
+        prev = switch(mode)
         try:
             for name, fn in fns.items():
                 for _ in range(3):
@@ -54,22 +61,24 @@ def alternate(fns, modes, rounds, iters):
                 torch.cuda.synchronize()
                 paths[(name, mode)] = int(_lib.load().ndcn_debug_last_rhs_path())
         finally:
-            hip.set_rhs_mid(prev)
+            switch(prev)
     for _ in range(rounds):
         for mode in modes:
-            prev = hip.set_rhs_mid(mode)
+            prev = switch(mode)
             try:
                 for name, fn in fns.items():
                     out.setdefault((name, mode), []).append(timed(fn, iters))
             finally:
-                hip.set_rhs_mid(prev)
+                switch(prev)
     return out, paths
 
 
-def report(rows, what, graph, n, H, res, paths, sink):
+def report(rows, what, graph, n, H, res, paths, sink, dropout=None):
     for (name, mode), ms in sorted(res.items()):
         row = {'what': what, 'launch': name, 'graph': graph, 'n': n, 'H': H, 'mode': mode, 'path': paths.get((name, mode)),
                'ms_median': round(statistics.median(ms), 5), 'ms_min': round(min(ms), 5), 'ms_max': round(max(ms), 5), 'rounds': len(ms)}
+        if dropout is not None:                                # the modes alternated were the dropout switch's, inside mode 2
+            row.update({'mode': 2, 'dropout': dropout, 'drop_switch': mode})
         rows.append(row)
         line = json.dumps(row)
         print(line, flush=True)
@@ -78,7 +87,7 @@ def report(rows, what, graph, n, H, res, paths, sink):
             sink.flush()
 
 
-def launches(m, H, dev):
+def launches(m, H, dev, dropout=None):
     A = graphs.to_device(m, dev)
     n = m.shape[0]
     g = torch.Generator(device=dev).manual_seed(0)
@@ -88,6 +97,12 @@ def launches(m, H, dev):
     y0 = torch.randn(n, H, generator=g, device=dev)
     ks = [torch.randn(n, H, generator=g, device=dev) for _ in range(5)]
     K, yn = torch.empty_like(X), torch.empty_like(X)
+    if dropout is not None:
+        d = lambda e: (dropout, 1234567, e)
+        return {'plain': lambda: hip.rhs(A, X, W, b, out=K, dropout=d(0)),
+                'combine0': lambda: hip.rhs_rk(A, X, W, b, 'combine', y0, [], CS[5:], out_K=K, out_y=yn, dropout=d(1)),
+                'combine5': lambda: hip.rhs_rk(A, X, W, b, 'combine', y0, ks, CS, out_K=K, out_y=yn, dropout=d(2)),
+                'rk4_stage3': lambda: hip.rhs_rk(A, X, W, b, 'rk4', y0, ks[:3], [0.37], out_K=K, out_y=yn, dropout=d(3))}
     return {'plain': lambda: hip.rhs(A, X, W, b, out=K),
             'combine5': lambda: hip.rhs_rk(A, X, W, b, 'combine', y0, ks, CS, out_K=K, out_y=yn)}
 
@@ -111,6 +126,8 @@ def main():
     p.add_argument('--iters', type=int, default=30)
     p.add_argument('--out', default=None)
     p.add_argument('--quick', action='store_true', help='one width and a 64 x 64 lattice: a rehearsal of every code path')
+    p.add_argument('--dropout', type=float, default=None, metavar='P',
+                   help='time the dropout launches with probability P: ndcn_set_rhs_mid_drop off against on, in mode 2')
     a = p.parse_args()
     assert torch.cuda.is_available(), 'a timing needs the device'
     dev = torch.device('cuda:0')
@@ -118,6 +135,21 @@ def main():
     rows = []
     side = 64 if a.quick else 316
     widths = (64,) if a.quick else (16, 20, 32, 64, 128)
+    if a.dropout is not None:
+        cases = [('lattice %d x %d' % (side, side), lattice(side), (64,) if a.quick else (16, 20, 32, 64, 96, 128))]
+        if not a.quick:
+            cases.append(('pubmed', pubmed(), (16, 64)))
+        prev = hip.set_rhs_mid(2)
+        try:
+            for graph, m, hs in cases:
+                for H in hs:
+                    res, paths = alternate(launches(m, H, dev, a.dropout), (0, 1), a.rounds, a.iters, switch=hip.set_rhs_mid_drop)
+                    report(rows, 'dropout launch', graph, m.shape[0], H, res, paths, sink, dropout=a.dropout)
+        finally:
+            hip.set_rhs_mid(prev)
+        if sink:
+            sink.close()
+        return
     cases = [('lattice %d x %d' % (side, side), lattice(side), widths)]
     if not a.quick:
         cases.append(('pubmed', pubmed(), (64,)))
