@@ -678,12 +678,15 @@ NDCN_API int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int
  * ndcn_solver_advance_many writes there.  The steps, their launches and the accept / reject log are ndcn_solver_advance_many's.
  *   dopri5      the ticks of a fresh accepted step are evaluated AND decoded in one pass over the step's panels (<= 8 per launch: a
  *               wave per row holds the fitted row in registers and dots it with Wd in the lane order of the decoder's row-dot
- *               kernel); the single-tick paths (a stored fit, a tick without a fresh step) evaluate into `scratch` first
+ *               kernel; H < 64, where the decoder runs one in-order fma chain per (row, output): a workgroup per tile of 64 rows
+ *               evaluates each tick into LDS and runs those chains from there); the single-tick paths (a stored fit, a tick without
+ *               a fresh step) evaluate into `scratch` first
  *   fixed grid  one step per tick with the state inside the solver (Euler whose update rides in the right-hand side's epilogue
  *               alternates between the solver's panel and `scratch`), each new state decoded by ndcn_linear_f32
  *   scratch     caller-owned device memory, room for two n_rows x H panels (the staged ticks and the Euler alternation use the
  *               first; the second is reserved); free after the call
- * Declines with NDCN_EINVAL: a sharded solver; H outside 64..512 or C outside 1..15 (the decoder's row-dot route); a fixed-grid
+ * Declines with NDCN_EINVAL: a sharded solver; H neither in 64..512 (the decoder's row-dot route) nor one of 16, 20, .. 60 (its small
+ * route at the widths of the one-launch right-hand side), or C outside 1..15; a fixed-grid
  * solve that ndcn_solve_small_supported would run as one launch (states of at most 1 MB: decode that trajectory instead).  The
  * step_size grid has no such form: ndcn_solver_advance_grid writes hidden ticks.  These are decided before anything else, so a call
  * with n_ticks = 0 (valid before ndcn_solver_begin, touches nothing) asks whether the solver would decline.
@@ -692,6 +695,7 @@ NDCN_API int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int
 #define NDCN_READOUT_FUSED   1      /* the fused dense-output kernel ran (interp_readout_kernel<ceil(H / 64)>)                       */
 #define NDCN_READOUT_STAGED  2      /* a dopri5 tick was evaluated into `scratch` and decoded from there                            */
 #define NDCN_READOUT_FIXED   4      /* fixed grid: the state decoded after each step                                                */
+#define NDCN_READOUT_NARROW  8      /* beside FUSED: H < 64, the 64-row tile kernel (readout_narrow_kernel<ceil(H / 16)>)           */
 NDCN_API int ndcn_solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd,
                                               int C, float *out, float *scratch, void *stream);
 NDCN_API int ndcn_last_readout_path(void);

@@ -34,6 +34,8 @@ SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 2
 (RKF_COMBINE, RKF_ERROR, RKF_SUMSQ, RKF_INTERP_FIT, RKF_INTERP_EVAL, RKF_INTERP_DIRECT, RKF_INTERP_DIRECT_MULTI, RKF_FIXED_STAGE,
  RKF_TICK_EMIT, RKF_FIXED_STAGE_EMIT, RKF_SCALE, RKF_COPY, RKF_RELU_BWD) = range(1, 14)
 RKF_KERNEL_MASK, RKF_OP_SHIFT, RKF_VEC, RKF_ATEN, RKF_PAR64, RKF_GRID_SHIFT = 0xff, 8, 0x1000, 0x2000, 0x4000, 32
+# ndcn_last_readout_path: what the last ndcn_solver_advance_many_readout call ran (include/ndcn_hip.h NDCN_READOUT_*)
+READOUT_FUSED, READOUT_STAGED, READOUT_FIXED, READOUT_NARROW = 1, 2, 4, 8
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6

@@ -226,7 +226,8 @@ int interp_direct_f32(const float *y0, const float *y1, const float *const *h_k,
 int interp_direct_multi_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                             const float *h_xp, float *const *h_out, int nt, int64_t n, hipStream_t st);
 // the same pass with the decoder Linear(H, C) applied in registers: h_out holds nt panels of n_rows x C, each bit for bit
-// linear_f32 (row-dot route) of the tick panel interp_direct_multi_f32 would write; 64 <= H <= 512, 1 <= C <= 15
+// linear_f32 of the tick panel interp_direct_multi_f32 would write; 64 <= H <= 512 (its row-dot route) or 16 <= H <= 60 in fours
+// (its small route: a 64-row tile per workgroup), 1 <= C <= 15
 int interp_readout_supported(int H, int C);
 int interp_readout_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, const float *h_xp,
                        float *const *h_out, int nt, const float *Wd, const float *bd, int64_t n_rows, int H, int C, hipStream_t st);

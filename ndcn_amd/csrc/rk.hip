@@ -599,6 +599,110 @@ __global__ __launch_bounds__(256) void interp_readout_kernel(ReadoutArgs p, cons
     }
 }
 
+// The same contract for narrow rows (16 <= H <= 60, H % 4 == 0: rhs_mid.hip's widths below the row-dot route), where ndcn_linear_f32
+// takes linear_small_kernel: acc = 0, acc = fmaf(s[k], w[k], acc) for k = 0 .. H - 1 in order, then acc += bias[o] - ONE sequential
+// chain per (row, o), no butterfly.  A wave per row would idle 44 of 64 lanes at H = 20, so a workgroup takes a tile of 64
+// consecutive rows - a contiguous span of 64 H floats in every panel - instead:
+//   fit    thread x holds the quads (4 consecutive elements of one row, H % 4 == 0) x + 256 j, j < NQ = ceil(H / 16), of the span:
+//          coalesced float4 loads, at most 16 elements' a, b, c, d, y0 in registers (fit1: the arithmetic of the tick panels)
+//   tick   the threads evaluate their elements (poly1) into an LDS tile [64][H + 1] - the odd leading dimension lets the 64 lanes of
+//          a wave walk 64 rows without a bank conflict - and after ONE barrier (two tiles alternate, so the next tick's writes need
+//          none) lane l of wave w runs the in-order chains of row l for the outputs o = w, w + 4, w + 8, w + 12 < C side by side: the
+//          element s[k] is read once for up to four chains, the decoder's row comes from LDS as a wave-wide broadcast float4
+// Rows past n_rows in the last tile are neither read nor written.  (2 + m) P read, nt N C 4 written.
+constexpr int kNarrowRows = 64;
+
+template <bool VEC>
+__device__ __forceinline__ float4 ldq(const float *p, int64_t q) {
+    return VEC ? ld4(p, q) : make_float4(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3]);
+}
+template <bool VEC>
+__device__ __forceinline__ float4 wsumq(const Terms &t, int64_t q) {
+    return VEC ? wsum4(t, q) : make_float4(wsum1(t, 4 * q), wsum1(t, 4 * q + 1), wsum1(t, 4 * q + 2), wsum1(t, 4 * q + 3));
+}
+
+template <int NQ, bool VEC>          // NQ = ceil(H / 16) <= 4; VEC: every panel is 16-byte aligned
+__global__ __launch_bounds__(256) void readout_narrow_kernel(ReadoutArgs p, const float *__restrict__ Wd,
+                                                             const float *__restrict__ bd, int64_t n_rows, int H, int C) {
+    extern __shared__ float4 narrow_smem[];                         // Wd [C][H] | bd [16] | two tiles [64][H + 1]
+    float *Wl = reinterpret_cast<float *>(narrow_smem);
+    float *bl = Wl + C * H;
+    float *tiles = bl + 16;
+    const int tid = threadIdx.x, LD = H + 1, H4 = H / 4;
+    const int row = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < C * H; i += 256) Wl[i] = Wd[i];
+    if (tid < 16) bl[tid] = (bd && tid < C) ? bd[tid] : 0.f;
+    int lofs[NQ];                                                   // where quad j of this thread starts in a tile
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int e = 4 * (tid + 256 * j), r = e / H;
+        lofs[j] = r * LD + (e - r * H);
+    }
+    __syncthreads();
+    const int64_t row0 = (int64_t)blockIdx.x * kNarrowRows;            // a tile per workgroup: what the fit reads is dead before the ticks
+    const int live = (int)(n_rows - row0 < kNarrowRows ? n_rows - row0 : kNarrowRows);
+    const int nq_live = live * H4;                              // quads of the tile's live rows (<= 16 H)
+    const int64_t q0 = row0 * H4;
+    float4 a[NQ], b[NQ], c[NQ], d[NQ], y0[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        a[j] = b[j] = c[j] = d[j] = y0[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid + 256 * j < nq_live) {
+            const int64_t q = q0 + tid + 256 * j;
+            const float4 ms = wsumq<VEC>(p.f.mid, q);
+            const float4 y1 = ldq<VEC>(p.f.y1, q), f0 = ldq<VEC>(p.f.f0, q), f1 = ldq<VEC>(p.f.f1, q);
+            y0[j] = ldq<VEC>(p.f.y0, q);
+            fit1(y0[j].x, y1.x, ms.x, f0.x, f1.x, p.f.dt, a[j].x, b[j].x, c[j].x, d[j].x);
+            fit1(y0[j].y, y1.y, ms.y, f0.y, f1.y, p.f.dt, a[j].y, b[j].y, c[j].y, d[j].y);
+            fit1(y0[j].z, y1.z, ms.z, f0.z, f1.z, p.f.dt, a[j].z, b[j].z, c[j].z, d[j].z);
+            fit1(y0[j].w, y1.w, ms.w, f0.w, f1.w, p.f.dt, a[j].w, b[j].w, c[j].w, d[j].w);
+        }
+    }
+    // (a run-time loop, as in the kernel above)
+#pragma unroll 1
+    for (int t = 0; t < p.nt; ++t) {
+        float *buf = tiles + (t & 1) * (kNarrowRows * LD);
+#pragma unroll
+        for (int j = 0; j < NQ; ++j)
+            if (tid + 256 * j < nq_live) {
+                float *h = buf + lofs[j];
+                h[0] = poly1(a[j].x, b[j].x, c[j].x, d[j].x, y0[j].x, p.xp[t]);
+                h[1] = poly1(a[j].y, b[j].y, c[j].y, d[j].y, y0[j].y, p.xp[t]);
+                h[2] = poly1(a[j].z, b[j].z, c[j].z, d[j].z, y0[j].z, p.xp[t]);
+                h[3] = poly1(a[j].w, b[j].w, c[j].w, d[j].w, y0[j].w, p.xp[t]);
+            }
+        __syncthreads();
+        if (row < live && wv < C) {
+            const float *s = buf + row * LD;
+            const float4 *W4 = reinterpret_cast<const float4 *>(Wl);
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int k4 = 0; k4 < H4; ++k4) {
+                const float s0 = s[4 * k4], s1 = s[4 * k4 + 1], s2 = s[4 * k4 + 2], s3 = s[4 * k4 + 3];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o = wv + 4 * j;                   // (wave-uniform)
+                    if (o < C) {
+                        const float4 w = W4[o * H4 + k4];
+                        acc[j] = fmaf(s0, w.x, acc[j]);
+                        acc[j] = fmaf(s1, w.y, acc[j]);
+                        acc[j] = fmaf(s2, w.z, acc[j]);
+                        acc[j] = fmaf(s3, w.w, acc[j]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int o = wv + 4 * j;
+                if (o < C) {
+                    float r = acc[j];
+                    if (bd) r += bl[o];
+                    p.out[t][(row0 + row) * C + o] = r;
+                }
+            }
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------- fixed-grid stages
 template <int OP>
 __device__ __forceinline__ float stage1(float y, float k1, float k2, float k3, float k4, float dt) {
@@ -1000,13 +1104,16 @@ int interp_direct_multi_f32(const float *y0, const float *y1, const float *const
     return NDCN_OK;
 }
 
-int interp_readout_supported(int H, int C) { return H >= 64 && H <= 512 && C >= 1 && C <= 15; }
+// 64..512: the wave-per-row kernel (the decoder's row-dot route); 16..60 in fours: the 64-row tile kernel (its small route)
+int interp_readout_supported(int H, int C) {
+    return ((H >= 64 && H <= 512) || (H >= 16 && H <= 60 && H % 4 == 0)) && C >= 1 && C <= 15;
+}
 
 int interp_readout_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, const float *h_xp,
                        float *const *h_out, int nt, const float *Wd, const float *bd, int64_t n_rows, int H, int C, hipStream_t st) {
     g_last_rk_path = 0;
     if (nt < 1 || nt > kMaxTicks) { set_error("interp_readout: 1..%d ticks per launch", kMaxTicks); return NDCN_EINVAL; }
-    if (!interp_readout_supported(H, C)) { set_error("interp_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C); return NDCN_EINVAL; }
+    if (!interp_readout_supported(H, C)) { set_error("interp_readout: 64 <= H <= 512 (the row-dot route of ndcn_linear_f32) or 16 <= H <= 60 in fours (its small route), and 1 <= C <= 15, got H = %d, C = %d", H, C); return NDCN_EINVAL; }
     if (!y0 || !y1 || !Wd) { set_error("interp_readout: null argument"); return NDCN_EINVAL; }
     ReadoutArgs p;
     const float *kk[kMaxTerms];
@@ -1030,6 +1137,28 @@ int interp_readout_f32(const float *y0, const float *y1, const float *const *h_k
     if (n_rows == 0) return NDCN_OK;
     const double P = (double)n_rows * H;
     ProfScope prof(PROF_EVAL, st, 4.0 * P * (2 + m) + 4.0 * nt * (double)n_rows * C, 2.0 * P * (m + 16 + (9 + C) * nt));
+    if (H < 64) {                                                   // a workgroup per tile of 64 rows
+        bool vec = aligned16(y0) && aligned16(y1) && aligned16(h_k[0]) && aligned16(h_k[6]);
+        for (int j = 0; j < m; ++j) vec = vec && aligned16(kk[j]);
+        const int64_t n_tiles = (n_rows + kNarrowRows - 1) / kNarrowRows;
+        if (n_tiles > 0x7fffffffll) { set_error("interp_readout: %lld rows are more tiles than one launch holds", (long long)n_rows); return NDCN_EINVAL; }
+        const int gn = (int)n_tiles;
+        const size_t lds = ((size_t)C * H + 16 + 2 * (size_t)kNarrowRows * (H + 1)) * sizeof(float);      // <= 34.9 KB
+#define NDCN_RON(NQ_)                                                                                                         \
+    do {                                                                                                                      \
+        if (vec) hipLaunchKernelGGL((readout_narrow_kernel<NQ_, true>), dim3(gn), dim3(256), lds, st, p, Wd, bd, n_rows, H, C);   \
+        else hipLaunchKernelGGL((readout_narrow_kernel<NQ_, false>), dim3(gn), dim3(256), lds, st, p, Wd, bd, n_rows, H, C);      \
+    } while (0)
+        switch ((H + 15) / 16) {
+            case 1: NDCN_RON(1); break;
+            case 2: NDCN_RON(2); break;
+            case 3: NDCN_RON(3); break;
+            default: NDCN_RON(4); break;
+        }
+#undef NDCN_RON
+        NDCN_LAUNCH_CHECK();
+        return NDCN_OK;
+    }
     const int g = stream_grid(n_rows * 64, 256);
 #define NDCN_RO(NV_) hipLaunchKernelGGL((interp_readout_kernel<NV_>), dim3(g), dim3(256), 0, st, p, Wd, bd, n_rows, H, C)
     switch ((H + 63) / 64) {

@@ -1261,7 +1261,8 @@ thread_local int g_last_readout_path = 0;
 // solver_advance_many with the decoder Linear(H, C) applied to every tick as it is produced (inference: neural_dynamics.py:148-160
 // decodes the whole (T, N, H) trajectory afterwards): the same steps, launches and accept / reject log, but out[i] is the n_rows x C
 // readout Wd y(h_ticks[i]) + bd - bit for bit linear_f32 of the panel solver_advance_many writes - and no tick panel is stored.
-//   dopri5: the ticks of a fresh accepted step go through interp_readout_f32 (<= 8 per launch); the single-tick paths (a stored fit,
+//   dopri5: the ticks of a fresh accepted step go through interp_readout_f32 (<= 8 per launch; H < 64: its 64-row tile kernel,
+//           NDCN_READOUT_NARROW beside NDCN_READOUT_FUSED); the single-tick paths (a stored fit,
 //           a tick without a fresh step) evaluate into `scratch` and decode from there.
 //   fixed grid: each step keeps the state inside the solver (Euler with its algebra in the RHS epilogue alternates between the
 //           solver's panel and `scratch`, as solver_advance_grid does with a stage panel), then linear_f32 decodes it.
@@ -1273,7 +1274,7 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
     const bool fixed = s->d.method != NDCN_M_DOPRI5;
     if (s->sharded) { set_error("ndcn_solver_advance_many_readout: un-sharded solvers only (decode the shard's trajectory instead)"); return NDCN_EINVAL; }
     if (!interp_readout_supported(H, C)) {
-        set_error("ndcn_solver_advance_many_readout: 64 <= H <= 512 and 1 <= C <= 15 (the row-dot route of ndcn_linear_f32), got H = %d, C = %d", H, C);
+        set_error("ndcn_solver_advance_many_readout: 64 <= H <= 512 (the row-dot route of ndcn_linear_f32) or 16 <= H <= 60 in fours (its small route), and 1 <= C <= 15, got H = %d, C = %d", H, C);
         return NDCN_EINVAL;
     }
     if (fixed && s->kind != Rhs::Dyn && solve_small_supported(&s->d.A, H, s->d.rhs_flags, s->d.method)) {
@@ -1311,7 +1312,7 @@ int solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n
             float *outs[8];
             for (int t = 0; t < nt; ++t) outs[t] = out + (size_t)(first + t) * ostride;
             const int rc1 = interp_readout_f32(s->ycur, s->ynext, kk, cm, s->fit_dt, xp, outs, nt, Wd, bd, rows, H, C, st);
-            if (!rc1) g_last_readout_path |= NDCN_READOUT_FUSED;
+            if (!rc1) g_last_readout_path |= NDCN_READOUT_FUSED | (H < 64 ? NDCN_READOUT_NARROW : 0);
             return rc1;
         },
         st);

@@ -72,8 +72,8 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_lo
 
     readout=(weight (C, H), bias (C,) or None): return `linear(odeint(...), weight, bias)`, shape (len(t), N, C), instead of the
     hidden states (neural_dynamics.py:148-160: NDCN decodes every tick).  Where nothing needs a gradient and the solve is
-    device-resident, the library decodes each tick as the solver produces it (ndcn_solver_advance_many_readout) and the
-    (len(t), N, H) trajectory is never stored; under a gradient, euler / midpoint / rk4 over ODEFunc on the fused-launch training
+    device-resident, the library decodes each tick as the solver produces it (ndcn_solver_advance_many_readout: H = 16, 20, .. 60
+    or 64 <= H <= 512, C <= 15) and the (len(t), N, H) trajectory is never stored; under a gradient, euler / midpoint / rk4 over ODEFunc on the fused-launch training
     path hold the decoder inside the solve's autograd node: the trajectory is stored once (the reverse sweep needs it) but the
     (len(t), N, H) gradient of it, which the Linear's own backward would write, is not - the sweep forms each tick's g . W where it
     adds it (ndcn_readout_bwd_f32); everywhere else the ordinary solve runs and the Linear is applied to its result - the
@@ -836,7 +836,8 @@ class DeviceSolver:
     def advance_many_readout(self, ticks, weight, bias, out, scratch):
         """advance_many with Linear(weight (C, H), bias (C,) or None) applied to every tick inside the library: out is
         (len(ticks), n_rows, C) and no hidden tick panel is stored; scratch: room for two n_rows x H panels.  Returns False where the
-        library declines (NDCN_EINVAL: a sharded solver, H outside 64..512, C outside 1..15, a state that the one-launch solve takes)
+        library declines (NDCN_EINVAL: a sharded solver, H neither in 64..512 nor one of 16, 20, .. 60, C outside 1..15, a state that
+        the one-launch solve takes)
         - nothing has been advanced then.  With no ticks (out and scratch may be None, before begin too) it only asks that question."""
         C = weight.shape[0]
         assert weight.is_contiguous() and weight.shape[1] == self.shape[1] and (bias is None or bias.is_contiguous())
