@@ -350,15 +350,13 @@ static int rhs_rk_entry(const ndcn_csr *A, const float *X, const float *X_halo, 
                        "x_mask / s_out: not supported for this operator / mode (ndcn_rhs_adj_supported), both given, or aliased");
     }
     const RkOpt opt = {y1, (flags & NDCN_F_ACCUM) ? 1 : 0, y_aux, h_c_aux, x_add, x_add_c, x_mask, s_out};
+    DropArgs d;
     if (drop) {
-        DropArgs d;
         int rc = drop_args(drop, &d);
         if (rc) return rc;
-        return rhs_rk_drop_f32(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol,
-                               d_out, d_ws, ST(stream), &opt, d);
     }
     return rhs_rk_f32(A, X, X_halo, n_own, W, b, K, work, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol,
-                      d_out, d_ws, ST(stream), &opt);
+                      d_out, d_ws, ST(stream), &opt, drop ? &d : nullptr);
 }
 
 int ndcn_rhs_rk_f32(const ndcn_csr *A, const float *X, const float *X_halo, int64_t n_own, const float *W, const float *b,

@@ -34,7 +34,7 @@ int gather_rows_f32(const float *X, const int32_t *idx, int64_t n_idx, int H, fl
 int linear_f32(const float *S, const float *W, const float *b, float *Y, int64_t n, int Hi, int Ho, uint32_t flags,
                hipStream_t st);
 int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-            float *work, int H, uint32_t flags, hipStream_t st);
+            float *work, int H, uint32_t flags, hipStream_t st, const DropArgs *drop = nullptr);
 int64_t rhs_work_bytes(int64_t n_rows, int H, uint32_t flags);
 int linear_bwd_f32(const float *g, const float *Y, const float *S, const float *W, float *gS, float *gW, float *gb, void *work,
                    int64_t n, int Hi, int Ho, hipStream_t st, uint32_t flags = 0, float acc_scale = 1.f, bool accumulate = false);
@@ -45,7 +45,7 @@ int copy_f32(float *dst, const float *src, int64_t n, hipStream_t st);
 int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
                const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
-               hipStream_t st, const RkOpt *opt = nullptr);
+               hipStream_t st, const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
 int rhs_fused_supported(int H, uint32_t flags);
 int pack_weight_256(const float *W, float *Wp, hipStream_t st);
 // the image at Wp was packed from weights whose in-row range exceeds the split product's guarantee (split16.h: kS16GuardBits): the
@@ -109,7 +109,7 @@ int rhs_small_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_
 // (with RkOpt::y_aux / c_aux) or NDCN_RK_RK4; every panel 16-byte aligned, no halo panel; the bits of the composed path.  The switch
 // (ndcn_set_rhs_mid / NDCN_RHS_MID): 0 off, 1 wherever rhs_small.hip does not take the shape, 2 every supported shape.  drop: the factor
 // of csrc/dropout.h in the epilogue (NDCN_F_RELU required) - K as stored and as consumed by the stage algebra is the masked one; the
-// dropout calls of rhs.hip come here only under a switch of their own (ndcn_set_rhs_mid_drop / NDCN_RHS_MID_DROP: 0 off, 1 on)
+// masked calls of rhs.hip come here only under a switch of their own (ndcn_set_rhs_mid_drop / NDCN_RHS_MID_DROP: 0 off, 1 on)
 int rhs_mid_mode();
 int set_rhs_mid(int mode);                    // ndcn_set_rhs_mid: returns the previous mode; < 0: back to the environment's
 int rhs_mid_drop_on();
@@ -135,20 +135,14 @@ int rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *At, const float *X, const flo
                 bool premasked, float acc_scale, float alpha, bool accumulate, bool direct, bool *packed, hipStream_t st);
 int64_t rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
 int64_t rhs_vjp_gs_offset(int64_t n_rows, int H);
-// dropout (csrc/dropout.h; rhs.hip): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1), the streaming pass K *= m, and
-// rhs_f32 / rhs_rk_f32 with the mask - in the epilogue of the narrow-panel launch and (under ndcn_set_rhs_mid_drop) of the rhs_mid.hip
-// launch, by the streaming pass behind every other route
+// dropout (csrc/dropout.h): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1) and the streaming pass K *= m.  rhs_f32 /
+// rhs_rk_f32 take the mask as their last argument (NULL: p = 0 or eval mode) and the one dispatch of rhs.hip places it: in the epilogue
+// of the narrow-panel launch and (under ndcn_set_rhs_mid_drop) of the rhs_mid.hip launch, by the streaming pass behind every other route
 int drop_args(const ndcn_dropout *desc, DropArgs *out);
 int dropout_apply_f32(float *K, int64_t n, const DropArgs &d, hipStream_t st);
 // dropout_apply_f32(K) and rk_combine_f32(out, y0, {h_kprev..., K}, h_c, n_prev + 1) as one pass (h_c[n_prev]: K's coefficient): the same bits
 int dropout_combine_f32(float *K, int64_t n, const DropArgs &d, float *out, const float *y0, const float *const *h_kprev, const float *h_c,
                         int n_prev, hipStream_t st);
-int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-                 float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st);
-int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
-                    float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
-                    const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
-                    hipStream_t st, const RkOpt *opt, const DropArgs &d);
 // solve_small.hip: a whole fixed-grid solve (all ticks) in ONE launch for states that fit one CU; h_dt: the n_ticks step sizes in
 // the state dtype; out: n_ticks panels.  Euler also has the reverse sweep (traj / g_out: n_ticks + 1 panels, y_0 first).
 int solve_small_supported(const ndcn_csr *A, int H, uint32_t flags, int method);

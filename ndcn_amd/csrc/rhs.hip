@@ -1,8 +1,8 @@
-// ODEFunc.forward as one entry point: Y = relu(W (A X) + b)   (neural_dynamics.py:20-39).
-// H = 256 runs the fused kernel (rhs_fused.hip); other widths compose the SpMM and the MFMA Linear through a
-// scratch panel.  rhs_f32 / rhs_rk_f32 are the p = 0 (and eval-mode) forms; rhs_drop_f32 / rhs_rk_drop_f32 at the end of the file
-// add the dropout factor of csrc/dropout.h - inside the narrow-panel launch and, under its own switch, inside the rhs_mid.hip launch,
-// as a streaming pass behind every other route.
+// ODEFunc.forward as one entry point: Y = relu(W (A X) + b)   (neural_dynamics.py:20-39), with or without the stage algebra of an RK
+// step behind it and with or without the dropout factor of csrc/dropout.h on it.  One dispatch serves every caller that is not the device
+// solver's own launch kind: pick() decides which launch forms K (the table on enum class Rhs), rhs_rk_f32 switches on it.  The mask is
+// an optional argument all the way down: in the epilogue of the narrow-panel launch and, under its own switch, of the rhs_mid.hip
+// launch; a streaming pass behind every other route.
 #include <stdio.h>
 
 #include <atomic>
@@ -44,15 +44,64 @@ int64_t rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) {
     return n_rows * (int64_t)H * (int64_t)sizeof(float);                        // S = A X between the two kernels
 }
 
-// rhs_mid.hip takes the launch: the switch is on for this shape, no halo panel, 16-byte aligned panels
-static bool mid_takes(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags) {
-    const int mode = rhs_mid_mode();
-    return mode != 0 && !Xh && rhs_mid_supported(A->n_rows, H, flags, mode) && aligned16(X) && aligned16(W) && aligned16(K);
-}
+// Which launch forms K for one call of rhs_rk_f32 (mode 0: rhs_f32), decided once by pick() - the first row that holds, top to bottom:
+//   kind      rides in the launch    chosen when                                                              the launch
+//   Fused     stage algebra          no mask, mode != 0, graph and control, rhs_fused2_supported (H = 256),   rhs_fused2_f32 / rhs_fused2_exact_f32
+//                                    rhs_fused2_variant
+//   Mid       stage algebra, mask    `mid` (below), and mode 0, or COMBINE / RK4 with y0, y_next, y_aux and   rhs_mid_f32
+//                                    every kprev 16-byte aligned
+//   Small     stage algebra, mask    small_takes - unless `mid` holds in ERROR mode (MidPlain keeps it)       rhs_small_f32
+//   Rec       stage algebra          no mask, mode != 0, no_control, aligned panels, spmm_rec_supported,      spmm_rec_f32
+//                                    spmm_rec_variant, rows * 1 KiB < 4 GiB
+//   Wide      stage algebra          no mask, mode != 0, no_control, aligned panels, spmm_wide_rk_supported,  spmm_wide_rk_f32
+//                                    not a shape of the column sweep (rhs_plain runs it)
+//   MidPlain  mask                   `mid` - ERROR mode, or a misaligned stage panel that Small left here -   rhs_mid_f32 in mode 0, then rk_stage_f32
+//                                    unless mask_combines
+//   Composed  nothing                everything else                                                          rhs_plain, then the mask pass and
+//                                                                                                             rk_stage_f32, or (mask_combines)
+//                                                                                                             dropout_combine_f32 for both
+//   mid: ndcn_set_rhs_mid takes the shape (rhs_mid_supported: graph and control, 16 <= H <= 128 in fours) - with a mask only under
+//   ndcn_set_rhs_mid_drop too -, no halo panel, X, W and K 16-byte aligned, none of the RkOpt fields of mid_declines.
+// Mode 0 reads neither stage arguments nor RkOpt, so only Mid, Small and Composed occur there.  H = 256 under a mask is always Composed.
+enum class Rhs { Fused, Mid, Small, Rec, Wide, MidPlain, Composed };
 
-// rhs_small.hip takes the launch (and, alone among the routes below H = 256, carries dropout and RkOpt::s_out in it)
-static bool small_takes(const ndcn_csr *A, int H, uint32_t flags) {
-    return !(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !rhs_fused_supported(H, flags) && rhs_small_supported(A, H, flags);
+// the RkOpt fields that exist only inside the H = 256 launches (s_out: and the narrow-panel one); none of them has a dropout form
+static bool fused_only(const RkOpt *o) { return o && (o->xadd || o->xmask || o->s_out || o->c_mid); }
+// ... and the ones rhs_mid.hip declines
+static bool mid_declines(const RkOpt *o) { return fused_only(o) || (o && o->no_k); }
+
+// rhs_small.hip takes the shape.  rhs_small_supported implies graph and control and H <= 128, hence never a shape of the H = 256 kernels
+static bool small_takes(const ndcn_csr *A, int H, uint32_t flags) { return rhs_small_supported(A, H, flags) != 0; }
+
+// under a mask, COMBINE without y_aux behind a launch that carries neither: dropout_combine_f32 masks K and forms the sum in ONE pass
+// (one launch and one panel read fewer than the mask pass and rk_combine_f32; the same bits)
+static bool mask_combines(int mode, const RkOpt *opt) { return mode == NDCN_RK_COMBINE && !(opt && opt->y_aux); }
+
+static Rhs pick(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags, int mode,
+                const float *y0, const float *const *h_kprev, int n_prev, const float *y_next, const RkOpt *opt, bool masked) {
+    const bool graph_only = !(flags & NDCN_F_NO_GRAPH) && (flags & NDCN_F_NO_CONTROL);
+    const bool bare_stage = !masked && mode != 0;       // the H = 256 and the graph-only launches carry the stage algebra only, and no mask
+    if (bare_stage && rhs_fused2_supported(A, H, flags) && rhs_fused2_variant(mode, n_prev)) return Rhs::Fused;
+    const int mid_mode = rhs_mid_mode();
+    const bool mid = mid_mode != 0 && (!masked || rhs_mid_drop_on()) && !Xh && !mid_declines(opt) &&
+                     rhs_mid_supported(A->n_rows, H, flags, mid_mode) && aligned16(X) && aligned16(W) && aligned16(K);
+    if (mid && mode != NDCN_RK_ERROR) {                 // ERROR: its plain launch and rk_error_f32, which keeps the record's summation
+        bool epi = true;
+        if (mode != 0) {
+            epi = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
+            for (int m = 0; m < n_prev; ++m) epi = epi && h_kprev && aligned16(h_kprev[m]);
+        }
+        if (epi) return Rhs::Mid;
+    }
+    if (!(mid && mode == NDCN_RK_ERROR) && small_takes(A, H, flags)) return Rhs::Small;
+    if (bare_stage && graph_only && aligned16(X) && aligned16(K) && (!Xh || aligned16(Xh))) {
+        // relu(A X) with the stage algebra in the epilogue of the group-record SpMM (spmm_rec.hip), or of the wide one on any other graph
+        if (spmm_rec_supported(A, H) && spmm_rec_variant(mode, n_prev) && A->n_rows * (int64_t)1024 < (1ll << 32)) return Rhs::Rec;
+        const bool swept = !Xh && H == 256 && spmm_sweep_supported(A, H);
+        if (!swept && spmm_wide_rk_supported(A, H)) return Rhs::Wide;
+    }
+    if (mid && !(masked && mask_combines(mode, opt))) return Rhs::MidPlain;
+    return Rhs::Composed;
 }
 
 // RkOpt::s_out can be honoured: the lattice-plan kernel (rhs_adj_supported), or the narrow-panel one
@@ -60,15 +109,13 @@ int rhs_s_out_supported(const ndcn_csr *A, int H, uint32_t flags, int mode, int 
     return rhs_adj_supported(A, H, flags, mode, n_prev) || small_takes(A, H, flags);
 }
 
-// allow_mid = false: the callers whose launch rhs_mid.hip declines (the composed dropout forms, which mask K behind this launch; RkOpt
-// fields of the H = 256 launches)
+// K by the launches that carry neither stage algebra nor mask (Rhs::Composed)
 static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-                     float *work, int H, uint32_t flags, hipStream_t st, bool allow_mid) {
+                     float *work, int H, uint32_t flags, hipStream_t st) {
     const bool graph = !(flags & NDCN_F_NO_GRAPH), ctl = !(flags & NDCN_F_NO_CONTROL);
     const uint32_t act = flags & NDCN_F_RELU;
     const int64_t n = A->n_rows;
     if (graph && ctl) {
-        if (!work) { set_error("rhs: scratch of ndcn_rhs_work_bytes() bytes required for H=%d", H); return NDCN_EINVAL; }
         if (rhs_fused_supported(H, flags)) {
             if (rhs_fused2_supported(A, H, flags)) {          // operator carries a row-group union plan
                 if (!(aligned16(X) && aligned16(Y) && aligned16(W) && aligned16(work) && (!Xh || aligned16(Xh)))) {
@@ -87,15 +134,7 @@ static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t
             }
             return rhs_fused_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, st);
         }
-        // 16 <= H <= 128 at any size: gather, MFMA Linear, ReLU in one launch.  The report's MID bit is this branch's own; its other bits
-        // belong to the launches with a stage epilogue and stay as the last of them left them (rhs_rk_f32 and the dropout forms zero them
-        // before they come here; after a plain ndcn_rhs_f32 they still name the thread's previous such launch)
-        const bool mid = allow_mid && mid_takes(A, X, Xh, W, Y, H, flags);
-        g_last_rhs_path = mid ? NDCN_PATH_MID : (g_last_rhs_path & ~NDCN_PATH_MID);
-        if (mid) return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st);
-        if (rhs_small_supported(A, H, flags))                     // narrow panels: SpMM -> Linear -> ReLU in one launch
-            return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr,
-                                 nullptr, st);
+        g_last_rhs_path &= ~NDCN_PATH_MID;                                     // (the report of a plain p = 0 call: rhs_rk_f32)
         int rc = spmm_f32(A, X, Xh, n_own, work, H, 1.f, 0, st);
         if (rc) return rc;
         return linear_f32(work, W, b, Y, n, H, H, act, st);
@@ -121,8 +160,9 @@ static int rhs_plain(const ndcn_csr *A, const float *X, const float *Xh, int64_t
 }
 
 int rhs_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-            float *work, int H, uint32_t flags, hipStream_t st) {
-    return rhs_plain(A, X, Xh, n_own, W, b, Y, work, H, flags, st, true);
+            float *work, int H, uint32_t flags, hipStream_t st, const DropArgs *drop) {
+    return rhs_rk_f32(A, X, Xh, n_own, W, b, Y, work, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st,
+                      nullptr, drop);
 }
 
 // the stage algebra over {kprev..., K} by the un-fused kernels, in the term order of the fused epilogues (K is the last term)
@@ -143,22 +183,44 @@ static int rk_stage_f32(int64_t n, const float *X, const float *K, int rk_mode, 
                         (opt && opt->accum) ? 1 : 0);
 }
 
+// drop (nullable): K' = relu(z) * m (csrc/dropout.h), K as stored and as the stage algebra consumes it.  Every route gives the bits of
+// Composed: the epilogues keep the term order of rk_stage_f32 on the (masked) K.
+// ndcn_debug_last_rhs_path: each launch with a stage epilogue or a mask sets the report outright (the H = 256 kernels their own).  A plain
+// p = 0 call owns only the MID bit: below H = 256, with graph and control, it sets or clears that one and leaves the others as the
+// thread's last such launch left them; on any other shape it leaves the report alone.
 int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
                const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
-               hipStream_t st, const RkOpt *opt) {
-    if (rk_mode == 0) return rhs_f32(A, X, Xh, n_own, W, b, K, work, H, flags, st);
+               hipStream_t st, const RkOpt *opt, const DropArgs *drop) {
+    if (drop && Xh) { set_error("dropout with a halo panel (sharded graphs) is not supported"); return NDCN_EINVAL; }
+    if (drop && !(flags & NDCN_F_RELU)) { set_error("dropout without NDCN_F_RELU is not supported"); return NDCN_EINVAL; }
+    if (rk_mode == 0) {                                 // reads neither the stage arguments nor RkOpt
+        y0 = nullptr; h_kprev = nullptr; h_c = nullptr; n_prev = 0; y_next = nullptr; rtol = atol = 0.f; d_out = nullptr; d_ws = nullptr;
+        opt = nullptr;
+    }
     if (n_prev < 0 || n_prev > 5) { set_error("rhs_rk: n_prev must be 0..5"); return NDCN_EINVAL; }
-    const bool both = !(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL));
-    if (both && rhs_fused2_supported(A, H, flags) && rhs_fused2_variant(rk_mode, n_prev)) {
+    if (drop && fused_only(opt)) { set_error("dropout with x_add / x_mask / s_out is not supported"); return NDCN_EINVAL; }
+    const Rhs kind = pick(A, X, Xh, W, K, H, flags, rk_mode, y0, h_kprev, n_prev, y_next, opt, drop != nullptr);
+    const bool plain_p0 = rk_mode == 0 && !drop;
+    // the scratch of rhs_work_bytes: rhs_plain's launches use it, and a p = 0 call without a stage epilogue asks for it whichever kernel runs
+    if (!(flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) && !work && (kind == Rhs::Composed || plain_p0 || (!drop && kind == Rhs::MidPlain))) {
+        set_error("rhs: scratch of ndcn_rhs_work_bytes() bytes required for H=%d", H);
+        return NDCN_EINVAL;
+    }
+    const int drop_epi = drop ? NDCN_PATH_DROP_EPI : 0;
+    const int halo = (Xh && A->n_cols > n_own) ? NDCN_PATH_HALO : 0;
+    const int64_t n = A->n_rows * (int64_t)H;
+    int rc;
+    switch (kind) {
+    case Rhs::Fused: {
         if (!work) { set_error("rhs_rk: scratch of ndcn_rhs_work_bytes() bytes required"); return NDCN_EINVAL; }
-        int rc = (flags & NDCN_F_PACKED) ? NDCN_OK : pack_weight_256(W, work, st);
+        rc = (flags & NDCN_F_PACKED) ? NDCN_OK : pack_weight_256(W, work, st);
         if (rc) return rc;
         const bool wide = weights_wide_range(work);
         // options that exist only inside the fused launches (input formed on the staged rows, S written on the side) have no composed
         // form: such a launch stays on the split product and says so (NDCN_PATH_RANGE; the solvers switch the options off instead)
-        const bool fused_only = opt && (opt->xadd || opt->xmask || opt->s_out);
-        if (!wide || fused_only) {
+        const bool no_fp32_form = opt && (opt->xadd || opt->xmask || opt->s_out);
+        if (!wide || no_fp32_form) {
             rc = rhs_fused2_f32(A, X, Xh, n_own, work, b, K, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol,
                                 d_out, d_ws, st, opt);
             if (wide) {
@@ -174,115 +236,35 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
         return rhs_fused2_exact_f32(A, X, Xh, n_own, work, b, K, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws,
                                     st, opt);
     }
-    // rhs_mid.hip: COMBINE and RK4 in its epilogue; an ERROR launch is its plain launch (rhs_plain below) and rk_error_f32, which keeps
-    // the record's summation.  It declines the RkOpt fields that exist only inside the H = 256 launches and misaligned panels.
-    const bool mid_opt = !(opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid || opt->no_k));
-    bool mid = both && mid_opt && mid_takes(A, X, Xh, W, K, H, flags);
-    if (mid && rk_mode != 2) {
-        mid = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
-        for (int m = 0; m < n_prev; ++m) mid = mid && h_kprev && aligned16(h_kprev[m]);
-        if (mid) {
-            g_last_rhs_path = NDCN_PATH_MID;
-            return rhs_mid_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt);
-        }
-    }
-    if (!mid && both && rhs_small_supported(A, H, flags)) {
-        g_last_rhs_path = NDCN_PATH_SMALL;
-        return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws,
-                             st, nullptr, opt);
-    }
-    // no_control: relu(A X) with the stage algebra in the epilogue of the group-record SpMM (spmm_rec.hip)
-    const bool graph_only = !(flags & NDCN_F_NO_GRAPH) && (flags & NDCN_F_NO_CONTROL);
-    if (graph_only && spmm_rec_supported(A, H) && spmm_rec_variant(rk_mode, n_prev) && A->n_rows * (int64_t)1024 < (1ll << 32) &&
-        aligned16(X) && aligned16(K) && (!Xh || aligned16(Xh))) {
-        g_last_rhs_path = NDCN_PATH_REC | ((Xh && A->n_cols > n_own) ? NDCN_PATH_HALO : 0);
+    case Rhs::Mid:
+        g_last_rhs_path = NDCN_PATH_MID | drop_epi;
+        return rhs_mid_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt, drop);
+    case Rhs::Small:
+        g_last_rhs_path = plain_p0 ? (g_last_rhs_path & ~NDCN_PATH_MID) : (NDCN_PATH_SMALL | drop_epi);
+        return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
+                             nullptr, opt, drop);
+    case Rhs::Rec:
+        g_last_rhs_path = NDCN_PATH_REC | halo;
         return spmm_rec_f32(A, X, Xh, n_own, K, 1.f, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                             nullptr, opt);
-    }
-    const bool swept = graph_only && !Xh && H == 256 && spmm_sweep_supported(A, H) && aligned16(X) && aligned16(K);
-    if (!swept && graph_only && spmm_wide_rk_supported(A, H) && aligned16(X) && aligned16(K) && (!Xh || aligned16(Xh))) {   // any other graph
-        g_last_rhs_path = NDCN_PATH_WIDE | ((Xh && A->n_cols > n_own) ? NDCN_PATH_HALO : 0);
+    case Rhs::Wide:
+        g_last_rhs_path = NDCN_PATH_WIDE | halo;
         return spmm_wide_rk_f32(A, X, Xh, n_own, K, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                                 nullptr, opt);
+    case Rhs::MidPlain:
+        g_last_rhs_path = NDCN_PATH_MID | drop_epi;
+        if ((rc = rhs_mid_f32(A, X, W, b, K, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st, nullptr, drop))) return rc;
+        return rk_stage_f32(n, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
+    case Rhs::Composed:
+        break;
     }
-    g_last_rhs_path = 0;
-    // composition with the same term order: K first, then the algebra over {kprev..., K}
-    int rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st, mid_opt);
-    if (rc) return rc;
-    return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
-}
-
-// ---------------------------------------------------------------------------------------------------- dropout
-// K' = relu(z) * m (csrc/dropout.h).  Narrow panels: the factor in the epilogue of the one launch (NDCN_PATH_DROP_EPI).  Every other
-// route: the launch without a stage epilogue, the streaming pass K *= m, then the un-fused stage kernel - the composition rhs_rk_f32
-// itself falls back to, hence the same bits as the fused epilogues would give on the masked K.  NDCN_RK_COMBINE without y_aux: the
-// last two as ONE pass (dropout_combine_f32), the same bits again.
-// Widths 16..128 with ndcn_set_rhs_mid_drop on: where rhs_rk_f32 would hand the p = 0 launch to rhs_mid.hip (mid_takes, no RkOpt field
-// of the H = 256 launches, aligned panels) the factor rides in that launch's epilogue (NDCN_PATH_MID | NDCN_PATH_DROP_EPI) - plain,
-// COMBINE with or without y_aux, RK4; ERROR as the plain dropout launch and rk_error_f32.  The bits of the composed forms above, and,
-// as for p = 0, ahead of the narrow-panel kernel where the mode takes the shape.
-// the dropout form of rhs_mid.hip takes the launch: its own switch on top of mid_takes (neither NO_ flag: rhs_mid_supported)
-static bool mid_drop_takes(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags) {
-    return rhs_mid_drop_on() && mid_takes(A, X, Xh, W, K, H, flags);
-}
-
-static int drop_check(const float *Xh, uint32_t flags) {
-    if (Xh) { set_error("dropout with a halo panel (sharded graphs) is not supported"); return NDCN_EINVAL; }
-    if (!(flags & NDCN_F_RELU)) { set_error("dropout without NDCN_F_RELU is not supported"); return NDCN_EINVAL; }
-    return NDCN_OK;
-}
-
-int rhs_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *Y,
-                 float *work, int H, uint32_t flags, const DropArgs &d, hipStream_t st) {
-    int rc = drop_check(Xh, flags);
-    if (rc) return rc;
-    if (mid_drop_takes(A, X, Xh, W, Y, H, flags)) {
-        g_last_rhs_path = NDCN_PATH_MID | NDCN_PATH_DROP_EPI;
-        return rhs_mid_f32(A, X, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st, nullptr, &d);
-    }
-    if (small_takes(A, H, flags)) {
-        g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
-        return rhs_small_f32(A, X, Xh, n_own, W, b, Y, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, nullptr, nullptr, st,
-                             nullptr, nullptr, &d);
-    }
-    g_last_rhs_path = 0;
-    if ((rc = rhs_plain(A, X, Xh, n_own, W, b, Y, work, H, flags, st, false))) return rc;
-    return dropout_apply_f32(Y, A->n_rows * (int64_t)H, d, st);
-}
-
-int rhs_rk_drop_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
-                    float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
-                    const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
-                    hipStream_t st, const RkOpt *opt, const DropArgs &d) {
-    if (rk_mode == 0) return rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st);
-    int rc = drop_check(Xh, flags);
-    if (rc) return rc;
-    if (n_prev < 0 || n_prev > 5) { set_error("rhs_rk: n_prev must be 0..5"); return NDCN_EINVAL; }
-    if (opt && (opt->xadd || opt->xmask || opt->s_out || opt->c_mid)) { set_error("dropout with x_add / x_mask / s_out is not supported"); return NDCN_EINVAL; }
-    // the predicate and precedence of rhs_rk_f32: COMBINE and RK4 in the launch's epilogue; an ERROR launch is the plain dropout launch
-    // (rhs_drop_f32 at the end) and rk_error_f32, not the narrow-panel kernel's
-    bool mid = !(opt && opt->no_k) && mid_drop_takes(A, X, Xh, W, K, H, flags);
-    if (mid && rk_mode != 2) {
-        mid = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
-        for (int m = 0; m < n_prev; ++m) mid = mid && h_kprev && aligned16(h_kprev[m]);
-        if (mid) {
-            g_last_rhs_path = NDCN_PATH_MID | NDCN_PATH_DROP_EPI;
-            return rhs_mid_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt, &d);
-        }
-    }
-    if (!mid && small_takes(A, H, flags)) {
-        g_last_rhs_path = NDCN_PATH_SMALL | NDCN_PATH_DROP_EPI;
-        return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
-                             nullptr, opt, &d);
-    }
-    if (rk_mode == 1 && !(opt && opt->y_aux)) {
-        // the stage sum consumes the masked K in the pass that forms it (dropout.hip): one launch and one panel read fewer
-        g_last_rhs_path = 0;
-        if ((rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st, false))) return rc;
-        return dropout_combine_f32(K, A->n_rows * (int64_t)H, d, y_next, y0, h_kprev, h_c, n_prev, st);
-    }
-    if ((rc = rhs_drop_f32(A, X, Xh, n_own, W, b, K, work, H, flags, d, st))) return rc;
-    return rk_stage_f32(A->n_rows * (int64_t)H, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
+    // composition with the same term order: K first, its mask, then the algebra over {kprev..., K}
+    if (!plain_p0) g_last_rhs_path = 0;
+    if ((rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st))) return rc;
+    if (drop && mask_combines(rk_mode, opt)) return dropout_combine_f32(K, n, *drop, y_next, y0, h_kprev, h_c, n_prev, st);
+    if (drop && (rc = dropout_apply_f32(K, n, *drop, st))) return rc;
+    if (rk_mode == 0) return NDCN_OK;
+    return rk_stage_f32(n, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
 }
 
 }  // namespace ndcn

@@ -189,14 +189,14 @@ DropArgs drop_at(const ndcn_tape *t, int64_t ev) {
     return d;
 }
 
-// ev: the evaluation's number within the solve (read with dropout only)
-int rhs_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st, int64_t ev, bool count = true) {
+// the flags of the tape's evaluations (the H = 256 launches read the image of W the tape packed once)
+uint32_t eval_flags(const ndcn_tape *t) { return t->flags | (t->packed ? NDCN_F_PACKED : 0u); }
+
+// out = f(x) without a stage epilogue.  ev: the evaluation's number within the solve (read with dropout only)
+int eval_plain(ndcn_tape *t, const float *x, float *out, hipStream_t st, int64_t ev, bool count = true) {
     if (count) t->nfe++;
-    uint32_t fl = t->flags | (t->packed ? NDCN_F_PACKED : 0u);
-    if (t->drop) return rhs_drop_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, fl, drop_at(t, ev), st);
-    int rc = rhs_rk_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, fl, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                        0.f, 0.f, nullptr, nullptr, st, nullptr);
-    return rc;
+    const DropArgs d = drop_at(t, ev);
+    return rhs_f32(&t->A, x, nullptr, t->A.n_cols, t->W, t->b, out, t->work, t->H, eval_flags(t), st, t->drop ? &d : nullptr);
 }
 
 // the n doubles the launches enqueued since the matching arm wrote at `d_src` -> hs->h[0..n) (polling mode: d_src IS hs->h's alias)
@@ -257,7 +257,7 @@ int initial_step(ndcn_tape *t, hipStream_t st, HostScratch *hs, int64_t &pending
     const float cp[1] = {t->h0};
     rc = rk_combine_f32(yh, t->y_in, kp, cp, 1, t->n, st);
     if (rc) return rc;
-    rc = rhs_plain(t, yh, f1, st, 1);
+    rc = eval_plain(t,yh, f1, st, 1);
     if (rc) return rc;
     t->yh = yh;
     t->f1 = f1;
@@ -305,12 +305,9 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
         if (t->keep_s && both && rhs_s_out_supported(&t->A, t->H, fl, NDCN_RK_COMBINE, mp)) {
             if ((rc = s_panel(i + 2, &opt.s_out))) return rc;
         }
-        if (t->drop)
-            rc = rhs_rk_drop_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
-                                 NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, nullptr, drop_at(t, ev0 + i));
-        else
-            rc = rhs_rk_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
-                            NDCN_RK_COMBINE, y0, kp, cp, mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr);
+        const DropArgs d = drop_at(t, ev0 + i);
+        rc = rhs_rk_f32(&t->A, u[i + 2], nullptr, t->A.n_cols, t->W, t->b, k[i + 1], t->work, t->H, eval_flags(t), NDCN_RK_COMBINE, y0, kp, cp,
+                        mp, u[i + 3], 0.f, 0.f, nullptr, nullptr, st, opt.s_out ? &opt : nullptr, t->drop ? &d : nullptr);
         if (rc) return rc;
     }
     *fused_err = !t->drop && t->n > aten_order_max_elems();
@@ -322,12 +319,12 @@ int attempt_launches(ndcn_tape *t, const float *y0, const float *k0, float dts, 
         if (t->keep_s && both && rhs_adj_supported(&t->A, t->H, fl, NDCN_RK_ERROR, mp)) {
             if ((rc = s_panel(7, &opt.s_out))) return rc;
         }
-        rc = rhs_rk_f32(&t->A, u[7], nullptr, t->A.n_cols, t->W, t->b, k[6], t->work, t->H, fl | (t->packed ? NDCN_F_PACKED : 0u),
+        rc = rhs_rk_f32(&t->A, u[7], nullptr, t->A.n_cols, t->W, t->b, k[6], t->work, t->H, eval_flags(t),
                         NDCN_RK_ERROR, y0, kp, cp, mp, nullptr, (float)t->rtol, (float)t->atol, d_red, t->d_ws2, st,
                         opt.s_out ? &opt : nullptr);
         if (rc) return rc;
     } else {
-        rc = rhs_plain(t, u[7], k[6], st, ev0 + 5, !rerun);
+        rc = eval_plain(t,u[7], k[6], st, ev0 + 5, !rerun);
         if (rc) return rc;
         m = dt_terms(dts, kCErr, 7, kall, kp, cp);
         rc = rk_error_f32(y0, u[7], kp, cp, m, (float)t->rtol, (float)t->atol, t->n, d_red, t->d_ws, st);
@@ -545,7 +542,7 @@ int ndcn_tape_dopri5_drop_f32(const ndcn_csr *A, const ndcn_csr *At, const float
     NDCN_HIP(hipMemcpyAsync(out, y0, (size_t)t->n * sizeof(float), hipMemcpyDeviceToDevice, st));
     float *f0;
     if ((rc = panel(t, &f0))) return rc;
-    if ((rc = rhs_plain(t, y0, f0, st, 0))) return rc;
+    if ((rc = eval_plain(t,y0, f0, st, 0))) return rc;
     t->f0 = f0;
     t->evals = ndcn_tape_attempt_evaluation(0, t->first_given ? 0 : 1, 0);       // (what the solve consumes before its first attempt)
     t->nfe = 2;                                    // (the count the python path reports: autograd_path.py nfe = 2)
@@ -1071,7 +1068,7 @@ int fixed_init(Fixed &F, const ndcn_csr *A, const ndcn_csr *At, const float *W, 
 // last_k: the step's last stage derivative is wanted too (the reverse pass needs its sign pattern; the forward pass does not)
 int fixed_step(Fixed &F, const float *y, float dt, float *out_y, float *const *u, float *const *K, bool last_k = true) {
     ndcn_tape *t = &F.t;
-    const uint32_t fl = t->flags | (t->packed ? NDCN_F_PACKED : 0u);
+    const uint32_t fl = eval_flags(t);
     auto eval = [&](const float *x, float *k, int mode, const float *const *kp, const float *cp, int n_prev, float *y_next, bool need_k = true) {
         RkOpt opt = {};
         opt.no_k = need_k ? 0 : 1;
