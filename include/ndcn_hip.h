@@ -757,6 +757,43 @@ NDCN_API int ndcn_solve_small_bwd_keep_f32(const ndcn_csr *A, const ndcn_csr *A_
                                            float *g_y0, float *g_W, float *g_b, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * explicit_adams: the reference's AdamsBashforth (torchdiffeq/_impl/fixed_adams.py:151-211), a fixed-grid linear multistep method - two
+ * RK4 (3/8 rule) steps, then ONE right-hand side per step combined with up to ten earlier ones.  Three calls added to ABI 29: no existing
+ * declaration changes.
+ * ndcn_ab_step_f32, one step of order n (fixed_adams.py:180-182, misc.py:22-25, solvers.py:92):
+ *     out = y + dt * ((((0 + a[0] f[0]) + a[1] f[1]) + ...) + a[n-1] f[n-1])
+ *   every product and every sum rounded to fp32 on its own, no contraction; the sum starts from an exact zero (Python's sum()), so a
+ *   lone -0 product becomes +0.  h_f: HOST array of the n newest evaluations, newest first (device panels of n_elem floats); h_a: HOST
+ *   array of their weights, float32((1 / div) * c_i) with the product taken in double.  3 <= n <= 11; NDCN_EINVAL - before any launch -
+ *   for any other n, a null panel, or `out` equal to one of the f panels (out == y is allowed).  Any pointer alignment and any
+ *   n_elem >= 0: where all panels share one offset from a 16-byte boundary the body runs by 16 bytes per lane behind a head of <= 3
+ *   single elements, else by single elements.  One streaming launch on a grid sized from the compute-unit count; the history panels are
+ *   read with the default cache policy (ten of them are read again by the next step).
+ * ndcn_solve_explicit_adams_f32: FixedGridODESolver.integrate (solvers.py:79-99) with that step over ODEFunc, enqueued on `stream`
+ *   without a read-back or a synchronisation:
+ *     h_dt [n_steps]        the grid's differences in the state dtype (solvers.py:91)
+ *     tick j < n_ticks      written to out[j] (panels back to back) after step h_tick_step[j] (HOST, non-decreasing, < n_steps): the new
+ *                           state itself where h_tick_same[j] != 0 (the tick is an end of the step), else through the expression of
+ *                           ndcn_tick_emit_f32 with h_tick_off[j] = t_j - t0 of that step (fp32)
+ *     max_order             fixed_adams.py:162-163 after its clamp: 2 .. 12; the history keeps max_order - 1 evaluations and a step has
+ *                           order min(evaluations so far, max_order - 1): below 3 it is the RK4 step with the new evaluation as k1 - the
+ *                           launches of ndcn_solver_advance's un-fused RK4 step (ndcn_rhs_f32, ndcn_fixed_stage_f32 ops 2..5: its bits) -
+ *                           else ONE ndcn_rhs_f32 written into the history slot of the oldest evaluation and ONE ndcn_ab_step_f32
+ *     workspace             ndcn_explicit_adams_workspace_bytes(n_rows, H, max_order) bytes, 256-byte aligned, owned by the caller: the
+ *                           history ring (max_order - 1 panels), three RK4 stage panels, a stage input, two state panels and the scratch of
+ *                           ndcn_rhs_f32 (H = 256: the weights are packed there once per solve)
+ *   Un-sharded, no dropout, flags == NDCN_F_RELU: NDCN_EINVAL (with a message) otherwise.  y0 is only read and may be the panel in
+ *   front of `out`.  The weights of each order are derived in the library from the exact rationals
+ *   beta_i = integral_0^1 prod_{j != i} (u + j) / (j - i) du over their least common denominator.                                   */
+NDCN_API int ndcn_ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_elem,
+                              void *stream);
+NDCN_API int64_t ndcn_explicit_adams_workspace_bytes(int64_t n_rows, int H, int max_order);
+NDCN_API int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                           const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                           const float *h_tick_off, int64_t n_ticks, int max_order, float *out, void *workspace,
+                                           int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): when enabled, every kernel launch made by this library is
  * bracketed by HIP events recorded on the launch stream.  ndcn_prof_read drains them into
  * h_out[kind*4 + {0: launches, 1: total ms, 2: total algorithmic bytes, 3: total flops}] for

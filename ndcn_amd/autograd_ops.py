@@ -179,6 +179,11 @@ class AutogradOps:
         return _LinMap.apply(lambda yy, *k: hip.fixed_stage(op, yy, *k, dt=dt), w, *ins)
 
     @staticmethod
+    def ab_step(y, fs, coeffs, dt, out=None):
+        w = (1.0,) + tuple(float(dt) * float(a) for a in coeffs)
+        return _LinMap.apply(lambda yy, *f: hip.ab_step(yy, list(f), coeffs, dt), w, y, *fs)
+
+    @staticmethod
     def tick_emit(y, dt, tms, outs=None):
         # y + ((y - y) / dt) * tm: the derivative with respect to y is 1 wherever the state is finite (the slope term is a constant
         # zero there), so every tick hands its gradient to the state that ended the step, unchanged

@@ -1,0 +1,305 @@
+// explicit_adams: the reference's AdamsBashforth (torchdiffeq/_impl/fixed_adams.py:151-211) - a fixed-grid linear multistep method that
+// is warmed up by two RK4 (3/8 rule) steps and then makes ONE right-hand-side evaluation per step.
+//
+//   ab_step_f32                      out = y + dt * sum_{i<n} a_i f_i, n = 3..11: one streaming pass over the history
+//   ndcn_solve_explicit_adams_f32    the whole solve over ODEFunc, enqueued on the caller's stream: history ring, stage panels and both
+//                                    state panels in a caller-owned workspace, nothing read back
+//
+// Rounding follows the reference term by term (fixed_adams.py:182, misc.py:22-25, solvers.py:92): p_i = a_i * f_i, s = ((0 + p_0) + p_1)
+// + ..., dy = dt * s, y1 = y + dy - every product and sum rounded on its own.  FP contraction is therefore switched OFF for this
+// translation unit, as in rk.hip, and the arithmetic is written with plain operators: hip's __fmul_rn / __fadd_rn are inline functions
+// of a header that is compiled under the default mode (contract=fast) - inlined here they fuse (seen in the ISA: v_pk_fma_f32).
+#include <stdint.h>
+
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace ndcn {
+
+namespace {
+
+constexpr int kAbMinTerms = 3;         // fixed_adams.py:146,174: below order 3 the step is RK4
+constexpr int kAbMaxTerms = 11;        // :147,163: max_order 12 keeps 11 evaluations
+constexpr int kAbMaxOrder = 12;
+
+struct AbArgs {
+    const float *f[kAbMaxTerms];       // newest first
+    float a[kAbMaxTerms];
+    const float *y;
+    float *out;
+    float dt;
+};
+
+__device__ __forceinline__ float ab1(float y, const float *f, const float *a, int n, float dt) {
+    float s = 0.f + a[0] * f[0];                            // Python's sum() starts from 0: a lone -0 product becomes +0
+#pragma unroll
+    for (int j = 1; j < n; ++j) s = s + a[j] * f[j];
+    return y + dt * s;
+}
+
+// Elements [head, head + 4 n4) by 16 bytes per lane - every panel is 16-byte aligned at element `head` -, the <= 3 elements in front and
+// the <= 3 behind by single lanes (n4 = 0: everything, panels that do not share an offset).  A grid-stride loop: the host sizes the
+// grid from the compute units, not from the panel.  The N loads of an item are issued before the first use (the loop over j is unrolled:
+// N independent global_load_dwordx4, one s_waitcnt per consumer); default cache policy - the next step reads N - 1 of the panels again.
+template <int N>
+__global__ __launch_bounds__(256) void ab_step_kernel(AbArgs p, int64_t head, int64_t n4, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = tid; i < n4; i += stride) {
+        const int64_t e = head + 4 * i;
+        float4 v[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) v[j] = *reinterpret_cast<const float4 *>(p.f[j] + e);
+        const float4 y = *reinterpret_cast<const float4 *>(p.y + e);
+        float fx[N], fy[N], fz[N], fw[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) { fx[j] = v[j].x; fy[j] = v[j].y; fz[j] = v[j].z; fw[j] = v[j].w; }
+        float4 o;
+        o.x = ab1(y.x, fx, p.a, N, p.dt);
+        o.y = ab1(y.y, fy, p.a, N, p.dt);
+        o.z = ab1(y.z, fz, p.a, N, p.dt);
+        o.w = ab1(y.w, fw, p.a, N, p.dt);
+        *reinterpret_cast<float4 *>(p.out + e) = o;
+    }
+    const int64_t rest = n - 4 * n4;
+    for (int64_t r = tid; r < rest; r += stride) {
+        const int64_t e = r < head ? r : r + 4 * n4;
+        float f[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) f[j] = p.f[j][e];
+        p.out[e] = ab1(p.y[e], f, p.a, N, p.dt);
+    }
+}
+
+// workgroups of a streaming launch: eight per compute unit (2048 on the whole chip), fewer when the panel is smaller
+int ab_grid(int64_t items) {
+    static std::atomic<int> cus_of[64];
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+        cus = cus_of[dev].load(std::memory_order_relaxed);
+        if (cus == 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            cus_of[dev].store(cus, std::memory_order_relaxed);
+    }
+    if (cus <= 0) cus = kCus;
+    int64_t g = (items + 255) / 256;
+    if (g > (int64_t)cus * 8) g = (int64_t)cus * 8;
+    return g < 1 ? 1 : (int)g;
+}
+
+template <int N>
+void ab_launch(const AbArgs &p, int64_t head, int64_t n4, int64_t n, hipStream_t st) {
+    const int64_t rest = n - 4 * n4;
+    hipLaunchKernelGGL(ab_step_kernel<N>, dim3(ab_grid(n4 > rest ? n4 : rest)), dim3(256), 0, st, p, head, n4, n);
+}
+
+}  // namespace
+
+int ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n_terms, float dt, int64_t n, hipStream_t st) {
+    if (n_terms < kAbMinTerms || n_terms > kAbMaxTerms) { set_error("ab_step: %d terms, the orders are %d..%d", n_terms, kAbMinTerms, kAbMaxTerms); return NDCN_EINVAL; }
+    if (!out || !y || !h_f || !h_a || n < 0) { set_error("ab_step: null argument"); return NDCN_EINVAL; }
+    AbArgs p;
+    p.y = y; p.out = out; p.dt = dt;
+    const uintptr_t off = reinterpret_cast<uintptr_t>(out) & 15u;
+    bool same_offset = (off & 3u) == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == off;
+    for (int j = 0; j < kAbMaxTerms; ++j) {
+        p.f[j] = h_f[j < n_terms ? j : 0];
+        p.a[j] = j < n_terms ? h_a[j] : 0.f;
+        if (j >= n_terms) continue;
+        if (!h_f[j]) { set_error("ab_step: term %d is null", j); return NDCN_EINVAL; }
+        if (h_f[j] == out) { set_error("ab_step: out aliases history panel %d (only y may be updated in place)", j); return NDCN_EINVAL; }
+        same_offset = same_offset && (reinterpret_cast<uintptr_t>(h_f[j]) & 15u) == off;
+    }
+    if (n == 0) return NDCN_OK;
+    int64_t head = 0, n4 = 0;
+    if (same_offset) {
+        head = (int64_t)((16u - off) & 15u) / 4;
+        if (head > n) head = n;
+        n4 = (n - head) / 4;
+    }
+    if (n4 == 0) head = 0;
+    ProfScope prof(PROF_COMBINE, st, 4.0 * n * (n_terms + 2), 2.0 * n * (n_terms + 1));
+    switch (n_terms) {
+        case 3: ab_launch<3>(p, head, n4, n, st); break;
+        case 4: ab_launch<4>(p, head, n4, n, st); break;
+        case 5: ab_launch<5>(p, head, n4, n, st); break;
+        case 6: ab_launch<6>(p, head, n4, n, st); break;
+        case 7: ab_launch<7>(p, head, n4, n, st); break;
+        case 8: ab_launch<8>(p, head, n4, n, st); break;
+        case 9: ab_launch<9>(p, head, n4, n, st); break;
+        case 10: ab_launch<10>(p, head, n4, n, st); break;
+        default: ab_launch<11>(p, head, n4, n, st); break;
+    }
+    NDCN_LAUNCH_CHECK();
+    return NDCN_OK;
+}
+
+namespace {
+
+int64_t gcd64(int64_t a, int64_t b) {
+    if (a < 0) a = -a;
+    if (b < 0) b = -b;
+    while (b) { const int64_t r = a % b; a = b; b = r; }
+    return a;
+}
+
+// The weights of order k, newest evaluation first.  beta_i = integral_0^1 prod_{j != i, j < k} (u + j) / (j - i) du as an exact rational
+// (k <= 11: every intermediate fits 64 bits - the polynomial's coefficients stay below 10!, lcm(1..11) = 27720), all of them over their
+// least common denominator div: beta_i = c_i / div.  The reference multiplies each evaluation by (1 / div) * c_i, a Python double that
+// torch rounds to the state dtype (fixed_adams.py:182, misc.py:25): a_i = (float)((1.0 / div) * c_i).
+void ab_weights(int k, float *a) {
+    int64_t num[kAbMaxTerms], den[kAbMaxTerms];
+    int64_t L = 1;
+    for (int m = 1; m <= k; ++m) L = L / gcd64(L, m) * m;
+    for (int i = 0; i < k; ++i) {
+        int64_t poly[kAbMaxTerms + 1] = {1};                 // prod_{j != i} (u + j), lowest power first
+        int deg = 0;
+        int64_t d = 1;
+        for (int j = 0; j < k; ++j) {
+            if (j == i) continue;
+            for (int m = deg + 1; m >= 0; --m) poly[m] = (m ? poly[m - 1] : 0) + (int64_t)j * (m <= deg ? poly[m] : 0);
+            ++deg;
+            d *= j - i;
+        }
+        int64_t s = 0;                                       // L * integral of the polynomial
+        for (int m = 0; m <= deg; ++m) s += poly[m] * (L / (m + 1));
+        int64_t q = L * d;
+        if (q < 0) { q = -q; s = -s; }
+        const int64_t g = gcd64(s, q);
+        num[i] = s / g;
+        den[i] = q / g;
+    }
+    int64_t div = 1;
+    for (int i = 0; i < k; ++i) div = div / gcd64(div, den[i]) * den[i];
+    for (int i = 0; i < k; ++i) a[i] = (float)((1.0 / (double)div) * (double)(num[i] * (div / den[i])));
+}
+
+inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+// panels of the workspace: the history ring, k2..k4 of a warm-up step, the stage input, two state panels
+inline int solve_panels(int max_order) { return (max_order - 1) + 3 + 1 + 2; }
+
+}  // namespace
+
+}  // namespace ndcn
+
+using namespace ndcn;
+
+extern "C" {
+
+int ndcn_ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_elem, void *stream) {
+    return ab_step_f32(out, y, h_f, h_a, n, dt, n_elem, static_cast<hipStream_t>(stream));
+}
+
+int64_t ndcn_explicit_adams_workspace_bytes(int64_t n_rows, int H, int max_order) {
+    if (n_rows < 0 || H <= 0 || max_order < 2 || max_order > kAbMaxOrder) return NDCN_EINVAL;
+    const size_t panel = up256((size_t)n_rows * (size_t)H * sizeof(float));
+    const int64_t wb = rhs_work_bytes(n_rows, H, NDCN_F_RELU);
+    return (int64_t)((size_t)solve_panels(max_order) * panel + up256((size_t)(wb > 0 ? wb : 0)));
+}
+
+int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                  const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                  const float *h_tick_off, int64_t n_ticks, int max_order, float *out, void *workspace,
+                                  int64_t workspace_bytes, void *stream) {
+    NDCN_CHECK_ARG(A && W && y0 && H > 0 && n_steps >= 0 && n_ticks >= 0, "null argument");
+    NDCN_CHECK_ARG(A->n_rows >= 0 && A->n_rows < (1ll << 31) - 1 && A->nnz >= 0 && A->rowptr && (A->nnz == 0 || (A->colidx && A->val)), "bad operator");
+    NDCN_CHECK_ARG(A->n_rows == A->n_cols, "an un-sharded solve: the operator must be square (no halo columns)");
+    NDCN_CHECK_ARG(flags == NDCN_F_RELU, "flags must be NDCN_F_RELU: no_graph / no_control / packed / accumulate have no form here");
+    NDCN_CHECK_ARG(max_order >= 2 && max_order <= kAbMaxOrder, "max_order must be 2..12 (fixed_adams.py:162 clamps at 12; below 2 the reference fails)");
+    NDCN_CHECK_ARG(n_steps == 0 || h_dt, "step sizes missing");
+    NDCN_CHECK_ARG(n_ticks == 0 || (h_tick_step && h_tick_same && h_tick_off && out), "tick arrays missing");
+    for (int64_t j = 0; j < n_ticks; ++j)
+        NDCN_CHECK_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
+    const int64_t need = ndcn_explicit_adams_workspace_bytes(A->n_rows, H, max_order);
+    NDCN_CHECK_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 && workspace_bytes >= need,
+                   "workspace of ndcn_explicit_adams_workspace_bytes() bytes, 256-byte aligned, required");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t n = A->n_rows * (int64_t)H;
+    if (n_steps == 0 || n == 0) return NDCN_OK;
+
+    // the workspace: ring | k2 k3 k4 | stage input | two state panels | rhs scratch
+    const size_t panel = up256((size_t)n * sizeof(float));
+    char *base = static_cast<char *>(workspace);
+    auto take = [&]() { float *p = reinterpret_cast<float *>(base); base += panel; return p; };
+    const int ring_n = max_order - 1;
+    float *ring[kAbMaxTerms];
+    for (int i = 0; i < ring_n; ++i) ring[i] = take();
+    float *k2 = take(), *k3 = take(), *k4 = take(), *ytmp = take();
+    float *state[2] = {take(), take()};
+    float *work = rhs_work_bytes(A->n_rows, H, flags) > 0 ? reinterpret_cast<float *>(base) : nullptr;
+    uint32_t fl = flags;
+    if (work && rhs_fused_supported(H, flags) && rhs_fused2_supported(A, H, flags)) {
+        // H = 256 on an operator with a row-group plan: the image of W once per solve, every evaluation reads it (rhs.hip)
+        int rc = pack_weight_256(W, work, st);
+        if (rc) return rc;
+        fl |= NDCN_F_PACKED;
+    }
+    auto eval = [&](const float *x, float *k) { return rhs_f32(A, x, nullptr, A->n_cols, W, b, k, work, H, fl, st); };
+
+    float weights[kAbMaxTerms + 1][kAbMaxTerms];
+    for (int k = kAbMinTerms; k <= kAbMaxTerms && k <= ring_n; ++k) ab_weights(k, weights[k]);
+
+    const float *y = y0;
+    int held = 0, newest = -1;                                 // evaluations in the ring; slot of the newest
+    int64_t j = 0;
+    std::vector<float *> outs;
+    std::vector<int> zeros;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const float dt = h_dt[i];
+        int64_t j1 = j;
+        while (j1 < n_ticks && h_tick_step[j1] == i) ++j1;
+        // where the new state goes: the caller's panel when the step's LAST tick is the state itself (an end of the step; only the last
+        // tick of a step can be), else the state panel the step does not read
+        float *dst = (j1 > j && h_tick_same[j1 - 1]) ? out + (size_t)(j1 - 1) * (size_t)n : (y == state[0] ? state[1] : state[0]);
+        // fixed_adams.py:166-173: the new evaluation takes the place of the oldest one
+        int rc;
+        float *f_new;
+        if (ring_n > 0) {
+            newest = (newest + 1) % ring_n;
+            f_new = ring[newest];
+            if (held < ring_n) ++held;
+        } else {
+            f_new = k4;                                        // (max_order 1 never reaches here)
+        }
+        if ((rc = eval(y, f_new))) return rc;
+        const int order = held < max_order - 1 ? held : max_order - 1;
+        if (order < kAbMinTerms) {
+            // rk_common.py:72-78 with k1 = the new evaluation: the un-fused RK4 step of the device solver (solver.hip: enqueue_fixed_stages)
+            if ((rc = fixed_stage_f32(2, ytmp, y, f_new, nullptr, nullptr, nullptr, dt, n, st))) return rc;
+            if ((rc = eval(ytmp, k2))) return rc;
+            if ((rc = fixed_stage_f32(3, ytmp, y, f_new, k2, nullptr, nullptr, dt, n, st))) return rc;
+            if ((rc = eval(ytmp, k3))) return rc;
+            if ((rc = fixed_stage_f32(4, ytmp, y, f_new, k2, k3, nullptr, dt, n, st))) return rc;
+            if ((rc = eval(ytmp, k4))) return rc;
+            if ((rc = fixed_stage_f32(5, dst, y, f_new, k2, k3, k4, dt, n, st))) return rc;
+        } else {
+            const float *f[kAbMaxTerms];
+            for (int q = 0; q < order; ++q) f[q] = ring[((newest - q) % ring_n + ring_n) % ring_n];
+            if ((rc = ab_step_f32(dst, y, f, weights[order], order, dt, n, st))) return rc;
+        }
+        y = dst;
+        // solvers.py:95-97: the ticks this step reports - the coincident one IS dst; the others pass through the reference's expression
+        outs.clear();
+        std::vector<float> tm;
+        for (int64_t q = j; q < j1; ++q) {
+            float *o = out + (size_t)q * (size_t)n;
+            if (h_tick_same[q]) {
+                if (o != dst) NDCN_HIP(hipMemcpyAsync(o, dst, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            } else {
+                outs.push_back(o);
+                tm.push_back(h_tick_off[q]);
+            }
+        }
+        if (!outs.empty()) {
+            zeros.assign(outs.size(), 0);
+            if ((rc = tick_emit_f32(dst, dt, tm.data(), zeros.data(), outs.data(), (int)outs.size(), n, st))) return rc;
+        }
+        j = j1;
+    }
+    return NDCN_OK;
+}
+
+}  // extern "C"

@@ -235,6 +235,10 @@ int tick_emit_f32(const float *y, float dt, const float *h_tm, const int *h_same
 int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, const float *k2, const float *k3, const float *k4,
                          float dt, const float *h_tm, const int *h_same, float *const *h_out, int nt, int64_t n, hipStream_t st);
 
+// adams.hip: one Adams-Bashforth step of order n_terms = 3..11, out = y + dt * (((0 + a_0 f_0) + a_1 f_1) + ...), every product and sum
+// rounded on its own; h_f newest first; out may be y, never one of h_f; any alignment (16-byte lanes where all panels share an offset)
+int ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n_terms, float dt, int64_t n, hipStream_t st);
+
 int row_l1_normalize_f32(const float *X, float *Y, int64_t n_rows, int H, hipStream_t st);
 int row_l1_normalize_bwd_f32(const float *G, const float *X, float *GX, int64_t n_rows, int H, hipStream_t st);
 int gene_rhs_f32(const ndcn_csr *A, const float *x, float *out, float b, float f, float h, hipStream_t st);

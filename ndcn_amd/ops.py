@@ -905,6 +905,20 @@ class HipOps:
         return out
 
     @staticmethod
+    def ab_step(y, fs, coeffs, dt, out=None):
+        """One Adams-Bashforth step (fixed_adams.py:180-182 + solvers.py:92): y + dt * (((0 + a_0 f_0) + a_1 f_1) + ...), every product
+        and sum rounded on its own - ndcn_ab_step_f32; fs: the 3..11 newest evaluations, newest first; coeffs: their float32 weights.
+        out may be y."""
+        y = _panel(y)
+        fs = [_panel(f) for f in fs]
+        if out is None:
+            out = torch.empty_like(y)
+        arr_f, arr_a, n = _terms(fs, coeffs)
+        with torch.cuda.device(y.device):
+            check(_lib.load().ndcn_ab_step_f32(ptr(out), ptr(y), arr_f, arr_a, n, float(dt), y.numel(), stream_ptr()))
+        return out
+
+    @staticmethod
     def tick_emit(y, dt, tms, outs=None):
         """The ticks a sub-stepped fixed-grid step reports that are NOT an end of the step (solvers.py:92-108, y0 already overwritten
         with y1): [y + ((y - y) / dt) * tm for tm in tms] - one pass over y per 8 ticks (ndcn_tick_emit_f32)."""

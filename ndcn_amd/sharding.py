@@ -485,6 +485,9 @@ def sharded_odeint(ops, odefunc, plan, n_global_rows, x_local, t, rtol=1e-7, ato
     stats (a dict, optional) receives which evaluation form ran and what travelled: {'form': 'row_split' | 'two_phase' |
     'one_launch', 'nfe', 'halo_bytes' (sent + received over the solve), 'halo_rows_received_per_rhs'}."""
     from .torchdiffeq._impl import core
+    if method == 'explicit_adams':
+        raise NotImplementedError("sharded_odeint: method 'explicit_adams' has no sharded form (dopri5, euler, midpoint and rk4 do); "
+                                  "solve the un-sharded graph with odeint")
     f = ShardedODEFunc(odefunc, plan, ops)
     training = f._training(x_local)
     if training:

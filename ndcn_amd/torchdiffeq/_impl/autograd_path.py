@@ -35,7 +35,9 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False,
         # deviation that is stated, not hidden: DESIGN section 2)
         return core.integrate_adams(autograd_ops, func, y0, t, rtol, atol, autonomous=autonomous, step_log=step_log, **options)
     # plan: the grid and tick placement of the step_size option (core.fixed_plan); None: the default grid
-    return core.integrate_fixed(autograd_ops, func, y0, t, method, autonomous=autonomous, plan=plan)
+    # (explicit_adams: the same control flow with ops.ab_step as one more linear map; max_order from core.fixed_options)
+    return core.integrate_fixed(autograd_ops, func, y0, t, method, autonomous=autonomous, plan=plan,
+                                max_order=options.get('max_order', core.AB_MAX_ORDER))
 
 
 class _HipValue(torch.autograd.Function):

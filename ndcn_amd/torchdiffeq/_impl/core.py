@@ -5,11 +5,14 @@ Mirrors the control flow and scalar arithmetic of the reference's vendored torch
   fixed grid        torchdiffeq/_impl/solvers.py:79-99 ; fixed_grid.py:7-8,17-19,28-29 ; rk_common.py:72-78
   dopri5            torchdiffeq/_impl/dopri5.py:58-122 ; rk_common.py:22-61 ; misc.py:84-170 ; interp.py:5-65
   adams             torchdiffeq/_impl/adams.py:11-170 (variable-coefficient Adams-Bashforth-Moulton)
+  explicit_adams    torchdiffeq/_impl/fixed_adams.py:151-211 (fixed-grid Adams-Bashforth, RK4 warm-up)
 All per-element work is delegated to `ops` (one fused HIP kernel per reference op chain); what stays
 here is scalar: times and the step-size controller in float64, every quantity the reference forms as a
 0-d tensor of the state dtype (dt*beta, stage times, initial-step heuristic, interpolation abscissa)
 in numpy float32.  State may be a tensor or a tuple of tensors (misc.py:175-182).
 """
+import collections
+import fractions
 import math
 import warnings
 
@@ -49,9 +52,10 @@ IFACTOR = 10.0
 DFACTOR = float(f32(0.2))
 
 FIXED_METHODS = ('euler', 'midpoint', 'rk4')
-METHODS = FIXED_METHODS + ('dopri5', 'adams')
+GRID_METHODS = FIXED_METHODS + ('explicit_adams',)      # every FixedGridODESolver: the step_size option, FixedPlan, emit_ticks
+METHODS = GRID_METHODS + ('dopri5', 'adams')
 # methods the reference lists (odeint.py:8-17) but this build does not provide
-UNSUPPORTED = ('explicit_adams', 'fixed_adams', 'tsit5')
+UNSUPPORTED = ('fixed_adams', 'tsit5')
 
 
 def _nan_max(a, b):
@@ -161,26 +165,37 @@ def assert_increasing(t):
 # fixed grid
 # ---------------------------------------------------------------------------------------------------
 
-FIXED_SOLVER_NAMES = {'euler': 'Euler', 'midpoint': 'Midpoint', 'rk4': 'RK4'}      # fixed_grid.py:5,15,26 (named in the warning)
+# fixed_grid.py:5,15,26 ; fixed_adams.py:208 (named in the warning)
+FIXED_SOLVER_NAMES = {'euler': 'Euler', 'midpoint': 'Midpoint', 'rk4': 'RK4', 'explicit_adams': 'AdamsBashforth'}
 MAX_EMIT = 8                                  # tick panels one tick_emit launch writes (csrc/rk.hip: kMaxTicks)
 
 
 def fixed_options(method, options):
-    """FixedGridODESolver.__init__ (solvers.py:39-53) on the caller's `options`: the step size (or None), after the reference's
-    warning about names it does not know and its ValueError for ANY grid_constructor (the `elif grid_constructor is None`
-    branch: with or without step_size)."""
+    """FixedGridODESolver.__init__ (solvers.py:39-53) on the caller's `options`, after the reference's warning about names it does
+    not know and its ValueError for ANY grid_constructor (the `elif grid_constructor is None` branch: with or without step_size).
+    Returns what the solve goes on with: {'step_size': h} where one was given and, for explicit_adams, {'max_order': m} always -
+    AdamsBashforthMoulton.__init__ (fixed_adams.py:153-163): int(min(max_order, 12)), default 12; max_iters is a name it knows,
+    `implicit` collides with the one AdamsBashforth passes itself (:211: a TypeError)."""
     options = dict(options or {})
     step_size = options.pop('step_size', None)
     grid_constructor = options.pop('grid_constructor', None)
     options.pop('rtol', None)
     options.pop('atol', None)
+    out = {}
+    if method == 'explicit_adams':
+        if 'implicit' in options:
+            raise TypeError("__init__() got multiple values for keyword argument 'implicit'")
+        options.pop('max_iters', None)
+        out['max_order'] = int(min(options.pop('max_order', AB_MAX_ORDER), AB_MAX_ORDER))
     if options:
         warnings.warn('{}: Unexpected arguments {}'.format(FIXED_SOLVER_NAMES[method], options))
     if grid_constructor is not None:
         raise ValueError("step_size and grid_constructor are exclusive arguments.")
     if step_size is not None and torch.is_tensor(step_size):
         step_size = float(step_size.detach())
-    return step_size
+    if step_size is not None:
+        out['step_size'] = step_size
+    return out
 
 
 class FixedPlan:
@@ -249,9 +264,67 @@ def emit_ticks(ops, plan, i, y, sol):
         sol.append(y if same else made[j])
 
 
-def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None):
+# explicit_adams: the fixed-grid Adams-Bashforth method (fixed_adams.py:151-211).  A step of order k adds
+#   dt * sum_{i<k} beta_i f_{n-i},   beta_i = integral over [0, 1] of prod_{j != i, j < k} (u + j) / (j - i) du
+# - the integral of the polynomial through the k newest evaluations.  The reference holds each order as integers c_i over one common
+# divisor and multiplies every evaluation by the float32 image of the DOUBLE product (1 / div) * c_i (misc.py:22-25): formed the same
+# way here from the exact rationals, so no table is kept.
+AB_MIN_ORDER = 4                   # fixed_adams.py:146: below order 3 (= 4 - 1) the step is RK4 by the 3/8 rule
+AB_MAX_ORDER = 12                  # :147: at most 11 evaluations are kept
+
+
+def bashforth_rationals(order):
+    """(beta_0 .. beta_{order-1}) as fractions.Fraction, newest evaluation first"""
+    betas = []
+    for i in range(order):
+        poly, den = [fractions.Fraction(1)], 1               # prod_{j != i} (u + j), lowest power first
+        for j in range(order):
+            if j == i:
+                continue
+            poly = [(poly[m - 1] if m else 0) + j * (poly[m] if m < len(poly) else 0) for m in range(len(poly) + 1)]
+            den *= j - i
+        betas.append(sum(c / (m + 1) for m, c in enumerate(poly)) / den)
+    return betas
+
+
+def bashforth_integers(order):
+    """([c_0 .. c_{order-1}], div): beta_i = c_i / div with div the least common denominator"""
+    betas = bashforth_rationals(order)
+    div = 1
+    for b in betas:
+        div = div * b.denominator // math.gcd(div, b.denominator)
+    return [int(b * div) for b in betas], div
+
+
+def bashforth_weights(order):
+    """float32((1 / div) * c_i), the product taken in doubles: the factor each evaluation is multiplied by (misc.py:25)"""
+    cs, div = bashforth_integers(order)
+    return [f32((1 / div) * c) for c in cs]
+
+
+_AB_WEIGHTS = {}
+
+
+def ab_weights(order):
+    if order not in _AB_WEIGHTS:
+        _AB_WEIGHTS[order] = bashforth_weights(order)
+    return _AB_WEIGHTS[order]
+
+
+def _rk4_step(ops, func, targ, t0, dt, y, k1):
+    """rk_common.py:72-78 + solvers.py:92: the 3/8 rule from the evaluation k1 = func(t0, y)"""
+    y2 = tuple(ops.fixed_stage(2, y_, a, dt=dt) for y_, a in zip(y, k1))
+    k2 = func(targ(t0 + dt / f32(3)), y2)
+    y3 = tuple(ops.fixed_stage(3, y_, a, b, dt=dt) for y_, a, b in zip(y, k1, k2))
+    k3 = func(targ(t0 + dt * f32(2) / f32(3)), y3)
+    y4 = tuple(ops.fixed_stage(4, y_, a, b, c, dt=dt) for y_, a, b, c in zip(y, k1, k2, k3))
+    k4 = func(targ(t0 + dt), y4)
+    return tuple(ops.fixed_stage(5, y_, a, b, c, d, dt=dt) for y_, a, b, c, d in zip(y, k1, k2, k3, k4))
+
+
+def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None, max_order=AB_MAX_ORDER):
     """solvers.py:79-99: the default grid (grid == t), or the grid of `plan` (fixed_plan: the step_size option).  Returns a list (per
-    tick) of tuples."""
+    tick) of tuples.  max_order: explicit_adams only (fixed_options)."""
     assert_increasing(t)
     dtype = y0[0].dtype
     if plan is None:
@@ -260,6 +333,10 @@ def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None):
     targ = TimeArg(y0[0], autonomous)
     sol = [y0]
     y = y0
+    if method == 'explicit_adams':
+        # fixed_adams.py:163: the history, newest first.  (max_order 1: nothing is kept and the first step fails on prev_f[0];
+        # below 1 the deque itself refuses - both as in the reference)
+        prev_f = collections.deque(maxlen=max_order - 1)
     for i in range(len(tg) - 1):
         t0 = tg[i]
         dt = plan.dts[i]                                  # float32 subtraction, as `t1 - t0` on 0-d tensors
@@ -271,15 +348,16 @@ def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None):
             ym = tuple(ops.fixed_stage(1, y_, k_, dt=dt) for y_, k_ in zip(y, k1))
             k2 = func(targ(t0 + dt / f32(2)), ym)
             y = tuple(ops.fixed_stage(0, y_, k_, dt=dt) for y_, k_ in zip(y, k2))
+        elif method == 'explicit_adams':
+            prev_f.appendleft(func(targ(t0), y))          # fixed_adams.py:166-172
+            order = min(len(prev_f), max_order - 1)
+            if order < AB_MIN_ORDER - 1:
+                y = _rk4_step(ops, func, targ, t0, dt, y, prev_f[0])
+            else:
+                # y + dt * (((0 + a_0 f_n) + a_1 f_{n-1}) + ...): one pass over the history (ndcn_ab_step_f32)
+                y = tuple(ops.ab_step(y_, [f[q] for f in prev_f], ab_weights(order), dt) for q, y_ in enumerate(y))
         else:
-            k1 = func(targ(t0), y)
-            y2 = tuple(ops.fixed_stage(2, y_, a, dt=dt) for y_, a in zip(y, k1))
-            k2 = func(targ(t0 + dt / f32(3)), y2)
-            y3 = tuple(ops.fixed_stage(3, y_, a, b, dt=dt) for y_, a, b in zip(y, k1, k2))
-            k3 = func(targ(t0 + dt * f32(2) / f32(3)), y3)
-            y4 = tuple(ops.fixed_stage(4, y_, a, b, c, dt=dt) for y_, a, b, c in zip(y, k1, k2, k3))
-            k4 = func(targ(t0 + dt), y4)
-            y = tuple(ops.fixed_stage(5, y_, a, b, c, d, dt=dt) for y_, a, b, c, d in zip(y, k1, k2, k3, k4))
+            y = _rk4_step(ops, func, targ, t0, dt, y, func(targ(t0), y))
         emit_ticks(ops, plan, i, y, sol)
     return sol
 

@@ -102,8 +102,8 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
 
     Same signature, defaults, return layout and exceptions as the reference (odeint.py:20-76):
     TypeError for non-float y0 / t, ValueError for `options` without `method`, KeyError for an unknown
-    method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / euler / midpoint / rk4 are
-    provided (tsit5 / explicit_adams / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
+    method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / explicit_adams / euler / midpoint / rk4 are
+    provided (tsit5 / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
     `step_log` (a list) optionally receives the dopri5 per-attempt log.  Returns (solution, decoded): decoded is True when
     `readout` was applied inside the solve (the device-resident inference path; the fixed-grid training nodes), else the solution
     is the hidden one.
@@ -114,6 +114,11 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     before it "interpolates", so nothing is interpolated; a tick strictly inside a step additionally has -0.0 turned into +0.0 and
     Inf into NaN.  Any `grid_constructor` raises the reference's ValueError; other names only warn.  One deviation: `step_size`
     with a `t` that requires grad raises NotImplementedError (the grid's dependence on t[0] / t[-1] is not differentiated).
+
+    explicit_adams is the reference's AdamsBashforth (fixed_adams.py:151-211) on the same grids: two RK4 (3/8 rule) steps, then ONE
+    evaluation per step combined with up to ten earlier ones (options={'max_order': m}, default 12: orders 3 .. m - 1; m = 2 or 3
+    never leaves RK4; m < 2 fails as in the reference).  Without a gradient a plain ODEFunc runs the whole solve inside the library
+    (ndcn_solve_explicit_adams_f32: nothing is read back); any other callable, a tuple state or a gradient steps through core.py.
     """
     user_func = func
     t_user = t
@@ -128,13 +133,13 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         method = 'dopri5'
     if method in core.UNSUPPORTED:
         raise NotImplementedError('method %r of the reference is outside the accelerated path '
-                                  '(dopri5, adams, euler, midpoint, rk4 are provided)' % method)
+                                  '(dopri5, adams, explicit_adams, euler, midpoint, rk4 are provided)' % method)
     method = SOLVERS[method]                     # KeyError for an unknown name, as the reference's dict lookup
 
     plan = None
-    if method in core.FIXED_METHODS:
-        step_size = core.fixed_options(method, options)     # solvers.py:39-53: warns about unknown names, ValueError for a grid_constructor
-        options = {} if step_size is None else {'step_size': step_size}
+    if method in core.GRID_METHODS:
+        options = core.fixed_options(method, options)       # solvers.py:39-53: warns about unknown names, ValueError for a grid_constructor
+        step_size = options.get('step_size')                # (what is left: the step size, explicit_adams' max_order)
         if step_size is not None:
             if t_user.requires_grad:
                 raise NotImplementedError('step_size with a time vector that requires grad: the dependence of the grid on t[0] / t[-1] '
@@ -169,6 +174,13 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
             return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
                                step_log=step_log, odefunc=user_func if plain else None, plan=plan)
+    elif method == 'explicit_adams':
+        out = None
+        if _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
+            out = _explicit_adams_solve(user_func, y0[0], t, plan, options['max_order'])
+        if out is not None:
+            return out, False
+        sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan, max_order=options['max_order'])
     elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_truth=True):
         return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan, readout)
     elif method == 'dopri5':
@@ -727,8 +739,8 @@ def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_d
         return False
     elif user_func.training and user_func.dropout > 0 and not (allow_dropout and _dropout.is_active(user_func)):
         return False
-    if method in core.FIXED_METHODS:
-        if set(options) - {'step_size'}:                      # (odeint hands over what core.fixed_options left: nothing, or the step size)
+    if method in core.GRID_METHODS:
+        if set(options) - {'step_size', 'max_order'}:         # (odeint hands over what core.fixed_options left)
             return False
     elif set(options) - set(core.DOPRI5_OPTIONS) or (method != 'dopri5' and options):
         return False
@@ -900,6 +912,47 @@ def _small_operator(odefunc, y0):
     if csr.device != y0.device or csr.shape[0] != y0.shape[0]:
         return None
     return csr, csr.view_ref(), flags
+
+
+def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
+    """The whole explicit_adams solve of a plain ODEFunc inside the library (ndcn_solve_explicit_adams_f32: RK4 warm-up, then one
+    right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the current stream without
+    a read-back.  None where the entry point has no form: no_graph / no_control, an operator that does not live with the state, a
+    max_order the reference itself fails on."""
+    import numpy as np
+    if odefunc.no_graph or odefunc.no_control or max_order < 2:
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, view, flags = op
+    core.assert_increasing(t)
+    if plan is None:
+        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    lib = _lib.load()
+    H = odefunc.hidden_size
+    n_ticks = len(plan.t)
+    out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+    out[0].copy_(y0)
+    n_steps, n_emit = len(plan.dts), n_ticks - 1
+    if n_steps == 0 or y0.numel() == 0:
+        return out
+    csr.ensure_plans(H)
+    view = csr.view_ref()
+    W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
+    b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
+    dts = (ctypes.c_float * n_steps)(*plan.dts.tolist())
+    steps = (ctypes.c_int64 * max(n_emit, 1))(*plan.tick_step[1:].tolist())
+    same = (ctypes.c_int * max(n_emit, 1))(*[int(v) for v in plan.tick_coincident[1:]])
+    offs = (ctypes.c_float * max(n_emit, 1))(*[float(np.float32(plan.t[j] - plan.grid[plan.tick_step[j]])) for j in range(1, n_ticks)])
+    nbytes = int(lib.ndcn_explicit_adams_workspace_bytes(y0.shape[0], H, max_order))
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
+    with torch.cuda.device(y0.device):
+        _lib.check(lib.ndcn_solve_explicit_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
+                                                     offs, n_emit, max_order, _lib.ptr(out[1:]) if n_emit else None, _lib.ptr(workspace),
+                                                     nbytes, _lib.stream_ptr()))
+    # (the workspace goes back to torch's stream-ordered allocator: a later allocation on this stream is ordered behind the solve)
+    return out
 
 
 def _small_solve(odefunc, y0, tt, method, plan=None):

@@ -21,6 +21,7 @@ Fixture families:
   G12 gconv_dense.npz GraphConvolution (dense A, flattened)  neural_dynamics.py:163-176
   G13 adams_*.npz     odeint adams + per-attempt step log    torchdiffeq/_impl/adams.py:62-170
   G14 substep_*.npz   fixed grid, options={'step_size': h}   torchdiffeq/_impl/solvers.py:55-68,79-108
+  G15 bashforth_*.npz odeint explicit_adams + nfe            torchdiffeq/_impl/fixed_adams.py:151-211
 """
 import os
 import sys
@@ -638,7 +639,41 @@ def gen_substep():
     save('substep_grids', table=np.array(fired + keep, dtype=np.float64), n_scanned=n_scan, n_fired=len(fired))
 
 
+# ----------------------------------------------------------------------------- G15
+def gen_bashforth():
+    """method='explicit_adams' (AdamsBashforth, fixed_adams.py:151-211) over the NDCN ODEFunc on the 6 x 6 lattice at H = 8, with the
+    evaluation count.  (Names start with bashforth_: the fixed_*.npz and adams_*.npz globs of the existing tests must not pick these
+    up.)  High-order Adams-Bashforth has a tiny stability region - an unstable trajectory amplifies last-bit differences and proves
+    nothing - so every case asserts that the reference's own trajectory stays finite and within 10 x max |x0|."""
+    _, OM = grid_operator(6)
+    OMs = ref_u.torch_sensor_to_torch_sparse_tensor(OM)
+    h = 1.0 / 128
+    cases = {
+        'default': (torch.linspace(0., 16 * 0.01, 17), {}, {}),                   # 16 steps: the order reaches 11, the history wraps
+        'order4': (torch.linspace(0., 16 * 0.01, 17), {'max_order': 4}, {}),
+        # 14 grid steps of 1 / 128: a tick inside a step, a coincident one, two inside one step, steps without a tick, the clamp-free end
+        'stepsize': (torch.tensor([0., 1.5 * h, 4 * h, 4.3 * h, 4.6 * h, 9 * h, 14 * h]), {'step_size': h}, {}),
+        'no_control': (torch.linspace(0., 16 * 0.01, 17), {}, {'no_control': True}),
+        'warmup': (torch.tensor([0., 0.01, 0.02]), {}, {}),                       # two steps: RK4 only
+    }
+    for name, (t, opts, fkw) in cases.items():
+        f, x = make_func(8, OMs, 53, **fkw)
+        cf = CountingFunc(f)
+        with torch.no_grad():
+            y = ref_ode.odeint(cf, x, t, method='explicit_adams', options=dict(opts) if opts else None)
+        n_steps = len(t) - 1
+        if 'step_size' in opts:
+            grid, ok = ref_step_grid(t, opts['step_size'])
+            assert ok
+            n_steps = len(grid) - 1
+            assert n_steps >= 14
+        assert bool(torch.isfinite(y).all()) and float(y.abs().max()) <= 10 * float(x.abs().max()), name
+        assert cf.nfe == n_steps + 6, (name, cf.nfe, n_steps)
+        save('bashforth_%s' % name, x0=x, t=t, W=f.wt.weight, b=f.wt.bias, traj=y, nfe=cf.nfe, n_steps=n_steps,
+             no_control=int(bool(fkw)), **{'opt_' + k: v for k, v in opts.items()}, **csr_of(OM))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep']
+    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep', 'bashforth']
     for w in which:
         globals()['gen_' + w]()
