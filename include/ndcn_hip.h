@@ -1040,7 +1040,7 @@ NDCN_API void ndcn_tape_destroy(ndcn_tape *tape);
  * way, without a tape object - the reverse pass re-forms the stages of a step from the stored trajectory:
  * ndcn_fixed_grid_train_f32 writes the n_ticks + 1 states (out[0] = y0) for the step sizes h_dt (the grid's differences in the state
  * dtype, solvers.py:81), ndcn_fixed_grid_backward_f32 maps g_out (n_ticks + 1 panels) to the gradients of y0, W and b.  Any size; the
- * launches of _impl/odeint.py::_FixedGridSolve.  alloc: scratch (<= 22 panels), may be released when the call returns (stream-ordered). */
+ * launches of _impl/fixed_train.py::_FixedGridSolve.  alloc: scratch (<= 22 panels), may be released when the call returns (stream-ordered). */
 NDCN_API int ndcn_fixed_grid_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, int method,
                                        const float *y0, const float *h_dt, int64_t n_ticks, float *out, ndcn_alloc_fn alloc,
                                        void *alloc_ctx, void *stream);

@@ -49,6 +49,11 @@ PROF_KINDS = ('spmm', 'linear', 'rhs_fused', 'combine', 'error', 'sumsq', 'inter
               'linear_wgrad', 'relu_bwd', 'rhs_adjoint_forward_half', 'rhs_adjoint_transposed_half')
 
 
+def operator_flags(odefunc):
+    """the NDCN_F_* word of an ODEFunc's right-hand side relu(W (A y) + b): its no_graph / no_control switches"""
+    return F_RELU | (F_NO_GRAPH if odefunc.no_graph else 0) | (F_NO_CONTROL if odefunc.no_control else 0)
+
+
 # Run-time switches (INTEGRATION.md, "Run-time switches"): the package's only reads of the environment.  Callers read per solve -
 # tests set and unset os.environ around single calls.
 def env_on(name):

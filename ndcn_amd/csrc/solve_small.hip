@@ -575,8 +575,8 @@ __global__ __launch_bounds__(1024) void solve_small_bwd_kernel(BwdArgs b, int sy
 // The same workgroup, the same LDS layout [T | S | Z | W^T | srow | CSR] as the Euler sweep above; per step, in reverse:
 //   the stage inputs are re-formed from y_i by the forward kernel's formulas (fixed_grid.py:18-19, rk_common.py:75-77; the stage
 //   derivatives stay in the registers of the thread that owns the element), then the stages' vector-Jacobian products in reverse -
-//   each the Euler sweep's block (S = A u, mask, g_W / g_b, gS = gZ W, A^T gS) - with the recurrences of `_FixedGridSolve.backward`
-//   (_impl/odeint.py) kept as running prefixes in registers:  RK4 3/8:  g_k3 = 3c a + dt g_u4;  g_k2 = 3c a - dt g_u4 + dt g_u3;
+//   each the Euler sweep's block (S = A u, mask, g_W / g_b, gS = gZ W, A^T gS) - with the recurrences of `_sweep_step`
+//   (_impl/fixed_train.py) kept as running prefixes in registers:  RK4 3/8:  g_k3 = 3c a + dt g_u4;  g_k2 = 3c a - dt g_u4 + dt g_u3;
 //   g_k1 = c a + dt g_u4 - (dt/3) g_u3 + (dt/3) g_u2, c = dt / 8;  a <- a + g_u4 + g_u3 + g_u2 + g_u1 + g_out[i].
 template <int METHOD, int MAXIT, bool CSR_LDS>
 __global__ __launch_bounds__(1024) void solve_small_bwd_rk_kernel(BwdArgs b, int symmetric) {

@@ -1020,7 +1020,7 @@ int ndcn_tape_backward_f32(ndcn_tape *t, const float *g_out, float *g_y0, float 
 // ====================================================================================================== fixed grids
 // FixedGridODESolver.integrate (solvers.py:79-99; fixed_grid.py:7-29, rk_common.py:72-78) over ODEFunc, differentiated as the drivers
 // train (heat_dynamics.py:313-334: plain backpropagation through every step), as two calls.  The launches and their order are those of
-// _impl/odeint.py::_FixedGridSolve (kept as the A/B partner: results are bit-identical): forward - every evaluation carries the stage
+// _impl/fixed_train.py::_FixedGridSolve (kept as the A/B partner: results are bit-identical): forward - every evaluation carries the stage
 // algebra that consumes it in its epilogue (ndcn_rhs_rk_f32), only the trajectory is kept; backward - per step, in reverse: the stages
 // re-formed from the stored state by the same launches, then the closed-form VJPs (S = A u, the masked Linear backward, A^T with the
 // step's factor folded into alpha) and the stage recurrences as one linear-combination launch each.  README-sized RK4 training was 34 ms
@@ -1156,7 +1156,7 @@ int fixed_backward(const ndcn_csr *A, const ndcn_csr *At, const float *W, const 
     if ((rc = panel(t, &a2[0])) || (rc = panel(t, &a2[1])) || (rc = panel(t, &gk)) || (rc = panel(t, &tmpS)) || (rc = panel(t, &tmpG)) ||
         (rc = panel(t, &scratch)))
         return rc;
-    // alpha J(x)^T g for K = relu(W (A x) + b) into out (_FixedGridSolve._vjp); g_W / g_b += scale * (this evaluation's)
+    // alpha J(x)^T g for K = relu(W (A x) + b) into out (fixed_train.py: _vjp); g_W / g_b += scale * (this evaluation's)
     auto vjp = [&](const float *x, const float *Kx, const float *g, float alpha, float scale, float *out) -> int {
         return rhs_vjp_f32(&t->A, &t->At, x, Kx, g, t->W, nullptr, out, g_W, t->b ? g_b : nullptr, tmpS, tmpG, t->bwork, H, flags, false,
                            scale, alpha, true, false, &t->bpacked, st);                       // gW_tot.add_(gW, alpha = scale)

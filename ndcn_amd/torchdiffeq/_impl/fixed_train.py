@@ -1,0 +1,595 @@
+"""Training through a fixed-grid solve (euler / midpoint / rk4) over ODEFunc: the routes of `odeint` under a gradient and their
+autograd nodes, one per route, each differentiated the way the reference's drivers train - plain backpropagation through every step
+(heat_dynamics.py:313-334).
+
+  _SmallEulerSolve   a state that fits one compute unit: the whole solve and its reverse sweep, one launch each (csrc/solve_small.hip);
+  _NativeFixedGrid   any size: the loops inside the library, two calls per solve (csrc/tape.hip: ndcn_fixed_grid_train_f32 /
+                     ndcn_fixed_grid_backward[_readout]_f32);
+  _FixedGridSolve    the same launches issued from Python, one step per tick: the A/B partner of the native loops
+                     (NDCN_FIXED_GRID_NATIVE=0) and the form that carries an active dropout;
+  _SubstepSolve      options={'step_size': h}: a grid finer than the ticks, checkpointed per tick interval.
+
+The last three take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
+the decoded solution (T, N, C) - hip.linear of the trajectory, the bits of the two-step form - the hidden trajectory is saved for the
+reverse sweep only, and that sweep takes the (T, N, C) gradient as it is: the (T, N, H) gradient of the trajectory is never written.
+Where a tick's gradient comes from is one object in the two Python sweeps (_PlainTicks, _ReadoutTicks: the Python mirror of TickGrad
+in csrc/tape.hip) and the `decoder` argument of _fixed_grid_reverse in the native one.
+
+Why _FixedGridSolve and _SubstepSolve stay two nodes.  A tick-per-step grid is a step_size plan whose every step reports one coincident
+tick, and the forward launches of the two are indeed the same; the reverse sweeps are not.  The per-tick sweep adds the entering tick
+gradient INSIDE the step's closing combination: combine_kernel and readout_bwd_kernel form a + ((((0 + gu_0) + gu_1) + ...) + g_i),
+the sum started from +0 and the base added last ("The decoder inside the fixed-grid reverse sweep").  The step_size sweep
+closes the step first and adds the tick gradients in a pass of their own: (a + sum gu) + sum g.  Those are different roundings, and
+the second form costs one more launch per step, so one merged sweep would change either the bits of one path or the launch count of
+the other.  They share the step launches, the closed-form sweep of one step and the tick-gradient objects, nothing more.
+
+Nothing here imports odeint.py at module level (it routes into this module)."""
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from ... import _lib
+from ... import dropout as _dropout
+from ..._lib import check, ptr, stream_ptr
+from ...ops import hip
+from . import core
+from .tape import Tape
+
+EVALS = {'euler': 1, 'midpoint': 2, 'rk4': 4}             # right-hand-side evaluations per step
+
+
+# ---- the repeated lines, once each ---------------------------------------------------------------------------------------------
+
+def _view(csr, n_rows, **kw):
+    """the library's view of the operator, or of the empty stand-in where there is none (no_graph: only n_rows is read)"""
+    return csr.view_ref(**kw) if csr is not None else ctypes.byref(_lib.empty_csr(n_rows))
+
+
+def _detached(*tensors):
+    """what the library reads of each: detached and contiguous (None stays None)"""
+    return tuple(None if x is None else x.detach().contiguous() for x in tensors)
+
+
+def _finish(scratch, rc):
+    """the tail of a library call that allocated through `scratch` (a Tape): the blocks go back (stream-ordered), what the allocator
+    callback caught is raised in preference to the return code it caused"""
+    err = scratch.error
+    scratch.close()
+    if rc < 0:
+        if err is not None:
+            raise err
+        check(rc)
+
+
+def _drop_at(drop, method, step):
+    """the (p, seed, evaluation) of the first evaluation of grid step `step`"""
+    return None if drop is None else (drop[0], drop[1], drop[2] + step * EVALS[method])
+
+
+# ---------------------------------------------------------------------------------------------------
+# a state that fits one compute unit: the whole solve and its reverse sweep, one launch each
+# ---------------------------------------------------------------------------------------------------
+
+class _SmallEulerSolve(torch.autograd.Function):
+    """FixedGridODESolver.integrate with Euler (and, round 5, midpoint / RK4 3-8) steps (solvers.py:79-99, fixed_grid.py:7-29,
+    rk_common.py:72-78) over ODEFunc with ndcn_solve_small_f32 / ndcn_solve_small_bwd_f32 (csrc/solve_small.hip): the forward's
+    trajectory IS the saved state."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, csr, flags, dts, method='euler'):
+        lib = _lib.load()
+        n_ticks = len(dts)
+        H = y0.shape[1]
+        ctx.method = _lib.METHODS[method]
+        out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        arr = (ctypes.c_float * n_ticks)(*dts)
+        if flags & _lib.F_NO_CONTROL:
+            W = b = None
+        Wd, bd = _detached(W, b)
+        view = _view(csr, y0.shape[0], need_symmetric=True)
+        # Euler on the README shapes: the forward launch keeps S_i = A y_i and K_i of every step for the reverse sweep (two panels per
+        # tick instead of a gather and a Linear per tick in backward: ndcn_solve_small_keep_*)
+        keep = None
+        if ctx.method == _lib.M_EULER and csr is not None and Wd is not None and lib.ndcn_solve_small_keep_supported(view, H, flags):
+            keep = torch.empty((n_ticks, 2) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        with torch.cuda.device(y0.device):
+            if keep is not None:
+                check(lib.ndcn_solve_small_keep_f32(view, ptr(Wd), ptr(bd), H, flags, ptr(out[0]), arr, n_ticks, ptr(out[1:]), ptr(keep),
+                                                    stream_ptr()))
+            else:
+                check(lib.ndcn_solve_small_f32(view, ptr(Wd), ptr(bd), H, flags, ctx.method, ptr(out[0]), arr, n_ticks, ptr(out[1:]),
+                                               stream_ptr()))
+        ctx.csr, ctx.flags, ctx.dts, ctx.keep = csr, flags, arr, keep
+        # (W and b through save_for_backward: an in-place parameter change between forward and backward raises, as it does for
+        # every other autograd node, instead of differentiating the wrong weights)
+        ctx.save_for_backward(out, W, b)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, W, b = ctx.saved_tensors
+        lib = _lib.load()
+        Wd, bd = _detached(W, b)
+        H = out.shape[2]
+        g = g.contiguous()
+        g_y0 = torch.empty_like(out[0])
+        g_W = torch.empty((H, H), dtype=torch.float32, device=out.device) if Wd is not None else None
+        g_b = torch.empty((H,), dtype=torch.float32, device=out.device) if Wd is not None else None
+        csr = ctx.csr
+        view = _view(csr, out.shape[1], need_symmetric=True)
+        view_t = csr.transpose().view_ref() if csr is not None else view
+        with torch.cuda.device(out.device):
+            if ctx.keep is not None:
+                check(lib.ndcn_solve_small_bwd_keep_f32(view, view_t, ptr(Wd), ptr(bd), H, ctx.flags, ptr(out), ptr(g), ctx.dts, len(ctx.dts),
+                                                        ptr(ctx.keep), ptr(g_y0), ptr(g_W), ptr(g_b), stream_ptr()))
+                ctx.keep = None
+            else:
+                check(lib.ndcn_solve_small_bwd_f32(view, view_t, ptr(Wd), ptr(bd), H, ctx.flags, ctx.method, ptr(out), ptr(g), ctx.dts,
+                                                   len(ctx.dts), ptr(g_y0), ptr(g_W), ptr(g_b), stream_ptr()))
+        return g_y0, g_W, (g_b if bd is not None else None), None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------
+# any size, from Python: fused launches forward, closed-form sweep backward
+# ---------------------------------------------------------------------------------------------------
+
+def _step(csr, y, W, b, no_graph, no_control, method, dt, out_y, keep=None, drop=None):
+    """one step by fused launches; keep (a list) receives [(stage input, K), ...] for the reverse sweep; drop: the dropout triple
+    of the step's first evaluation (the following ones count on from it)"""
+    kw = dict(no_graph=no_graph, no_control=no_control)
+    ev = lambda j: {} if drop is None else {'dropout': (drop[0], drop[1], drop[2] + j)}
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    if method == 'euler':
+        K, _ = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(0))              # y + dt k1
+        stages = [(y, K)]
+    elif method == 'midpoint':
+        K1, ym = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [f32(dt / 2.0)], **kw, **ev(0))             # y + k1 dt / 2 (an exact halving)
+        K2, _ = hip.rhs_rk(csr, ym, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(1))           # y + dt k2
+        stages = [(y, K1), (ym, K2)]
+    else:
+        stages, x, ks = [], y, []
+        for i in range(4):
+            K, nxt = hip.rhs_rk(csr, x, W, b, 'rk4', y, ks, [dt], out_y=out_y if i == 3 else None, **kw, **ev(i))
+            stages.append((x, K))
+            ks = ks + [K]
+            x = nxt
+    if keep is not None:
+        keep.extend(stages)
+
+
+def _vjp(csr, u, K, g, W, b, no_graph, no_control, alpha):
+    """alpha * J(u)^T g for K = relu(W (A u) + b): (g_u, g_W, g_b) with g_W / g_b UNSCALED (the caller scales the small ones)"""
+    gW = gb = None
+    if no_control:
+        gS = hip.relu_bwd(g, K)
+    else:
+        S = u if no_graph else hip.spmm(csr, u)
+        gS, gW, gb = hip.linear_bwd(g, W, S=S, Y=K)
+    gu = hip.scale(gS, alpha) if no_graph else hip.spmm(csr.transpose(), gS, alpha=alpha)
+    return gu, gW, gb
+
+
+def _sweep_totals(out, csr, W, b, no_graph, no_control, drop):
+    """(gW_tot, gb_tot, vj, acc): the zeroed parameter gradients of a reverse sweep (None under no_control) and the two closures of
+    _sweep_step that fill them.  With dropout K is the masked K' = relu(z) * m, m in {0, s}: J^T g = s * (the p = 0 closed form masked
+    by K'), so s multiplies the alpha of the transposed SpMM and the scale of the parameter gradients"""
+    H = out.shape[2]
+    gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
+    gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
+    s = 1.0 if drop is None else _dropout.scale(drop[0])
+    vj = lambda u, K, gk, alpha: _vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha * s)
+
+    def acc(gW, gb, scale):
+        if gW is not None:
+            gW_tot.add_(gW, alpha=scale * s)
+            gb_tot.add_(gb, alpha=scale * s)
+    return gW_tot, gb_tot, vj, acc
+
+
+def _sweep_step(method, dt, st, a, vj, acc, close):
+    """the adjoint before one step from the adjoint `a` after it: st = the step's [(stage input, K), ...], vj / acc as _sweep_totals
+    makes them; close(a, [gu, ...]) is the step's last pass, a + the sum of the stages' gu (+ whatever enters at the state the step
+    starts from: the per-tick sweep adds that tick's gradient in the same pass)"""
+    if method == 'euler':                                   # y1 = y + dt k1
+        (u1, K1), = st
+        gu1, gW, gb = vj(u1, K1, a, dt)
+        acc(gW, gb, dt)
+        return close(a, [gu1])
+    if method == 'midpoint':                                # ym = y + (dt / 2) k1 ; y1 = y + dt k2
+        (u1, K1), (u2, K2) = st
+        gu2, gW, gb = vj(u2, K2, a, dt)                     # dL/d ym
+        acc(gW, gb, dt)
+        gu1, gW, gb = vj(u1, K1, gu2, dt / 2.0)
+        acc(gW, gb, dt / 2.0)
+        return close(a, [gu2, gu1])
+    (u1, K1), (u2, K2), (u3, K3), (u4, K4) = st             # the 3/8 rule, rk_common.py:72-78
+    c8 = dt / 8.0
+    gu4, gW, gb = vj(u4, K4, a, c8)                         # J4^T (c8 a)
+    acc(gW, gb, c8)
+    gk3 = hip.lincomb([a, gu4], [3.0 * c8, dt])
+    gu3, gW, gb = vj(u3, K3, gk3, 1.0)
+    acc(gW, gb, 1.0)
+    gk2 = hip.lincomb([a, gu4, gu3], [3.0 * c8, -dt, dt])
+    gu2, gW, gb = vj(u2, K2, gk2, 1.0)
+    acc(gW, gb, 1.0)
+    gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
+    gu1, gW, gb = vj(u1, K1, gk1, 1.0)
+    acc(gW, gb, 1.0)
+    return close(a, [gu4, gu3, gu2, gu1])
+
+
+def _sum_onto(a, panels):
+    """a + the panels, left to right from +0, in one pass"""
+    return hip.lincomb(panels, [1.0] * len(panels), y0=a)
+
+
+class _PlainTicks:
+    """Where the reverse sweeps take the gradient of tick j from - without a decoder: the panel g[j] of the trajectory's gradient."""
+
+    def __init__(self, g):
+        self.g = g
+
+    def seed(self, j):
+        """the adjoint at the last tick"""
+        return self.g[j]
+
+    def close(self, a, gus, j):
+        """the closing combination of the step that starts at tick j, the tick's gradient inside the same pass"""
+        return _sum_onto(a, gus + [self.g[j]])
+
+    def enter(self, a, ticks):
+        """the step_size sweep: the adjoint `a` (None: nothing yet) plus the gradients of the ticks reported at this state"""
+        gs = [self.g[j] for j in ticks]
+        if a is None:
+            a, gs = gs[0], gs[1:]
+        for q in range(0, len(gs), 8):
+            a = _sum_onto(a, gs[q:q + 8])
+        return a
+
+    def decoder_grads(self):
+        return None, None
+
+
+class _ReadoutTicks:
+    """With the decoder inside the node: g is the gradient of the DECODED ticks (T, N, C), and tick j's g[j] . Wd is formed inside the
+    pass that adds it (hip.readout_bwd), which also accumulates the decoder's own gradients from the stored state out[j] in fp64 (when
+    either is wanted) - rounded to float32 once, after the last tick."""
+
+    def __init__(self, g, out, Wd, needs_W, needs_b):
+        C, H = Wd.shape
+        self.g, self.out, self.Wd, self.needs = g, out, Wd, (needs_W, needs_b)
+        self.acc = torch.zeros(C * H + C, dtype=torch.float64, device=Wd.device) if (needs_W or needs_b) else None
+
+    def seed(self, j):
+        return hip.readout_bwd(self.g[j], self.Wd, y=self.out[j], acc=self.acc)
+
+    def close(self, a, gus, j):
+        return hip.readout_bwd(self.g[j], self.Wd, y=self.out[j], base=a, addends=gus, acc=self.acc)
+
+    def enter(self, a, ticks):
+        """one call per tick (an interval's last step may report several)"""
+        for j in ticks:
+            a = hip.readout_bwd(self.g[j], self.Wd, y=self.out[j], base=a, acc=self.acc)
+        return a
+
+    def decoder_grads(self):
+        if self.acc is None:
+            return None, None
+        C, H = self.Wd.shape
+        f = self.acc.to(torch.float32)
+        return (f[:C * H].view(C, H) if self.needs[0] else None), (f[C * H:] if self.needs[1] else None)
+
+
+def _ticks(ctx, g, out, Wd):
+    """the tick-gradient source of a node's backward: Wd (input 3, bd input 4) is None without a decoder"""
+    if Wd is None:
+        return _PlainTicks(g.contiguous())
+    return _ReadoutTicks(g.contiguous(), out, Wd, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+
+
+class _FixedGridSolve(torch.autograd.Function):
+    """FixedGridODESolver.integrate (solvers.py:79-99) over ODEFunc at ANY size on the kernels of the inference path:
+      forward   the launches of the device-resident solver - the stage algebra of every step rides in the epilogues of its
+                right-hand-side launches (ndcn_rhs_rk_f32: Euler / midpoint 1 launch per evaluation, RK4 4 per step); only the
+                trajectory is kept;
+      backward  per step, in reverse: the stages are re-formed from the stored state by the same launches (checkpointing: the
+                reference's autograd keeps every stage of every step), then the step's vector-Jacobian products in closed
+                form - SpMM, the masked Linear backward (g_S, g_W, g_b in one call), SpMM with A^T with the step size folded
+                into its alpha - and the stage recurrences as one linear-combination launch each.
+    No autograd graph per operation: the torch `add` / `mul` launches between the kernels are gone (they were 17 % of the
+    kernel time of a 100k-node Euler training step).
+    Active dropout (drop = (p, seed, first evaluation number of the solve)): evaluation e of the solve - EVALS[method] per step, in the
+    solver's order - runs with the mask of (seed, first + e) in its launch; the reverse pass re-forms the stages with the same
+    numbers, so the K it masks the backward kernels with are the forward's, and the scalar s = 1 / (1 - p) rides in the alphas."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, dts, drop=None):
+        n_ticks = len(dts)
+        out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
+        ctx.meta = (csr, no_graph, no_control, method, dts, drop)
+        for i, dt in enumerate(dts):
+            _step(csr, out[i], W, b, no_graph, no_control, method, dt, out[i + 1], drop=_drop_at(drop, method, i))
+        ctx.save_for_backward(out, W, b, Wd)
+        return out if Wd is None else hip.linear(out, Wd, bd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, W, b, Wd = ctx.saved_tensors
+        csr, no_graph, no_control, method, dts, drop = ctx.meta
+        ticks = _ticks(ctx, g, out, Wd)
+        a = ticks.seed(len(dts))
+        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, no_graph, no_control, drop)
+        for i in range(len(dts) - 1, -1, -1):
+            st = []
+            _step(csr, out[i], W, b, no_graph, no_control, method, dts[i], torch.empty_like(out[0]), keep=st, drop=_drop_at(drop, method, i))
+            a = _sweep_step(method, dts[i], st, a, vj, acc, lambda a, gus, i=i: ticks.close(a, gus, i))
+        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 5
+
+
+class _SubstepSolve(torch.autograd.Function):
+    """_FixedGridSolve on a grid finer than the ticks (options={'step_size': h}; core.FixedPlan) WITHOUT a record per grid step:
+      forward   the same fused launches, step after step; kept are the ticks and the state each tick interval starts from - the
+                tick panel itself where the interval's last tick coincides with the end of its step, else one panel;
+      backward  one tick interval at a time, last first: the interval is run again from its start by the same launches, this time
+                keeping the stages of its steps, then swept backwards in closed form (_sweep_step).  The gradient of a tick enters
+                at the end of the step that reported it (the VJP of ops.tick_emit is the identity).
+    Memory: ticks + interval starts + ONE interval's stages, whatever the number of grid steps."""
+
+    @staticmethod
+    def _segments(plan):
+        """[(first step, last step)]: runs of grid steps that end with a step reporting ticks"""
+        segs, lo = [], 0
+        for i, em in enumerate(plan.emits):
+            if em:
+                segs.append((lo, i))
+                lo = i + 1
+        return segs
+
+    @staticmethod
+    def _run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, last_out, keep=None, drop=None):
+        """steps lo .. hi from the state y; the last one writes to `last_out`; keep (a list) receives each step's stages; drop: the
+        solve's dropout triple - grid step i evaluates with the numbers it had in the forward pass, whenever it is run"""
+        pp = [None, None]
+        for i in range(lo, hi + 1):
+            if i == hi:
+                dst = last_out
+            else:
+                q = (i - lo) & 1
+                if pp[q] is None or keep is not None:         # (kept stages hold on to the panels they read)
+                    pp[q] = torch.empty_like(last_out)
+                dst = pp[q]
+            st = None if keep is None else []
+            _step(csr, y, W, b, no_graph, no_control, method, float(plan.dts[i]), dst, keep=st, drop=_drop_at(drop, method, i))
+            if keep is not None:
+                keep.append(st)
+            y = dst
+        return y
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, plan, drop=None):
+        n_ticks = len(plan.t)
+        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
+        segs = _SubstepSolve._segments(plan)
+        starts, own = [], []                 # per segment: where its first state lives - ('out', tick) or ('own', index into `own`)
+        y, where = out[0], ('out', 0)
+        for lo, hi in segs:
+            starts.append(where)
+            em = plan.emits[hi]
+            j_last, same_last, _ = em[-1]
+            if same_last:
+                y1, where = out[j_last], ('out', j_last)
+            else:
+                y1 = torch.empty_like(out[0])
+                own.append(y1)
+                where = ('own', len(own) - 1)
+            y = _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, y1, drop=drop)
+            loose = [e for e in em if not e[1]]
+            for q in range(0, len(loose), core.MAX_EMIT):
+                part = loose[q:q + core.MAX_EMIT]
+                hip.tick_emit(y, plan.dts[hi], [e[2] for e in part], outs=[out[e[0]] for e in part])
+        if own and where[0] == 'own':
+            own.pop()                        # nothing starts from the state after the last step
+        ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts, drop)
+        ctx.save_for_backward(out, W, b, Wd, *own)
+        return out if Wd is None else hip.linear(out, Wd, bd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, W, b, Wd, *own = ctx.saved_tensors
+        csr, no_graph, no_control, method, plan, segs, starts, drop = ctx.meta
+        ticks = _ticks(ctx, g, out, Wd)
+        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, no_graph, no_control, drop)
+        a = None
+        for (lo, hi), (kind, idx) in zip(reversed(segs), reversed(starts)):           # the tick intervals, last first
+            a = ticks.enter(a, [e[0] for e in plan.emits[hi]])                        # the ticks this interval's last step reported
+            y = out[idx] if kind == 'out' else own[idx]
+            keep = []
+            _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep, drop=drop)
+            for i in range(hi, lo - 1, -1):
+                a = _sweep_step(method, float(plan.dts[i]), keep.pop(), a, vj, acc, _sum_onto)
+        if a is None:
+            a = torch.zeros_like(out[0])
+        a = ticks.enter(a, [0])                                                       # the first tick is y0 itself
+        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 5
+
+
+# ---------------------------------------------------------------------------------------------------
+# any size, the loops inside the library
+# ---------------------------------------------------------------------------------------------------
+
+def _fixed_grid_train(y0c, Wc, bc, csr, flags, method, dts):
+    """ndcn_fixed_grid_train_f32 -> (trajectory (n_ticks + 1, N, H), the step sizes as the C array)"""
+    lib = _lib.load()
+    n_ticks = len(dts)
+    out = torch.empty((n_ticks + 1,) + tuple(y0c.shape), dtype=torch.float32, device=y0c.device)
+    scratch = Tape(y0c.device)
+    arr = (ctypes.c_float * n_ticks)(*dts)
+    with torch.cuda.device(y0c.device):
+        rc = lib.ndcn_fixed_grid_train_f32(_view(csr, y0c.shape[0]), ptr(Wc), ptr(bc), y0c.shape[1], flags, _lib.METHODS[method], ptr(y0c),
+                                           arr, n_ticks, ptr(out), ctypes.cast(scratch.cb, ctypes.c_void_p), None, stream_ptr())
+    _finish(scratch, rc)
+    return out, arr
+
+
+def _fixed_grid_reverse(out, Wc, bc, csr, flags, method, arr, n_ticks, g, decoder=None):
+    """The reverse sweep in the library -> (g_y0, g_W, g_b, g_Wd, g_bd).  g: the gradient of the trajectory (n_ticks + 1, N, H), or
+    with decoder = (Wd (C, H), want g_Wd, want g_bd) the gradient of the DECODED ticks (n_ticks + 1, N, C): the sweep then forms every
+    tick's g[i] . Wd where it adds it (ndcn_fixed_grid_backward_readout_f32) and returns the decoder's gradients too."""
+    lib = _lib.load()
+    g = g.contiguous()
+    no_control = bool(flags & _lib.F_NO_CONTROL)
+    gy = torch.empty_like(out[0])
+    gW = torch.empty_like(Wc) if (Wc is not None and not no_control) else None
+    gb = torch.empty_like(bc) if (bc is not None and not no_control) else None
+    scratch = Tape(g.device)
+    view = _view(csr, out.shape[1])
+    view_t = csr.transpose().view_ref() if csr is not None else None
+    alloc = ctypes.cast(scratch.cb, ctypes.c_void_p)
+    gWd = gbd = None
+    with torch.cuda.device(g.device):
+        if decoder is None:
+            rc = lib.ndcn_fixed_grid_backward_f32(view, view_t, ptr(Wc), ptr(bc), out.shape[2], flags, _lib.METHODS[method], ptr(out), ptr(g), arr,
+                                                  n_ticks, ptr(gy), ptr(gW), ptr(gb), alloc, None, stream_ptr())
+        else:
+            Wd, want_W, want_b = decoder
+            if want_W or want_b:
+                gWd = torch.empty_like(Wd)
+                gbd = torch.empty((Wd.shape[0],), dtype=torch.float32, device=g.device) if want_b else None
+            rc = lib.ndcn_fixed_grid_backward_readout_f32(view, view_t, ptr(Wc), ptr(bc), out.shape[2], flags, _lib.METHODS[method], ptr(out),
+                                                          ptr(g), ptr(Wd), Wd.shape[0], arr, n_ticks, ptr(gy), ptr(gW), ptr(gb), ptr(gWd),
+                                                          ptr(gbd), alloc, None, stream_ptr())
+    _finish(scratch, rc)
+    return gy, gW, gb, gWd, gbd
+
+
+class _NativeFixedGrid(torch.autograd.Function):
+    """Euler / midpoint / RK4 over ODEFunc with the loops of _FixedGridSolve inside the library (ndcn_fixed_grid_train_f32 /
+    ndcn_fixed_grid_backward_f32, with a decoder ndcn_fixed_grid_backward_readout_f32): the same launches, two calls instead of ~10
+    per step."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, dts):
+        y0c, Wc, bc = _detached(y0, W, b)
+        out, arr = _fixed_grid_train(y0c, Wc, bc, csr, flags, method, dts)
+        ctx.keep = (Wc, bc, csr, flags, method, arr, len(dts))
+        # Without a decoder `out` is this node's own output: saved through autograd (no out -> grad_fn -> ctx -> out cycle that only the
+        # cyclic collector would break - a (T, N, H) trajectory - and an in-place edit of the returned trajectory before backward
+        # raises).  With one the hidden trajectory is no output of the node: nothing differentiates through it, and it is released
+        # with the graph.
+        ctx.save_for_backward(out, W, b, Wd)
+        return out if Wd is None else hip.linear(out, Wd.detach(), None if bd is None else bd.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, _, _, Wd = ctx.saved_tensors
+        Wc, bc, csr, flags, method, arr, n_ticks = ctx.keep
+        needs = ctx.needs_input_grad
+        decoder = None if Wd is None else (Wd.detach().contiguous(), needs[3], needs[4])
+        grads = _fixed_grid_reverse(out, Wc, bc, csr, flags, method, arr, n_ticks, g, decoder=decoder)
+        return tuple(x if want else None for x, want in zip(grads, needs)) + (None,) * 4
+
+
+def fixed_grid(y0, W, b, Wd, bd, csr, flags, method, dts):
+    """-> the solution from _NativeFixedGrid, or None when the native loops are switched off (NDCN_FIXED_GRID_NATIVE=0)"""
+    if not _lib.env_on('NDCN_FIXED_GRID_NATIVE') or _lib.env_str('NDCN_VJP', 'hip') == 'torch':
+        return None
+    if csr is not None:
+        csr.ensure_plans(y0.shape[1])
+        csr.transpose().ensure_plans(y0.shape[1])
+    return _NativeFixedGrid.apply(y0, W, b, Wd, bd, csr, flags, method, dts)
+
+
+# ---------------------------------------------------------------------------------------------------
+# routing (odeint under a gradient calls these, in this order)
+# ---------------------------------------------------------------------------------------------------
+
+def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
+    """The one-launch training path when the library supports the shape (H <= 31, the state and three work panels in one
+    CU's LDS: the reference's README commands), else None - the caller falls back to the fused-launch nodes."""
+    from .odeint import _small_operator
+    if t.requires_grad or not _lib.env_on('NDCN_SOLVE_SMALL_GRAD') or t.numel() < 2:
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, view, flags = op
+    if not _lib.load().ndcn_solve_small_supported(view, odefunc.hidden_size, flags, _lib.METHODS[method], 1):
+        return None
+    if method != 'euler' and not _lib.env_on('NDCN_SOLVE_SMALL_RK_GRAD'):
+        return None
+    core.assert_increasing(t)
+    y0 = _lib.require_device(y0, 'state y0').contiguous()
+    W, b = odefunc.wt.weight, odefunc.wt.bias
+    if plan is not None:
+        # the step_size option: the one-launch pair on the explicit grid into a scratch trajectory (kilobytes per step at sizes that
+        # fit one compute unit), the ticks gathered from it - coincident ticks are its rows, the others pass through tick_emit
+        from ...autograd_ops import autograd_ops
+        fine = _SmallEulerSolve.apply(y0, W, b, csr, flags, plan.dts.tolist(), method)
+        ticks = [fine[0]]
+        for i, em in enumerate(plan.emits):
+            loose = [e for e in em if not e[1]]
+            made = {}
+            for q in range(0, len(loose), core.MAX_EMIT):
+                part = loose[q:q + core.MAX_EMIT]
+                for e, o in zip(part, autograd_ops.tick_emit(fine[i + 1], plan.dts[i], [e[2] for e in part])):
+                    made[e[0]] = o
+            ticks.extend(fine[i + 1] if same else made[j] for j, same, _ in em)
+        return torch.stack(ticks)
+    tt = core.host_grid(t).to(y0.dtype)                    # solvers.py:81: the grid in the state dtype
+    dts = (tt[1:] - tt[:-1]).tolist()
+    return _SmallEulerSolve.apply(y0, W, b, csr, flags, dts, method)
+
+
+def _readout_for_grad(readout, y0):
+    """(Wd, bd) when the fixed-grid training nodes can hold this decoder (hip.readout_bwd: float32 on the state's device, (C, H) with
+    1 <= C <= 15), else None - odeint then decodes the hidden solution in a step of its own"""
+    if readout is None:
+        return None
+    Wd, bd = readout
+    ok = torch.is_tensor(Wd) and Wd.dim() == 2 and Wd.dtype == torch.float32 and Wd.device == y0.device and Wd.shape[1] == y0.shape[1] and \
+        1 <= Wd.shape[0] <= hip.READOUT_BWD_MAX_C
+    if ok and bd is not None:
+        ok = torch.is_tensor(bd) and bd.dtype == torch.float32 and bd.device == y0.device and tuple(bd.shape) == (Wd.shape[0],)
+    return (Wd, bd) if ok else None
+
+
+def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None, readout=None):
+    """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size).
+    readout = (Wd, bd) (checked by _readout_for_grad): the DECODED solution, the decoder's Linear inside the solve's autograd node."""
+    from .odeint import _small_operator
+    if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, _, flags = op
+    core.assert_increasing(t)
+    drop = None
+    n_steps = len(plan.dts) if plan is not None else t.numel() - 1
+    if _dropout.is_active(odefunc):
+        # the solve's seed and a block of evaluation numbers, one per evaluation in the solver's order - the numbers the per-operation
+        # path hands out one by one (ODEFunc.forward), so both paths apply the same masks
+        stream = _dropout.current() or _dropout.Stream()
+        drop = (float(odefunc.dropout), stream.seed, stream.take(n_steps * EVALS[method]))
+    y0 = _lib.require_device(y0, 'state y0').contiguous()
+    W, b = odefunc.wt.weight, odefunc.wt.bias
+    Wd, bd = readout if readout is not None else (None, None)
+    if plan is not None:                                      # the step_size option: checkpointed per tick interval
+        return _SubstepSolve.apply(y0, W, b, Wd, bd, csr, flags, method, plan, drop)
+    tt = core.host_grid(t).to(y0.dtype)
+    dts = (tt[1:] - tt[:-1]).tolist()
+    if drop is None:                                          # (the C++ tape has no dropout form)
+        sol = fixed_grid(y0, W, b, Wd, bd, csr, flags, method, dts)
+        if sol is not None:
+            return sol
+    return _FixedGridSolve.apply(y0, W, b, Wd, bd, csr, flags, method, dts, drop)

@@ -21,7 +21,7 @@ from ... import _lib
 from ... import dropout as _dropout
 from ...ops import hip, new_solve_epoch
 from ...truth import TRUTH_CLASSES
-from . import core
+from . import core, fixed_train
 
 SOLVERS = {m: m for m in core.METHODS}      # the in-scope subset of odeint.py:8-17
 GRAPH_MAX_ELEMS = 1 << 23                   # below ~8M state elements (Pubmed x 256) a step is launch-bound
@@ -156,11 +156,11 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         # (an active dropout: the one-launch pair declines; the fused launches carry the mask and re-create it in the reverse sweep)
         sol = None
         if not _dropout.is_active(user_func):
-            sol = _small_solve_with_grad(user_func, y0[0], t, method, plan)                  # one launch forward, one backward
+            sol = fixed_train._small_solve_with_grad(user_func, y0[0], t, method, plan)                  # one launch forward, one backward
         if sol is None:
             # any size: fused launches forward, closed-form sweep backward - with `readout` the decoder inside the same node
-            dec = _readout_for_grad(readout, y0[0])
-            sol = _fixed_grid_with_grad(user_func, y0[0], t, method, plan, readout=dec)
+            dec = fixed_train._readout_for_grad(readout, y0[0])
+            sol = fixed_train._fixed_grid_with_grad(user_func, y0[0], t, method, plan, readout=dec)
             if sol is not None:
                 return sol, dec is not None
         if sol is not None:
@@ -193,508 +193,6 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan)
     out = tuple(torch.stack([s[i] for s in sol]) for i in range(len(y0)))
     return (out[0] if tensor_input else out), False
-
-
-# ---------------------------------------------------------------------------------------------------
-# training on a state that fits one compute unit: the whole Euler solve and its reverse sweep, one launch each
-# ---------------------------------------------------------------------------------------------------
-
-class _SmallEulerSolve(torch.autograd.Function):
-    """FixedGridODESolver.integrate with Euler (and, round 5, midpoint / RK4 3-8) steps (solvers.py:79-99, fixed_grid.py:7-29,
-    rk_common.py:72-78) over ODEFunc, differentiated the
-    way the reference's drivers train - plain backpropagation through every step (heat_dynamics.py:313-334) - with
-    ndcn_solve_small_f32 / ndcn_solve_small_bwd_f32 (csrc/solve_small.hip): the forward's trajectory IS the saved state."""
-
-    @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, dts, method='euler'):
-        lib = _lib.load()
-        n_ticks = len(dts)
-        H = y0.shape[1]
-        ctx.method = _lib.METHODS[method]
-        out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-        arr = (ctypes.c_float * n_ticks)(*dts)
-        no_control = bool(flags & _lib.F_NO_CONTROL)
-        Wd = None if no_control else W.detach().contiguous()
-        bd = None if (no_control or b is None) else b.detach().contiguous()
-        view = csr.view_ref(need_symmetric=True) if csr is not None else ctypes.byref(_lib.empty_csr(y0.shape[0]))
-        # Euler on the README shapes: the forward launch keeps S_i = A y_i and K_i of every step for the reverse sweep (two panels per
-        # tick instead of a gather and a Linear per tick in backward: ndcn_solve_small_keep_*)
-        keep = None
-        if ctx.method == _lib.M_EULER and csr is not None and Wd is not None and lib.ndcn_solve_small_keep_supported(view, H, flags):
-            keep = torch.empty((n_ticks, 2) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        with torch.cuda.device(y0.device):
-            if keep is not None:
-                _lib.check(lib.ndcn_solve_small_keep_f32(view, _lib.ptr(Wd), _lib.ptr(bd), H, flags, _lib.ptr(out[0]), arr, n_ticks,
-                                                         _lib.ptr(out[1:]), _lib.ptr(keep), _lib.stream_ptr()))
-            else:
-                _lib.check(lib.ndcn_solve_small_f32(view, _lib.ptr(Wd), _lib.ptr(bd), H, flags, ctx.method, _lib.ptr(out[0]), arr,
-                                                    n_ticks, _lib.ptr(out[1:]), _lib.stream_ptr()))
-        ctx.csr, ctx.flags, ctx.dts, ctx.keep = csr, flags, arr, keep
-        ctx.has_W, ctx.has_b = Wd is not None, bd is not None
-        # (W and b through save_for_backward: an in-place parameter change between forward and backward raises, as it does for
-        # every other autograd node, instead of differentiating the wrong weights)
-        ctx.save_for_backward(out, *([W] if Wd is not None else []), *([b] if bd is not None else []))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        out, *wb = ctx.saved_tensors
-        lib = _lib.load()
-        Wd = wb[0].detach().contiguous() if ctx.has_W else None
-        bd = wb[1 if ctx.has_W else 0].detach().contiguous() if ctx.has_b else None
-        H = out.shape[2]
-        g = g.contiguous()
-        g_y0 = torch.empty_like(out[0])
-        g_W = torch.empty((H, H), dtype=torch.float32, device=out.device) if Wd is not None else None
-        g_b = torch.empty((H,), dtype=torch.float32, device=out.device) if Wd is not None else None
-        csr = ctx.csr
-        view = csr.view_ref(need_symmetric=True) if csr is not None else ctypes.byref(_lib.empty_csr(out.shape[1]))
-        view_t = csr.transpose().view_ref() if csr is not None else view
-        with torch.cuda.device(out.device):
-            if ctx.keep is not None:
-                _lib.check(lib.ndcn_solve_small_bwd_keep_f32(view, view_t, _lib.ptr(Wd), _lib.ptr(bd), H, ctx.flags, _lib.ptr(out), _lib.ptr(g),
-                                                             ctx.dts, len(ctx.dts), _lib.ptr(ctx.keep), _lib.ptr(g_y0), _lib.ptr(g_W),
-                                                             _lib.ptr(g_b), _lib.stream_ptr()))
-                ctx.keep = None
-            else:
-                _lib.check(lib.ndcn_solve_small_bwd_f32(view, view_t, _lib.ptr(Wd), _lib.ptr(bd), H, ctx.flags, ctx.method, _lib.ptr(out),
-                                                        _lib.ptr(g), ctx.dts, len(ctx.dts), _lib.ptr(g_y0), _lib.ptr(g_W), _lib.ptr(g_b),
-                                                        _lib.stream_ptr()))
-        return g_y0, g_W, (g_b if bd is not None else None), None, None, None, None
-
-
-class _FixedGridSolve(torch.autograd.Function):
-    """FixedGridODESolver.integrate (solvers.py:79-99) over ODEFunc at ANY size, differentiated the way the drivers train (plain
-    backpropagation through every step, heat_dynamics.py:313-334), on the kernels of the inference path:
-      forward   the launches of the device-resident solver - the stage algebra of every step rides in the epilogues of its
-                right-hand-side launches (ndcn_rhs_rk_f32: Euler / midpoint 1 launch per evaluation, RK4 4 per step); only the
-                trajectory - the output - is kept;
-      backward  per step, in reverse: the stages are re-formed from the stored state by the same launches (checkpointing: the
-                reference's autograd keeps every stage of every step), then the step's vector-Jacobian products in closed
-                form - SpMM, the masked Linear backward (g_S, g_W, g_b in one call), SpMM with A^T with the step size folded
-                into its alpha - and the stage recurrences as one linear-combination launch each.
-    No autograd graph per operation: the torch `add` / `mul` launches between the kernels are gone (they were 17 % of the
-    kernel time of a 100k-node Euler training step).
-    Active dropout (drop = (p, seed, first evaluation number of the solve)): evaluation e of the solve - EVALS[method] per step, in the
-    solver's order - runs with the mask of (seed, first + e) in its launch; the reverse pass re-forms the stages with the same
-    numbers, so the K it masks the backward kernels with are the forward's, and the scalar s = 1 / (1 - p) rides in the alphas."""
-
-    EVALS = {'euler': 1, 'midpoint': 2, 'rk4': 4}
-
-    @staticmethod
-    def _drop_at(drop, method, step):
-        """the (p, seed, evaluation) of the first evaluation of grid step `step`"""
-        return None if drop is None else (drop[0], drop[1], drop[2] + step * _FixedGridSolve.EVALS[method])
-
-    @staticmethod
-    def _solve(ctx, y0, W, b, csr, flags, method, dts, drop):
-        """the forward launches -> the trajectory; ctx.meta set"""
-        n_ticks = len(dts)
-        out = torch.empty((n_ticks + 1,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-        no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
-        ctx.meta = (csr, no_graph, no_control, method, dts, drop)
-        for i, dt in enumerate(dts):
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dt, out[i + 1],
-                                  drop=_FixedGridSolve._drop_at(drop, method, i))
-        return out
-
-    @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, dts, drop=None):
-        out = _FixedGridSolve._solve(ctx, y0, W, b, csr, flags, method, dts, drop)
-        ctx.save_for_backward(out, W, b)
-        return out
-
-    @staticmethod
-    def _step(csr, y, W, b, no_graph, no_control, method, dt, out_y, keep=None, drop=None):
-        """one step by fused launches; keep (a list) receives [(stage input, K), ...] for the reverse sweep; drop: the dropout triple
-        of the step's first evaluation (the following ones count on from it)"""
-        kw = dict(no_graph=no_graph, no_control=no_control)
-        ev = lambda j: {} if drop is None else {'dropout': (drop[0], drop[1], drop[2] + j)}
-        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
-        if method == 'euler':
-            K, _ = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(0))              # y + dt k1
-            stages = [(y, K)]
-        elif method == 'midpoint':
-            K1, ym = hip.rhs_rk(csr, y, W, b, 'combine', y, [], [f32(dt / 2.0)], **kw, **ev(0))             # y + k1 dt / 2 (an exact halving)
-            K2, _ = hip.rhs_rk(csr, ym, W, b, 'combine', y, [], [dt], out_y=out_y, **kw, **ev(1))           # y + dt k2
-            stages = [(y, K1), (ym, K2)]
-        else:
-            stages, x, ks = [], y, []
-            for i in range(4):
-                K, nxt = hip.rhs_rk(csr, x, W, b, 'rk4', y, ks, [dt], out_y=out_y if i == 3 else None, **kw, **ev(i))
-                stages.append((x, K))
-                ks = ks + [K]
-                x = nxt
-        if keep is not None:
-            keep.extend(stages)
-
-    @staticmethod
-    def _vjp(csr, u, K, g, W, b, no_graph, no_control, alpha):
-        """alpha * J(u)^T g for K = relu(W (A u) + b): (g_u, g_W, g_b) with g_W / g_b UNSCALED (the caller scales the small ones)"""
-        gW = gb = None
-        if no_control:
-            gS = hip.relu_bwd(g, K)
-        else:
-            S = u if no_graph else hip.spmm(csr, u)
-            gS, gW, gb = hip.linear_bwd(g, W, S=S, Y=K)
-        gu = hip.scale(gS, alpha) if no_graph else hip.spmm(csr.transpose(), gS, alpha=alpha)
-        return gu, gW, gb
-
-    @staticmethod
-    def _sweep_step(method, dt, st, a, vj, acc, extra):
-        """the adjoint before one step from the adjoint `a` after it: st = the step's [(stage input, K), ...], vj / acc as in backward;
-        extra: gradients that enter at the state the step starts from, added in the same pass - a list of panels, or a callable
-        extra(a, [gu, ...]) that makes the pass itself (the readout form: the entering gradient is formed inside hip.readout_bwd)"""
-        if callable(extra):
-            close = lambda gus: extra(a, gus)
-        else:
-            close = lambda gus: hip.lincomb(gus + extra, [1.0] * (len(gus) + len(extra)), y0=a)
-        if method == 'euler':                                   # y1 = y + dt k1
-            (u1, K1), = st
-            gu1, gW, gb = vj(u1, K1, a, dt)
-            acc(gW, gb, dt)
-            return close([gu1])
-        if method == 'midpoint':                                # ym = y + (dt / 2) k1 ; y1 = y + dt k2
-            (u1, K1), (u2, K2) = st
-            gu2, gW, gb = vj(u2, K2, a, dt)                     # dL/d ym
-            acc(gW, gb, dt)
-            gu1, gW, gb = vj(u1, K1, gu2, dt / 2.0)
-            acc(gW, gb, dt / 2.0)
-            return close([gu2, gu1])
-        (u1, K1), (u2, K2), (u3, K3), (u4, K4) = st             # the 3/8 rule, rk_common.py:72-78
-        c8 = dt / 8.0
-        gu4, gW, gb = vj(u4, K4, a, c8)                         # J4^T (c8 a)
-        acc(gW, gb, c8)
-        gk3 = hip.lincomb([a, gu4], [3.0 * c8, dt])
-        gu3, gW, gb = vj(u3, K3, gk3, 1.0)
-        acc(gW, gb, 1.0)
-        gk2 = hip.lincomb([a, gu4, gu3], [3.0 * c8, -dt, dt])
-        gu2, gW, gb = vj(u2, K2, gk2, 1.0)
-        acc(gW, gb, 1.0)
-        gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
-        gu1, gW, gb = vj(u1, K1, gk1, 1.0)
-        acc(gW, gb, 1.0)
-        return close([gu4, gu3, gu2, gu1])
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        out, W, b = ctx.saved_tensors
-        csr, no_graph, no_control, method, dts, drop = ctx.meta
-        g = g.contiguous()
-        n_ticks = len(dts)
-        H = out.shape[2]
-        a = g[n_ticks]
-        gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
-        gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
-        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
-        for i in range(n_ticks - 1, -1, -1):
-            st = []
-            scratch = torch.empty_like(out[0])
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st,
-                                  drop=_FixedGridSolve._drop_at(drop, method, i))
-            a = _FixedGridSolve._sweep_step(method, dts[i], st, a, vj, acc, [g[i]])
-        return a, gW_tot, (gb_tot if b is not None else None), None, None, None, None, None
-
-    @staticmethod
-    def _vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot):
-        """the two closures of _sweep_step.  With dropout K is the masked K' = relu(z) * m, m in {0, s}: J^T g = s * (the p = 0 closed
-        form masked by K'), so s multiplies the alpha of the transposed SpMM and the scale of the parameter gradients"""
-        s = 1.0 if drop is None else _dropout.scale(drop[0])
-        vj = lambda u, K, gk, alpha: _FixedGridSolve._vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha * s)
-
-        def acc(gW, gb, scale):
-            if gW is not None:
-                gW_tot.add_(gW, alpha=scale * s)
-                gb_tot.add_(gb, alpha=scale * s)
-        return vj, acc
-
-
-def _decoder_acc(Wd, needs_W, needs_b):
-    """the fp64 accumulator of the decoder's gradients over a reverse sweep (hip.readout_bwd), or None when neither is wanted"""
-    if not (needs_W or needs_b):
-        return None
-    C, H = Wd.shape
-    return torch.zeros(C * H + C, dtype=torch.float64, device=Wd.device)
-
-
-def _decoder_grads(acc, Wd, needs_W, needs_b):
-    """(g_Wd, g_bd): the accumulator rounded to float32 once, after the last tick"""
-    if acc is None:
-        return None, None
-    C, H = Wd.shape
-    f = acc.to(torch.float32)
-    return (f[:C * H].view(C, H) if needs_W else None), (f[C * H:] if needs_b else None)
-
-
-class _FixedGridSolveReadout(torch.autograd.Function):
-    """_FixedGridSolve with the decoder Linear(Wd, bd) of every tick inside the node (odeint's `readout` under a gradient): the output
-    is the decoded solution (T, N, C), hip.linear of the trajectory; the reverse sweep takes the (T, N, C) gradient and forms tick i's
-    g[i] . Wd inside the pass that adds it (hip.readout_bwd in _sweep_step's last combination) - the (T, N, H) gradient of the
-    trajectory is never written - and accumulates the decoder's own gradients from the stored states on the way."""
-
-    @staticmethod
-    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, dts, drop=None):
-        out = _FixedGridSolve._solve(ctx, y0, W, b, csr, flags, method, dts, drop)
-        ctx.save_for_backward(out, W, b, Wd)
-        return hip.linear(out, Wd, bd)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        out, W, b, Wd = ctx.saved_tensors
-        csr, no_graph, no_control, method, dts, drop = ctx.meta
-        g = g.contiguous()
-        n_ticks = len(dts)
-        H = out.shape[2]
-        needs = ctx.needs_input_grad
-        dacc = _decoder_acc(Wd, needs[3], needs[4])
-        a = hip.readout_bwd(g[n_ticks], Wd, y=out[n_ticks], acc=dacc)
-        gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
-        gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
-        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
-        for i in range(n_ticks - 1, -1, -1):
-            st = []
-            scratch = torch.empty_like(out[0])
-            _FixedGridSolve._step(csr, out[i], W, b, no_graph, no_control, method, dts[i], scratch, keep=st,
-                                  drop=_FixedGridSolve._drop_at(drop, method, i))
-            a = _FixedGridSolve._sweep_step(method, dts[i], st, a, vj, acc,
-                                            lambda base, gus, i=i: hip.readout_bwd(g[i], Wd, y=out[i], base=base, addends=gus, acc=dacc))
-        gWd, gbd = _decoder_grads(dacc, Wd, needs[3], needs[4])
-        return a, gW_tot, (gb_tot if b is not None else None), gWd, gbd, None, None, None, None, None
-
-
-class _SubstepSolve(torch.autograd.Function):
-    """_FixedGridSolve on a grid finer than the ticks (options={'step_size': h}; core.FixedPlan) WITHOUT a record per grid step:
-      forward   the same fused launches, step after step; kept are the ticks (the output) and the state each tick interval starts
-                from - the output panel itself where the interval's last tick coincides with the end of its step, else one panel;
-      backward  one tick interval at a time, last first: the interval is run again from its start by the same launches, this time
-                keeping the stages of its steps, then swept backwards in closed form (_FixedGridSolve._sweep_step).  The gradient
-                of a tick enters at the end of the step that reported it (the VJP of ops.tick_emit is the identity).
-    Memory: ticks + interval starts + ONE interval's stages, whatever the number of grid steps."""
-
-    @staticmethod
-    def _segments(plan):
-        """[(first step, last step)]: runs of grid steps that end with a step reporting ticks"""
-        segs, lo = [], 0
-        for i, em in enumerate(plan.emits):
-            if em:
-                segs.append((lo, i))
-                lo = i + 1
-        return segs
-
-    @staticmethod
-    def _run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, last_out, keep=None, drop=None):
-        """steps lo .. hi from the state y; the last one writes to `last_out`; keep (a list) receives each step's stages; drop: the
-        solve's dropout triple - grid step i evaluates with the numbers it had in the forward pass, whenever it is run"""
-        pp = [None, None]
-        for i in range(lo, hi + 1):
-            if i == hi:
-                dst = last_out
-            else:
-                q = (i - lo) & 1
-                if pp[q] is None or keep is not None:         # (kept stages hold on to the panels they read)
-                    pp[q] = torch.empty_like(last_out)
-                dst = pp[q]
-            st = None if keep is None else []
-            _FixedGridSolve._step(csr, y, W, b, no_graph, no_control, method, float(plan.dts[i]), dst, keep=st,
-                                  drop=_FixedGridSolve._drop_at(drop, method, i))
-            if keep is not None:
-                keep.append(st)
-            y = dst
-        return y
-
-    @staticmethod
-    def _solve(ctx, y0, W, b, csr, flags, method, plan, drop):
-        """the forward launches -> (the ticks, the interval starts that are no tick); ctx.meta set"""
-        n_ticks = len(plan.t)
-        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-        no_graph, no_control = bool(flags & _lib.F_NO_GRAPH), bool(flags & _lib.F_NO_CONTROL)
-        segs = _SubstepSolve._segments(plan)
-        starts, own = [], []                 # per segment: where its first state lives - ('out', tick) or ('own', index into `own`)
-        y, where = out[0], ('out', 0)
-        for lo, hi in segs:
-            starts.append(where)
-            em = plan.emits[hi]
-            j_last, same_last, _ = em[-1]
-            if same_last:
-                y1, where = out[j_last], ('out', j_last)
-            else:
-                y1 = torch.empty_like(out[0])
-                own.append(y1)
-                where = ('own', len(own) - 1)
-            y = _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, y1, drop=drop)
-            loose = [e for e in em if not e[1]]
-            for q in range(0, len(loose), core.MAX_EMIT):
-                part = loose[q:q + core.MAX_EMIT]
-                hip.tick_emit(y, plan.dts[hi], [e[2] for e in part], outs=[out[e[0]] for e in part])
-        if own and where[0] == 'own':
-            own.pop()                        # nothing starts from the state after the last step
-        ctx.meta = (csr, no_graph, no_control, method, plan, segs, starts, drop)
-        return out, own
-
-    @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, plan, drop=None):
-        out, own = _SubstepSolve._solve(ctx, y0, W, b, csr, flags, method, plan, drop)
-        ctx.save_for_backward(out, W, b, *own)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        out, W, b, *own = ctx.saved_tensors
-        g = g.contiguous()
-
-        def enter(a, ticks):
-            """the adjoint `a` (None: nothing yet) plus the gradients of the ticks reported at this state"""
-            gs = [g[j] for j in ticks]
-            if a is None:
-                a, gs = gs[0], gs[1:]
-            for q in range(0, len(gs), 8):
-                a = hip.lincomb(gs[q:q + 8], [1.0] * len(gs[q:q + 8]), y0=a)
-            return a
-        return _SubstepSolve._reverse(ctx, out, W, b, own, enter) + (None, None, None, None, None)
-
-    @staticmethod
-    def _reverse(ctx, out, W, b, own, enter):
-        """(g_y0, g_W, g_b): the tick intervals last first; enter(a, ticks) adds the gradients of the listed ticks to the adjoint"""
-        csr, no_graph, no_control, method, plan, segs, starts, drop = ctx.meta
-        H = out.shape[2]
-        gW_tot = torch.zeros((H, H), dtype=torch.float32, device=out.device) if not no_control else None
-        gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
-        vj, acc = _FixedGridSolve._vj_acc(csr, W, b, no_graph, no_control, drop, gW_tot, gb_tot)
-        a = None
-        for (lo, hi), (kind, idx) in zip(reversed(segs), reversed(starts)):
-            a = enter(a, [e[0] for e in plan.emits[hi]])                 # the ticks this interval's last step reported
-            y = out[idx] if kind == 'out' else own[idx]
-            keep = []
-            _SubstepSolve._run(csr, y, W, b, no_graph, no_control, method, plan, lo, hi, torch.empty_like(out[0]), keep=keep, drop=drop)
-            for i in range(hi, lo - 1, -1):
-                a = _FixedGridSolve._sweep_step(method, float(plan.dts[i]), keep.pop(), a, vj, acc, [])
-        if a is None:
-            a = torch.zeros_like(out[0])
-        a = enter(a, [0])                                               # the first tick is y0 itself
-        return a, gW_tot, (gb_tot if b is not None else None)
-
-
-class _SubstepSolveReadout(torch.autograd.Function):
-    """_SubstepSolve with the decoder of every tick inside the node, as _FixedGridSolveReadout: a tick's gradient enters the adjoint
-    at the end of the step that reported it, one hip.readout_bwd call per tick (an interval's last step may report several)."""
-
-    @staticmethod
-    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, plan, drop=None):
-        out, own = _SubstepSolve._solve(ctx, y0, W, b, csr, flags, method, plan, drop)
-        ctx.save_for_backward(out, W, b, Wd, *own)
-        return hip.linear(out, Wd, bd)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        out, W, b, Wd, *own = ctx.saved_tensors
-        g = g.contiguous()
-        needs = ctx.needs_input_grad
-        dacc = _decoder_acc(Wd, needs[3], needs[4])
-
-        def enter(a, ticks):
-            for j in ticks:
-                a = hip.readout_bwd(g[j], Wd, y=out[j], base=a, acc=dacc)
-            return a
-        ga, gW, gb = _SubstepSolve._reverse(ctx, out, W, b, own, enter)
-        gWd, gbd = _decoder_grads(dacc, Wd, needs[3], needs[4])
-        return ga, gW, gb, gWd, gbd, None, None, None, None, None
-
-
-def _readout_for_grad(readout, y0):
-    """(Wd, bd) when the fixed-grid training nodes can hold this decoder (hip.readout_bwd: float32 on the state's device, (C, H) with
-    1 <= C <= 15), else None - odeint then decodes the hidden solution in a step of its own"""
-    if readout is None:
-        return None
-    Wd, bd = readout
-    ok = torch.is_tensor(Wd) and Wd.dim() == 2 and Wd.dtype == torch.float32 and Wd.device == y0.device and Wd.shape[1] == y0.shape[1] and \
-        1 <= Wd.shape[0] <= hip.READOUT_BWD_MAX_C
-    if ok and bd is not None:
-        ok = torch.is_tensor(bd) and bd.dtype == torch.float32 and bd.device == y0.device and tuple(bd.shape) == (Wd.shape[0],)
-    return (Wd, bd) if ok else None
-
-
-def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None, readout=None):
-    """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size).
-    readout = (Wd, bd) (checked by _readout_for_grad): the DECODED solution, the decoder's Linear inside the solve's autograd node."""
-    if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
-        return None
-    op = _small_operator(odefunc, y0)
-    if op is None:
-        return None
-    csr, _, flags = op
-    core.assert_increasing(t)
-    drop = None
-    n_steps = len(plan.dts) if plan is not None else t.numel() - 1
-    if _dropout.is_active(odefunc):
-        # the solve's seed and a block of evaluation numbers, one per evaluation in the solver's order - the numbers the per-operation
-        # path hands out one by one (ODEFunc.forward), so both paths apply the same masks
-        stream = _dropout.current() or _dropout.Stream()
-        drop = (float(odefunc.dropout), stream.seed, stream.take(n_steps * _FixedGridSolve.EVALS[method]))
-    y0 = _lib.require_device(y0, 'state y0').contiguous()
-    W, b = odefunc.wt.weight, odefunc.wt.bias
-    if plan is not None:                                      # the step_size option: checkpointed per tick interval
-        if readout is not None:
-            return _SubstepSolveReadout.apply(y0, W, b, readout[0], readout[1], csr, flags, method, plan, drop)
-        return _SubstepSolve.apply(y0, W, b, csr, flags, method, plan, drop)
-    tt = core.host_grid(t).to(y0.dtype)
-    dts = (tt[1:] - tt[:-1]).tolist()
-    if drop is None:                                          # (the C++ tape has no dropout form)
-        from . import tape
-        sol = tape.fixed_grid(y0, W, b, csr, flags, method, dts, readout=readout)
-        if sol is not None:
-            return sol
-    if readout is not None:
-        return _FixedGridSolveReadout.apply(y0, W, b, readout[0], readout[1], csr, flags, method, dts, drop)
-    return _FixedGridSolve.apply(y0, W, b, csr, flags, method, dts, drop)
-
-
-def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
-    """The one-launch training path when the library supports the shape (H <= 31, the state and three work panels in one
-    CU's LDS: the reference's README commands), else None - the caller falls back to the per-step autograd path."""
-    from ...csr import as_csr
-    if t.requires_grad or not _lib.env_on('NDCN_SOLVE_SMALL_GRAD') or t.numel() < 2:
-        return None
-    lib = _lib.load()
-    H = odefunc.hidden_size
-    flags = _lib.F_RELU | (_lib.F_NO_GRAPH if odefunc.no_graph else 0) | (_lib.F_NO_CONTROL if odefunc.no_control else 0)
-    csr = None
-    if not odefunc.no_graph:
-        csr = as_csr(odefunc.A)
-        if csr.device != y0.device or csr.shape[0] != y0.shape[0]:
-            return None
-    view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(y0.shape[0]))
-    if not lib.ndcn_solve_small_supported(view, H, flags, _lib.METHODS[method], 1):
-        return None
-    if method != 'euler' and not _lib.env_on('NDCN_SOLVE_SMALL_RK_GRAD'):
-        return None
-    core.assert_increasing(t)
-    if plan is not None:
-        # the step_size option: the one-launch pair on the explicit grid into a scratch trajectory (kilobytes per step at sizes that
-        # fit one compute unit), the ticks gathered from it - coincident ticks are its rows, the others pass through tick_emit
-        from ...autograd_ops import autograd_ops
-        fine = _SmallEulerSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags,
-                                      plan.dts.tolist(), method)
-        ticks = [fine[0]]
-        for i, em in enumerate(plan.emits):
-            loose = [e for e in em if not e[1]]
-            made = {}
-            for q in range(0, len(loose), core.MAX_EMIT):
-                part = loose[q:q + core.MAX_EMIT]
-                for e, o in zip(part, autograd_ops.tick_emit(fine[i + 1], plan.dts[i], [e[2] for e in part])):
-                    made[e[0]] = o
-            ticks.extend(fine[i + 1] if same else made[j] for j, same, _ in em)
-        return torch.stack(ticks)
-    tt = core.host_grid(t).to(y0.dtype)                    # solvers.py:81: the grid in the state dtype
-    dts = (tt[1:] - tt[:-1]).tolist()
-    return _SmallEulerSolve.apply(_lib.require_device(y0, 'state y0').contiguous(), odefunc.wt.weight, odefunc.wt.bias, csr, flags, dts, method)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -766,7 +264,7 @@ class DeviceSolver:
             self._init_truth(odefunc, n_rows, method, rtol, atol, max_num_steps, use_graph, safety, ifactor, dfactor, shard)
             return
         H = odefunc.hidden_size
-        flags = _lib.F_RELU | (_lib.F_NO_GRAPH if odefunc.no_graph else 0) | (_lib.F_NO_CONTROL if odefunc.no_control else 0)
+        flags = _lib.operator_flags(odefunc)
         dev = odefunc.wt.weight.device
         self.csr = None
         if shard is not None:
@@ -905,7 +403,7 @@ def _small_operator(odefunc, y0):
     """(csr or None, ctypes view ref, flags) of an ODEFunc for the ndcn_solve_small_* entry points, or None when the operator
     does not live with the state."""
     from ...csr import as_csr
-    flags = _lib.F_RELU | (_lib.F_NO_GRAPH if odefunc.no_graph else 0) | (_lib.F_NO_CONTROL if odefunc.no_control else 0)
+    flags = _lib.operator_flags(odefunc)
     if odefunc.no_graph:
         return None, ctypes.byref(_lib.empty_csr(y0.shape[0])), flags
     csr = as_csr(odefunc.A)
@@ -957,7 +455,7 @@ def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
 
 def _small_solve(odefunc, y0, tt, method, plan=None):
     """ndcn_solve_small_f32 without a solver object (no workspace, no host synchronisation): the inference counterpart of
-    _SmallEulerSolve.  tt: the time grid as Python floats ALREADY rounded to the state dtype (solvers.py:81).  plan (the step_size
+    fixed_train._SmallEulerSolve.  tt: the time grid as Python floats ALREADY rounded to the state dtype (solvers.py:81).  plan (the step_size
     option): ndcn_solve_small_grid_f32 - the steps of plan.grid, still one launch per 128 steps, only the ticks written."""
     import numpy as np
     if type(odefunc) in TRUTH_CLASSES:                        # (the one-launch solve is ODEFunc's)

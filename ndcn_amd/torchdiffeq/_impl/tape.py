@@ -199,7 +199,7 @@ def solve(odefunc, y0, t, rtol, atol, options, step_log):
     from ...csr import as_csr
     opt = core.dopri5_options(options, 1)
     rt, at = core.per_state_tolerance(rtol, 1)[0], core.per_state_tolerance(atol, 1)[0]
-    flags = _lib.F_RELU | (_lib.F_NO_GRAPH if odefunc.no_graph else 0) | (_lib.F_NO_CONTROL if odefunc.no_control else 0)
+    flags = _lib.operator_flags(odefunc)
     csr = csr_t = None
     if not odefunc.no_graph:
         csr = as_csr(odefunc.A)
@@ -221,133 +221,3 @@ def solve(odefunc, y0, t, rtol, atol, options, step_log):
         stream = _dropout.current() or _dropout.Stream()
         drop = (float(odefunc.dropout), stream.seed, stream.evaluations, stream)
     return _TapeDopri5.apply(y0, W, b, (csr, csr_t, flags, odefunc.hidden_size), ticks, rt, at, opts, step_log, budget, drop)
-
-
-# ---- fixed grids ---------------------------------------------------------------------------------------------------------------
-
-def _fixed_grid_train(y0c, Wc, bc, csr, flags, method, dts):
-    """ndcn_fixed_grid_train_f32 -> (trajectory (n_ticks + 1, N, H), the step sizes as the C array)"""
-    lib = _lib.load()
-    n_ticks = len(dts)
-    out = torch.empty((n_ticks + 1,) + tuple(y0c.shape), dtype=torch.float32, device=y0c.device)
-    scratch = Tape(y0c.device)
-    arr = (ctypes.c_float * n_ticks)(*dts)
-    view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(y0c.shape[0]))
-    H = y0c.shape[1]
-    with torch.cuda.device(y0c.device):
-        rc = lib.ndcn_fixed_grid_train_f32(view, ptr(Wc), ptr(bc), H, flags, _lib.METHODS[method], ptr(y0c), arr, n_ticks, ptr(out),
-                                           ctypes.cast(scratch.cb, ctypes.c_void_p), None, stream_ptr())
-    err = scratch.error
-    scratch.close()
-    if rc < 0:
-        if err is not None:
-            raise err
-        check(rc)
-    return out, arr
-
-
-def _fixed_grid_reverse(out, Wc, bc, csr, flags, method, arr, n_ticks, g, decoder=None):
-    """The reverse sweep in the library -> (g_y0, g_W, g_b[, g_Wd, g_bd]).  g: the gradient of the trajectory (n_ticks + 1, N, H), or
-    with decoder = (Wd (C, H), want g_Wd, want g_bd) the gradient of the DECODED ticks (n_ticks + 1, N, C): the sweep then forms every
-    tick's g[i] . Wd where it adds it (ndcn_fixed_grid_backward_readout_f32) and returns the decoder's gradients too."""
-    lib = _lib.load()
-    g = g.contiguous()
-    no_control = bool(flags & _lib.F_NO_CONTROL)
-    gy = torch.empty_like(out[0])
-    gW = torch.empty_like(Wc) if (Wc is not None and not no_control) else None
-    gb = torch.empty_like(bc) if (bc is not None and not no_control) else None
-    scratch = Tape(g.device)
-    view = csr.view_ref() if csr is not None else ctypes.byref(_lib.empty_csr(out.shape[1]))
-    view_t = csr.transpose().view_ref() if csr is not None else None
-    alloc = ctypes.cast(scratch.cb, ctypes.c_void_p)
-    gWd = gbd = None
-    with torch.cuda.device(g.device):
-        if decoder is None:
-            rc = lib.ndcn_fixed_grid_backward_f32(view, view_t, ptr(Wc), ptr(bc), out.shape[2], flags, _lib.METHODS[method], ptr(out), ptr(g), arr,
-                                                  n_ticks, ptr(gy), ptr(gW), ptr(gb), alloc, None, stream_ptr())
-        else:
-            Wd, want_W, want_b = decoder
-            if want_W or want_b:
-                gWd = torch.empty_like(Wd)
-                gbd = torch.empty((Wd.shape[0],), dtype=torch.float32, device=g.device) if want_b else None
-            rc = lib.ndcn_fixed_grid_backward_readout_f32(view, view_t, ptr(Wc), ptr(bc), out.shape[2], flags, _lib.METHODS[method], ptr(out),
-                                                          ptr(g), ptr(Wd), Wd.shape[0], arr, n_ticks, ptr(gy), ptr(gW), ptr(gb), ptr(gWd),
-                                                          ptr(gbd), alloc, None, stream_ptr())
-    err = scratch.error
-    scratch.close()
-    if rc < 0:
-        if err is not None:
-            raise err
-        check(rc)
-    return gy, gW, gb, gWd, gbd
-
-
-class _NativeFixedGrid(torch.autograd.Function):
-    """Euler / midpoint / RK4 over ODEFunc with the loops of `_impl/odeint.py::_FixedGridSolve` inside the library
-    (ndcn_fixed_grid_train_f32 / ndcn_fixed_grid_backward_f32): the same launches, two calls instead of ~10 per step."""
-
-    @staticmethod
-    def forward(ctx, y0, W, b, csr, flags, method, dts):
-        y0c = y0.detach().contiguous()
-        Wc = W.detach().contiguous() if W is not None else None
-        bc = b.detach().contiguous() if b is not None else None
-        out, arr = _fixed_grid_train(y0c, Wc, bc, csr, flags, method, dts)
-        ctx.keep = (Wc, bc, csr, flags, method, arr, len(dts))
-        ctx.has = (W is not None, b is not None)
-        # `out` is this node's own output: saved through autograd (no out -> grad_fn -> ctx -> out cycle that only the cyclic collector
-        # would break - a (T, N, H) trajectory - and an in-place edit of the returned trajectory before backward raises)
-        ctx.save_for_backward(out, W, b)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        out = ctx.saved_tensors[0]
-        Wc, bc, csr, flags, method, arr, n_ticks = ctx.keep
-        gy, gW, gb, _, _ = _fixed_grid_reverse(out, Wc, bc, csr, flags, method, arr, n_ticks, g)
-        needs = ctx.needs_input_grad
-        return (gy if needs[0] else None, gW if needs[1] else None, gb if needs[2] else None, None, None, None, None)
-
-
-class _NativeFixedGridReadout(torch.autograd.Function):
-    """_NativeFixedGrid with the decoder Linear(Wd, bd) of every tick inside the node (odeint's `readout` under a gradient): the
-    differentiable output is the decoded solution (T, N, C) - hip.linear of the trajectory, the bits of the two-step form -, the hidden
-    trajectory is kept for the reverse sweep only, and that sweep takes the (T, N, C) gradient as it is
-    (ndcn_fixed_grid_backward_readout_f32): the (T, N, H) tensor g . Wd of the Linear's own backward is never written."""
-
-    @staticmethod
-    def forward(ctx, y0, W, b, Wd, bd, csr, flags, method, dts):
-        from ...ops import hip
-        y0c = y0.detach().contiguous()
-        Wc = W.detach().contiguous() if W is not None else None
-        bc = b.detach().contiguous() if b is not None else None
-        out, arr = _fixed_grid_train(y0c, Wc, bc, csr, flags, method, dts)
-        dec = hip.linear(out, Wd.detach(), None if bd is None else bd.detach())
-        ctx.keep = (Wc, bc, csr, flags, method, arr, len(dts))
-        # (the hidden trajectory is no output of the node: nothing differentiates through it, and it is released with the graph)
-        ctx.save_for_backward(out, W, b, Wd)
-        return dec
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        out, _, _, Wd = ctx.saved_tensors
-        Wc, bc, csr, flags, method, arr, n_ticks = ctx.keep
-        needs = ctx.needs_input_grad
-        gy, gW, gb, gWd, gbd = _fixed_grid_reverse(out, Wc, bc, csr, flags, method, arr, n_ticks, g,
-                                                   decoder=(Wd.detach().contiguous(), needs[3], needs[4]))
-        return (gy if needs[0] else None, gW if needs[1] else None, gb if needs[2] else None, gWd if needs[3] else None,
-                gbd if needs[4] else None, None, None, None, None)
-
-
-def fixed_grid(y0, W, b, csr, flags, method, dts, readout=None):
-    """-> trajectory (T, N, H), or None when the native loops are switched off (NDCN_FIXED_GRID_NATIVE=0); readout = (Wd, bd): the
-    decoded solution (T, N, C) from the node that holds the decoder"""
-    if not _lib.env_on('NDCN_FIXED_GRID_NATIVE') or _lib.env_str('NDCN_VJP', 'hip') == 'torch':
-        return None
-    if csr is not None:
-        csr.ensure_plans(y0.shape[1])
-        csr.transpose().ensure_plans(y0.shape[1])
-    if readout is not None:
-        return _NativeFixedGridReadout.apply(y0, W, b, readout[0], readout[1], csr, flags, method, dts)
-    return _NativeFixedGrid.apply(y0, W, b, csr, flags, method, dts)

@@ -115,7 +115,7 @@ def _operator(shape):
 def sweep_case(dev):
     """per (shape, variant, method): the operator, weights and the forward trajectory, made once"""
     from ndcn_amd import _lib, graphs
-    from ndcn_amd.torchdiffeq._impl import tape
+    from ndcn_amd.torchdiffeq._impl import fixed_train
     made = {}
 
     def get(shape, variant, method):
@@ -134,7 +134,7 @@ def sweep_case(dev):
             b = ((torch.rand(H, generator=g) - 0.3) * 0.2).to(dev)
             y0 = torch.rand(n, H, generator=g).to(dev)
             dts = [0.25, 0.125, 0.25, 0.5, 0.125]
-            out, arr = tape._fixed_grid_train(y0, W, b, csr, flags, method, dts)
+            out, arr = fixed_train._fixed_grid_train(y0, W, b, csr, flags, method, dts)
             made[key] = (csr, flags, W, b, out, arr, len(dts))
         return made[key]
     return get
@@ -147,7 +147,7 @@ def sweep_case(dev):
 def test_library_sweep_equals_its_partner_on_the_materialised_gradient(dev, sweep_case, shape, variant, method, C):
     """ndcn_fixed_grid_backward_readout_f32 on g_dec against ndcn_fixed_grid_backward_f32 on g = chain(g_dec, Wd) formed on the host:
     g_y0, g_W and g_b bit for bit; the decoder's gradients against the float64 sums over all ticks."""
-    from ndcn_amd.torchdiffeq._impl import tape
+    from ndcn_amd.torchdiffeq._impl import fixed_train
     csr, flags, W, b, out, arr, n_ticks = sweep_case(shape, variant, method)
     n, H = out.shape[1], out.shape[2]
     rng = np.random.RandomState(7 + C)
@@ -155,8 +155,8 @@ def test_library_sweep_equals_its_partner_on_the_materialised_gradient(dev, swee
     Wd = (rng.randn(C, H) / H ** 0.5).astype(np.float32)
     g = np.stack([tick_gradient(g_dec[i], Wd) for i in range(n_ticks + 1)])
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    a = tape._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g))
-    r = tape._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g_dec), decoder=(T(Wd), True, True))
+    a = fixed_train._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g))
+    r = fixed_train._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g_dec), decoder=(T(Wd), True, True))
     for name, x, z in zip(('g_y0', 'g_W', 'g_b'), a[:3], r[:3]):
         if x is None:
             assert z is None
@@ -169,7 +169,7 @@ def test_library_sweep_equals_its_partner_on_the_materialised_gradient(dev, swee
     assert np.all(np.abs(gWd - s[0]) <= 2.0 ** -23 * np.abs(s[0]) + 1e-12 * s[2])
     assert np.all(np.abs(gbd - s[1]) <= 2.0 ** -23 * np.abs(s[1]) + 1e-12 * s[3])
     # the decoder's gradients not asked for: the same three, and nothing else written
-    q = tape._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g_dec), decoder=(T(Wd), False, False))
+    q = fixed_train._fixed_grid_reverse(out, W, b, csr, flags, method, arr, n_ticks, T(g_dec), decoder=(T(Wd), False, False))
     assert q[3] is None and q[4] is None and torch.equal(q[0], r[0])
 
 
@@ -265,18 +265,18 @@ def test_odeint_readout_under_a_gradient(dev, route, method):
     t = torch.tensor([0., .25, .375, .625, 1.125, 1.25])
     G = torch.randn(len(t), x0.shape[0], Wd.shape[0], generator=torch.Generator().manual_seed(8))
     options, grid_pick, masks, seed = None, None, None, None
-    want = '_NativeFixedGridReadoutBackward'
+    want = '_NativeFixedGridBackward'
     env = {}
     if route == 'python':
-        env, want = {'NDCN_FIXED_GRID_NATIVE': '0'}, '_FixedGridSolveReadoutBackward'
+        env, want = {'NDCN_FIXED_GRID_NATIVE': '0'}, '_FixedGridSolveBackward'
     elif route == 'step_size':
         t = torch.tensor([0., .13, .5, .55, .6, 1.0])                 # .13, .55: strictly inside steps of 0.1; .5, .6: step ends
-        options, want = {'step_size': 0.1}, '_SubstepSolveReadoutBackward'
+        options, want = {'step_size': 0.1}, '_SubstepSolveBackward'
         plan = core.fixed_plan(t.numpy(), 0.1)
         assert not all(plan.tick_coincident[1:])
         grid_pick = (torch.from_numpy(np.asarray(plan.grid, np.float32)), [0] + [int(s) + 1 for s in plan.tick_step[1:]])
     elif route == 'dropout':
-        seed, want = 21, '_FixedGridSolveReadoutBackward'
+        seed, want = 21, '_FixedGridSolveBackward'
         torch.manual_seed(seed)
         s = _dropout.draw_seed()
         masks = [torch.from_numpy(_philox.mask(0.5, s, e, x0.shape[0], x0.shape[1]).astype(np.float64)) for e in range(len(t) - 1)]
@@ -345,7 +345,8 @@ def test_ndcn_adam_step_has_no_decoder_node(dev):
     while fn is not None and len(names) < 4:
         names.append(type(fn).__name__)
         fn = fn.next_functions[0][0] if fn.next_functions else None
-    assert names[0] == '_NativeFixedGridReadoutBackward' and '_LinearBackward' not in names[:1], names
+    assert names[0] == '_NativeFixedGridBackward' and '_LinearBackward' not in names[:1], names
+    assert out.shape[-1] == model.output_layer.weight.shape[0] != model.hidden_size, out.shape      # (what the node returns is decoded: C columns)
     assert type(out_t.grad_fn).__name__ == '_LinearBackward'
     assert torch.equal(out.detach(), out_t.detach()) and float(loss) == float(loss_t)
     sd = {k: v.cpu().double().requires_grad_(True) for k, v in before.items()}
