@@ -792,6 +792,31 @@ NDCN_API int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, co
                                            const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
                                            const float *h_tick_off, int64_t n_ticks, int max_order, float *out, void *workspace,
                                            int64_t workspace_bytes, void *stream);
+/* explicit_adams under a gradient (three more calls added to ABI 29: no existing declaration changes).
+ * ndcn_explicit_adams_train_f32: ndcn_solve_explicit_adams_f32 - the same loop, launches, arguments, checks and bits in `out` - that KEEPS
+ *   what a reverse sweep needs in a record the caller owns, in place of the history ring and the two state panels:
+ *     rec_f [n_steps panels]   f_i, the evaluation grid step i starts with (a step's history is read from the panels i, i - 1, ...)
+ *     rec_y [n_steps panels]   the state after step i (panels of n_rows * H floats back to back, as `out`)
+ *   rec_y may be `out` itself when every step reports exactly one tick and that tick is an end of its step (the default grid: tick j
+ *   after step j): the state is then stored once.  Neither record may overlap y0.
+ *     workspace                ndcn_explicit_adams_train_workspace_bytes(n_rows, H) bytes, 256-byte aligned: three RK4 stage panels, the
+ *                              stage input and the scratch of ndcn_rhs_f32, nothing else - a host function of its own rather than the
+ *                              solve's formula at max_order = 2, which would add a ring panel and two state panels that are never touched
+ * ndcn_ab_adjoint_f32, the gradient of one evaluation gathered from the adjoints of the <= 11 Adams-Bashforth steps that used it:
+ *     out = [base +] ((((0 + c[0] g[0]) + c[1] g[1]) + ...) + c[n-1] g[n-1])
+ *   every product and every sum rounded to fp32 on its own, no contraction, the sum started from an exact zero and the base added
+ *   last.  h_g: HOST array of n device panels of n_elem floats, h_c: HOST array of their coefficients (fl32(dt * a), formed by the
+ *   caller); base nullable.  1 <= n <= 11; NDCN_EINVAL - before any launch - for any other n, a null term, or `out` equal to one of the
+ *   g panels (out == base is allowed).  Any alignment and any n_elem >= 0 (0: nothing is launched), the lanes of ndcn_ab_step_f32: 16
+ *   bytes each where all panels share one offset from a 16-byte boundary, behind a head of <= 3 single elements, else single elements.
+ *   It is not ndcn_ab_step_f32 with dt = 1: that call needs a state, starts at three terms and rounds dt * sum.                        */
+NDCN_API int ndcn_ab_adjoint_f32(float *out, const float *base, const float *const *h_g, const float *h_c, int n, int64_t n_elem,
+                                 void *stream);
+NDCN_API int64_t ndcn_explicit_adams_train_workspace_bytes(int64_t n_rows, int H);
+NDCN_API int ndcn_explicit_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                           const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                           const float *h_tick_off, int64_t n_ticks, int max_order, float *out, float *rec_f,
+                                           float *rec_y, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): when enabled, every kernel launch made by this library is

@@ -262,6 +262,10 @@ SIGNATURES = {
     'ndcn_explicit_adams_workspace_bytes': (_L, [_L, _I, _I]),
     'ndcn_solve_explicit_adams_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
                                            ctypes.POINTER(_F), _L, _I, _P, _P, _L, _P]),
+    'ndcn_ab_adjoint_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _L, _P]),
+    'ndcn_explicit_adams_train_workspace_bytes': (_L, [_L, _I]),
+    'ndcn_explicit_adams_train_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
+                                           ctypes.POINTER(_F), _L, _I, _P, _P, _P, _P, _L, _P]),
     'ndcn_row_l1_normalize_f32': (_I, [_P, _P, _L, _I, _P]),
     'ndcn_row_l1_normalize_bwd_f32': (_I, [_P, _P, _P, _L, _I, _P]),
     'ndcn_gene_rhs_f32': (_I, [_CSR, _P, _P, _F, _F, _F, _P]),

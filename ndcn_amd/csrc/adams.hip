@@ -4,6 +4,8 @@
 //   ab_step_f32                      out = y + dt * sum_{i<n} a_i f_i, n = 3..11: one streaming pass over the history
 //   ndcn_solve_explicit_adams_f32    the whole solve over ODEFunc, enqueued on the caller's stream: history ring, stage panels and both
 //                                    state panels in a caller-owned workspace, nothing read back
+//   ndcn_explicit_adams_train_f32    the same loop (adams_run) writing every evaluation and every state into a caller-owned record: the
+//                                    forward pass of training (the reverse sweep: adams_bwd.hip, fixed_train.py)
 //
 // Rounding follows the reference term by term (fixed_adams.py:182, misc.py:22-25, solvers.py:92): p_i = a_i * f_i, s = ((0 + p_0) + p_1)
 // + ..., dy = dt * s, y1 = y + dy - every product and sum rounded on its own.  FP contraction is therefore switched OFF for this
@@ -74,7 +76,10 @@ __global__ __launch_bounds__(256) void ab_step_kernel(AbArgs p, int64_t head, in
     }
 }
 
-// workgroups of a streaming launch: eight per compute unit (2048 on the whole chip), fewer when the panel is smaller
+}  // namespace
+
+// workgroups of a streaming launch: eight per compute unit (2048 on the whole chip), fewer when the panel is smaller (adams_bwd.hip
+// sizes its launches with it too)
 int ab_grid(int64_t items) {
     static std::atomic<int> cus_of[64];
     int dev = 0, cus = 0;
@@ -88,6 +93,8 @@ int ab_grid(int64_t items) {
     if (g > (int64_t)cus * 8) g = (int64_t)cus * 8;
     return g < 1 ? 1 : (int)g;
 }
+
+namespace {
 
 template <int N>
 void ab_launch(const AbArgs &p, int64_t head, int64_t n4, int64_t n, hipStream_t st) {
@@ -178,57 +185,60 @@ void ab_weights(int k, float *a) {
 
 inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
-// panels of the workspace: the history ring, k2..k4 of a warm-up step, the stage input, two state panels
-inline int solve_panels(int max_order) { return (max_order - 1) + 3 + 1 + 2; }
+// panels of the workspace: k2..k4 of a warm-up step and the stage input - what a solve WITH a record needs besides the record -; a solve
+// without one adds the history ring and two state panels
+constexpr int kStagePanels = 3 + 1;
+inline int solve_panels(int max_order) { return (max_order - 1) + kStagePanels + 2; }
 
-}  // namespace
-
-}  // namespace ndcn
-
-using namespace ndcn;
-
-extern "C" {
-
-int ndcn_ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_elem, void *stream) {
-    return ab_step_f32(out, y, h_f, h_a, n, dt, n_elem, static_cast<hipStream_t>(stream));
-}
-
-int64_t ndcn_explicit_adams_workspace_bytes(int64_t n_rows, int H, int max_order) {
-    if (n_rows < 0 || H <= 0 || max_order < 2 || max_order > kAbMaxOrder) return NDCN_EINVAL;
+inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
     const size_t panel = up256((size_t)n_rows * (size_t)H * sizeof(float));
     const int64_t wb = rhs_work_bytes(n_rows, H, NDCN_F_RELU);
-    return (int64_t)((size_t)solve_panels(max_order) * panel + up256((size_t)(wb > 0 ? wb : 0)));
+    return (int64_t)((size_t)panels * panel + up256((size_t)(wb > 0 ? wb : 0)));
 }
 
-int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
-                                  const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
-                                  const float *h_tick_off, int64_t n_ticks, int max_order, float *out, void *workspace,
-                                  int64_t workspace_bytes, void *stream) {
-    NDCN_CHECK_ARG(A && W && y0 && H > 0 && n_steps >= 0 && n_ticks >= 0, "null argument");
-    NDCN_CHECK_ARG(A->n_rows >= 0 && A->n_rows < (1ll << 31) - 1 && A->nnz >= 0 && A->rowptr && (A->nnz == 0 || (A->colidx && A->val)), "bad operator");
-    NDCN_CHECK_ARG(A->n_rows == A->n_cols, "an un-sharded solve: the operator must be square (no halo columns)");
-    NDCN_CHECK_ARG(flags == NDCN_F_RELU, "flags must be NDCN_F_RELU: no_graph / no_control / packed / accumulate have no form here");
-    NDCN_CHECK_ARG(max_order >= 2 && max_order <= kAbMaxOrder, "max_order must be 2..12 (fixed_adams.py:162 clamps at 12; below 2 the reference fails)");
-    NDCN_CHECK_ARG(n_steps == 0 || h_dt, "step sizes missing");
-    NDCN_CHECK_ARG(n_ticks == 0 || (h_tick_step && h_tick_same && h_tick_off && out), "tick arrays missing");
+#define ADAMS_ARG(cond, msg)                                  \
+    do {                                                      \
+        if (!(cond)) {                                        \
+            set_error("%s: %s", who, msg);                    \
+            return NDCN_EINVAL;                               \
+        }                                                     \
+    } while (0)
+
+// FixedGridODESolver.integrate with the AdamsBashforth step: the one loop behind both entry points (`who`: the caller's name in
+// messages).  Without a record (rec_f == nullptr) the evaluations live in a ring of max_order - 1 workspace panels and the state
+// alternates between two more, or stands in the caller's tick panel.  With one, evaluation i is written to panel i of rec_f and the
+// state after step i to panel i of rec_y - the history of a step is then the panels i, i - 1, ... of rec_f and nothing else is kept:
+// the same launches on the same values, only the addresses differ.
+int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
+              int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off, int64_t n_ticks, int max_order,
+              float *out, float *rec_f, float *rec_y, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+    ADAMS_ARG(A && W && y0 && H > 0 && n_steps >= 0 && n_ticks >= 0, "null argument");
+    ADAMS_ARG(A->n_rows >= 0 && A->n_rows < (1ll << 31) - 1 && A->nnz >= 0 && A->rowptr && (A->nnz == 0 || (A->colidx && A->val)), "bad operator");
+    ADAMS_ARG(A->n_rows == A->n_cols, "an un-sharded solve: the operator must be square (no halo columns)");
+    ADAMS_ARG(flags == NDCN_F_RELU, "flags must be NDCN_F_RELU: no_graph / no_control / packed / accumulate have no form here");
+    ADAMS_ARG(max_order >= 2 && max_order <= kAbMaxOrder, "max_order must be 2..12 (fixed_adams.py:162 clamps at 12; below 2 the reference fails)");
+    ADAMS_ARG(n_steps == 0 || h_dt, "step sizes missing");
+    ADAMS_ARG(n_ticks == 0 || (h_tick_step && h_tick_same && h_tick_off && out), "tick arrays missing");
     for (int64_t j = 0; j < n_ticks; ++j)
-        NDCN_CHECK_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
-    const int64_t need = ndcn_explicit_adams_workspace_bytes(A->n_rows, H, max_order);
-    NDCN_CHECK_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 && workspace_bytes >= need,
-                   "workspace of ndcn_explicit_adams_workspace_bytes() bytes, 256-byte aligned, required");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+        ADAMS_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
+    const bool rec = rec_f != nullptr;
+    ADAMS_ARG(!rec || n_steps == 0 || rec_y, "the record of the states is missing");
+    const int64_t need = workspace_need(A->n_rows, H, rec ? kStagePanels : solve_panels(max_order));
+    ADAMS_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 && workspace_bytes >= need,
+              "workspace of the size its host function returns, 256-byte aligned, required");
     const int64_t n = A->n_rows * (int64_t)H;
     if (n_steps == 0 || n == 0) return NDCN_OK;
 
-    // the workspace: ring | k2 k3 k4 | stage input | two state panels | rhs scratch
+    // the workspace: [ring |] k2 k3 k4 | stage input [| two state panels] | rhs scratch
     const size_t panel = up256((size_t)n * sizeof(float));
     char *base = static_cast<char *>(workspace);
     auto take = [&]() { float *p = reinterpret_cast<float *>(base); base += panel; return p; };
     const int ring_n = max_order - 1;
-    float *ring[kAbMaxTerms];
-    for (int i = 0; i < ring_n; ++i) ring[i] = take();
+    float *ring[kAbMaxTerms] = {};
+    for (int i = 0; i < ring_n && !rec; ++i) ring[i] = take();
     float *k2 = take(), *k3 = take(), *k4 = take(), *ytmp = take();
-    float *state[2] = {take(), take()};
+    float *state[2] = {nullptr, nullptr};
+    if (!rec) { state[0] = take(); state[1] = take(); }
     float *work = rhs_work_bytes(A->n_rows, H, flags) > 0 ? reinterpret_cast<float *>(base) : nullptr;
     uint32_t fl = flags;
     if (work && rhs_fused_supported(H, flags) && rhs_fused2_supported(A, H, flags)) {
@@ -243,7 +253,7 @@ int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float
     for (int k = kAbMinTerms; k <= kAbMaxTerms && k <= ring_n; ++k) ab_weights(k, weights[k]);
 
     const float *y = y0;
-    int held = 0, newest = -1;                                 // evaluations in the ring; slot of the newest
+    int held = 0, newest = -1;                                 // evaluations held; the ring slot of the newest
     int64_t j = 0;
     std::vector<float *> outs;
     std::vector<int> zeros;
@@ -251,21 +261,17 @@ int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float
         const float dt = h_dt[i];
         int64_t j1 = j;
         while (j1 < n_ticks && h_tick_step[j1] == i) ++j1;
-        // where the new state goes: the caller's panel when the step's LAST tick is the state itself (an end of the step; only the last
-        // tick of a step can be), else the state panel the step does not read
-        float *dst = (j1 > j && h_tick_same[j1 - 1]) ? out + (size_t)(j1 - 1) * (size_t)n : (y == state[0] ? state[1] : state[0]);
-        // fixed_adams.py:166-173: the new evaluation takes the place of the oldest one
+        // where the new state goes: its panel of the record; without one the caller's panel when the step's LAST tick is the state
+        // itself (an end of the step; only the last tick of a step can be), else the state panel the step does not read
+        float *dst = rec ? rec_y + (size_t)i * (size_t)n
+                         : ((j1 > j && h_tick_same[j1 - 1]) ? out + (size_t)(j1 - 1) * (size_t)n : (y == state[0] ? state[1] : state[0]));
+        // fixed_adams.py:166-173: the new evaluation takes the place of the oldest one (a record keeps them all)
         int rc;
-        float *f_new;
-        if (ring_n > 0) {
-            newest = (newest + 1) % ring_n;
-            f_new = ring[newest];
-            if (held < ring_n) ++held;
-        } else {
-            f_new = k4;                                        // (max_order 1 never reaches here)
-        }
+        newest = (newest + 1) % ring_n;
+        float *f_new = rec ? rec_f + (size_t)i * (size_t)n : ring[newest];
+        if (held < ring_n) ++held;
         if ((rc = eval(y, f_new))) return rc;
-        const int order = held < max_order - 1 ? held : max_order - 1;
+        const int order = held;
         if (order < kAbMinTerms) {
             // rk_common.py:72-78 with k1 = the new evaluation: the un-fused RK4 step of the device solver (solver.hip: enqueue_fixed_stages)
             if ((rc = fixed_stage_f32(2, ytmp, y, f_new, nullptr, nullptr, nullptr, dt, n, st))) return rc;
@@ -277,7 +283,7 @@ int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float
             if ((rc = fixed_stage_f32(5, dst, y, f_new, k2, k3, k4, dt, n, st))) return rc;
         } else {
             const float *f[kAbMaxTerms];
-            for (int q = 0; q < order; ++q) f[q] = ring[((newest - q) % ring_n + ring_n) % ring_n];
+            for (int q = 0; q < order; ++q) f[q] = rec ? rec_f + (size_t)(i - q) * (size_t)n : ring[((newest - q) % ring_n + ring_n) % ring_n];
             if ((rc = ab_step_f32(dst, y, f, weights[order], order, dt, n, st))) return rc;
         }
         y = dst;
@@ -300,6 +306,47 @@ int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float
         j = j1;
     }
     return NDCN_OK;
+}
+
+#undef ADAMS_ARG
+
+}  // namespace
+
+}  // namespace ndcn
+
+using namespace ndcn;
+
+extern "C" {
+
+int ndcn_ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_elem, void *stream) {
+    return ab_step_f32(out, y, h_f, h_a, n, dt, n_elem, static_cast<hipStream_t>(stream));
+}
+
+int64_t ndcn_explicit_adams_workspace_bytes(int64_t n_rows, int H, int max_order) {
+    if (n_rows < 0 || H <= 0 || max_order < 2 || max_order > kAbMaxOrder) return NDCN_EINVAL;
+    return workspace_need(n_rows, H, solve_panels(max_order));
+}
+
+int64_t ndcn_explicit_adams_train_workspace_bytes(int64_t n_rows, int H) {
+    if (n_rows < 0 || H <= 0) return NDCN_EINVAL;
+    return workspace_need(n_rows, H, kStagePanels);
+}
+
+int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                  const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                  const float *h_tick_off, int64_t n_ticks, int max_order, float *out, void *workspace,
+                                  int64_t workspace_bytes, void *stream) {
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
+                     nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int ndcn_explicit_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                  const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                  const float *h_tick_off, int64_t n_ticks, int max_order, float *out, float *rec_f, float *rec_y,
+                                  void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!rec_f && n_steps > 0) { set_error("%s: the record of the evaluations is missing", __func__); return NDCN_EINVAL; }
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, rec_f, rec_y,
+                     workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -238,6 +238,11 @@ int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, co
 // adams.hip: one Adams-Bashforth step of order n_terms = 3..11, out = y + dt * (((0 + a_0 f_0) + a_1 f_1) + ...), every product and sum
 // rounded on its own; h_f newest first; out may be y, never one of h_f; any alignment (16-byte lanes where all panels share an offset)
 int ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n_terms, float dt, int64_t n, hipStream_t st);
+// workgroups of a streaming launch over `items` work items of 256 lanes: eight per compute unit of the current device, fewer for less work
+int ab_grid(int64_t items);
+// adams_bwd.hip: the gradient of one evaluation gathered from the adjoints of the Adams-Bashforth steps that used it,
+// out = [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), n_terms = 1..11, base nullable and added last; out may be base, never one of h_g
+int ab_adjoint_f32(float *out, const float *base, const float *const *h_g, const float *h_c, int n_terms, int64_t n, hipStream_t st);
 
 int row_l1_normalize_f32(const float *X, float *Y, int64_t n_rows, int H, hipStream_t st);
 int row_l1_normalize_bwd_f32(const float *G, const float *X, float *GX, int64_t n_rows, int H, hipStream_t st);

@@ -919,6 +919,20 @@ class HipOps:
         return out
 
     @staticmethod
+    def ab_adjoint(gs, cs, base=None, out=None):
+        """The gradient of one evaluation of an explicit_adams solve, gathered from the adjoints of the Adams-Bashforth steps that used
+        it (ndcn_ab_adjoint_f32): [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), every product and sum rounded on its own, the base added
+        last.  gs: 1..11 panels, cs: their float32 coefficients (core.ab_adjoint_terms).  out may be base, never one of gs."""
+        gs = [_panel(g) for g in gs]
+        base = _panel(base) if base is not None else None
+        if out is None:
+            out = torch.empty_like(gs[0])
+        arr_g, arr_c, n = _terms(gs, cs)
+        with torch.cuda.device(out.device):
+            check(_lib.load().ndcn_ab_adjoint_f32(ptr(out), ptr(base), arr_g, arr_c, n, out.numel(), stream_ptr()))
+        return out
+
+    @staticmethod
     def tick_emit(y, dt, tms, outs=None):
         """The ticks a sub-stepped fixed-grid step reports that are NOT an end of the step (solvers.py:92-108, y0 already overwritten
         with y1): [y + ((y - y) / dt) * tm for tm in tms] - one pass over y per 8 ticks (ndcn_tick_emit_f32)."""

@@ -311,6 +311,22 @@ def ab_weights(order):
     return _AB_WEIGHTS[order]
 
 
+def ab_adjoint_terms(i, dts, max_order):
+    """Which adjoints the gradient of evaluation f_i = F(y_i) of an explicit_adams solve gathers from, and with which weights:
+    [(j, c), ...] such that gf_i = sum c * lam_j, lam_j the full adjoint of the state y_j, in the order the sum is taken (j rising).
+    Grid step i' (0-based, dts[i'] its size) holds k = min(i' + 1, max_order - 1) evaluations; with k >= 3 it is the Adams-Bashforth step
+    y_{i'+1} = y_i' + dt_i' * sum_{q<k} a_q f_{i'-q}, so f_i is its term q = i' - i where that is below k: j = i' + 1 and
+    c = fl32(dt_i' * a_q), the product of the two float32 numbers rounded once.  RK4 warm-up steps use no history: f_i enters them only as
+    their own k1, which the sweep of that step accounts for.  Empty where no later step reads f_i (the last steps of a grid that never
+    leaves the warm-up, max_order < 4)."""
+    n_steps, terms = len(dts), []
+    for step in range(i, min(n_steps - 1, i + max_order - 2) + 1):
+        k = min(step + 1, max_order - 1)
+        if k >= AB_MIN_ORDER - 1 and step - i < k:
+            terms.append((step + 1, f32(f32(dts[step]) * ab_weights(k)[step - i])))
+    return terms
+
+
 def _rk4_step(ops, func, targ, t0, dt, y, k1):
     """rk_common.py:72-78 + solvers.py:92: the 3/8 rule from the evaluation k1 = func(t0, y)"""
     y2 = tuple(ops.fixed_stage(2, y_, a, dt=dt) for y_, a in zip(y, k1))

@@ -1,4 +1,4 @@
-"""Training through a fixed-grid solve (euler / midpoint / rk4) over ODEFunc: the routes of `odeint` under a gradient and their
+"""Training through a fixed-grid solve (euler / midpoint / rk4 / explicit_adams) over ODEFunc: the routes of `odeint` under a gradient and their
 autograd nodes, one per route, each differentiated the way the reference's drivers train - plain backpropagation through every step
 (heat_dynamics.py:313-334).
 
@@ -7,9 +7,11 @@ autograd nodes, one per route, each differentiated the way the reference's drive
                      ndcn_fixed_grid_backward[_readout]_f32);
   _FixedGridSolve    the same launches issued from Python, one step per tick: the A/B partner of the native loops
                      (NDCN_FIXED_GRID_NATIVE=0) and the form that carries an active dropout;
-  _SubstepSolve      options={'step_size': h}: a grid finer than the ticks, checkpointed per tick interval.
+  _SubstepSolve      options={'step_size': h}: a grid finer than the ticks, checkpointed per tick interval;
+  _ExplicitAdamsSolve  method='explicit_adams' (NDCN_ADAMS_TRAIN=1): the library's loop forward with a record of every evaluation, the
+                     reverse sweep of a multistep method in closed form (csrc/adams.hip, csrc/adams_bwd.hip).
 
-The last three take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
+The last four take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
 the decoded solution (T, N, C) - hip.linear of the trajectory, the bits of the two-step form - the hidden trajectory is saved for the
 reverse sweep only, and that sweep takes the (T, N, C) gradient as it is: the (T, N, H) gradient of the trajectory is never written.
 Where a tick's gradient comes from is one object in the two Python sweeps (_PlainTicks, _ReadoutTicks: the Python mirror of TickGrad
@@ -189,10 +191,11 @@ def _sweep_totals(out, csr, W, b, no_graph, no_control, drop):
     return gW_tot, gb_tot, vj, acc
 
 
-def _sweep_step(method, dt, st, a, vj, acc, close):
+def _sweep_step(method, dt, st, a, vj, acc, close, gk1_extra=None):
     """the adjoint before one step from the adjoint `a` after it: st = the step's [(stage input, K), ...], vj / acc as _sweep_totals
     makes them; close(a, [gu, ...]) is the step's last pass, a + the sum of the stages' gu (+ whatever enters at the state the step
-    starts from: the per-tick sweep adds that tick's gradient in the same pass)"""
+    starts from: the per-tick sweep adds that tick's gradient in the same pass).  gk1_extra (rk4 only): one more addend of the gradient
+    of k1, last in its sum - the RK4 warm-up step of explicit_adams, whose k1 is also a history term of later steps"""
     if method == 'euler':                                   # y1 = y + dt k1
         (u1, K1), = st
         gu1, gW, gb = vj(u1, K1, a, dt)
@@ -215,7 +218,8 @@ def _sweep_step(method, dt, st, a, vj, acc, close):
     gk2 = hip.lincomb([a, gu4, gu3], [3.0 * c8, -dt, dt])
     gu2, gW, gb = vj(u2, K2, gk2, 1.0)
     acc(gW, gb, 1.0)
-    gk1 = hip.lincomb([a, gu4, gu3, gu2], [c8, dt, -dt / 3.0, dt / 3.0])
+    more = ([gk1_extra], [1.0]) if gk1_extra is not None else ([], [])
+    gk1 = hip.lincomb([a, gu4, gu3, gu2] + more[0], [c8, dt, -dt / 3.0, dt / 3.0] + more[1])
     gu1, gW, gb = vj(u1, K1, gk1, 1.0)
     acc(gW, gb, 1.0)
     return close(a, [gu4, gu3, gu2, gu1])
@@ -420,6 +424,128 @@ class _SubstepSolve(torch.autograd.Function):
             a = torch.zeros_like(out[0])
         a = ticks.enter(a, [0])                                                       # the first tick is y0 itself
         return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 5
+
+
+# ---------------------------------------------------------------------------------------------------
+# explicit_adams: the library's forward loop with a record, the reverse sweep of a multistep method
+# ---------------------------------------------------------------------------------------------------
+
+def plan_arrays(plan):
+    """(dts, n_steps, tick steps, coincident flags, tick offsets, n_emit): a core.FixedPlan as the C arrays of the explicit_adams entry
+    points (ndcn_solve_explicit_adams_f32, ndcn_explicit_adams_train_f32) - the ticks after the first"""
+    import numpy as np
+    n_ticks, n_steps = len(plan.t), len(plan.dts)
+    n_emit = n_ticks - 1
+    dts = (ctypes.c_float * max(n_steps, 1))(*plan.dts.tolist())
+    steps = (ctypes.c_int64 * max(n_emit, 1))(*plan.tick_step[1:].tolist())
+    same = (ctypes.c_int * max(n_emit, 1))(*[int(v) for v in plan.tick_coincident[1:]])
+    offs = (ctypes.c_float * max(n_emit, 1))(*[float(np.float32(plan.t[j] - plan.grid[plan.tick_step[j]])) for j in range(1, n_ticks)])
+    return dts, n_steps, steps, same, offs, n_emit
+
+
+class _ExplicitAdamsSolve(torch.autograd.Function):
+    """FixedGridODESolver.integrate with the AdamsBashforth step (fixed_adams.py:151-211) over ODEFunc, one node per solve:
+      forward   ndcn_explicit_adams_train_f32: the loop of the un-differentiated solve, which keeps f_i = F(y_i) of every grid step and
+                the state after it in a record (2 panels per step; the per-operation graph keeps y_i, A y_i, the pre-activation and
+                f_i).  On the default grid the states ARE the ticks: the record of the states is the solution itself;
+      backward  from the last step to the first.  lam_j is the full adjoint of the state y_j.  The evaluation f_i is a term of the
+                Adams-Bashforth steps i .. i + max_order - 2, so its gradient gathers from their adjoints in one pass,
+                gf_i = sum c * lam_j (core.ab_adjoint_terms; hip.ab_adjoint), and one reverse evaluation gives gu = J(y_i)^T gf_i
+                (hip.rhs_vjp, which follows NDCN_RHS_MID_BWD and accumulates the parameter gradients).  An Adams-Bashforth step closes
+                with lam_i = lam_{i+1} + gu; an RK4 warm-up step re-forms its stages from the stored y_i and f_i by the forward loop's
+                own calls (fixed_stage ops 2..4, the plain right-hand side: its bits) and runs _sweep_step's closed form, gf_i one
+                more addend of the gradient of k1.  Kept meanwhile: the max_order - 1 newest adjoints.
+    Tick gradients: on the default grid inside the step's closing pass (the `close` form of _FixedGridSolve), on a step_size plan at the
+    end of the step that reported the tick, in a pass of their own (the `enter` form of _SubstepSolve; the VJP of tick_emit is the
+    identity).  With a decoder the output is hip.linear of the ticks and the sweep takes the (T, N, C) gradient as it is."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, plan, max_order):
+        lib = _lib.load()
+        y0c, Wc, bc = _detached(y0, W, b)
+        dts, n_steps, steps, same, offs, n_emit = plan_arrays(plan)
+        shape, H = tuple(y0c.shape), y0c.shape[1]
+        out = torch.empty((n_emit + 1,) + shape, dtype=torch.float32, device=y0c.device)
+        out[0].copy_(y0c)
+        rec_f = torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
+        # the default grid: step i reports tick i + 1 and nothing else, the state after it - no state is stored twice
+        rec_y = out[1:] if plan.default else torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
+        nbytes = int(lib.ndcn_explicit_adams_train_workspace_bytes(shape[0], H))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0c.device)
+        with torch.cuda.device(y0c.device):
+            check(lib.ndcn_explicit_adams_train_f32(_view(csr, shape[0]), ptr(Wc), ptr(bc), H, flags, ptr(out[0]), dts, n_steps, steps, same,
+                                                    offs, n_emit, max_order, ptr(out[1:]), ptr(rec_f), ptr(rec_y), ptr(workspace), nbytes,
+                                                    stream_ptr()))
+        ctx.meta = (csr, plan, max_order)
+        ctx.save_for_backward(out, rec_f, W, b, Wd, *(() if plan.default else (rec_y,)))
+        return out if Wd is None else hip.linear(out, Wd.detach(), None if bd is None else bd.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, rec_f, W, b, Wd, *own = ctx.saved_tensors
+        csr, plan, max_order = ctx.meta
+        rec_y = own[0] if own else out[1:]
+        Wc, bc = _detached(W, b)
+        dts = plan.dts
+        n_steps = len(dts)
+        ticks = _ticks(ctx, g, out, Wd)
+        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, False, False, None)
+        lam = {}                                                  # the adjoints that evaluations still to come gather from
+        a = ticks.seed(n_steps) if plan.default else None
+        for i in range(n_steps - 1, -1, -1):
+            if not plan.default and plan.emits[i]:                # the ticks step i reported enter at the state it ends in
+                a = ticks.enter(a, [e[0] for e in plan.emits[i]])
+            if a is None:
+                a = torch.zeros_like(out[0])
+            lam[i + 1] = a
+            lam.pop(i + max_order, None)
+            terms = core.ab_adjoint_terms(i, dts, max_order)
+            gf = hip.ab_adjoint([lam[j] for j, _ in terms], [c for _, c in terms]) if terms else None
+            y, f, dt = (out[0] if i == 0 else rec_y[i - 1]), rec_f[i], float(dts[i])
+            if min(i + 1, max_order - 1) >= core.AB_MIN_ORDER - 1:
+                gu, _, _ = hip.rhs_vjp(csr, y, Wc, f, gf, need_b=bc is not None, gW=gW_tot, gb=gb_tot)
+                a = ticks.close(a, [gu], i) if plan.default else _sum_onto(a, [gu])
+            else:
+                u2 = hip.fixed_stage(2, y, f, dt=dt)
+                K2 = hip.rhs(csr, u2, Wc, bc)
+                u3 = hip.fixed_stage(3, y, f, K2, dt=dt)
+                K3 = hip.rhs(csr, u3, Wc, bc)
+                u4 = hip.fixed_stage(4, y, f, K2, K3, dt=dt)
+                K4 = hip.rhs(csr, u4, Wc, bc)
+                close = (lambda a, gus, i=i: ticks.close(a, gus, i)) if plan.default else _sum_onto
+                a = _sweep_step('rk4', dt, [(y, f), (u2, K2), (u3, K3), (u4, K4)], a, vj, acc, close, gk1_extra=gf)
+        if not plan.default:
+            a = ticks.enter(a, [0])                               # the first tick is y0 itself
+        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 4
+
+
+def adams_train_enabled():
+    """NDCN_ADAMS_TRAIN=1: explicit_adams under a gradient runs on _ExplicitAdamsSolve (default: the per-operation graph)"""
+    return _lib.env_str('NDCN_ADAMS_TRAIN', '0') == '1'
+
+
+def _explicit_adams_with_grad(odefunc, y0, t, plan, max_order, readout=None):
+    """explicit_adams over a plain ODEFunc under a gradient on _ExplicitAdamsSolve, or None where the node has no form: the switch is
+    off, `t` requires grad, no_graph / no_control, an operator that does not live with the state, a max_order the reference fails on,
+    fewer than two ticks.  readout = (Wd, bd) (checked by _readout_for_grad): the decoded solution, the decoder inside the node."""
+    from .odeint import _small_operator
+    if not adams_train_enabled() or t.requires_grad or t.numel() < 2 or max_order < 2 or odefunc.no_graph or odefunc.no_control:
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, _, flags = op
+    core.assert_increasing(t)
+    if plan is None:
+        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    y0 = _lib.require_device(y0, 'state y0').contiguous()
+    if y0.numel() == 0:
+        return None
+    csr.ensure_plans(y0.shape[1])
+    csr.transpose().ensure_plans(y0.shape[1])
+    Wd, bd = readout if readout is not None else (None, None)
+    return _ExplicitAdamsSolve.apply(y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -118,7 +118,9 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     explicit_adams is the reference's AdamsBashforth (fixed_adams.py:151-211) on the same grids: two RK4 (3/8 rule) steps, then ONE
     evaluation per step combined with up to ten earlier ones (options={'max_order': m}, default 12: orders 3 .. m - 1; m = 2 or 3
     never leaves RK4; m < 2 fails as in the reference).  Without a gradient a plain ODEFunc runs the whole solve inside the library
-    (ndcn_solve_explicit_adams_f32: nothing is read back); any other callable, a tuple state or a gradient steps through core.py.
+    (ndcn_solve_explicit_adams_f32: nothing is read back); any other callable, a tuple state or a gradient steps through core.py -
+    except that with NDCN_ADAMS_TRAIN=1 a plain ODEFunc under a gradient (no active dropout, no no_graph / no_control, `t` without grad)
+    trains on one autograd node per solve (fixed_train._ExplicitAdamsSolve), `readout` inside it as for rk4.
     """
     user_func = func
     t_user = t
@@ -165,6 +167,14 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
                 return sol, dec is not None
         if sol is not None:
             return sol, False
+    if needs_grad and method == 'explicit_adams' and fixed_train.adams_train_enabled() and \
+            _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
+        # NDCN_ADAMS_TRAIN=1: one autograd node per solve - the library's loop forward, the multistep reverse sweep backward (an active
+        # dropout, no_graph / no_control and every other callable stay on the per-operation graph below)
+        dec = fixed_train._readout_for_grad(readout, y0[0])
+        sol = fixed_train._explicit_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], readout=dec)
+        if sol is not None:
+            return sol, dec is not None
     if needs_grad:
         from .autograd_path import odeint_with_grad
         plain, taped = _dopri5_tape_route(user_func, tensor_input, y0, t_user, method, options)
@@ -417,7 +427,6 @@ def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
     right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the current stream without
     a read-back.  None where the entry point has no form: no_graph / no_control, an operator that does not live with the state, a
     max_order the reference itself fails on."""
-    import numpy as np
     if odefunc.no_graph or odefunc.no_control or max_order < 2:
         return None
     op = _small_operator(odefunc, y0)
@@ -432,17 +441,13 @@ def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
     n_ticks = len(plan.t)
     out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
     out[0].copy_(y0)
-    n_steps, n_emit = len(plan.dts), n_ticks - 1
+    dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
     if n_steps == 0 or y0.numel() == 0:
         return out
     csr.ensure_plans(H)
     view = csr.view_ref()
     W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
     b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
-    dts = (ctypes.c_float * n_steps)(*plan.dts.tolist())
-    steps = (ctypes.c_int64 * max(n_emit, 1))(*plan.tick_step[1:].tolist())
-    same = (ctypes.c_int * max(n_emit, 1))(*[int(v) for v in plan.tick_coincident[1:]])
-    offs = (ctypes.c_float * max(n_emit, 1))(*[float(np.float32(plan.t[j] - plan.grid[plan.tick_step[j]])) for j in range(1, n_ticks)])
     nbytes = int(lib.ndcn_explicit_adams_workspace_bytes(y0.shape[0], H, max_order))
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
     with torch.cuda.device(y0.device):
