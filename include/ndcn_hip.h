@@ -475,6 +475,49 @@ NDCN_API int ndcn_rk_error_f32(const float *y0, const float *y1, const float *co
  * (-1: none).  odeint_adjoint's fused reverse pass lowers it around its parameter-gradient vector (65 792 elements riding next
  * to 10^5..10^6-row panels: 0.6 ms serial against 10 us parallel).                                                               */
 NDCN_API int64_t ndcn_set_aten_norm_max(int64_t n_elem);
+/* The bound in effect (override, else environment, else 2^18; 0: no panel keeps ATen's order).  Added to ABI 29.                   */
+NDCN_API int64_t ndcn_aten_norm_max(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * One step of method 'adams' (VariableCoefficientAdamsBashforth, adams.py:62-170) as three passes (csrc/adams_vc.hip).  Added to
+ * ABI 29: nothing existing changes.  With e_0 = phi_0 and e_j = fl(beta_j * phi_j) - the bits ndcn_scale_f32 writes; here they are
+ * re-formed in registers and never stored - every result below is, bit for bit, what the composition of ndcn_scale_f32,
+ * ndcn_rk_combine_f32 and ndcn_rk_error_f32 calls named next to it gives: products and sums rounded separately, left to right, the
+ * first product of a sum added to +0; a difference a - b is a + (0 + (-1) * b) (combine with the single coefficient -1).
+ * h_phi: HOST array of `order` device pointers phi_0 .. phi_{order-1} (newest first); h_beta: HOST array of `order` fp32 factors,
+ * h_beta[0] is not read (adams.py:37-42).  16 bytes per lane where n_elem % 4 == 0 and every panel is 16-byte aligned, single
+ * elements otherwise.  NDCN_EINVAL (text: ndcn_last_error): order outside 1..12, n_elem < 1, a null panel, an output that overlaps
+ * an input or another output, scratch too small.  Nothing is launched then.
+ */
+/* p_next = y + ((0 + h_c[0] e_0) + h_c[1] e_1 + ... + h_c[m-1] e_{m-1}), m = max(1, order - 1); h_c[j] = fl(dt * g_j)  (adams.py:44-50).
+ * = m - 1 ndcn_scale_f32 + ndcn_rk_combine_f32(p_next, y, {e_j}, h_c, m) - which takes m <= 8; this call takes every order.
+ * Reads m + 1 panels, writes 1.                                                                                                */
+NDCN_API int ndcn_adams_predict_f32(float *p_next, const float *y, const float *const *h_phi, const float *h_beta, const float *h_c,
+                           int order, int64_t n_elem, void *stream);
+
+/* The implicit phi of the predictor ip_0 = nf = f(p_next), ip_j = ip_{j-1} - e_{j-1}, j = 1 .. order (adams.py:53-59; `order`
+ * ndcn_rk_combine_f32 calls), of which only the last three links are kept; y_next = p_next + (0 + c_corr * ip_{order-1}) (:129-132);
+ * and up to four sums of squared error ratios r = (0 + coef * ip_q) / (atol + rtol * max(|y0|, |y_next|)) (misc.py:146-157):
+ *   d_out4[0]: q = order,     h_coef4[0] = fl(dt * fl(g_order - g_{order-1}))       the step's error (:135-139)
+ *   d_out4[1]: q = order - 1, h_coef4[1] = fl(dt * fl(g_{order-1} - g_{order-2}))   order selection, one lower (:154-157)
+ *   d_out4[2]: q = order - 2, h_coef4[2] = fl(dt * fl(g_{order-2} - g_{order-3}))   order selection, two lower (needs order >= 2)
+ *   d_out4[3]: q = order,     h_coef4[3] = fl(dt * GAMMA_STAR[order])               order selection, one higher (:161-165)
+ * mask bit q enables sum q (a disabled sum costs nothing and reads 0).  Each enabled sum is the fp64 value ndcn_rk_error_f32(y0,
+ * y_next, {ip_q}, {coef}, 1, ...) returns in d_out[0] ABOVE the ATen-order bound (ndcn_aten_norm_max) or below 8 elements: the same
+ * element-to-thread map, grid, per-thread order, workgroup sum and finish.  This call never sums in ATen's order, whatever the size;
+ * the non-finite count of y_next is not formed.  d_out4: four doubles on the device.  d_ws: device scratch, ws_bytes >=
+ * ndcn_adams_correct_ws_bytes().  Reads order + 3 panels, writes 1.                                                             */
+NDCN_API int ndcn_adams_correct_f32(float *y_next, const float *nf, const float *const *h_phi, const float *h_beta, int order,
+                           const float *p_next, const float *y0, float c_corr, const float *h_coef4, uint32_t mask, float rtol,
+                           float atol, int64_t n_elem, double *d_out4, void *d_ws, int64_t ws_bytes, void *stream);
+NDCN_API int64_t ndcn_adams_correct_ws_bytes(void);
+
+/* The implicit phi of an accepted step (adams.py:142 via :53-59): new_phi_0 = nf2 = f(y_next) is the caller's panel and is not
+ * copied; h_new_phi[j] = new_phi_j = new_phi_{j-1} - e_{j-1} for j = 1 .. n_out - 1 (h_new_phi: HOST array of n_out device pointers,
+ * entry 0 is not read).  1 <= n_out <= min(order + 1, 12); the solver keeps min(order + 1, max_order).  Out of place: the old phi
+ * are read until the kernel is done.  = n_out - 1 ndcn_rk_combine_f32 calls.  Reads n_out panels, writes n_out - 1.             */
+NDCN_API int ndcn_adams_update_f32(float *const *h_new_phi, const float *nf2, const float *const *h_phi, const float *h_beta,
+                          int order, int n_out, int64_t n_elem, void *stream);
 
 /* d_out[0] = sum ((a - b) / (atol + |y| * rtol))^2  (b nullable), d_out[1] = non-finite count of a.
  * The three RMS norms of misc.py:123-138 (d0, d1, d2).                                               */

@@ -252,6 +252,12 @@ SIGNATURES = {
     'ndcn_rk_error_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _F, _F, _L, _P, _P, _P]),
     'ndcn_scaled_sumsq_f32': (_I, [_P, _P, _P, _F, _F, _L, _P, _P, _P]),
     'ndcn_reduce_ws_bytes': (_L, []),
+    'ndcn_aten_norm_max': (_L, []),
+    'ndcn_adams_predict_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), ctypes.POINTER(_F), _I, _L, _P]),
+    'ndcn_adams_correct_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _P, _P, _F, ctypes.POINTER(_F), _U, _F, _F, _L,
+                                    _P, _P, _L, _P]),
+    'ndcn_adams_correct_ws_bytes': (_L, []),
+    'ndcn_adams_update_f32': (_I, [ctypes.POINTER(_P), _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _I, _L, _P]),
     'ndcn_dopri5_interp_fit_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _F, _P, _P, _P, _P, _L, _P]),
     'ndcn_dopri5_interp_direct_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _F, ctypes.POINTER(_F), _P, _L, _P]),
     'ndcn_interp_eval_f32': (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(_F), _P, _L, _P]),

@@ -466,6 +466,27 @@ int64_t ndcn_reduce_ws_bytes(void) { return reduce_ws_bytes(); }
 
 int64_t ndcn_set_aten_norm_max(int64_t n_elem) { return set_aten_order_max_elems(n_elem); }
 
+int64_t ndcn_aten_norm_max(void) { return aten_order_max_elems(); }
+
+int ndcn_adams_predict_f32(float *p_next, const float *y, const float *const *h_phi, const float *h_beta, const float *h_c, int order,
+                           int64_t n_elem, void *stream) {
+    return adams_predict_f32(p_next, y, h_phi, h_beta, h_c, order, n_elem, ST(stream));
+}
+
+int64_t ndcn_adams_correct_ws_bytes(void) { return adams_correct_ws_bytes(); }
+
+int ndcn_adams_correct_f32(float *y_next, const float *nf, const float *const *h_phi, const float *h_beta, int order,
+                           const float *p_next, const float *y0, float c_corr, const float *h_coef4, uint32_t mask, float rtol,
+                           float atol, int64_t n_elem, double *d_out4, void *d_ws, int64_t ws_bytes, void *stream) {
+    return adams_correct_f32(y_next, nf, h_phi, h_beta, order, p_next, y0, c_corr, h_coef4, mask, rtol, atol, n_elem, d_out4, d_ws,
+                             ws_bytes, ST(stream));
+}
+
+int ndcn_adams_update_f32(float *const *h_new_phi, const float *nf2, const float *const *h_phi, const float *h_beta, int order,
+                          int n_out, int64_t n_elem, void *stream) {
+    return adams_update_f32(h_new_phi, nf2, h_phi, h_beta, order, n_out, n_elem, ST(stream));
+}
+
 int ndcn_dopri5_interp_fit_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,
                                float *a, float *b, float *c, float *d, int64_t n_elem, void *stream) {
     NDCN_CHECK_ARG(n_elem >= 0 && h_k && h_cmid, "bad argument");

@@ -212,6 +212,17 @@ int scaled_sumsq_pair_f32(const float *f, const float *y, float rtol, float atol
                           void *d_ws2, hipStream_t st);
 int64_t set_aten_order_max_elems(int64_t v);   // run-time override of the bound below (< 0: back to the environment's); returns the previous override
 int64_t aten_order_max_elems();   // rk_error_f32 / scaled_sumsq_f32 reduce panels up to this size in ATen's float32 order (0: disabled)
+// adams_vc.hip: one step of method 'adams' in three streaming passes, the bits of the scale / combine / error calls core.Adams.step
+// composes it from.  h_phi / h_beta: `order` host entries (beta[0] is not read); the explicit phi beta_j phi_j are re-formed in
+// registers.  n >= 1, order 1..12; an output must not overlap an input or another output (NDCN_EINVAL).
+int adams_predict_f32(float *p_next, const float *y, const float *const *h_phi, const float *h_beta, const float *h_c, int order,
+                      int64_t n, hipStream_t st);
+int64_t adams_correct_ws_bytes();
+int adams_correct_f32(float *y_next, const float *nf, const float *const *h_phi, const float *h_beta, int order, const float *p_next,
+                      const float *y0, float c_corr, const float *h_coef4, unsigned mask, float rtol, float atol, int64_t n,
+                      double *d_out4, void *d_ws, int64_t ws_bytes, hipStream_t st);
+int adams_update_f32(float *const *h_out, const float *nf2, const float *const *h_phi, const float *h_beta, int order, int n_out,
+                     int64_t n, hipStream_t st);
 int interp_fit_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt, float *a,
                    float *b, float *c, float *d, int64_t n, hipStream_t st);
 int interp_direct_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_cmid, float dt,

@@ -12,10 +12,11 @@
 
 #pragma clang fp contract(off)
 
+#include "rk_shared.h"          // ld4 / st4, err_ratio_sq, block_sum2, reduce_finish, red_grid: shared with adams_vc.hip
+
 namespace ndcn {
 
 constexpr int kMaxTerms = 8;
-constexpr int kRedBlocks = 2048;       // partial sums per reduction (deterministic two-pass)
 
 // ndcn_debug_last_rk_path (include/ndcn_hip.h NDCN_RKF_*): every host wrapper below clears it on entry and records its LAST launch
 thread_local int64_t g_last_rk_path = 0;
@@ -39,9 +40,6 @@ __device__ __forceinline__ void apply_dt(Terms &t) {
         for (int j = 0; j < kMaxTerms; ++j) t.c[j] = dt * t.c[j];
     }
 }
-
-__device__ __forceinline__ float4 ld4(const float *p, int64_t i) { return reinterpret_cast<const float4 *>(p)[i]; }
-__device__ __forceinline__ void st4(float *p, int64_t i, float4 v) { reinterpret_cast<float4 *>(p)[i] = v; }
 
 // sum_j c_j * k_j[i], left to right, separate roundings  (misc.py:22-25).  Python's sum() starts from 0: the first product is
 // added to +0, which turns a -0 product into +0 (contraction is off, so the addition stays)
@@ -84,25 +82,7 @@ __global__ __launch_bounds__(256) void combine_kernel(float *__restrict__ out, c
 }
 
 // -------------------------------------------------------------------------------- reductions
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// block-level sum of two doubles; result valid in thread 0
-__device__ __forceinline__ void block_sum2(double &a, double &b) {
-    __shared__ double sa[4], sb[4];
-    a = wave_sum(a);
-    b = wave_sum(b);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sa[w] = a; sb[w] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = ((sa[0] + sa[1]) + sa[2]) + sa[3];
-        b = ((sb[0] + sb[1]) + sb[2]) + sb[3];
-    }
-}
+// (wave_sum, block_sum2, err_ratio_sq and the finish: rk_shared.h)
 
 // Panels up to this many elements are reduced in ATen's SINGLE-THREAD float32 order - the order of ONE torch CPU build: torch 2.10.0,
 // x86-64 (8-lane vectors, 4 interleaved accumulators, the cascade sum of SumKernel.cpp), which is what the reference's
@@ -119,13 +99,6 @@ constexpr int64_t kAtenNormMaxDefault = 1ll << 18;
 constexpr int kAtenBlock = 2048;
 
 __device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= 3.402823466e38f); }
-
-__device__ __forceinline__ float err_ratio_sq(float e, float a, float b, float rtol, float atol) {
-    // misc.py:151-156: tol = atol + rtol * max(|y0|, |y1|); r = err / tol; r * r
-    const float tol = atol + rtol * max_nan(fabsf(a), fabsf(b));
-    const float r = e / tol;
-    return r * r;
-}
 
 // The mean squared error ratio in the order ATen's float32 `sum` forms it (torch.mean = sum / n on the CPU; SumKernel.cpp's
 // cascade sum, matched bit for bit against torch on random vectors like the norm above - tools/micro/aten_norm_order.py):
@@ -408,10 +381,7 @@ __global__ __launch_bounds__(256) void scaled_sumsq_pair_kernel(const float *__r
 // fixed-order final sum of the per-block partials
 __global__ __launch_bounds__(256) void reduce_finish_kernel(const double *__restrict__ partial, int n_partial,
                                                             double *__restrict__ out, int accum) {
-    double s = 0.0, bad = 0.0;
-    for (int i = threadIdx.x; i < n_partial; i += 256) { s += partial[2 * i]; bad += partial[2 * i + 1]; }
-    block_sum2(s, bad);
-    if (threadIdx.x == 0) { out[0] = accum ? out[0] + s : s; out[1] = accum ? out[1] + bad : bad; }
+    reduce_finish(partial, n_partial, out, accum);
 }
 
 // -------------------------------------------------------------------------------- dense output
@@ -936,11 +906,6 @@ int64_t reduce_ws_bytes() {
     const int64_t c = (int64_t)kCus * 4 * 4 * 2 * sizeof(double);       // row SpMM with the ERROR epilogue: one slot per wave
     const int64_t m = a > b ? a : b;
     return m > c ? m : c;      // one scratch serves the reductions of rk.hip and of the RHS epilogues
-}
-
-static int red_grid(int64_t items) {
-    int g = stream_grid(items, 256);
-    return g > kRedBlocks ? kRedBlocks : g;
 }
 
 int rk_error_f32(const float *y0, const float *y1, const float *const *h_k, const float *h_c, int n_k, float rtol,

@@ -39,6 +39,7 @@ def _terms(ks, cs):
 # device thread and the nodes of the solver's CPU scalar chain (error ratio, norms) on the calling thread - so launch +
 # read-back of one reduction is one critical section.
 _REDUCE_LOCK = threading.RLock()
+_ADAMS_FUSED_OVERRIDE = None        # HipOps.set_adams_fused; None: the environment's NDCN_ADAMS_FUSED
 
 
 class _Reducer:
@@ -709,6 +710,97 @@ class HipOps:
             check(_lib.load().ndcn_scaled_sumsq_f32(ptr(a), ptr(b), ptr(y), float(rtol), float(atol), a.numel(),
                                                     ptr(red.out), ptr(red.ws), stream_ptr()))
             return red.fetch()
+
+    # ---------------------------------------------------------------- method 'adams': a step's algebra in three passes (csrc/adams_vc.hip)
+    @staticmethod
+    def set_adams_fused(mode):
+        """The three-pass form of core.Adams.step for panels above the ATen-order bound: 0 off - every step runs the scale / combine /
+        error calls -, 1 on; < 0: the environment's (NDCN_ADAMS_FUSED, default 1).  The results are the same bits either way.
+        Process-wide; returns the previous mode."""
+        global _ADAMS_FUSED_OVERRIDE
+        prev = HipOps.adams_fused_on()
+        _ADAMS_FUSED_OVERRIDE = None if int(mode) < 0 else (1 if int(mode) else 0)
+        return prev
+
+    @staticmethod
+    def adams_fused_on():
+        if _ADAMS_FUSED_OVERRIDE is not None:
+            return _ADAMS_FUSED_OVERRIDE
+        return 1 if _lib.env_int('NDCN_ADAMS_FUSED', 1) > 0 else 0
+
+    @staticmethod
+    def adams_fusable(*panels):
+        """May core.Adams.step take the three-pass form for these panels of one state tensor?  Contiguous float32 device panels of more
+        elements than the ATen-order bound (at or below it ndcn_rk_error_f32 sums in ATen's float32 order, which the fused sums do not
+        reproduce), 16-byte aligned (so that both forms take the same element path)."""
+        if not HipOps.adams_fused_on():
+            return False
+        n = panels[0].numel()
+        if n <= int(_lib.load().ndcn_aten_norm_max()):
+            return False
+        return all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.numel() == n and p.data_ptr() % 16 == 0
+                   for p in panels)
+
+    @staticmethod
+    def _adams_phi(phis, betas, order):
+        phis = [_panel(p) for p in phis[:order]]
+        assert len(phis) == order and len(betas) >= order
+        arr_p = (_P * order)(*[p.data_ptr() for p in phis])
+        arr_b = (_F * order)(*[0.0 if (j == 0 or betas[j] is None) else float(betas[j]) for j in range(order)])
+        return phis, arr_p, arr_b
+
+    @staticmethod
+    def adams_predict(y, phis, betas, cs, order):
+        """p_next = y + sum_j cs[j] e_j over the first max(1, order - 1) explicit phi e_0 = phis[0], e_j = betas[j] * phis[j] - the bits of
+        scale x (order - 2) + combine, the explicit phi never stored (ndcn_adams_predict_f32)."""
+        y = _panel(y)
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        m = max(1, order - 1)
+        assert len(cs) == m
+        arr_c = (_F * m)(*[float(c) for c in cs])
+        out = torch.empty_like(y)
+        with torch.cuda.device(y.device):
+            check(_lib.load().ndcn_adams_predict_f32(ptr(out), ptr(y), arr_p, arr_b, arr_c, order, y.numel(), stream_ptr()))
+        return out
+
+    @staticmethod
+    def adams_correct(nf, phis, betas, order, p_next, y0, c_corr, coefs, rtol, atol):
+        """(y_next, sums): y_next = p_next + c_corr * ip_{order-1} with the predictor's implicit phi chain ip_0 = nf, ip_j = ip_{j-1} - e_{j-1}
+        held in registers, and for every coefs[q] that is not None the sum of squared error ratios of coefs[q] * {ip_order, ip_{order-1},
+        ip_{order-2}, ip_order}[q] against (y0, y_next) as a host float - what `error` returns above the ATen-order bound -, None for the
+        others; one 32-byte read-back (ndcn_adams_correct_f32)."""
+        nf, p_next, y0 = _panel(nf), _panel(p_next), _panel(y0)
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        assert len(coefs) == 4
+        mask = sum(1 << q for q in range(4) if coefs[q] is not None)
+        arr_c = (_F * 4)(*[0.0 if c is None else float(c) for c in coefs])
+        red = _Reducer.get(y0.device)
+        lib = _lib.load()
+        out = torch.empty_like(p_next)
+        with _REDUCE_LOCK, torch.cuda.device(y0.device):
+            if getattr(red, 'ws4', None) is None:
+                red.ws4 = torch.empty(int(lib.ndcn_adams_correct_ws_bytes()), dtype=torch.uint8, device=y0.device)
+                red.out4 = torch.zeros(4, dtype=torch.float64, device=y0.device)
+                red.host4 = torch.zeros(4, dtype=torch.float64).pin_memory()
+            check(lib.ndcn_adams_correct_f32(ptr(out), ptr(nf), arr_p, arr_b, order, ptr(p_next), ptr(y0), float(c_corr), arr_c, mask,
+                                             float(rtol), float(atol), y0.numel(), ptr(red.out4), ptr(red.ws4), red.ws4.numel(), stream_ptr()))
+            red.host4.copy_(red.out4, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            sums = [float(red.host4[q]) if coefs[q] is not None else None for q in range(4)]
+        return out, sums
+
+    @staticmethod
+    def adams_update(nf2, phis, betas, order, n_out):
+        """The implicit phi of an accepted step: [nf2, nf2 - e_0, (nf2 - e_0) - e_1, ...], n_out panels, the first nf2 itself; one pass,
+        out of place (ndcn_adams_update_f32)."""
+        nf2 = _panel(nf2)
+        assert 1 <= n_out <= order + 1
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        outs = [nf2] + [torch.empty_like(nf2) for _ in range(n_out - 1)]
+        arr_o = (_P * n_out)(*[o.data_ptr() for o in outs])
+        with torch.cuda.device(nf2.device):
+            check(_lib.load().ndcn_adams_update_f32(arr_o, ptr(nf2), arr_p, arr_b, order, n_out, nf2.numel(), stream_ptr()))
+        return outs
 
     # ---------------------------------------------------------------- VJPs of the dopri5 panel operations
     @staticmethod

@@ -699,6 +699,9 @@ class Adams:
     through three panel ops of `ops`: combine (y + sum c_j k_j: predictor, corrector, and - with c = -1 - the phi
     differences), scale (beta * phi) and error (the mean squared error ratio of ONE scaled phi); the g / beta
     coefficients, the order selection and the step-size controller are scalar host code in the reference's dtypes.
+    Where the plain device ops offer them for a state tensor (ops.adams_fusable: large aligned panels, no gradient), three passes
+    replace those calls - adams_predict, adams_correct (y_next and every error sum of the step behind one read-back) and adams_update -
+    with the same bits, so the log does not depend on which form ran.
     Quirks kept: the state that is carried on (and returned at the ticks) is the PREDICTOR value p_next, not the
     corrected y_next (:170); every tick is a step end (next_t is clipped to it, :105-106) - no dense output."""
 
@@ -711,6 +714,9 @@ class Adams:
         self.safety, self.ifactor, self.dfactor = safety, ifactor, dfactor
         self.targ = TimeArg(y0[0], autonomous)
         self.n_elem = [_numel(ops, y) for y in y0]
+        # the three-pass step is offered by the plain device ops alone (looked up on the type: wrappers that forward unknown names -
+        # sharded reductions, the autograd graph - keep the per-operation calls)
+        self.fused = getattr(type(ops), 'adams_fusable', None) is not None
         self.log = []                 # (t_n, attempted next_t, order, accepted, max error ratio, next next_t)
         self.nfe = 0
 
@@ -731,11 +737,15 @@ class Adams:
         self.nfe += 1
         return self.func(tt, yy)
 
-    def _ratio(self, coef, phis, y0, y1):
-        """misc.py:146-157 on coef * phi per state tensor: float32 means."""
+    def _ratio(self, coef, phis, y0, y1, have=None):
+        """misc.py:146-157 on coef * phi per state tensor: float32 means.  have[q] (not None): the sum of tensor q, already formed by
+        the fused corrector pass."""
         out = []
-        for p, a, b, n, rt, at in zip(phis, y0, y1, self.n_elem, self.rtol, self.atol):
-            s, _ = self.ops.error(a, b, [p], [coef], rt, at)
+        for q, (p, a, b, n, rt, at) in enumerate(zip(phis, y0, y1, self.n_elem, self.rtol, self.atol)):
+            if have is not None and have[q] is not None:
+                s = have[q]
+            else:
+                s, _ = self.ops.error(a, b, [p], [coef], rt, at)
             out.append(f32(s / n) if n else f32('nan'))
         return out
 
@@ -748,19 +758,55 @@ class Adams:
         dt32 = f32(dt)
         g64, betas = adams_g_and_beta(prev_t, next_t, order)
         g = g64.astype(f32)
+        b32 = [None] + [f32(betas[j]) for j in range(1, order)]
+        nq = len(y0)
+        phi_of = lambda q: [self.phi[j][q] for j in range(order)]
+        # Per state tensor: the step's algebra as three passes of ops (adams_predict / adams_correct / adams_update: the same bits, the
+        # explicit phi and the links of the phi chains never stored) where the plain device ops offer them for the tensor - large
+        # aligned float32 panels, no gradient asked; the calls below otherwise
+        fz = [self.fused and ops.adams_fusable(y0[q], *phi_of(q)) for q in range(nq)]
         # explicit phi (:37-42): phi_0 as is, phi_j scaled by beta_j cast to the state dtype
-        ephi = [self.phi[0]] + [tuple(ops.scale(p, f32(betas[j])) for p in self.phi[j]) for j in range(1, order)]
+        ephi = [self.phi[0]] + [tuple(None if fz[q] else ops.scale(p, b32[j]) for q, p in enumerate(self.phi[j]))
+                                for j in range(1, order)]
+
+        def unfuse(q):                 # tensor q leaves the fused form mid-step (an evaluation returned an unsuitable panel)
+            fz[q] = False
+            for j in range(1, order):
+                if ephi[j][q] is None:
+                    ephi[j] = tuple(ops.scale(self.phi[j][q], b32[j]) if i == q else e for i, e in enumerate(ephi[j]))
+
         m = max(1, order - 1)
         cs = [f32(dt32 * g[j]) for j in range(m)]
-        p_next = tuple(ops.combine(y_, [ephi[j][q] for j in range(m)], cs) for q, y_ in enumerate(y0))
+        p_next = tuple(ops.adams_predict(y_, phi_of(q), b32, cs, order) if fz[q] else
+                       ops.combine(y_, [ephi[j][q] for j in range(m)], cs) for q, y_ in enumerate(y0))
         nf = self._f(f32(next_t), p_next)
+        for q in range(nq):
+            if fz[q] and not ops.adams_fusable(y0[q], nf[q], p_next[q]):
+                unfuse(q)
         # implicit phi of the predictor (:53-59): phi_j = phi_{j-1} - explicit phi_{j-1}
         k = min(len(ephi) + 1, order + 1)
         iphi_p = [nf]
         for j in range(1, k):
-            iphi_p.append(tuple(ops.combine(a, [b], [f32(-1.0)]) for a, b in zip(iphi_p[j - 1], ephi[j - 1])))
-        y_next = tuple(ops.combine(p_, [ip], [f32(dt32 * g[order - 1])]) for p_, ip in zip(p_next, iphi_p[order - 1]))
-        error_k = self._ratio(f32(dt32 * f32(g[order] - g[order - 1])), iphi_p[order], y0, y_next)
+            iphi_p.append(tuple(None if fz[q] else ops.combine(a, [b], [f32(-1.0)])
+                                for q, (a, b) in enumerate(zip(iphi_p[j - 1], ephi[j - 1]))))
+        c_corr = f32(dt32 * g[order - 1])
+        coef_k = f32(dt32 * f32(g[order] - g[order - 1]))
+        select = not (len(prev_t) <= 4 or order < 3)                # the order selection below reads e1, e2 and perhaps e3
+        coef_1 = f32(dt32 * f32(g[order - 1] - g[order - 2])) if select else None
+        coef_2 = f32(dt32 * f32(g[order - 2] - g[order - 3])) if select else None
+        coef_3 = f32(dt32 * f32(GAMMA_STAR[order])) if select and order < self.max_order else None
+        y_next, sums = [], []
+        for q in range(nq):
+            if fz[q]:
+                yq, sq = ops.adams_correct(nf[q], phi_of(q), b32, order, p_next[q], y0[q], c_corr, [coef_k, coef_1, coef_2, coef_3],
+                                           self.rtol[q], self.atol[q])
+            else:
+                yq, sq = ops.combine(p_next[q], [iphi_p[order - 1][q]], [c_corr]), [None] * 4
+            y_next.append(yq)
+            sums.append(sq)
+        y_next = tuple(y_next)
+        have = lambda i: [s[i] for s in sums]
+        error_k = self._ratio(coef_k, iphi_p[order], y0, y_next, have(0))
         accept = all(bool(r <= 1) for r in error_k)
         worst = f32('nan') if any(np.isnan(r) for r in error_k) else max(error_k)
         if not accept:
@@ -770,19 +816,28 @@ class Adams:
             return False
         nf = self._f(f32(next_t), y_next)
         k = min(len(ephi) + 1, order + 2)
+        fu = [fz[q] and ops.adams_fusable(y0[q], nf[q]) for q in range(nq)]       # the new phi of tensor q in one pass
+        for q in range(nq):
+            if fz[q] and not fu[q]:
+                unfuse(q)
         iphi = [nf]
         for j in range(1, k):
-            iphi.append(tuple(ops.combine(a, [b], [f32(-1.0)]) for a, b in zip(iphi[j - 1], ephi[j - 1])))
+            iphi.append(tuple(None if fu[q] else ops.combine(a, [b], [f32(-1.0)])
+                              for q, (a, b) in enumerate(zip(iphi[j - 1], ephi[j - 1]))))
+        if any(fu):
+            n_out = min(k, self.max_order)                              # what iphi[:max_order] keeps below
+            new = [ops.adams_update(nf[q], phi_of(q), b32, order, n_out) if fu[q] else None for q in range(nq)]
+            iphi = [tuple(new[q][j] if fu[q] else iphi[j][q] for q in range(nq)) for j in range(n_out)]
         next_order = order
-        if len(prev_t) <= 4 or order < 3:
+        if not select:
             next_order = min(order + 1, 3, self.max_order)
         else:
-            e1 = self._ratio(f32(dt32 * f32(g[order - 1] - g[order - 2])), iphi_p[order - 1], y0, y_next)
-            e2 = self._ratio(f32(dt32 * f32(g[order - 2] - g[order - 3])), iphi_p[order - 2], y0, y_next)
+            e1 = self._ratio(coef_1, iphi_p[order - 1], y0, y_next, have(1))
+            e2 = self._ratio(coef_2, iphi_p[order - 2], y0, y_next, have(2))
             if min(e1 + e2) < max(error_k):
                 next_order = order - 1
             elif order < self.max_order:
-                e3 = self._ratio(f32(dt32 * f32(GAMMA_STAR[order])), iphi_p[order], y0, y_next)
+                e3 = self._ratio(coef_3, iphi_p[order], y0, y_next, have(3))
                 if max(e3) < max(error_k):
                     next_order = order + 1
         dt_next = dt if next_order > order else optimal_step_size(dt, worst, self.safety, self.ifactor, self.dfactor,
