@@ -861,6 +861,47 @@ NDCN_API int ndcn_explicit_adams_train_f32(const ndcn_csr *A, const float *W, co
                                            const float *h_tick_off, int64_t n_ticks, int max_order, float *out, float *rec_f,
                                            float *rec_y, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* fixed_adams: the reference's AdamsBashforthMoulton (torchdiffeq/_impl/fixed_adams.py:151-205) - explicit_adams' predictor corrected
+ * by the Adams-Moulton formula over the same history, the corrector iterated until every element of the step's increment has settled.
+ * Four calls added to ABI 29: no existing declaration changes.
+ * ndcn_abm_predict_f32, the predictor and the explicit part of the corrector of a step that holds n evaluations (:180-188):
+ *     dy    = dt * ((((0 + a[0] f[0]) + a[1] f[1]) + ...) + a[n-1] f[n-1])       a: the Adams-Bashforth weights of order n
+ *     delta = dt * ((((0 + m[0] f[0]) + m[1] f[1]) + ...) + m[n-1] f[n-1])       m: the Adams-Moulton weights of the formula over the
+ *     u     = y + dy                                                             n + 1 points t + dt, t, .. WITHOUT its leading one
+ *   in ONE streaming pass over y and the history (the reference reads it twice), with the rounding, the argument conventions (h_f, h_a,
+ *   h_m: HOST arrays), the lanes and the grid of ndcn_ab_step_f32.  3 <= n <= 11; NDCN_EINVAL - before any launch - for any other n, a
+ *   null panel, an output that is a history panel, or outputs that alias each other or y (u == y alone is allowed).
+ * ndcn_abm_correct_f32, one corrector iteration (:192-194, misc.py:33-37) on the evaluation f = func(t + dt, u):
+ *     dy <- c0 * f + delta  (in place),   u = y + dy,   c0 = fl32(dt) * fl32(m_0 / div) formed by the caller
+ *     *d_count = the number of elements for which  |dy_old - dy_new| < atol + rtol * max(|dy_old|, |dy_new|)  does NOT hold
+ *   - float32 throughout, a strict `<`: err == tol fails, a NaN fails, rtol = atol = 0 fails everywhere.  d_count: a DEVICE uint64,
+ *   8-byte aligned, zeroed by the call on `stream`; every workgroup counts in integers and adds its count with one integer atomic, so the
+ *   result does not depend on the order of the workgroups.  The caller reads it back (8 bytes) to decide whether to iterate again.  u is
+ *   the next iterate and, after the last iteration, the new state y1 (solvers.py:92).  NDCN_EINVAL before any launch for a null panel or
+ *   u / dy overlapping an input.  Any alignment, any n_elem >= 0 (0: the counter is zeroed, nothing is launched).
+ * ndcn_solve_fixed_adams_f32: ndcn_solve_explicit_adams_f32 - the same arguments, restrictions (plain ODEFunc, flags == NDCN_F_RELU,
+ *   un-sharded, no dropout), history ring, warm-up launches and tick handling - with the corrector:
+ *     rtol, atol, max_iters    of the convergence test (float32, as the reference forms them on the state dtype); max_iters >= 1
+ *     h_iters [n_steps]        HOST, written: corrector iterations run by grid step i (0: an RK4 warm-up step)
+ *     h_converged [n_steps]    HOST, written: 1 where step i converged (warm-up steps: 1), 0 where it ran max_iters iterations without
+ *   UNLIKE the explicit solve this one is not enqueued blindly: every corrector iteration ends with ONE 8-byte read-back of the counter
+ *   and a synchronisation of `stream`, because the HOST decides whether to iterate again and - a step that did not converge drops the
+ *   OLDEST evaluation of its history (:199) - how long the ring is for the next step.  The evaluation of the corrector never enters the
+ *   history.  The caller prints the reference's warning line (:198) for every step with h_converged[i] == 0.
+ *     workspace                ndcn_fixed_adams_workspace_bytes(n_rows, H, max_order) bytes, 256-byte aligned: the explicit solve's panels,
+ *                              three more (dy, delta, the corrector's evaluation) and the counter
+ *   The Moulton weights of each order are derived in the library in 64-bit integers from the exact rationals
+ *   mu_i = integral_0^1 prod_{j != i} (u + j - 1) / (j - i) du over their least common denominator, as the Bashforth ones are.          */
+NDCN_API int ndcn_abm_predict_f32(float *dy, float *delta, float *u, const float *y, const float *const *h_f, const float *h_a,
+                                  const float *h_m, int n, float dt, int64_t n_elem, void *stream);
+NDCN_API int ndcn_abm_correct_f32(float *dy, float *u, const float *f, const float *delta, const float *y, float c0, float rtol, float atol,
+                                  int64_t n_elem, uint64_t *d_count, void *stream);
+NDCN_API int64_t ndcn_fixed_adams_workspace_bytes(int64_t n_rows, int H, int max_order);
+NDCN_API int ndcn_solve_fixed_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                        const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                        const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol, int max_iters,
+                                        float *out, int *h_iters, int *h_converged, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): when enabled, every kernel launch made by this library is
  * bracketed by HIP events recorded on the launch stream.  ndcn_prof_read drains them into

@@ -76,6 +76,12 @@ class NdcnHipError(RuntimeError):
         self.code = code
 
 
+class NdcnHostStateError(NdcnHipError, NotImplementedError):
+    """A host tensor handed to a method this build provides on the device only, refused where the methods the build does not provide
+    at all are refused: callers that probe a method with a host state and expect NotImplementedError - what the name got before the
+    method existed - and callers that expect the 'no CPU fallback' NdcnHipError both catch it."""
+
+
 class CsrView(ctypes.Structure):
     """struct ndcn_csr"""
     _fields_ = [('n_rows', ctypes.c_int64), ('n_cols', ctypes.c_int64), ('nnz', ctypes.c_int64),
@@ -268,6 +274,11 @@ SIGNATURES = {
     'ndcn_explicit_adams_workspace_bytes': (_L, [_L, _I, _I]),
     'ndcn_solve_explicit_adams_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
                                            ctypes.POINTER(_F), _L, _I, _P, _P, _L, _P]),
+    'ndcn_abm_predict_f32': (_I, [_P, _P, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), ctypes.POINTER(_F), _I, _F, _L, _P]),
+    'ndcn_abm_correct_f32': (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _L, _P, _P]),
+    'ndcn_fixed_adams_workspace_bytes': (_L, [_L, _I, _I]),
+    'ndcn_solve_fixed_adams_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
+                                        ctypes.POINTER(_F), _L, _I, _F, _F, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _L, _P]),
     'ndcn_ab_adjoint_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _L, _P]),
     'ndcn_explicit_adams_train_workspace_bytes': (_L, [_L, _I]),
     'ndcn_explicit_adams_train_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
@@ -347,11 +358,11 @@ def check(code):
     return code
 
 
-def require_device(t, what='tensor'):
+def require_device(t, what='tensor', error=NdcnHipError):
     """The HIP path is the only path: refuse host tensors instead of computing on the CPU."""
     if not t.is_cuda:
-        raise NdcnHipError(EINVAL, '%s lives on %s; ndcn_amd computes on a ROCm device only (no CPU fallback). '
-                                   'Move it with .to("cuda").' % (what, t.device))
+        raise error(EINVAL, '%s lives on %s; ndcn_amd computes on a ROCm device only (no CPU fallback). '
+                            'Move it with .to("cuda").' % (what, t.device))
     if t.dtype != torch.float32:
         raise NdcnHipError(EINVAL, '%s has dtype %s; the HIP path computes in float32' % (what, t.dtype))
     return t

@@ -184,6 +184,29 @@ class AutogradOps:
         return _LinMap.apply(lambda yy, *f: hip.ab_step(yy, list(f), coeffs, dt), w, y, *fs)
 
     @staticmethod
+    def abm_predict(y, fs, a, m, dt):
+        # the three panels of ndcn_abm_predict_f32 as linear maps of (y, f_0, ..): the bits of the kernel (one pass each under a
+        # gradient: every output is its own node)
+        n = len(fs)
+        pick = lambda q: (lambda yy, *f: hip.abm_predict(yy, list(f), a, m, dt)[q])
+        wa = tuple(float(dt) * float(c) for c in a)
+        wm = tuple(float(dt) * float(c) for c in m)
+        dy = _LinMap.apply(pick(0), (0.0,) + wa, y, *fs)
+        delta = _LinMap.apply(pick(1), (0.0,) + wm, y, *fs)
+        u = _LinMap.apply(pick(2), (1.0,) + wa, y, *fs)
+        return dy, delta, u
+
+    @staticmethod
+    def abm_correct(f, delta, y, dy, c0, rtol, atol):
+        # the count comes from the kernel on detached tensors (on a copy of dy: the graph keeps the old one); the values are composed
+        # from the differentiable maps - c0 * f + delta and y + dy', the kernel's own roundings - so the iteration count is a constant
+        # of the graph
+        _, _, failed = hip.abm_correct(f.detach(), delta.detach(), y.detach(), dy.detach().clone(), c0, rtol, atol)
+        new = _LinMap.apply(lambda dl, ff: hip.combine(dl, [ff], [c0]), (1.0, float(c0)), delta, f)
+        u = _LinMap.apply(lambda yy, dd: hip.combine(yy, [dd], [np.float32(1)]), (1.0, 1.0), y, new)
+        return new, u, failed
+
+    @staticmethod
     def tick_emit(y, dt, tms, outs=None):
         # y + ((y - y) / dt) * tm: the derivative with respect to y is 1 wherever the state is finite (the slope term is a constant
         # zero there), so every tick hands its gradient to the state that ended the step, unchanged

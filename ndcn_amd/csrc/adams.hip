@@ -4,6 +4,8 @@
 //   ab_step_f32                      out = y + dt * sum_{i<n} a_i f_i, n = 3..11: one streaming pass over the history
 //   ndcn_solve_explicit_adams_f32    the whole solve over ODEFunc, enqueued on the caller's stream: history ring, stage panels and both
 //                                    state panels in a caller-owned workspace, nothing read back
+//   ndcn_solve_fixed_adams_f32       the same loop with the Adams-Moulton corrector of fixed_adams (its two passes: adams_pc.hip) iterated per
+//                                    step; one 8-byte read-back per iteration - the host decides whether to iterate again
 //   ndcn_explicit_adams_train_f32    the same loop (adams_run) writing every evaluation and every state into a caller-owned record: the
 //                                    forward pass of training (the reverse sweep: adams_bwd.hip, fixed_train.py)
 //
@@ -183,12 +185,61 @@ void ab_weights(int k, float *a) {
     for (int i = 0; i < k; ++i) a[i] = (float)((1.0 / (double)div) * (double)(num[i] * (div / den[i])));
 }
 
+// The Adams-Moulton weights for a step that holds k evaluations: the formula over the k + 1 points t + dt, t, t - dt, ..,
+// mu_i = integral_0^1 prod_{j != i, j <= k} (u + j - 1) / (j - i) du = c_i / div as above (k <= 11: a polynomial of degree 11 with
+// coefficients below 11!, lcm(1..12) = 27720, div <= 958003200 - every intermediate fits 64 bits and every c_i a double exactly).
+// m[i - 1] = (float)((1.0 / div) * c_i) for the history (fixed_adams.py:188); *lead = c_0 / div, the double the reference multiplies dt
+// by (:193).
+void am_weights(int k, float *m, double *lead) {
+    constexpr int P = kAbMaxTerms + 1;
+    int64_t num[P], den[P];
+    int64_t L = 1;
+    for (int q = 1; q <= k + 1; ++q) L = L / gcd64(L, q) * q;
+    for (int i = 0; i <= k; ++i) {
+        int64_t poly[P + 1] = {1};                           // prod_{j != i} (u + j - 1), lowest power first
+        int deg = 0;
+        int64_t d = 1;
+        for (int j = 0; j <= k; ++j) {
+            if (j == i) continue;
+            for (int q = deg + 1; q >= 0; --q) poly[q] = (q ? poly[q - 1] : 0) + (int64_t)(j - 1) * (q <= deg ? poly[q] : 0);
+            ++deg;
+            d *= j - i;
+        }
+        int64_t s = 0;
+        for (int q = 0; q <= deg; ++q) s += poly[q] * (L / (q + 1));
+        int64_t den_i = L * d;
+        if (den_i < 0) { den_i = -den_i; s = -s; }
+        const int64_t g = gcd64(s, den_i);
+        num[i] = s / g;
+        den[i] = den_i / g;
+    }
+    int64_t div = 1;
+    for (int i = 0; i <= k; ++i) div = div / gcd64(div, den[i]) * den[i];
+    *lead = (double)(num[0] * (div / den[0])) / (double)div;
+    for (int i = 1; i <= k; ++i) m[i - 1] = (float)((1.0 / (double)div) * (double)(num[i] * (div / den[i])));
+}
+
+// the corrector of fixed_adams: absent (nullptr) in the explicit solves
+struct Corrector {
+    float rtol, atol;
+    int max_iters;
+    int *h_iters, *h_converged;
+};
+
+// an 8-byte pinned mirror of the device counter, owned by one solve
+struct PinnedCount {
+    unsigned long long *p = nullptr;
+    ~PinnedCount() { if (p) (void)hipHostFree(p); }
+};
+
 inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 // panels of the workspace: k2..k4 of a warm-up step and the stage input - what a solve WITH a record needs besides the record -; a solve
 // without one adds the history ring and two state panels
 constexpr int kStagePanels = 3 + 1;
 inline int solve_panels(int max_order) { return (max_order - 1) + kStagePanels + 2; }
+constexpr int kCorrectorPanels = 3;    // dy, delta, the corrector's evaluation (the iterate is the new state's panel)
+constexpr size_t kCounterBytes = 256;
 
 inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
     const size_t panel = up256((size_t)n_rows * (size_t)H * sizeof(float));
@@ -211,7 +262,8 @@ inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
 // the same launches on the same values, only the addresses differ.
 int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
               int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off, int64_t n_ticks, int max_order,
-              float *out, float *rec_f, float *rec_y, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+              float *out, float *rec_f, float *rec_y, void *workspace, int64_t workspace_bytes, hipStream_t st,
+              const Corrector *pc = nullptr) {
     ADAMS_ARG(A && W && y0 && H > 0 && n_steps >= 0 && n_ticks >= 0, "null argument");
     ADAMS_ARG(A->n_rows >= 0 && A->n_rows < (1ll << 31) - 1 && A->nnz >= 0 && A->rowptr && (A->nnz == 0 || (A->colidx && A->val)), "bad operator");
     ADAMS_ARG(A->n_rows == A->n_cols, "an un-sharded solve: the operator must be square (no halo columns)");
@@ -223,7 +275,10 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
         ADAMS_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
     const bool rec = rec_f != nullptr;
     ADAMS_ARG(!rec || n_steps == 0 || rec_y, "the record of the states is missing");
-    const int64_t need = workspace_need(A->n_rows, H, rec ? kStagePanels : solve_panels(max_order));
+    ADAMS_ARG(!pc || (!rec && pc->max_iters >= 1 && (n_steps == 0 || (pc->h_iters && pc->h_converged))),
+              "the corrector needs max_iters >= 1 and the two per-step host arrays");
+    const int64_t need = workspace_need(A->n_rows, H, rec ? kStagePanels : solve_panels(max_order) + (pc ? kCorrectorPanels : 0)) +
+                         (pc ? (int64_t)kCounterBytes : 0);
     ADAMS_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 && workspace_bytes >= need,
               "workspace of the size its host function returns, 256-byte aligned, required");
     const int64_t n = A->n_rows * (int64_t)H;
@@ -239,6 +294,15 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
     float *k2 = take(), *k3 = take(), *k4 = take(), *ytmp = take();
     float *state[2] = {nullptr, nullptr};
     if (!rec) { state[0] = take(); state[1] = take(); }
+    float *dy = nullptr, *delta = nullptr, *fc = nullptr;
+    unsigned long long *d_count = nullptr;
+    PinnedCount h_count;
+    if (pc) {
+        dy = take(); delta = take(); fc = take();
+        d_count = reinterpret_cast<unsigned long long *>(base);
+        base += kCounterBytes;
+        NDCN_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_count.p), sizeof(unsigned long long), hipHostMallocDefault));
+    }
     float *work = rhs_work_bytes(A->n_rows, H, flags) > 0 ? reinterpret_cast<float *>(base) : nullptr;
     uint32_t fl = flags;
     if (work && rhs_fused_supported(H, flags) && rhs_fused2_supported(A, H, flags)) {
@@ -251,6 +315,9 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
 
     float weights[kAbMaxTerms + 1][kAbMaxTerms];
     for (int k = kAbMinTerms; k <= kAbMaxTerms && k <= ring_n; ++k) ab_weights(k, weights[k]);
+    float moulton[kAbMaxTerms + 1][kAbMaxTerms];
+    double lead[kAbMaxTerms + 1] = {};
+    for (int k = kAbMinTerms; pc && k <= kAbMaxTerms && k <= ring_n; ++k) am_weights(k, moulton[k], &lead[k]);
 
     const float *y = y0;
     int held = 0, newest = -1;                                 // evaluations held; the ring slot of the newest
@@ -281,6 +348,27 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
             if ((rc = fixed_stage_f32(4, ytmp, y, f_new, k2, k3, nullptr, dt, n, st))) return rc;
             if ((rc = eval(ytmp, k4))) return rc;
             if ((rc = fixed_stage_f32(5, dst, y, f_new, k2, k3, k4, dt, n, st))) return rc;
+            if (pc) { pc->h_iters[i] = 0; pc->h_converged[i] = 1; }
+        } else if (pc) {
+            // fixed_adams.py:180-200: predictor and the corrector's explicit part in one pass, the iterate in the new state's panel;
+            // then evaluate / correct / read the count back until no element fails or max_iters passes have run
+            const float *f[kAbMaxTerms];
+            for (int q = 0; q < order; ++q) f[q] = ring[((newest - q) % ring_n + ring_n) % ring_n];
+            if ((rc = abm_predict_f32(dy, delta, dst, y, f, weights[order], moulton[order], order, dt, n, st))) return rc;
+            const float c0 = dt * (float)lead[order];          // torch: the double becomes a float32 scalar, then one float32 product
+            int its = 0;
+            bool converged = false;
+            while (its < pc->max_iters && !converged) {
+                if ((rc = eval(dst, fc))) return rc;
+                if ((rc = abm_correct_f32(dy, dst, fc, delta, y, c0, pc->rtol, pc->atol, n, d_count, st))) return rc;
+                NDCN_HIP(hipMemcpyAsync(h_count.p, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+                NDCN_HIP(hipStreamSynchronize(st));
+                ++its;
+                converged = *h_count.p == 0;
+            }
+            pc->h_iters[i] = its;
+            pc->h_converged[i] = converged ? 1 : 0;
+            if (!converged) --held;                            // :199: the oldest evaluation leaves the history
         } else {
             const float *f[kAbMaxTerms];
             for (int q = 0; q < order; ++q) f[q] = rec ? rec_f + (size_t)(i - q) * (size_t)n : ring[((newest - q) % ring_n + ring_n) % ring_n];
@@ -338,6 +426,20 @@ int ndcn_solve_explicit_adams_f32(const ndcn_csr *A, const float *W, const float
                                   int64_t workspace_bytes, void *stream) {
     return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
                      nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int64_t ndcn_fixed_adams_workspace_bytes(int64_t n_rows, int H, int max_order) {
+    if (n_rows < 0 || H <= 0 || max_order < 2 || max_order > kAbMaxOrder) return NDCN_EINVAL;
+    return workspace_need(n_rows, H, solve_panels(max_order) + kCorrectorPanels) + (int64_t)kCounterBytes;
+}
+
+int ndcn_solve_fixed_adams_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
+                               int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off,
+                               int64_t n_ticks, int max_order, float rtol, float atol, int max_iters, float *out, int *h_iters,
+                               int *h_converged, void *workspace, int64_t workspace_bytes, void *stream) {
+    const Corrector pc = {rtol, atol, max_iters, h_iters, h_converged};
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
+                     nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &pc);
 }
 
 int ndcn_explicit_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,

@@ -254,6 +254,14 @@ int ab_grid(int64_t items);
 // adams_bwd.hip: the gradient of one evaluation gathered from the adjoints of the Adams-Bashforth steps that used it,
 // out = [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), n_terms = 1..11, base nullable and added last; out may be base, never one of h_g
 int ab_adjoint_f32(float *out, const float *base, const float *const *h_g, const float *h_c, int n_terms, int64_t n, hipStream_t st);
+// adams_pc.hip: the predictor and one corrector pass of fixed_adams (fixed_adams.py:179-194).  predict: dy = dt * sum a_i f_i,
+// delta = dt * sum m_i f_i, u = y + dy in one pass over the n_terms = 3..11 history panels (u may be y; no output may be a history panel).
+// correct: dy <- c0 * f + delta in place, u = y + dy, *d_count = the elements that fail |old - new| < atol + rtol * max(|old|, |new|)
+// (the counter is zeroed on the stream first; nothing else may overlap u or dy).  The lanes of ab_step_f32, any alignment, any n >= 0.
+int abm_predict_f32(float *dy, float *delta, float *u, const float *y, const float *const *h_f, const float *h_a, const float *h_m,
+                    int n_terms, float dt, int64_t n, hipStream_t st);
+int abm_correct_f32(float *dy, float *u, const float *f, const float *delta, const float *y, float c0, float rtol, float atol, int64_t n,
+                    unsigned long long *d_count, hipStream_t st);
 
 int row_l1_normalize_f32(const float *X, float *Y, int64_t n_rows, int H, hipStream_t st);
 int row_l1_normalize_bwd_f32(const float *G, const float *X, float *GX, int64_t n_rows, int H, hipStream_t st);

@@ -1011,6 +1011,43 @@ class HipOps:
         return out
 
     @staticmethod
+    def abm_predict(y, fs, a, m, dt):
+        """(dy, delta, u) of a fixed_adams step that holds len(fs) = 3..11 evaluations (fixed_adams.py:180-188): dy = dt * sum a_i f_i,
+        delta = dt * sum m_i f_i, u = y + dy - one pass over the history, every product and sum rounded on its own
+        (ndcn_abm_predict_f32).  a: the Adams-Bashforth weights, m: the Adams-Moulton weights of the history (core.am_weights)."""
+        y = _panel(y)
+        fs = [_panel(f) for f in fs]
+        assert len(a) == len(fs) == len(m)
+        dy, delta, u = torch.empty_like(y), torch.empty_like(y), torch.empty_like(y)
+        arr_f, arr_a, n = _terms(fs, a)
+        arr_m = (_F * n)(*[float(c) for c in m])
+        with torch.cuda.device(y.device):
+            check(_lib.load().ndcn_abm_predict_f32(ptr(dy), ptr(delta), ptr(u), ptr(y), arr_f, arr_a, arr_m, n, float(dt), y.numel(),
+                                                   stream_ptr()))
+        return dy, delta, u
+
+    @staticmethod
+    def abm_correct(f, delta, y, dy, c0, rtol, atol):
+        """One corrector iteration (fixed_adams.py:192-194): (dy, u, failed) with dy <- c0 * f + delta IN PLACE, u = y + dy a new panel and
+        `failed` the number of elements for which |dy_old - dy_new| < atol + rtol * max(|dy_old|, |dy_new|) does not hold, as a host int -
+        counted in integers on the device, one 8-byte read-back (ndcn_abm_correct_f32)."""
+        f, delta, y = _panel(f), _panel(delta), _panel(y)
+        require_device(dy, 'dy')
+        assert dy.is_contiguous()
+        u = torch.empty_like(y)
+        red = _Reducer.get(y.device)
+        with _REDUCE_LOCK, torch.cuda.device(y.device):
+            if getattr(red, 'count', None) is None:
+                red.count = torch.zeros(1, dtype=torch.int64, device=y.device)
+                red.count_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+            check(_lib.load().ndcn_abm_correct_f32(ptr(dy), ptr(u), ptr(f), ptr(delta), ptr(y), float(c0), float(rtol), float(atol),
+                                                   y.numel(), ptr(red.count), stream_ptr()))
+            red.count_host.copy_(red.count, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            failed = int(red.count_host[0])
+        return dy, u, failed
+
+    @staticmethod
     def ab_adjoint(gs, cs, base=None, out=None):
         """The gradient of one evaluation of an explicit_adams solve, gathered from the adjoints of the Adams-Bashforth steps that used
         it (ndcn_ab_adjoint_f32): [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), every product and sum rounded on its own, the base added

@@ -485,6 +485,10 @@ def sharded_odeint(ops, odefunc, plan, n_global_rows, x_local, t, rtol=1e-7, ato
     stats (a dict, optional) receives which evaluation form ran and what travelled: {'form': 'row_split' | 'two_phase' |
     'one_launch', 'nfe', 'halo_bytes' (sent + received over the solve), 'halo_rows_received_per_rhs'}."""
     from .torchdiffeq._impl import core
+    if method == 'fixed_adams':
+        raise NotImplementedError("sharded_odeint: method 'fixed_adams' has no sharded form (dopri5, euler, midpoint and rk4 do): whether "
+                                  "a step has converged is decided over ALL elements, which across ranks needs a reduction per corrector "
+                                  "iteration")
     if method == 'explicit_adams':
         raise NotImplementedError("sharded_odeint: method 'explicit_adams' has no sharded form (dopri5, euler, midpoint and rk4 do); "
                                   "solve the un-sharded graph with odeint")

@@ -26,7 +26,8 @@ from . import core
 f32 = np.float32
 
 
-def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False, step_log=None, odefunc=None, plan=None):
+def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False, step_log=None, odefunc=None, plan=None,
+                     max_iters=core.ABM_MAX_ITERS):
     if method == 'dopri5':
         return integrate_dopri5_grad(func, y0, t, rtol, atol, autonomous=autonomous, step_log=step_log, odefunc=odefunc, **options)
     if method == 'adams':
@@ -35,9 +36,11 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=False,
         # deviation that is stated, not hidden: DESIGN section 2)
         return core.integrate_adams(autograd_ops, func, y0, t, rtol, atol, autonomous=autonomous, step_log=step_log, **options)
     # plan: the grid and tick placement of the step_size option (core.fixed_plan); None: the default grid
-    # (explicit_adams: the same control flow with ops.ab_step as one more linear map; max_order from core.fixed_options)
+    # (explicit_adams: the same control flow with ops.ab_step as one more linear map; max_order from core.fixed_options.  fixed_adams:
+    # predictor and corrector composed from linear maps, the convergence count taken from the kernel on detached tensors)
     return core.integrate_fixed(autograd_ops, func, y0, t, method, autonomous=autonomous, plan=plan,
-                                max_order=options.get('max_order', core.AB_MAX_ORDER))
+                                max_order=options.get('max_order', core.AB_MAX_ORDER), max_iters=max_iters, rtol=rtol, atol=atol,
+                                step_log=step_log if method == 'fixed_adams' else None)
 
 
 class _HipValue(torch.autograd.Function):

@@ -6,6 +6,7 @@ Mirrors the control flow and scalar arithmetic of the reference's vendored torch
   dopri5            torchdiffeq/_impl/dopri5.py:58-122 ; rk_common.py:22-61 ; misc.py:84-170 ; interp.py:5-65
   adams             torchdiffeq/_impl/adams.py:11-170 (variable-coefficient Adams-Bashforth-Moulton)
   explicit_adams    torchdiffeq/_impl/fixed_adams.py:151-211 (fixed-grid Adams-Bashforth, RK4 warm-up)
+  fixed_adams       torchdiffeq/_impl/fixed_adams.py:151-205 (the same with an Adams-Moulton corrector iterated to a tolerance)
 All per-element work is delegated to `ops` (one fused HIP kernel per reference op chain); what stays
 here is scalar: times and the step-size controller in float64, every quantity the reference forms as a
 0-d tensor of the state dtype (dt*beta, stage times, initial-step heuristic, interpolation abscissa)
@@ -14,6 +15,7 @@ in numpy float32.  State may be a tensor or a tuple of tensors (misc.py:175-182)
 import collections
 import fractions
 import math
+import sys
 import warnings
 
 import numpy as np
@@ -52,10 +54,10 @@ IFACTOR = 10.0
 DFACTOR = float(f32(0.2))
 
 FIXED_METHODS = ('euler', 'midpoint', 'rk4')
-GRID_METHODS = FIXED_METHODS + ('explicit_adams',)      # every FixedGridODESolver: the step_size option, FixedPlan, emit_ticks
+GRID_METHODS = FIXED_METHODS + ('explicit_adams', 'fixed_adams')      # every FixedGridODESolver: the step_size option, FixedPlan, emit_ticks
 METHODS = GRID_METHODS + ('dopri5', 'adams')
 # methods the reference lists (odeint.py:8-17) but this build does not provide
-UNSUPPORTED = ('fixed_adams', 'tsit5')
+UNSUPPORTED = ('tsit5',)
 
 
 def _nan_max(a, b):
@@ -166,7 +168,8 @@ def assert_increasing(t):
 # ---------------------------------------------------------------------------------------------------
 
 # fixed_grid.py:5,15,26 ; fixed_adams.py:208 (named in the warning)
-FIXED_SOLVER_NAMES = {'euler': 'Euler', 'midpoint': 'Midpoint', 'rk4': 'RK4', 'explicit_adams': 'AdamsBashforth'}
+FIXED_SOLVER_NAMES = {'euler': 'Euler', 'midpoint': 'Midpoint', 'rk4': 'RK4', 'explicit_adams': 'AdamsBashforth',
+                      'fixed_adams': 'AdamsBashforthMoulton'}
 MAX_EMIT = 8                                  # tick panels one tick_emit launch writes (csrc/rk.hip: kMaxTicks)
 
 
@@ -175,13 +178,23 @@ def fixed_options(method, options):
     not know and its ValueError for ANY grid_constructor (the `elif grid_constructor is None` branch: with or without step_size).
     Returns what the solve goes on with: {'step_size': h} where one was given and, for explicit_adams, {'max_order': m} always -
     AdamsBashforthMoulton.__init__ (fixed_adams.py:153-163): int(min(max_order, 12)), default 12; max_iters is a name it knows,
-    `implicit` collides with the one AdamsBashforth passes itself (:211: a TypeError)."""
+    `implicit` collides with the one AdamsBashforth passes itself (:211: a TypeError).  fixed_adams (AdamsBashforthMoulton itself) adds
+    {'max_iters': n, 'implicit': flag} always (defaults 4, True: what __init__ stores, unchecked); rtol / atol among its options collide
+    with the keyword arguments odeint passes (odeint.py:74: a TypeError)."""
     options = dict(options or {})
+    if method == 'fixed_adams':
+        for name in ('rtol', 'atol'):
+            if name in options:
+                raise TypeError("__init__() got multiple values for keyword argument '%s'" % name)
     step_size = options.pop('step_size', None)
     grid_constructor = options.pop('grid_constructor', None)
     options.pop('rtol', None)
     options.pop('atol', None)
     out = {}
+    if method == 'fixed_adams':
+        out['implicit'] = options.pop('implicit', True)
+        out['max_iters'] = options.pop('max_iters', ABM_MAX_ITERS)
+        out['max_order'] = int(min(options.pop('max_order', AB_MAX_ORDER), AB_MAX_ORDER))
     if method == 'explicit_adams':
         if 'implicit' in options:
             raise TypeError("__init__() got multiple values for keyword argument 'implicit'")
@@ -311,6 +324,56 @@ def ab_weights(order):
     return _AB_WEIGHTS[order]
 
 
+# fixed_adams: the predictor above, corrected by the Adams-Moulton formula over the same history and the evaluation at the step's end
+# (fixed_adams.py:184-200).  With `order` evaluations held the corrector has order + 1 points t_{n+1}, t_n, ..:
+#   mu_i = integral over [0, 1] of prod_{j != i, j <= order} (u + j - 1) / (j - i) du
+# held like the Bashforth set as integers over one divisor; mu_0 multiplies the evaluation that is iterated on.
+ABM_MAX_ITERS = 4                  # fixed_adams.py:148
+
+
+def moulton_rationals(order):
+    """(mu_0 .. mu_order) as fractions.Fraction: the Adams-Moulton formula over order + 1 points, the point at the step's END first"""
+    mus = []
+    for i in range(order + 1):
+        poly, den = [fractions.Fraction(1)], 1               # prod_{j != i} (u + j - 1), lowest power first
+        for j in range(order + 1):
+            if j == i:
+                continue
+            poly = [(poly[m - 1] if m else 0) + (j - 1) * (poly[m] if m < len(poly) else 0) for m in range(len(poly) + 1)]
+            den *= j - i
+        mus.append(sum(c / (m + 1) for m, c in enumerate(poly)) / den)
+    return mus
+
+
+def moulton_integers(order):
+    """([m_0 .. m_order], div): mu_i = m_i / div with div the least common denominator"""
+    mus = moulton_rationals(order)
+    div = 1
+    for m in mus:
+        div = div * m.denominator // math.gcd(div, m.denominator)
+    return [int(m * div) for m in mus], div
+
+
+_AM_WEIGHTS = {}
+
+
+def am_weights(order):
+    """(the double m_0 / div that multiplies the iterated evaluation - fixed_adams.py:193 -, [float32((1 / div) * m_i) for i >= 1] - the
+    weights of the history in `delta`, :188), for a step that holds `order` evaluations"""
+    if order not in _AM_WEIGHTS:
+        ms, div = moulton_integers(order)
+        _AM_WEIGHTS[order] = (ms[0] / div, [f32((1 / div) * m) for m in ms[1:]])
+    return _AM_WEIGHTS[order]
+
+
+def abm_lead(dt, order):
+    """`dt * (m_0 / div)` as torch forms it on the float32 0-d tensor dt: the double is rounded to float32, then one float32 product"""
+    return f32(f32(dt) * f32(am_weights(order)[0]))
+
+
+NOT_CONVERGED = 'Warning: Functional iteration did not converge. Solution may be incorrect.'        # fixed_adams.py:198
+
+
 def ab_adjoint_terms(i, dts, max_order):
     """Which adjoints the gradient of evaluation f_i = F(y_i) of an explicit_adams solve gathers from, and with which weights:
     [(j, c), ...] such that gf_i = sum c * lam_j, lam_j the full adjoint of the state y_j, in the order the sum is taken (j rising).
@@ -338,9 +401,11 @@ def _rk4_step(ops, func, targ, t0, dt, y, k1):
     return tuple(ops.fixed_stage(5, y_, a, b, c, d, dt=dt) for y_, a, b, c, d in zip(y, k1, k2, k3, k4))
 
 
-def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None, max_order=AB_MAX_ORDER):
+def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None, max_order=AB_MAX_ORDER, max_iters=ABM_MAX_ITERS, rtol=1e-7,
+                    atol=1e-9, step_log=None):
     """solvers.py:79-99: the default grid (grid == t), or the grid of `plan` (fixed_plan: the step_size option).  Returns a list (per
-    tick) of tuples.  max_order: explicit_adams only (fixed_options)."""
+    tick) of tuples.  max_order: explicit_adams and fixed_adams (fixed_options); max_iters, rtol, atol: fixed_adams.  step_log (a list):
+    fixed_adams appends (corrector iterations, converged) per grid step - (0, True) for a warm-up step - and ('nfe', evaluations)."""
     assert_increasing(t)
     dtype = y0[0].dtype
     if plan is None:
@@ -349,7 +414,8 @@ def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None, max_o
     targ = TimeArg(y0[0], autonomous)
     sol = [y0]
     y = y0
-    if method == 'explicit_adams':
+    nfe = 0
+    if method in ('explicit_adams', 'fixed_adams'):
         # fixed_adams.py:163: the history, newest first.  (max_order 1: nothing is kept and the first step fails on prev_f[0];
         # below 1 the deque itself refuses - both as in the reference)
         prev_f = collections.deque(maxlen=max_order - 1)
@@ -372,9 +438,43 @@ def integrate_fixed(ops, func, y0, t, method, autonomous=False, plan=None, max_o
             else:
                 # y + dt * (((0 + a_0 f_n) + a_1 f_{n-1}) + ...): one pass over the history (ndcn_ab_step_f32)
                 y = tuple(ops.ab_step(y_, [f[q] for f in prev_f], ab_weights(order), dt) for q, y_ in enumerate(y))
+        elif method == 'fixed_adams':
+            prev_f.appendleft(func(targ(t0), y))          # fixed_adams.py:166-172
+            order = min(len(prev_f), max_order - 1)
+            iters, converged = 0, True
+            if order < AB_MIN_ORDER - 1:
+                y = _rk4_step(ops, func, targ, t0, dt, y, prev_f[0])
+                nfe += 4
+            else:
+                # one pass over the history: dy = dt * sum a_i f_i, delta = dt * sum m_{i+1} f_i and the iterate u = y + dy (:180-188)
+                lead, am = am_weights(order)
+                pred = [ops.abm_predict(y_, [f[q] for f in prev_f], ab_weights(order), am, dt) for q, y_ in enumerate(y)]
+                dy, delta, u = [p[0] for p in pred], [p[1] for p in pred], tuple(p[2] for p in pred)
+                c0 = abm_lead(dt, order)
+                converged = False
+                for _ in range(max_iters):                # :190-196
+                    f = func(targ(t0 + dt), u)
+                    res = [ops.abm_correct(f_, dl_, y_, dy_, c0, rtol, atol) for f_, dl_, y_, dy_ in zip(f, delta, y, dy)]
+                    dy, u = [r[0] for r in res], tuple(r[1] for r in res)
+                    iters += 1
+                    converged = all(r[2] == 0 for r in res)
+                    if converged:
+                        break
+                nfe += 1 + iters
+                if not converged:
+                    print(NOT_CONVERGED, file=sys.stderr)
+                    prev_f.pop()                          # :199: the OLDEST evaluation leaves (the corrector's never enters, :200)
+                if iters == 0:
+                    # :200 reads the corrector's evaluation, which a loop that never ran has not assigned
+                    raise UnboundLocalError("local variable 'f' referenced before assignment")
+                y = u                                     # solvers.py:92: y + dy, formed by the last corrector pass
+            if step_log is not None:
+                step_log.append((iters, converged))
         else:
             y = _rk4_step(ops, func, targ, t0, dt, y, func(targ(t0), y))
         emit_ticks(ops, plan, i, y, sol)
+    if method == 'fixed_adams' and step_log is not None:
+        step_log.append(('nfe', nfe))
     return sol
 
 

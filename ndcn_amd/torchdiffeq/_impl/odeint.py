@@ -13,6 +13,7 @@ Host tensors are refused: there is no CPU fallback.
 import collections
 import ctypes
 import os
+import sys
 import weakref
 
 import torch
@@ -102,9 +103,10 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
 
     Same signature, defaults, return layout and exceptions as the reference (odeint.py:20-76):
     TypeError for non-float y0 / t, ValueError for `options` without `method`, KeyError for an unknown
-    method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / explicit_adams / euler / midpoint / rk4 are
-    provided (tsit5 / fixed_adams raise NotImplementedError); the state must be float32 on a ROCm device;
-    `step_log` (a list) optionally receives the dopri5 per-attempt log.  Returns (solution, decoded): decoded is True when
+    method, AssertionError for a non-monotone t.  Deviations: dopri5 / adams / explicit_adams / fixed_adams / euler / midpoint / rk4 are
+    provided (tsit5 raises NotImplementedError); the state must be float32 on a ROCm device;
+    `step_log` (a list) optionally receives the dopri5 per-attempt log - for fixed_adams one (corrector iterations, converged) pair per
+    grid step and ('nfe', evaluations).  Returns (solution, decoded): decoded is True when
     `readout` was applied inside the solve (the device-resident inference path; the fixed-grid training nodes), else the solution
     is the hidden one.
 
@@ -121,6 +123,17 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     (ndcn_solve_explicit_adams_f32: nothing is read back); any other callable, a tuple state or a gradient steps through core.py -
     except that with NDCN_ADAMS_TRAIN=1 a plain ODEFunc under a gradient (no active dropout, no no_graph / no_control, `t` without grad)
     trains on one autograd node per solve (fixed_train._ExplicitAdamsSolve), `readout` inside it as for rk4.
+
+    fixed_adams is the reference's AdamsBashforthMoulton (fixed_adams.py:151-205): the same history, warm-up and predictor, then the
+    Adams-Moulton corrector over the history and the evaluation at the step's end, iterated up to options={'max_iters': n} (default 4)
+    times until EVERY element of the increment satisfies |dy_old - dy_new| < atol + rtol * max(|dy_old|, |dy_new|) - `rtol` and `atol`
+    are this function's arguments (naming them in `options` is the reference's TypeError).  A step that does not converge writes the
+    reference's warning line to stderr and drops the oldest evaluation of its history.  options={'implicit': False} is explicit_adams,
+    bit for bit.  Without a gradient a plain ODEFunc runs inside the library (ndcn_solve_fixed_adams_f32: one 8-byte read-back per
+    corrector iteration, the host decides whether to iterate again); any other callable, a tuple state, dropout, no_graph / no_control
+    or a gradient steps through core.py over ndcn_abm_predict_f32 / ndcn_abm_correct_f32 - under a gradient the iteration counts are
+    constants of the graph.  A host state is refused here, where unsupported methods are, with an exception that is both NdcnHipError
+    and NotImplementedError.
     """
     user_func = func
     t_user = t
@@ -135,12 +148,20 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         method = 'dopri5'
     if method in core.UNSUPPORTED:
         raise NotImplementedError('method %r of the reference is outside the accelerated path '
-                                  '(dopri5, adams, explicit_adams, euler, midpoint, rk4 are provided)' % method)
+                                  '(dopri5, adams, explicit_adams, fixed_adams, euler, midpoint, rk4 are provided)' % method)
+    if method == 'fixed_adams':
+        for y in y0:
+            _lib.require_device(y, 'state y0', error=_lib.NdcnHostStateError)
     method = SOLVERS[method]                     # KeyError for an unknown name, as the reference's dict lookup
 
     plan = None
+    max_iters = core.ABM_MAX_ITERS
     if method in core.GRID_METHODS:
         options = core.fixed_options(method, options)       # solvers.py:39-53: warns about unknown names, ValueError for a grid_constructor
+        if method == 'fixed_adams':
+            max_iters = options.pop('max_iters')
+            if not options.pop('implicit'):                 # fixed_adams.py:185: the corrector is skipped - AdamsBashforth's step
+                method = 'explicit_adams'
         step_size = options.get('step_size')                # (what is left: the step size, explicit_adams' max_order)
         if step_size is not None:
             if t_user.requires_grad:
@@ -183,7 +204,15 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
             from . import tape
             return tape.solve(user_func, y0[0], t, rtol, atol, options, step_log), False
         sol = odeint_with_grad(func, y0, t, rtol, atol, method, options, autonomous=_autonomous(user_func),
-                               step_log=step_log, odefunc=user_func if plain else None, plan=plan)
+                               step_log=step_log, odefunc=user_func if plain else None, plan=plan, max_iters=max_iters)
+    elif method == 'fixed_adams':
+        out = None
+        if _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
+            out = _fixed_adams_solve(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log)
+        if out is not None:
+            return out, False
+        sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan, max_order=options['max_order'],
+                                   max_iters=max_iters, rtol=rtol, atol=atol, step_log=step_log)
     elif method == 'explicit_adams':
         out = None
         if _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
@@ -455,6 +484,55 @@ def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
                                                      offs, n_emit, max_order, _lib.ptr(out[1:]) if n_emit else None, _lib.ptr(workspace),
                                                      nbytes, _lib.stream_ptr()))
     # (the workspace goes back to torch's stream-ordered allocator: a later allocation on this stream is ordered behind the solve)
+    return out
+
+
+def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None):
+    """The whole fixed_adams solve of a plain ODEFunc inside the library (ndcn_solve_fixed_adams_f32: the launches of the explicit solve,
+    then per step one ndcn_abm_predict_f32 and up to max_iters x (right-hand side + ndcn_abm_correct_f32 + an 8-byte read-back)).  The
+    reference's warning line is written here, once per step the library reports as not converged.  None where the entry point has no
+    form: as _explicit_adams_solve, and a max_iters or tolerances that are not plain numbers (the generic branch fails on them as the
+    reference does)."""
+    if odefunc.no_graph or odefunc.no_control or max_order < 2:
+        return None
+    if type(max_iters) is not int or max_iters < 1 or not all(isinstance(v, (int, float)) for v in (rtol, atol)):
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, view, flags = op
+    core.assert_increasing(t)
+    if plan is None:
+        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    lib = _lib.load()
+    H = odefunc.hidden_size
+    n_ticks = len(plan.t)
+    out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+    out[0].copy_(y0)
+    dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
+    if n_steps == 0 or y0.numel() == 0:
+        if step_log is not None:
+            step_log.extend([(0, True)] * n_steps + [('nfe', 0)])
+        return out
+    csr.ensure_plans(H)
+    view = csr.view_ref()
+    W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
+    b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
+    nbytes = int(lib.ndcn_fixed_adams_workspace_bytes(y0.shape[0], H, max_order))
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
+    iters, conv = (ctypes.c_int * n_steps)(), (ctypes.c_int * n_steps)()
+    with torch.cuda.device(y0.device):
+        _lib.check(lib.ndcn_solve_fixed_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
+                                                  offs, n_emit, max_order, float(rtol), float(atol), max_iters,
+                                                  _lib.ptr(out[1:]) if n_emit else None, iters, conv, _lib.ptr(workspace), nbytes,
+                                                  _lib.stream_ptr()))
+    for c in conv:
+        if not c:
+            print(core.NOT_CONVERGED, file=sys.stderr)      # fixed_adams.py:198
+    if step_log is not None:
+        warm = sum(1 for i, c in zip(iters, conv) if i == 0)
+        step_log.extend((int(i), bool(c)) for i, c in zip(iters, conv))
+        step_log.append(('nfe', n_steps + 3 * warm + sum(iters)))
     return out
 
 

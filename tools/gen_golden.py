@@ -22,6 +22,7 @@ Fixture families:
   G13 adams_*.npz     odeint adams + per-attempt step log    torchdiffeq/_impl/adams.py:62-170
   G14 substep_*.npz   fixed grid, options={'step_size': h}   torchdiffeq/_impl/solvers.py:55-68,79-108
   G15 bashforth_*.npz odeint explicit_adams + nfe            torchdiffeq/_impl/fixed_adams.py:151-211
+  G16 moulton_*.npz   odeint fixed_adams + iterations, flags  torchdiffeq/_impl/fixed_adams.py:151-205
 """
 import os
 import sys
@@ -673,7 +674,92 @@ def gen_bashforth():
              no_control=int(bool(fkw)), **{'opt_' + k: v for k, v in opts.items()}, **csr_of(OM))
 
 
+# ----------------------------------------------------------------------------- G16
+def gen_moulton():
+    """method='fixed_adams' (AdamsBashforthMoulton, fixed_adams.py:151-205) over the NDCN ODEFunc on the 6 x 6 lattice at H = 8, with the
+    evaluation count and, per grid step, the corrector iterations run (0: an RK4 warm-up step) and whether the step converged.  (Names
+    start with moulton_: no glob of the existing tests - fixed_*, adams_*, bashforth_* - picks them up.)  The per-step record comes from
+    the reference's own convergence test, wrapped while the solve runs.  Every recorded decision must have a margin, so that a last-bit
+    difference between this CPU and a GPU cannot flip it: a converged iteration has max(err / tol) <= 0.5, a failed one an element with
+    err >= 2 tol (or tol == 0); the step sizes and tolerances below were chosen until the reference alone satisfies that."""
+    import torchdiffeq._impl.fixed_adams as ref_fa
+    _, OM = grid_operator(6)
+    OMs = ref_u.torch_sensor_to_torch_sparse_tensor(OM)
+    h = 1.0 / 128
+    lin = lambda n, dt: torch.linspace(0., n * dt, n + 1)
+    cases = {
+        # the drivers' tolerances (dynamics.py: rtol 0.01, atol 0.001): every step converges at the first iteration
+        'default': (lin(18, 0.01), 1e-2, 1e-3, {}),
+        'iterate': (lin(16, MOULTON_ITERATE[0]), MOULTON_ITERATE[1], MOULTON_ITERATE[2], {}),     # two or more iterations on some steps
+        'never': (lin(16, 0.01), 0.0, 0.0, {}),                                   # err < 0 is false: max_iters iterations, history stays at 3
+        'one_iter': (lin(16, MOULTON_ONE[0]), MOULTON_ONE[1], MOULTON_ONE[2], {'max_iters': 1}),
+        'order4': (lin(16, 0.01), 1e-2, 1e-3, {'max_order': 4}),
+        'stepsize': (torch.tensor([0., 1.5 * h, 4 * h, 4.3 * h, 4.6 * h, 9 * h, 14 * h]), 1e-2, 1e-3, {'step_size': h}),
+        'warmup': (torch.tensor([0., 0.01, 0.02]), 1e-2, 1e-3, {}),
+    }
+    for name, (t, rtol, atol, opts) in cases.items():
+        f, x = make_func(8, OMs, 53)
+        cf = CountingFunc(f)
+        calls, steps = [], []
+        orig_conv, orig_step = ref_fa._has_converged, ref_fa.AdamsBashforthMoulton.step_func
+
+        def conv(y0, y1, rt, at):
+            out = orig_conv(y0, y1, rt, at)
+            tol = at + rt * torch.max(torch.abs(y0[0]), torch.abs(y1[0]))
+            err = torch.abs(y0[0] - y1[0])
+            if bool(out):
+                assert float((err / tol).max()) <= 0.5, (name, len(steps), float((err / tol).max()))
+            else:
+                assert bool((tol == 0).all()) or bool((err >= 2 * tol).any()), (name, len(steps))
+            calls.append(bool(out))
+            return out
+
+        def step(self, func, tt, dt, y):
+            n0 = len(calls)
+            dy = orig_step(self, func, tt, dt, y)
+            steps.append((len(calls) - n0, all(calls[n0:][-1:])))
+            return dy
+
+        ref_fa._has_converged, ref_fa.AdamsBashforthMoulton.step_func = conv, step
+        err_text = io.StringIO()
+        try:
+            with torch.no_grad(), contextlib.redirect_stderr(err_text):
+                y = ref_ode.odeint(cf, x, t, rtol=rtol, atol=atol, method='fixed_adams', options=dict(opts) if opts else None)
+        finally:
+            ref_fa._has_converged, ref_fa.AdamsBashforthMoulton.step_func = orig_conv, orig_step
+        n_steps = len(t) - 1
+        if 'step_size' in opts:
+            grid, ok = ref_step_grid(t, opts['step_size'])
+            assert ok
+            n_steps = len(grid) - 1
+            assert n_steps >= 14
+        iters = np.array([s[0] for s in steps], dtype=np.int32)
+        flags = np.array([int(s[1]) for s in steps], dtype=np.int32)
+        assert len(steps) == n_steps
+        assert bool(torch.isfinite(y).all()) and float(y.abs().max()) <= 10 * float(x.abs().max()), name
+        assert cf.nfe == n_steps + 6 + int(iters.sum()), (name, cf.nfe, n_steps, iters)
+        n_warn = err_text.getvalue().count('Functional iteration did not converge')
+        assert n_warn == int((flags == 0).sum())
+        print('moulton_%-9s iterations %s  warnings %d' % (name, iters.tolist(), n_warn))
+        if name in ('default', 'order4', 'stepsize'):
+            assert iters[2:].tolist() == [1] * (n_steps - 2) and flags.all()
+        if name == 'iterate':
+            assert iters.max() >= 2 and flags.all()
+        if name == 'never':
+            assert iters[2:].tolist() == [4] * (n_steps - 2) and not flags[2:].any()
+        if name == 'one_iter':
+            assert iters.max() == 1 and not flags.all() and flags[2:].any()
+        save('moulton_%s' % name, x0=x, t=t, W=f.wt.weight, b=f.wt.bias, traj=y, nfe=cf.nfe, n_steps=n_steps, no_control=0,
+             rtol=np.float64(rtol), atol=np.float64(atol), iters=iters, converged=flags, n_warnings=n_warn,
+             **{'opt_' + k: v for k, v in opts.items()}, **csr_of(OM))
+
+
+# (dt, rtol, atol) of moulton_iterate and of moulton_one_iter: found by scanning the reference for decisions with a margin (gen_moulton)
+MOULTON_ITERATE = (0.015, 1.2e-4, 2.1e-5)
+MOULTON_ONE = (0.02, 3e-4, 3e-6)
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep', 'bashforth']
+    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep', 'bashforth', 'moulton']
     for w in which:
         globals()['gen_' + w]()
