@@ -38,6 +38,7 @@ extern "C" {
 #define NDCN_EUNDERFLOW -4   /* solver: t0 + dt <= t0     (dopri5.py:100 assertion)              */
 #define NDCN_EMAXSTEPS  -5   /* solver: max_num_steps exceeded (dopri5.py:89 assertion)          */
 #define NDCN_ESTATE     -6   /* solver handle used out of order                                   */
+#define NDCN_ECAPACITY  -7   /* ndcn_fixed_adams_train_f32: the record of the corrector's evaluations is full */
 
 /* rhs / spmm flags */
 #define NDCN_F_RELU        1u   /* apply relu to the result            (neural_dynamics.py:36)   */
@@ -901,6 +902,40 @@ NDCN_API int ndcn_solve_fixed_adams_f32(const ndcn_csr *A, const float *W, const
                                         const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
                                         const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol, int max_iters,
                                         float *out, int *h_iters, int *h_converged, void *workspace, int64_t workspace_bytes, void *stream);
+/* fixed_adams under a gradient (three more calls added to ABI 29: no existing declaration changes).
+ * ndcn_fixed_adams_train_f32: ndcn_solve_fixed_adams_f32 - the same loop, launches, checks, read-backs, h_iters / h_converged and bits
+ *   in `out` - that KEEPS what a reverse sweep needs in records the caller owns, in place of the history ring, the two state panels and
+ *   the panel of the corrector's evaluation:
+ *     rec_f [n_steps panels]   f_i, the evaluation grid step i starts with (as ndcn_explicit_adams_train_f32)
+ *     rec_y [n_steps panels]   the state after step i; may be `out` itself on the default grid (tick j after step j)
+ *     rec_u, rec_c [cap panels each]   per CORRECTOR evaluation, in the order they run: the iterate u_{r-1} it reads and F_r = func(u_{r-1})
+ *     h_slot [n_steps]         HOST, written: the first slot of step i; the step uses the slots h_slot[i] .. h_slot[i] + h_iters[i] - 1
+ *                              (a warm-up step uses none).  u_0 of a step is the predictor's u; u_R is the state in rec_y.
+ *   The predictor writes u_0 into its slot, every evaluation writes into its slot, the corrector pass writes the new iterate into the
+ *   state's panel: a step that iterates once copies nothing; each further iteration copies one panel (the iterate into its slot).
+ *   The number of iterations is not known in advance.  When an evaluation would need slot `cap`, the call returns NDCN_ECAPACITY
+ *   before anything is enqueued for it: no panel at or past `cap` is touched; the earlier steps' launches run to their end inside the
+ *   caller's panels; `out`, the records and the host arrays are then incomplete and the caller runs the solve again with
+ *   cap = n_steps * max_iters, which always suffices (cap = n_steps is the natural first attempt: one iteration per step).
+ *     workspace                ndcn_fixed_adams_train_workspace_bytes(n_rows, H) bytes, 256-byte aligned: three RK4 stage panels, the
+ *                              stage input, dy, delta, the counter and the scratch of ndcn_rhs_f32 - no ring, no state pair
+ * ndcn_abm_adjoint_f32, the gradient of one evaluation gathered from the adjoints of the <= 11 predictor-corrector steps that held it -
+ *   P_q the adjoint of step q's predictor increment, D_q that of the explicit part of its corrector:
+ *     out = [base +] (((((0 + cp[0] P[0]) + cd[0] D[0]) + cp[1] P[1]) + cd[1] D[1]) + ...)
+ *   every product and every sum rounded to fp32 on its own, no contraction, the sum started from an exact zero and the base added last:
+ *   the chain of ndcn_ab_adjoint_f32 over the 2 n interleaved panels, n = 1..11 pairs, in ONE pass (up to 22 panels and the base read,
+ *   every load of an item issued before its first use).  h_p, h_d: HOST arrays of n device panels; h_cp, h_cd: HOST arrays of their
+ *   coefficients (fl32(dt * a), fl32(dt * m), formed by the caller).  P[q] and D[q] may be the same panel.  NDCN_EINVAL - before any
+ *   launch - for any other n, a null panel, or `out` equal to a term (out == base is allowed).  Any alignment, any n_elem >= 0, the lanes
+ *   of ndcn_ab_adjoint_f32.                                                                                                          */
+NDCN_API int ndcn_abm_adjoint_f32(float *out, const float *base, const float *const *h_p, const float *h_cp, const float *const *h_d,
+                                  const float *h_cd, int n, int64_t n_elem, void *stream);
+NDCN_API int64_t ndcn_fixed_adams_train_workspace_bytes(int64_t n_rows, int H);
+NDCN_API int ndcn_fixed_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                        const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                        const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol, int max_iters,
+                                        float *out, int *h_iters, int *h_converged, float *rec_f, float *rec_y, float *rec_u, float *rec_c,
+                                        int64_t cap, int64_t *h_slot, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): when enabled, every kernel launch made by this library is

@@ -39,6 +39,7 @@ READOUT_FUSED, READOUT_STAGED, READOUT_FIXED, READOUT_NARROW = 1, 2, 4, 8
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6
+ECAPACITY = -7            # ndcn_fixed_adams_train_f32: the record of the corrector's evaluations is full (run again with the full cap)
 
 F_RELU, F_NO_GRAPH, F_NO_CONTROL, F_PACKED, F_ACCUM = 1, 2, 4, 8, 16
 RK_NONE, RK_COMBINE, RK_ERROR, RK_RK4 = 0, 1, 2, 3
@@ -283,6 +284,11 @@ SIGNATURES = {
     'ndcn_explicit_adams_train_workspace_bytes': (_L, [_L, _I]),
     'ndcn_explicit_adams_train_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
                                            ctypes.POINTER(_F), _L, _I, _P, _P, _P, _P, _L, _P]),
+    'ndcn_abm_adjoint_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _L, _P]),
+    'ndcn_fixed_adams_train_workspace_bytes': (_L, [_L, _I]),
+    'ndcn_fixed_adams_train_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
+                                        ctypes.POINTER(_F), _L, _I, _F, _F, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _P, _P, _P,
+                                        _L, ctypes.POINTER(_L), _P, _L, _P]),
     'ndcn_row_l1_normalize_f32': (_I, [_P, _P, _L, _I, _P]),
     'ndcn_row_l1_normalize_bwd_f32': (_I, [_P, _P, _P, _L, _I, _P]),
     'ndcn_gene_rhs_f32': (_I, [_CSR, _P, _P, _F, _F, _F, _P]),

@@ -8,6 +8,8 @@
 //                                    step; one 8-byte read-back per iteration - the host decides whether to iterate again
 //   ndcn_explicit_adams_train_f32    the same loop (adams_run) writing every evaluation and every state into a caller-owned record: the
 //                                    forward pass of training (the reverse sweep: adams_bwd.hip, fixed_train.py)
+//   ndcn_fixed_adams_train_f32       the corrector loop with that record AND, per corrector evaluation, the pair (iterate, evaluation) in
+//                                    caller-owned slots handed out in order - NDCN_ECAPACITY before a slot past `cap` is touched
 //
 // Rounding follows the reference term by term (fixed_adams.py:182, misc.py:22-25, solvers.py:92): p_i = a_i * f_i, s = ((0 + p_0) + p_1)
 // + ..., dy = dt * s, y1 = y + dy - every product and sum rounded on its own.  FP contraction is therefore switched OFF for this
@@ -224,6 +226,11 @@ struct Corrector {
     float rtol, atol;
     int max_iters;
     int *h_iters, *h_converged;
+    // with a record (training): corrector evaluation r of a step reads its iterate u_{r-1} from slot s of rec_u and writes F_r to slot s
+    // of rec_c, s = h_slot[step] + r - 1; `cap` slots each, handed out in order
+    float *rec_u = nullptr, *rec_c = nullptr;
+    int64_t cap = 0;
+    int64_t *h_slot = nullptr;
 };
 
 // an 8-byte pinned mirror of the device counter, owned by one solve
@@ -239,6 +246,7 @@ inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 constexpr int kStagePanels = 3 + 1;
 inline int solve_panels(int max_order) { return (max_order - 1) + kStagePanels + 2; }
 constexpr int kCorrectorPanels = 3;    // dy, delta, the corrector's evaluation (the iterate is the new state's panel)
+constexpr int kCorrectorRecPanels = 2; // with a record: dy and delta (iterates and evaluations stand in the caller's slots)
 constexpr size_t kCounterBytes = 256;
 
 inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
@@ -247,7 +255,15 @@ inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
     return (int64_t)((size_t)panels * panel + up256((size_t)(wb > 0 ? wb : 0)));
 }
 
-#define ADAMS_ARG(cond, msg)                                  \
+// the record of the corrector's evaluations is full: nothing was enqueued for the slot that does not exist; what earlier steps enqueued
+// runs to its end inside the caller's panels.  h_iters / h_converged / h_slot from `step` on are not written.
+int slots_exhausted(const char *who, int64_t step, int64_t cap) {
+    set_error("%s: grid step %lld needs more than the cap = %lld corrector evaluations of rec_u / rec_c; run again with cap = n_steps * max_iters",
+              who, (long long)step, (long long)cap);
+    return NDCN_ECAPACITY;
+}
+
+#define ADAMS_ARG(cond, msg)                                 \
     do {                                                      \
         if (!(cond)) {                                        \
             set_error("%s: %s", who, msg);                    \
@@ -259,7 +275,10 @@ inline int64_t workspace_need(int64_t n_rows, int H, int panels) {
 // messages).  Without a record (rec_f == nullptr) the evaluations live in a ring of max_order - 1 workspace panels and the state
 // alternates between two more, or stands in the caller's tick panel.  With one, evaluation i is written to panel i of rec_f and the
 // state after step i to panel i of rec_y - the history of a step is then the panels i, i - 1, ... of rec_f and nothing else is kept:
-// the same launches on the same values, only the addresses differ.
+// the same launches on the same values, only the addresses differ.  A corrector with a record (pc->rec_u) keeps every corrector evaluation
+// too: the predictor writes the first iterate u_0 straight into the step's first slot of rec_u, evaluation r writes F_r into its slot of
+// rec_c, abm_correct writes the new iterate into the state's panel, and only when another iteration follows is that panel copied into the
+// next slot of rec_u - a step that iterates once copies nothing.  A slot past pc->cap: NDCN_ECAPACITY, before anything is enqueued for it.
 int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
               int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off, int64_t n_ticks, int max_order,
               float *out, float *rec_f, float *rec_y, void *workspace, int64_t workspace_bytes, hipStream_t st,
@@ -275,9 +294,12 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
         ADAMS_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
     const bool rec = rec_f != nullptr;
     ADAMS_ARG(!rec || n_steps == 0 || rec_y, "the record of the states is missing");
-    ADAMS_ARG(!pc || (!rec && pc->max_iters >= 1 && (n_steps == 0 || (pc->h_iters && pc->h_converged))),
+    ADAMS_ARG(!pc || (pc->max_iters >= 1 && (n_steps == 0 || (pc->h_iters && pc->h_converged))),
               "the corrector needs max_iters >= 1 and the two per-step host arrays");
-    const int64_t need = workspace_need(A->n_rows, H, rec ? kStagePanels : solve_panels(max_order) + (pc ? kCorrectorPanels : 0)) +
+    ADAMS_ARG(!pc || !rec || n_steps == 0 || (pc->rec_u && pc->rec_c && pc->h_slot && pc->cap >= 0),
+              "a corrector with a record needs rec_u, rec_c, the per-step slot array and cap >= 0");
+    const int64_t need = workspace_need(A->n_rows, H, rec ? kStagePanels + (pc ? kCorrectorRecPanels : 0)
+                                                          : solve_panels(max_order) + (pc ? kCorrectorPanels : 0)) +
                          (pc ? (int64_t)kCounterBytes : 0);
     ADAMS_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 && workspace_bytes >= need,
               "workspace of the size its host function returns, 256-byte aligned, required");
@@ -298,7 +320,8 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
     unsigned long long *d_count = nullptr;
     PinnedCount h_count;
     if (pc) {
-        dy = take(); delta = take(); fc = take();
+        dy = take(); delta = take();
+        if (!rec) fc = take();
         d_count = reinterpret_cast<unsigned long long *>(base);
         base += kCounterBytes;
         NDCN_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_count.p), sizeof(unsigned long long), hipHostMallocDefault));
@@ -322,6 +345,7 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
     const float *y = y0;
     int held = 0, newest = -1;                                 // evaluations held; the ring slot of the newest
     int64_t j = 0;
+    int64_t next_slot = 0;                                     // of rec_u / rec_c
     std::vector<float *> outs;
     std::vector<int> zeros;
     for (int64_t i = 0; i < n_steps; ++i) {
@@ -349,18 +373,35 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
             if ((rc = eval(ytmp, k4))) return rc;
             if ((rc = fixed_stage_f32(5, dst, y, f_new, k2, k3, k4, dt, n, st))) return rc;
             if (pc) { pc->h_iters[i] = 0; pc->h_converged[i] = 1; }
+            if (pc && rec) pc->h_slot[i] = next_slot;          // (a warm-up step takes no slot)
         } else if (pc) {
             // fixed_adams.py:180-200: predictor and the corrector's explicit part in one pass, the iterate in the new state's panel;
             // then evaluate / correct / read the count back until no element fails or max_iters passes have run
             const float *f[kAbMaxTerms];
-            for (int q = 0; q < order; ++q) f[q] = ring[((newest - q) % ring_n + ring_n) % ring_n];
-            if ((rc = abm_predict_f32(dy, delta, dst, y, f, weights[order], moulton[order], order, dt, n, st))) return rc;
+            for (int q = 0; q < order; ++q) f[q] = rec ? rec_f + (size_t)(i - q) * (size_t)n : ring[((newest - q) % ring_n + ring_n) % ring_n];
+            if (rec) {
+                pc->h_slot[i] = next_slot;
+                if (next_slot >= pc->cap) return slots_exhausted(who, i, pc->cap);
+            }
+            // the iterate the next evaluation reads: the new state's panel, with a record the slot of that evaluation
+            float *u = rec ? pc->rec_u + (size_t)next_slot * (size_t)n : dst;
+            if ((rc = abm_predict_f32(dy, delta, u, y, f, weights[order], moulton[order], order, dt, n, st))) return rc;
             const float c0 = dt * (float)lead[order];          // torch: the double becomes a float32 scalar, then one float32 product
             int its = 0;
             bool converged = false;
             while (its < pc->max_iters && !converged) {
-                if ((rc = eval(dst, fc))) return rc;
-                if ((rc = abm_correct_f32(dy, dst, fc, delta, y, c0, pc->rtol, pc->atol, n, d_count, st))) return rc;
+                float *fr = fc;
+                if (rec) {
+                    if (its > 0) {                             // another iteration: the iterate abm_correct left in dst enters its slot
+                        if (next_slot >= pc->cap) return slots_exhausted(who, i, pc->cap);
+                        u = pc->rec_u + (size_t)next_slot * (size_t)n;
+                        NDCN_HIP(hipMemcpyAsync(u, dst, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+                    }
+                    fr = pc->rec_c + (size_t)next_slot * (size_t)n;
+                    ++next_slot;
+                }
+                if ((rc = eval(u, fr))) return rc;
+                if ((rc = abm_correct_f32(dy, dst, fr, delta, y, c0, pc->rtol, pc->atol, n, d_count, st))) return rc;
                 NDCN_HIP(hipMemcpyAsync(h_count.p, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
                 NDCN_HIP(hipStreamSynchronize(st));
                 ++its;
@@ -440,6 +481,26 @@ int ndcn_solve_fixed_adams_f32(const ndcn_csr *A, const float *W, const float *b
     const Corrector pc = {rtol, atol, max_iters, h_iters, h_converged};
     return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
                      nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &pc);
+}
+
+int64_t ndcn_fixed_adams_train_workspace_bytes(int64_t n_rows, int H) {
+    if (n_rows < 0 || H <= 0) return NDCN_EINVAL;
+    return workspace_need(n_rows, H, kStagePanels + kCorrectorRecPanels) + (int64_t)kCounterBytes;
+}
+
+int ndcn_fixed_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
+                               int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off,
+                               int64_t n_ticks, int max_order, float rtol, float atol, int max_iters, float *out, int *h_iters,
+                               int *h_converged, float *rec_f, float *rec_y, float *rec_u, float *rec_c, int64_t cap, int64_t *h_slot,
+                               void *workspace, int64_t workspace_bytes, void *stream) {
+    if (n_steps > 0 && (!rec_f || !rec_u || !rec_c || !h_slot || cap < 0)) {
+        set_error("%s: the records (rec_f, rec_u, rec_c), the slot array and cap >= 0 are required", __func__);
+        return NDCN_EINVAL;
+    }
+    Corrector pc = {rtol, atol, max_iters, h_iters, h_converged};
+    pc.rec_u = rec_u; pc.rec_c = rec_c; pc.cap = cap; pc.h_slot = h_slot;
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, rec_f, rec_y,
+                     workspace, workspace_bytes, static_cast<hipStream_t>(stream), &pc);
 }
 
 int ndcn_explicit_adams_train_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,

@@ -254,6 +254,10 @@ int ab_grid(int64_t items);
 // adams_bwd.hip: the gradient of one evaluation gathered from the adjoints of the Adams-Bashforth steps that used it,
 // out = [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), n_terms = 1..11, base nullable and added last; out may be base, never one of h_g
 int ab_adjoint_f32(float *out, const float *base, const float *const *h_g, const float *h_c, int n_terms, int64_t n, hipStream_t st);
+// ... and of fixed_adams, from pairs of adjoints (predictor, explicit part of the corrector):
+// out = [base +] ((((0 + cp_0 P_0) + cd_0 D_0) + cp_1 P_1) + cd_1 D_1 ...), n_pairs = 1..11; P_q may be D_q; out may be base, never a term
+int abm_adjoint_f32(float *out, const float *base, const float *const *h_p, const float *h_cp, const float *const *h_d, const float *h_cd,
+                    int n_pairs, int64_t n, hipStream_t st);
 // adams_pc.hip: the predictor and one corrector pass of fixed_adams (fixed_adams.py:179-194).  predict: dy = dt * sum a_i f_i,
 // delta = dt * sum m_i f_i, u = y + dy in one pass over the n_terms = 3..11 history panels (u may be y; no output may be a history panel).
 // correct: dy <- c0 * f + delta in place, u = y + dy, *d_count = the elements that fail |old - new| < atol + rtol * max(|old|, |new|)

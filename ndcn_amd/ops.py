@@ -1062,6 +1062,23 @@ class HipOps:
         return out
 
     @staticmethod
+    def abm_adjoint(ps, cps, ds, cds, base=None, out=None):
+        """The gradient of one evaluation of a fixed_adams solve, gathered from the adjoints of the predictor-corrector steps that held
+        it (ndcn_abm_adjoint_f32): [base +] ((((0 + cp_0 P_0) + cd_0 D_0) + cp_1 P_1) + cd_1 D_1 ...), every product and sum rounded on
+        its own, the base added last.  ps / ds: 1..11 panels each (P_q may be D_q), cps / cds: their float32 coefficients
+        (core.abm_adjoint_terms).  out may be base, never a term."""
+        ps, ds = [_panel(g) for g in ps], [_panel(g) for g in ds]
+        assert len(ps) == len(ds) == len(cps) == len(cds)
+        base = _panel(base) if base is not None else None
+        if out is None:
+            out = torch.empty_like(ps[0])
+        arr_p, arr_cp, n = _terms(ps, cps)
+        arr_d, arr_cd, _ = _terms(ds, cds)
+        with torch.cuda.device(out.device):
+            check(_lib.load().ndcn_abm_adjoint_f32(ptr(out), ptr(base), arr_p, arr_cp, arr_d, arr_cd, n, out.numel(), stream_ptr()))
+        return out
+
+    @staticmethod
     def tick_emit(y, dt, tms, outs=None):
         """The ticks a sub-stepped fixed-grid step reports that are NOT an end of the step (solvers.py:92-108, y0 already overwritten
         with y1): [y + ((y - y) / dt) * tm for tm in tms] - one pass over y per 8 ticks (ndcn_tick_emit_f32)."""

@@ -390,6 +390,37 @@ def ab_adjoint_terms(i, dts, max_order):
     return terms
 
 
+def abm_history_lengths(n_steps, max_order, converged):
+    """[n_0 .. n_{S-1}]: the evaluations grid step i' of a fixed_adams solve holds - always its n newest, f_i' first.  The history grows
+    by one per step up to max_order - 1 and loses its oldest evaluation after every step whose corrector did not converge
+    (fixed_adams.py:163-172,199); below three the step is the RK4 warm-up, which iterates nothing.  converged: the per-step flags (only
+    those of the predictor-corrector steps are read)."""
+    lengths, held = [], 0
+    for step in range(n_steps):
+        n = min(held + 1, max_order - 1)
+        lengths.append(n)
+        held = n - 1 if (n >= AB_MIN_ORDER - 1 and not converged[step]) else n
+    return lengths
+
+
+def abm_adjoint_terms(i, dts, max_order, converged):
+    """Which adjoints the gradient of evaluation f_i = F(y_i) of a fixed_adams solve gathers from, and with which weights:
+    [(i', cP, cD), ...], i' rising, such that gf_i = sum cP * P_i' + cD * D_i' in this order - P_i' the adjoint of the predictor increment
+    dy_0 = dt_i' sum_q a_q f_{i'-q} of grid step i', D_i' that of the explicit part delta = dt_i' sum_q m_{q+1} f_{i'-q} of its corrector.
+    Step i' holds n = abm_history_lengths(..)[i'] evaluations; with n >= 3 it is a predictor-corrector step and f_i its term q = i' - i
+    where that is below n: cP = fl32(dt_i' * a^(n)_q), cD = fl32(dt_i' * m^(n)_{q+1}), each the product of two float32 numbers rounded
+    once.  A pure function of the step sizes and the converged flags, and the one place that decides both; with every step converged
+    [(i' + 1, cP)] is ab_adjoint_terms(i, dts, max_order).  RK4 warm-up steps read no history."""
+    n_steps, terms = len(dts), []
+    lengths = abm_history_lengths(n_steps, max_order, converged)
+    for step in range(i, min(n_steps - 1, i + max_order - 2) + 1):
+        n, q = lengths[step], step - i
+        if n >= AB_MIN_ORDER - 1 and q < n:
+            dt = f32(dts[step])
+            terms.append((step, f32(dt * ab_weights(n)[q]), f32(dt * am_weights(n)[1][q])))
+    return terms
+
+
 def _rk4_step(ops, func, targ, t0, dt, y, k1):
     """rk_common.py:72-78 + solvers.py:92: the 3/8 rule from the evaluation k1 = func(t0, y)"""
     y2 = tuple(ops.fixed_stage(2, y_, a, dt=dt) for y_, a in zip(y, k1))

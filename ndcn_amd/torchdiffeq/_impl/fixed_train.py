@@ -9,9 +9,11 @@ autograd nodes, one per route, each differentiated the way the reference's drive
                      (NDCN_FIXED_GRID_NATIVE=0) and the form that carries an active dropout;
   _SubstepSolve      options={'step_size': h}: a grid finer than the ticks, checkpointed per tick interval;
   _ExplicitAdamsSolve  method='explicit_adams' (NDCN_ADAMS_TRAIN=1): the library's loop forward with a record of every evaluation, the
-                     reverse sweep of a multistep method in closed form (csrc/adams.hip, csrc/adams_bwd.hip).
+                     reverse sweep of a multistep method in closed form (csrc/adams.hip, csrc/adams_bwd.hip);
+  _FixedAdamsSolve   method='fixed_adams' (the same switch): that loop with the Adams-Moulton corrector, a record of every corrector
+                     evaluation too, the reverse of a predictor-corrector step in closed form.
 
-The last four take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
+The last five take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
 the decoded solution (T, N, C) - hip.linear of the trajectory, the bits of the two-step form - the hidden trajectory is saved for the
 reverse sweep only, and that sweep takes the (T, N, C) gradient as it is: the (T, N, H) gradient of the trajectory is never written.
 Where a tick's gradient comes from is one object in the two Python sweeps (_PlainTicks, _ReadoutTicks: the Python mirror of TickGrad
@@ -27,6 +29,7 @@ the other.  They share the step launches, the closed-form sweep of one step and 
 
 Nothing here imports odeint.py at module level (it routes into this module)."""
 import ctypes
+import sys
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -521,7 +524,8 @@ class _ExplicitAdamsSolve(torch.autograd.Function):
 
 
 def adams_train_enabled():
-    """NDCN_ADAMS_TRAIN=1: explicit_adams under a gradient runs on _ExplicitAdamsSolve (default: the per-operation graph)"""
+    """NDCN_ADAMS_TRAIN=1: explicit_adams under a gradient runs on _ExplicitAdamsSolve, fixed_adams on _FixedAdamsSolve (default: the
+    per-operation graph)"""
     return _lib.env_str('NDCN_ADAMS_TRAIN', '0') == '1'
 
 
@@ -546,6 +550,157 @@ def _explicit_adams_with_grad(odefunc, y0, t, plan, max_order, readout=None):
     csr.transpose().ensure_plans(y0.shape[1])
     Wd, bd = readout if readout is not None else (None, None)
     return _ExplicitAdamsSolve.apply(y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order)
+
+
+# ---------------------------------------------------------------------------------------------------
+# fixed_adams: the predictor-corrector loop with a record, its reverse sweep in closed form
+# ---------------------------------------------------------------------------------------------------
+
+def _first_cap(n_steps):
+    """corrector evaluations the first attempt of a fixed_adams training solve has room for: one per grid step, what the drivers'
+    tolerances give (the second attempt: n_steps * max_iters, which always suffices)"""
+    return n_steps
+
+
+def _fixed_adams_attempt(view, Wc, bc, flags, out, arrays, max_order, rtol, atol, max_iters, rec_f, rec_y, cap):
+    """one call of ndcn_fixed_adams_train_f32 with room for `cap` corrector evaluations -> (return code, iterations, converged flags, first
+    slots, rec_u, rec_c)"""
+    lib = _lib.load()
+    dts, n_steps, steps, same, offs, n_emit = arrays
+    shape, H = tuple(out.shape[1:]), out.shape[2]
+    rec_u = torch.empty((max(cap, 1),) + shape, dtype=torch.float32, device=out.device)
+    rec_c = torch.empty((max(cap, 1),) + shape, dtype=torch.float32, device=out.device)
+    nbytes = int(lib.ndcn_fixed_adams_train_workspace_bytes(shape[0], H))
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+    iters, conv, slots = (ctypes.c_int * n_steps)(), (ctypes.c_int * n_steps)(), (ctypes.c_int64 * n_steps)()
+    with torch.cuda.device(out.device):
+        rc = lib.ndcn_fixed_adams_train_f32(view, ptr(Wc), ptr(bc), H, flags, ptr(out[0]), dts, n_steps, steps, same, offs, n_emit, max_order,
+                                            float(rtol), float(atol), int(max_iters), ptr(out[1:]), iters, conv, ptr(rec_f), ptr(rec_y),
+                                            ptr(rec_u), ptr(rec_c), cap, slots, ptr(workspace), nbytes, stream_ptr())
+    return rc, list(iters), [bool(c) for c in conv], list(slots), rec_u, rec_c
+
+
+class _FixedAdamsSolve(torch.autograd.Function):
+    """FixedGridODESolver.integrate with the AdamsBashforthMoulton step (fixed_adams.py:151-205) over ODEFunc, one node per solve:
+      forward   ndcn_fixed_adams_train_f32: the loop, read-backs and bits of the un-differentiated solve, which keeps f_i = F(y_i) and the
+                state after every grid step (as _ExplicitAdamsSolve) and, per corrector evaluation, the iterate it read and its result
+                (u_{r-1}, F_r) in slots handed out in order.  Room for one evaluation per step first; where a step iterates more and the
+                room runs out the library says so (NDCN_ECAPACITY) and the solve runs once more with room for max_iters per step.  The
+                iteration counts and converged flags are constants of the graph, as on the per-operation path;
+      backward  from the last step to the first, lam_{i+1} the full adjoint of y_{i+1}.  A step that held n >= 3 evaluations ran
+                u_0 = y_i + dy_0, u_r = y_i + c0 F_r + delta (F_r = F(u_{r-1}), r = 1..R), y_{i+1} = u_R.  So G_R = lam_{i+1},
+                G_{r-1} = J(u_{r-1})^T (c0 G_r) - one hip.scale (the factor c0 by a pass of its own: every G is then a panel the
+                existing closing forms take with unit weights) and one hip.rhs_vjp at the stored pair, which accumulates gW / gb -,
+                P_i = G_0 the adjoint of dy_0, D_i = sum_{r>=1} G_r that of delta (R = 1: lam_{i+1} itself, no pass).  f_i is a term of
+                dy_0 and of delta of every later step that holds it: gf_i = sum cP P_i' + cD D_i' in one pass (core.abm_adjoint_terms,
+                hip.abm_adjoint), gu = J(y_i)^T gf_i, and lam_i = D_i + (P_i + gu [+ the tick]).  RK4 warm-up steps as in
+                _ExplicitAdamsSolve, gf_i one more addend of the gradient of k1.  Kept meanwhile: the max_order - 1 newest P and D.
+    Ticks and the decoder as in _ExplicitAdamsSolve."""
+
+    @staticmethod
+    def forward(ctx, y0, W, b, Wd, bd, csr, flags, plan, max_order, rtol, atol, max_iters, step_log):
+        y0c, Wc, bc = _detached(y0, W, b)
+        arrays = plan_arrays(plan)
+        n_steps, n_emit = arrays[1], arrays[5]
+        shape = tuple(y0c.shape)
+        out = torch.empty((n_emit + 1,) + shape, dtype=torch.float32, device=y0c.device)
+        out[0].copy_(y0c)
+        rec_f = torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
+        rec_y = out[1:] if plan.default else torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
+        view = _view(csr, shape[0])
+        full = n_steps * max_iters
+        cap = min(_first_cap(n_steps), full)
+        res = _fixed_adams_attempt(view, Wc, bc, flags, out, arrays, max_order, rtol, atol, max_iters, rec_f, rec_y, cap)
+        if res[0] == _lib.ECAPACITY and cap < full:
+            del res                                               # (the first attempt's slots go back before the larger ones are taken)
+            res = _fixed_adams_attempt(view, Wc, bc, flags, out, arrays, max_order, rtol, atol, max_iters, rec_f, rec_y, full)
+        rc, iters, conv, slots, rec_u, rec_c = res
+        check(rc)
+        for c in conv:
+            if not c:
+                print(core.NOT_CONVERGED, file=sys.stderr)        # fixed_adams.py:198
+        if step_log is not None:                                  # as odeint._fixed_adams_solve fills it
+            warm = sum(1 for i in iters if i == 0)
+            step_log.extend(zip(iters, conv))
+            step_log.append(('nfe', n_steps + 3 * warm + sum(iters)))
+        ctx.meta = (csr, plan, max_order, iters, conv, slots)
+        ctx.save_for_backward(out, rec_f, rec_u, rec_c, W, b, Wd, *(() if plan.default else (rec_y,)))
+        return out if Wd is None else hip.linear(out, Wd.detach(), None if bd is None else bd.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        out, rec_f, rec_u, rec_c, W, b, Wd, *own = ctx.saved_tensors
+        csr, plan, max_order, iters, conv, slots = ctx.meta
+        rec_y = own[0] if own else out[1:]
+        Wc, bc = _detached(W, b)
+        dts = plan.dts
+        n_steps = len(dts)
+        lengths = core.abm_history_lengths(n_steps, max_order, conv)
+        ticks = _ticks(ctx, g, out, Wd)
+        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, False, False, None)
+        rvjp = lambda u, K, gk: hip.rhs_vjp(csr, u, Wc, K, gk, need_b=bc is not None, gW=gW_tot, gb=gb_tot)[0]
+        Ps, Ds = {}, {}                                           # the adjoints that evaluations still to come gather from
+        a = ticks.seed(n_steps) if plan.default else None
+        for i in range(n_steps - 1, -1, -1):
+            if not plan.default and plan.emits[i]:                # the ticks step i reported enter at the state it ends in
+                a = ticks.enter(a, [e[0] for e in plan.emits[i]])
+            if a is None:
+                a = torch.zeros_like(out[0])
+            y, f, dt = (out[0] if i == 0 else rec_y[i - 1]), rec_f[i], float(dts[i])
+            close = (lambda a, gus, i=i: ticks.close(a, gus, i)) if plan.default else _sum_onto
+            pc_step = lengths[i] >= core.AB_MIN_ORDER - 1
+            if pc_step:
+                c0 = float(core.abm_lead(dts[i], lengths[i]))
+                G, later = a, []
+                for s in range(slots[i] + iters[i] - 1, slots[i] - 1, -1):
+                    if G is not a:
+                        later.append(G)
+                    G = rvjp(rec_u[s], rec_c[s], hip.scale(G, c0))
+                Ps[i], Ds[i] = G, (a if not later else _sum_onto(a, later))
+                Ps.pop(i + max_order - 1, None)
+                Ds.pop(i + max_order - 1, None)
+            terms = core.abm_adjoint_terms(i, dts, max_order, conv)
+            gf = hip.abm_adjoint([Ps[s] for s, _, _ in terms], [c for _, c, _ in terms], [Ds[s] for s, _, _ in terms],
+                                 [c for _, _, c in terms]) if terms else None
+            if pc_step:
+                a = close(Ds[i], [Ps[i], rvjp(y, f, gf)])
+            else:
+                u2 = hip.fixed_stage(2, y, f, dt=dt)
+                K2 = hip.rhs(csr, u2, Wc, bc)
+                u3 = hip.fixed_stage(3, y, f, K2, dt=dt)
+                K3 = hip.rhs(csr, u3, Wc, bc)
+                u4 = hip.fixed_stage(4, y, f, K2, K3, dt=dt)
+                K4 = hip.rhs(csr, u4, Wc, bc)
+                a = _sweep_step('rk4', dt, [(y, f), (u2, K2), (u3, K3), (u4, K4)], a, vj, acc, close, gk1_extra=gf)
+        if not plan.default:
+            a = ticks.enter(a, [0])                               # the first tick is y0 itself
+        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 8
+
+
+def _fixed_adams_with_grad(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None, readout=None):
+    """fixed_adams over a plain ODEFunc under a gradient on _FixedAdamsSolve, or None where the node has no form: what
+    _explicit_adams_with_grad declines, and a max_iters or tolerances that are not plain numbers (the per-operation branch fails on them as
+    the reference does)."""
+    from .odeint import _small_operator
+    if not adams_train_enabled() or t.requires_grad or t.numel() < 2 or max_order < 2 or odefunc.no_graph or odefunc.no_control:
+        return None
+    if type(max_iters) is not int or max_iters < 1 or not all(isinstance(v, (int, float)) for v in (rtol, atol)):
+        return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, _, flags = op
+    core.assert_increasing(t)
+    if plan is None:
+        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    y0 = _lib.require_device(y0, 'state y0').contiguous()
+    if y0.numel() == 0:
+        return None
+    csr.ensure_plans(y0.shape[1])
+    csr.transpose().ensure_plans(y0.shape[1])
+    Wd, bd = readout if readout is not None else (None, None)
+    return _FixedAdamsSolve.apply(y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order, rtol, atol, max_iters, step_log)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -132,7 +132,8 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     bit for bit.  Without a gradient a plain ODEFunc runs inside the library (ndcn_solve_fixed_adams_f32: one 8-byte read-back per
     corrector iteration, the host decides whether to iterate again); any other callable, a tuple state, dropout, no_graph / no_control
     or a gradient steps through core.py over ndcn_abm_predict_f32 / ndcn_abm_correct_f32 - under a gradient the iteration counts are
-    constants of the graph.  A host state is refused here, where unsupported methods are, with an exception that is both NdcnHipError
+    constants of the graph.  With NDCN_ADAMS_TRAIN=1 a plain ODEFunc under a gradient (the conditions of the explicit_adams node)
+    trains on one autograd node per solve (fixed_train._FixedAdamsSolve), `readout` inside it.  A host state is refused here, where unsupported methods are, with an exception that is both NdcnHipError
     and NotImplementedError.
     """
     user_func = func
@@ -194,6 +195,13 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
         # dropout, no_graph / no_control and every other callable stay on the per-operation graph below)
         dec = fixed_train._readout_for_grad(readout, y0[0])
         sol = fixed_train._explicit_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], readout=dec)
+        if sol is not None:
+            return sol, dec is not None
+    if needs_grad and method == 'fixed_adams' and fixed_train.adams_train_enabled() and \
+            _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
+        # the same switch: the predictor-corrector loop with a record forward, its closed-form reverse sweep backward
+        dec = fixed_train._readout_for_grad(readout, y0[0])
+        sol = fixed_train._fixed_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log, readout=dec)
         if sol is not None:
             return sol, dec is not None
     if needs_grad:
