@@ -1213,6 +1213,40 @@ NDCN_API int ndcn_fixed_grid_backward_readout_f32(const ndcn_csr *A, const ndcn_
                                                   int C, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W, float *g_b,
                                                   float *g_Wd, float *g_bd, ndcn_alloc_fn alloc, void *alloc_ctx, void *stream);
 
+/* ---- TemporalGCN (neural_dynamics.py:179-238): the LSTM-GNN / GRU-GNN / RNN-GNN baselines (csrc/tgcn.hip) ------------------------
+ * Per tick the reference runs a GraphConvolution on an N x 1 column, flattened to 1 x (N Hg), into an LSTMCell / GRUCell / RNNCell whose
+ * input weight W_ih is M x (N Hg), M = G Hr with G = 4 / 3 / 1.  With S = A X (N x T, ticks in columns, row-major) and r = A 1 the
+ * convolution is Z[i, j, tau] = S[i, tau] w[j] + r[i] b[j] (w, b: the Hg weights and biases of the convolution's Linear(1, Hg)).
+ * ndcn_tgcn_proj_f32: GI[tau, g] = b_ih[g] + sum_{i, j} W_ih[g, i Hg + j] relu(Z[i, j, tau]) for ALL ticks, GI (T x M, row-major); W_ih
+ *   is read once per ndcn_tgcn_chunk(0) ticks; a NaN in Z reaches GI.  ws: ndcn_tgcn_proj_ws_bytes(N, T, M) bytes (per-workgroup partial
+ *   blocks, summed by a second launch in workgroup order: no atomics, the same inputs give the same bits).
+ * ndcn_tgcn_proj_bwd_f32: from GGI = dL/dGI (T x M): g_Wih[g, i Hg + j] = sum_tau GGI[tau, g] relu(Z)[i, j, tau], written once, never
+ *   read; with gZ = [Z > 0] sum_g W_ih[g, .] GGI[tau, g] (0 at Z = 0; a NaN Z passes the gradient), g_w[j] = sum gZ S, g_b[j] = sum gZ r
+ *   (per-workgroup partials summed in fp64 in workgroup order); g_bih[g] = sum_tau GGI[tau, g] (fp64, tick order).
+ *   ws: ndcn_tgcn_proj_bwd_ws_bytes(N) bytes.
+ * Both: N >= 1, T >= 1, 1 <= Hg <= 8, 1 <= M <= 64; NDCN_EINVAL - before any launch - otherwise, for a null pointer and for an output
+ * that is an input or another output.
+ * ndcn_tgcn_cell_f32: the recurrence over all T ticks in one launch.  rnn_type 0 rnn (tanh), 1 gru, 2 lstm, torch's cell definitions
+ *   (lstm gates in order i, f, g, o; gru n = tanh(gi_n + r (W_hn h + b_hn)), h' = (1 - z) n + z h).  GI (T x G Hr) carries b_ih already;
+ *   W_hh (G Hr x Hr), b_hh (G Hr); h0, c0 (Hr; nullable: zeros; c0 lstm only).  Writes H (T x Hr) and the record the reverse reads:
+ *   gates (T x 4 Hr: lstm i, f, g, o; gru r, z, n, W_hn h + b_hn; rnn h' in the first Hr) and, lstm only, c_rec (T x Hr); hT / cT
+ *   (nullable): the state after the last tick.
+ * ndcn_tgcn_cell_bwd_f32: its reverse from gH = dL/dH (T x Hr): GGI (T x G Hr), g_Whh, g_bhh and (nullable) g_h0, g_c0.
+ * Both: T >= 1, Hr >= 1, G Hr <= 64; NDCN_EINVAL - before any launch - otherwise, for a null pointer and for aliased outputs.       */
+NDCN_API int ndcn_tgcn_chunk(int reverse);
+NDCN_API int64_t ndcn_tgcn_proj_ws_bytes(int64_t n_nodes, int T, int M);
+NDCN_API int ndcn_tgcn_proj_f32(const float *S, const float *r, const float *w, const float *b, const float *W_ih, const float *b_ih,
+                                float *GI, void *ws, int64_t n_nodes, int T, int Hg, int M, void *stream);
+NDCN_API int64_t ndcn_tgcn_proj_bwd_ws_bytes(int64_t n_nodes);
+NDCN_API int ndcn_tgcn_proj_bwd_f32(const float *S, const float *r, const float *w, const float *b, const float *W_ih, const float *GGI,
+                                    float *g_Wih, float *g_w, float *g_b, float *g_bih, void *ws, int64_t n_nodes, int T, int Hg, int M,
+                                    void *stream);
+NDCN_API int ndcn_tgcn_cell_f32(int rnn_type, const float *GI, const float *W_hh, const float *b_hh, const float *h0, const float *c0,
+                                float *H, float *gates, float *c_rec, float *hT, float *cT, int T, int Hr, void *stream);
+NDCN_API int ndcn_tgcn_cell_bwd_f32(int rnn_type, const float *gH, const float *gates, const float *c_rec, const float *H, const float *h0,
+                                    const float *c0, const float *W_hh, float *GGI, float *g_Whh, float *g_bhh, float *g_h0, float *g_c0,
+                                    int T, int Hr, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

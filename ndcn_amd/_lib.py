@@ -36,6 +36,10 @@ SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 2
 RKF_KERNEL_MASK, RKF_OP_SHIFT, RKF_VEC, RKF_ATEN, RKF_PAR64, RKF_GRID_SHIFT = 0xff, 8, 0x1000, 0x2000, 0x4000, 32
 # ndcn_last_readout_path: what the last ndcn_solver_advance_many_readout call ran (include/ndcn_hip.h NDCN_READOUT_*)
 READOUT_FUSED, READOUT_STAGED, READOUT_FIXED, READOUT_NARROW = 1, 2, 4, 8
+# ndcn_tgcn_cell_f32 / ndcn_tgcn_cell_bwd_f32: rnn_type, and the gates G of each (the input weight of the cell is (G Hr) x (N Hg))
+TGCN_RNN, TGCN_GRU, TGCN_LSTM = 0, 1, 2
+TGCN_TYPES = {'rnn': TGCN_RNN, 'gru': TGCN_GRU, 'lstm': TGCN_LSTM}
+TGCN_GATES = {TGCN_RNN: 1, TGCN_GRU: 3, TGCN_LSTM: 4}
 
 OK = 0
 EINVAL, EHIP, ENONFINITE, EUNDERFLOW, EMAXSTEPS, ESTATE = -1, -2, -3, -4, -5, -6
@@ -334,6 +338,13 @@ SIGNATURES = {
     'ndcn_set_rhs_mid_bwd': (_I, [_I]),
     'ndcn_rhs_mid_bwd_supported': (_I, [_L, _I, _U, _I]),
     'ndcn_debug_last_rhs_vjp_path': (_I, []),
+    'ndcn_tgcn_chunk': (_I, [_I]),
+    'ndcn_tgcn_proj_ws_bytes': (_L, [_L, _I, _I]),
+    'ndcn_tgcn_proj_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'ndcn_tgcn_proj_bwd_ws_bytes': (_L, [_L]),
+    'ndcn_tgcn_proj_bwd_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'ndcn_tgcn_cell_f32': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'ndcn_tgcn_cell_bwd_f32': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
 }
 
 _lib = None

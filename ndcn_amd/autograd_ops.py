@@ -113,6 +113,32 @@ def rhs(A, x, W, b, no_graph, no_control, dropout=None):
     return _Rhs.apply(x, W, b, None if no_graph else as_csr(A), no_graph, no_control, dropout)
 
 
+class _TgcnSequence(torch.autograd.Function):
+    """The teacher-forced part of TemporalGCN up to the hidden states, as one node over the input projection of all ticks and the
+    recurrence (csrc/tgcn.hip): H (T, Hr) from S = A X, r = A 1 and the six parameters.  S and r are saved by reference, with the
+    gate record and the hidden states; the backward is the reverse of the recurrence, then of the projection - W_ih is read once
+    and its gradient written once.  The decoder stays a node of its own."""
+
+    @staticmethod
+    def forward(ctx, w, b, W_ih, W_hh, b_ih, b_hh, S, r, rnn_type):
+        GI = hip.tgcn_proj(S, r, w.detach(), b.detach(), W_ih.detach(), b_ih.detach())
+        H, gates, c_rec, _, _ = hip.tgcn_cell(rnn_type, GI, W_hh.detach(), b_hh.detach())
+        ctx.rnn_type, ctx.S, ctx.r, ctx.gates, ctx.c_rec = rnn_type, S, r, gates, c_rec
+        ctx.save_for_backward(w, b, W_ih, W_hh, H)
+        return H
+
+    @staticmethod
+    def backward(ctx, gH):
+        w, b, W_ih, W_hh, H = ctx.saved_tensors
+        GGI, g_Whh, g_bhh, _, _ = hip.tgcn_cell_bwd(ctx.rnn_type, gH.contiguous(), ctx.gates, ctx.c_rec, H.detach(), W_hh.detach())
+        g_Wih, g_w, g_b, g_bih = hip.tgcn_proj_bwd(ctx.S, ctx.r, w.detach(), b.detach(), W_ih.detach(), GGI)
+        return g_w.view_as(w), g_b, g_Wih, g_Whh, g_bih, g_bhh, None, None, None
+
+
+def tgcn_sequence(S, r, w, b, W_ih, W_hh, b_ih, b_hh, rnn_type):
+    return _TgcnSequence.apply(w, b, W_ih, W_hh, b_ih, b_hh, S, r, rnn_type)
+
+
 # ---------------------------------------------------------------------------------------------------
 # Runge-Kutta algebra: linear maps whose VJP is a per-input scalar times the incoming gradient
 # ---------------------------------------------------------------------------------------------------

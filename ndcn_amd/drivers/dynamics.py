@@ -8,7 +8,12 @@ utils_in_learn_dynamics.py:212-247), the truth solve with dopri5 at odeint's def
 variants (:245-268), Adam + L1 / relative-L1 (:295-321), the log line formats (:374-388), the dump dictionary
 keys and file naming (:300-311, :434-438).  Different by construction: graphs and operators are built in O(nnz)
 (ndcn_amd/graphs.py, so --n can be 10^6), everything runs on the ROCm device, `--seed` also seeds torch / numpy
-(the reference leaves them unseeded), the RNN-GNN baselines and --viz are out of scope.
+(the reference leaves them unseeded), --viz is out of scope.
+
+The discrete baselines --baseline lstm_gnn | gru_gnn | rnn_gnn (TemporalGCN, heat_dynamics.py:164-167, 236-240, 270-284, 322-328,
+350-355, 400-403) run on the device too: the Kipf operator whatever --operator says, TemporalGCN(1, 5, n, 10, OM), training on
+model(true_y_train[:, :-1]) against true_y_train[:, 1:], evaluation with future=len(id_test); --method / --rtol / --atol are ignored
+as in the reference.  With --sampled_time irregular the reference ends in a NameError there (loss2 is never set): refused up front.
 
     python -m ndcn_amd.drivers.heat_dynamics --network grid --sampled_time equal --baseline ndcn --gpu 0
 """
@@ -24,9 +29,10 @@ import torch.optim as optim
 
 from .. import graphs
 from .. import torchdiffeq as ode
-from ..neural_dynamics import NDCN
+from ..neural_dynamics import NDCN, TemporalGCN
 from ..truth import HeatDiffusion, GeneDynamics, MutualDynamics
 
+RNN_BASELINES = {'lstm_gnn': 'lstm', 'gru_gnn': 'gru', 'rnn_gnn': 'rnn'}
 TITLES = {'heat': 'Heat Diffusion Dynamic Case', 'gene': 'Gene Regulatory Dynamic Case',
           'mutualistic': 'Mutualistic Interaction Dynamic Case'}
 
@@ -88,9 +94,12 @@ def truth_rhs(kind, A_op, L_op):
 
 
 def main(kind, argv=None):
-    args = build_parser(kind).parse_args(argv)
-    if args.baseline in ('lstm_gnn', 'rnn_gnn', 'gru_gnn'):
-        raise NotImplementedError('the discrete RNN-GNN baselines (TemporalGCN) are outside the accelerated path')
+    parser = build_parser(kind)
+    args = parser.parse_args(argv)
+    discrete = args.baseline in RNN_BASELINES
+    if discrete and args.sampled_time == 'irregular':
+        parser.error('--baseline %s needs --sampled_time equal: with irregular sampling the reference computes no interpolation '
+                     'loss for the discrete baselines and ends in a NameError (loss2 is never set)' % args.baseline)
     assert torch.cuda.is_available() and args.gpu >= 0, 'ndcn_amd runs on a ROCm device (--gpu >= 0); there is no CPU path'
     device = torch.device('cuda:%d' % args.gpu)
     torch.manual_seed(args.seed)
@@ -106,7 +115,10 @@ def main(kind, argv=None):
     L = graphs.laplacian(A)
     names = {'lap': 'Laplacian', 'kipf': 'Kipf', 'norm_adj': 'Normalized Adjacency', 'norm_lap': 'Normalized Laplacian'}
     print('Graph Operator%s: %s' % ('[Default]' if args.operator == 'norm_lap' else '', names[args.operator]))
-    OM = graphs.to_device(graphs.make_operator(A, args.operator), device)
+    if discrete:
+        print('For temporal-gnn model lstm_gnn, rnn_gnn, and gru_gnn'
+              'Graph Operator Choose: Kipf in GCN')                 # heat_dynamics.py:164-167
+    OM = graphs.to_device(graphs.make_operator(A, 'kipf' if discrete else args.operator), device)
     A_op, L_op = graphs.to_device(A, device), graphs.to_device(L, device)
     x0 = torch.from_numpy(graphs.x0_blocks(S)[:n]).to(device)
 
@@ -125,9 +137,13 @@ def main(kind, argv=None):
     # ---- model
     print('Choose model:' + args.baseline)
     hidden = 1 if args.baseline == 'no_embed' else args.hidden
-    model = NDCN(input_size=1, hidden_size=hidden, A=OM, num_classes=1, dropout=args.dropout,
-                 no_embed=args.baseline == 'no_embed', no_graph=args.baseline == 'no_graph',
-                 no_control=args.baseline == 'no_control', rtol=args.rtol, atol=args.atol, method=args.method).to(device)
+    if discrete:
+        # hidden_size_gnn = 5, hidden_size_rnn = 10 (heat_dynamics.py:238-240, 270-284)
+        model = TemporalGCN(1, 5, n, 10, OM, dropout=args.dropout, rnn_type=RNN_BASELINES[args.baseline]).to(device)
+    else:
+        model = NDCN(input_size=1, hidden_size=hidden, A=OM, num_classes=1, dropout=args.dropout,
+                     no_embed=args.baseline == 'no_embed', no_graph=args.baseline == 'no_graph',
+                     no_control=args.baseline == 'no_control', rtol=args.rtol, atol=args.atol, method=args.method).to(device)
     num_paras = sum(p.numel() for p in model.parameters())
     print({'Total': num_paras, 'Trainable': sum(p.numel() for p in model.parameters() if p.requires_grad)})
 
@@ -140,7 +156,10 @@ def main(kind, argv=None):
 
     def evaluate():
         with torch.no_grad():
-            pred = model(t, x0).squeeze().t()
+            if discrete:
+                pred = model(true_y_train, future=len(id_test))       # heat_dynamics.py:350-355
+            else:
+                pred = model(t, x0).squeeze().t()
             loss = criterion(pred[:, id_test], true_y_test)
             rel = loss / true_y_test.mean()
             loss2 = rel2 = None
@@ -163,9 +182,12 @@ def main(kind, argv=None):
     itr, loss_train, rel_train = 0, torch.zeros(()), torch.zeros(())
     for itr in range(1, args.niters + 1):
         optimizer.zero_grad()
-        pred_y = model(t_train, x0).squeeze().t()
-        loss_train = criterion(pred_y, true_y_train)
-        rel_train = loss_train.detach() / true_y_train.mean()
+        if discrete:
+            pred_y, want = model(true_y_train[:, :-1]), true_y_train[:, 1:]      # heat_dynamics.py:322-328
+        else:
+            pred_y, want = model(t_train, x0).squeeze().t(), true_y_train
+        loss_train = criterion(pred_y, want)
+        rel_train = loss_train.detach() / want.mean()
         loss_train.backward()
         optimizer.step()
         if itr % args.test_freq == 0:

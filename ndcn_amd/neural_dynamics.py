@@ -1,12 +1,12 @@
-"""Drop-in for the hot-path classes of the reference's neural_dynamics.py: ODEFunc, ODEBlock, ODEBlock2,
-NDCN, GraphConvolution - same constructor signatures, attribute names and state_dict keys
+"""Drop-in for the classes of the reference's neural_dynamics.py: ODEFunc, ODEBlock, ODEBlock2, NDCN,
+GraphConvolution, TemporalGCN - same constructor signatures, attribute names and state_dict keys
 (SURVEY.md 8b), computed by the HIP kernels of libndcn_hip.so.
-
-Out of scope: TemporalGCN (discrete RNN baselines, neural_dynamics.py:179-238).
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
+from . import _lib
 from . import dropout as _dropout
 from . import torchdiffeq as ode
 from .ops import hip
@@ -171,3 +171,123 @@ class GraphConvolution(nn.Module):
         else:
             output = hip.spmm(propagation_adj, support)
         return output.view(1, -1)
+
+
+class TemporalGCN(nn.Module):
+    """The LSTM-GNN / GRU-GNN / RNN-GNN baselines   -- reference neural_dynamics.py:179-238: per tick a GraphConvolution on an N x 1
+    column, flattened to 1 x (N Hg), an LSTMCell / GRUCell / RNNCell and a Linear(Hr, N) decoder; `future` further ticks feed the
+    last output back.  forward(input (N, T), future=0) -> (N, T + future).  The cell is a parameter holder in the fused form.
+
+    Composed form: the reference's loop over the existing pieces - any shapes, any dropout, gradients by autograd.
+    Fused form (csrc/tgcn.hip), taken when every condition of `_fusable` holds and NDCN_TGCN_FUSED / hip.set_tgcn_fused is on: the
+    input projections of all teacher-forced ticks as ONE product that streams the (G Hr) x (N Hg) input weight once (not once per
+    tick), the recurrence in one launch, the decoder as one Linear on the (T, Hr) hidden states; under a gradient one autograd node
+    (autograd_ops.tgcn_sequence) plus the decoder's.  The future ticks, inference only, run one tick at a time from the same calls.
+    `last_route` ('fused' / 'composed') and `route_counts` say what the last forward took."""
+
+    def __init__(self, input_size_gnn, hidden_size_gnn, input_n_graph, hidden_size_rnn, A, dropout=0.5, rnn_type='lstm'):
+        super(TemporalGCN, self).__init__()
+        self.input_size_gnn = input_size_gnn
+        self.hidden_size_gnn = hidden_size_gnn
+        self.input_size_rnn = input_n_graph * hidden_size_gnn
+        self.hidden_size_rnn = hidden_size_rnn
+        self.output_size = input_n_graph
+        self.dropout = dropout
+        self.dropout_layer = nn.Dropout(dropout)
+        self.A = A
+        # construction order = parameter order = the order of the seeded initial draws (neural_dynamics.py:191-201)
+        self.gc = GraphConvolution(input_size_gnn, hidden_size_gnn)
+        self.rnn_type = rnn_type
+        if rnn_type == 'lstm':
+            self.rnn = nn.LSTMCell(self.input_size_rnn, hidden_size_rnn)
+        elif rnn_type == 'gru':
+            self.rnn = nn.GRUCell(self.input_size_rnn, hidden_size_rnn)
+        elif rnn_type == 'rnn':
+            self.rnn = nn.RNNCell(self.input_size_rnn, hidden_size_rnn)
+        self.linear = _HipLinear(hidden_size_rnn, input_n_graph)
+        self.last_route = None
+        self.route_counts = {'fused': 0, 'composed': 0}
+
+    def _fusable(self, input, future):
+        if not hip.tgcn_fused_on() or self.rnn_type not in _lib.TGCN_TYPES:
+            return False
+        gates = _lib.TGCN_GATES[_lib.TGCN_TYPES[self.rnn_type]]
+        if self.input_size_gnn != 1 or not 1 <= self.hidden_size_gnn <= 8 or gates * self.hidden_size_rnn > 64:
+            return False
+        if input.dim() != 2 or input.shape[1] < 1 or not input.is_cuda or input.dtype != torch.float32 or input.requires_grad:
+            return False
+        if any(p.dtype != torch.float32 or p.device != input.device for p in self.parameters()):
+            return False
+        if self.dropout > 0 and self.training:
+            return False
+        if type(self.gc) is not GraphConvolution or type(self.linear) is not _HipLinear or getattr(self.rnn, 'nonlinearity', 'tanh') != 'tanh':
+            return False
+        if any(_has_hooks(m) for m in (self.gc, self.gc.fc, self.rnn, self.linear, self.dropout_layer)):
+            return False
+        return future == 0 or not _needs_grad(self)
+
+    def forward(self, input, future=0):
+        route = 'fused' if self._fusable(input, future) else 'composed'
+        self.last_route = route
+        self.route_counts[route] += 1
+        return self._forward_fused(input, future) if route == 'fused' else self._forward_composed(input, future)
+
+    def _forward_composed(self, input, future):
+        outputs = []
+        h_t = torch.zeros(1, self.hidden_size_rnn, device=input.device)
+        c_t = torch.zeros(1, self.hidden_size_rnn, device=input.device) if self.rnn_type == 'lstm' else None
+        output = None
+
+        def tick(input_t, h_t, c_t):
+            input_t = self.dropout_layer(input_t)
+            input_t = F.relu(self.gc(input_t, self.A))
+            if self.rnn_type == 'lstm':
+                h_t, c_t = self.rnn(input_t, (h_t, c_t))
+            else:
+                h_t = self.rnn(input_t, h_t)
+            return self.linear(h_t).t(), h_t, c_t
+
+        for input_t in input.chunk(input.size(1), dim=1):
+            output, h_t, c_t = tick(input_t, h_t, c_t)
+            outputs += [output]
+        for _ in range(future):
+            output, h_t, c_t = tick(output, h_t, c_t)
+            outputs += [output]
+        return torch.stack(outputs, 1).squeeze(2)
+
+    def _row_sums(self, A):
+        """r = A 1, once per operator: kept on the operator's converted form (csr.as_csr caches that on the tensor it came from, keyed
+        on its version counter - a changed operator gets a new converted form and with it a new r)."""
+        r = getattr(A, '_tgcn_row_sums', None)
+        if r is None:
+            r = hip.spmm(A, torch.ones(A.shape[1], dtype=torch.float32, device=A.device))
+            A._tgcn_row_sums = r
+        return r
+
+    def _forward_fused(self, input, future):
+        from .csr import as_csr
+        A = as_csr(self.A)
+        gc, rnn = self.gc.fc, self.rnn
+        r = self._row_sums(A)
+        S = hip.spmm(A, input.detach().contiguous())                  # (N, T): A X for all ticks in one call
+        if _needs_grad(self):
+            from .autograd_ops import tgcn_sequence
+            H = tgcn_sequence(S, r, gc.weight, gc.bias, rnn.weight_ih, rnn.weight_hh, rnn.bias_ih, rnn.bias_hh, self.rnn_type)
+            return self.linear(H).t()
+        w, b = gc.weight.detach(), gc.bias.detach()
+        W_ih, W_hh, b_ih, b_hh = (p.detach() for p in (rnn.weight_ih, rnn.weight_hh, rnn.bias_ih, rnn.bias_hh))
+        GI = hip.tgcn_proj(S, r, w, b, W_ih, b_ih)
+        H, _, _, h_t, c_t = hip.tgcn_cell(self.rnn_type, GI, W_hh, b_hh)
+        Wd, bd = self.linear.weight.detach(), self.linear.bias.detach()
+        out = hip.linear(H, Wd, bd).t()
+        if future == 0:
+            return out
+        # the rollout, one tick at a time from the same calls: the input weight is read once per future tick
+        cols = [out]
+        x = out[:, -1].contiguous()
+        for _ in range(future):
+            GI = hip.tgcn_proj(hip.spmm(A, x).view(-1, 1), r, w, b, W_ih, b_ih)
+            H, _, _, h_t, c_t = hip.tgcn_cell(self.rnn_type, GI, W_hh, b_hh, h0=h_t, c0=c_t)
+            x = hip.linear(H, Wd, bd).view(-1)
+            cols.append(x.view(-1, 1))
+        return torch.cat(cols, 1)

@@ -40,6 +40,7 @@ def _terms(ks, cs):
 # read-back of one reduction is one critical section.
 _REDUCE_LOCK = threading.RLock()
 _ADAMS_FUSED_OVERRIDE = None        # HipOps.set_adams_fused; None: the environment's NDCN_ADAMS_FUSED
+_TGCN_FUSED_OVERRIDE = None         # HipOps.set_tgcn_fused; None: the environment's NDCN_TGCN_FUSED
 
 
 class _Reducer:
@@ -556,6 +557,103 @@ class HipOps:
         csrc/rhs_mid_bwd.hip): 0 off, 1 on for the widths that measured not slower than the composed launches, 2 on for every
         supported shape; < 0: the environment's (NDCN_RHS_MID_BWD).  Process-wide; returns the previous mode."""
         return int(_lib.load().ndcn_set_rhs_mid_bwd(int(mode)))
+
+    # ---------------------------------------------------------------- TemporalGCN: the hoisted input projection and the recurrence (csrc/tgcn.hip)
+    @staticmethod
+    def set_tgcn_fused(mode):
+        """The fused form of neural_dynamics.TemporalGCN (one projection of all ticks, one launch for the recurrence): 0 off - every
+        forward takes the composed per-tick loop -, 1 on wherever the module's conditions hold; < 0: the environment's
+        (NDCN_TGCN_FUSED, default 1).  Process-wide; returns the previous mode."""
+        global _TGCN_FUSED_OVERRIDE
+        prev = HipOps.tgcn_fused_on()
+        _TGCN_FUSED_OVERRIDE = None if int(mode) < 0 else (1 if int(mode) else 0)
+        return prev
+
+    @staticmethod
+    def tgcn_fused_on():
+        if _TGCN_FUSED_OVERRIDE is not None:
+            return _TGCN_FUSED_OVERRIDE
+        return 1 if _lib.env_int('NDCN_TGCN_FUSED', 1) > 0 else 0
+
+    @staticmethod
+    def tgcn_chunk(reverse=False):
+        """ticks per pass over W_ih in tgcn_proj (reverse: per staging step of tgcn_proj_bwd)"""
+        return int(_lib.load().ndcn_tgcn_chunk(1 if reverse else 0))
+
+    @staticmethod
+    def tgcn_proj(S, r, w, b, W_ih, b_ih):
+        """GI (T, M) = b_ih + sum_{i,j} W_ih[:, i Hg + j] relu(S[i, :] w_j + r_i b_j) for all T ticks (ndcn_tgcn_proj_f32).  S (N, T) = A X,
+        r (N,) = A 1, w / b (Hg,): the graph convolution's Linear(1, Hg), W_ih (M, N Hg), b_ih (M,)."""
+        S, r, W_ih, b_ih = _panel(S, 'S'), _panel(r, 'row sums'), _panel(W_ih, 'input weight'), _panel(b_ih, 'input bias')
+        w, b = _panel(w, 'weight').reshape(-1), _panel(b, 'bias').reshape(-1)
+        N, T = S.shape
+        Hg, M = w.numel(), W_ih.shape[0]
+        assert r.numel() == N and b.numel() == Hg and tuple(W_ih.shape) == (M, N * Hg) and b_ih.numel() == M
+        lib = _lib.load()
+        GI = torch.empty((T, M), dtype=torch.float32, device=S.device)
+        ws = torch.empty(max(int(lib.ndcn_tgcn_proj_ws_bytes(N, T, M)), 4), dtype=torch.uint8, device=S.device)
+        with torch.cuda.device(S.device):
+            check(lib.ndcn_tgcn_proj_f32(ptr(S), ptr(r), ptr(w), ptr(b), ptr(W_ih), ptr(b_ih), ptr(GI), ptr(ws), N, T, Hg, M, stream_ptr()))
+        return GI
+
+    @staticmethod
+    def tgcn_proj_bwd(S, r, w, b, W_ih, GGI):
+        """(g_Wih, g_w, g_b, g_bih) of tgcn_proj for GGI = dL/dGI (T, M) (ndcn_tgcn_proj_bwd_f32): g_Wih is written once, W_ih read once."""
+        S, r, W_ih, GGI = _panel(S, 'S'), _panel(r, 'row sums'), _panel(W_ih, 'input weight'), _panel(GGI, 'gradient')
+        w, b = _panel(w, 'weight').reshape(-1), _panel(b, 'bias').reshape(-1)
+        N, T = S.shape
+        Hg, M = w.numel(), W_ih.shape[0]
+        assert r.numel() == N and b.numel() == Hg and tuple(W_ih.shape) == (M, N * Hg) and tuple(GGI.shape) == (T, M)
+        lib = _lib.load()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=S.device)
+        g_Wih, g_w, g_b, g_bih = new(M, N * Hg), new(Hg), new(Hg), new(M)
+        ws = torch.empty(max(int(lib.ndcn_tgcn_proj_bwd_ws_bytes(N)), 4), dtype=torch.uint8, device=S.device)
+        with torch.cuda.device(S.device):
+            check(lib.ndcn_tgcn_proj_bwd_f32(ptr(S), ptr(r), ptr(w), ptr(b), ptr(W_ih), ptr(GGI), ptr(g_Wih), ptr(g_w), ptr(g_b),
+                                             ptr(g_bih), ptr(ws), N, T, Hg, M, stream_ptr()))
+        return g_Wih, g_w, g_b, g_bih
+
+    @staticmethod
+    def tgcn_cell(rnn_type, GI, W_hh, b_hh, h0=None, c0=None):
+        """The recurrence of an LSTMCell / GRUCell / RNNCell ('lstm' / 'gru' / 'rnn') over the T rows of GI in one launch
+        (ndcn_tgcn_cell_f32): (H (T, Hr), gates (T, 4 Hr), c_rec (T, Hr) or None, hT, cT or None); h0 / c0 None: zeros."""
+        kind = _lib.TGCN_TYPES[rnn_type]
+        GI, W_hh, b_hh = _panel(GI, 'GI'), _panel(W_hh, 'hidden weight'), _panel(b_hh, 'hidden bias')
+        T, M = GI.shape
+        Hr = W_hh.shape[1]
+        assert M == _lib.TGCN_GATES[kind] * Hr and tuple(W_hh.shape) == (M, Hr) and b_hh.numel() == M
+        h0 = _panel(h0, 'h0').reshape(-1) if h0 is not None else None
+        c0 = _panel(c0, 'c0').reshape(-1) if c0 is not None else None
+        assert (h0 is None or h0.numel() == Hr) and (c0 is None or c0.numel() == Hr)
+        lstm = kind == _lib.TGCN_LSTM
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=GI.device)
+        H, gates, hT = new(T, Hr), new(T, 4 * Hr), new(Hr)
+        c_rec, cT = (new(T, Hr), new(Hr)) if lstm else (None, None)
+        with torch.cuda.device(GI.device):
+            check(_lib.load().ndcn_tgcn_cell_f32(kind, ptr(GI), ptr(W_hh), ptr(b_hh), ptr(h0), ptr(c0), ptr(H), ptr(gates), ptr(c_rec),
+                                                 ptr(hT), ptr(cT), T, Hr, stream_ptr()))
+        return H, gates, c_rec, hT, cT
+
+    @staticmethod
+    def tgcn_cell_bwd(rnn_type, gH, gates, c_rec, H, W_hh, h0=None, c0=None):
+        """The reverse of tgcn_cell for gH = dL/dH (T, Hr) (ndcn_tgcn_cell_bwd_f32): (GGI (T, M), g_Whh, g_bhh, g_h0, g_c0 or None)."""
+        kind = _lib.TGCN_TYPES[rnn_type]
+        gH, gates, H, W_hh = _panel(gH, 'gradient'), _panel(gates, 'gate record'), _panel(H, 'hidden states'), _panel(W_hh, 'hidden weight')
+        T, Hr = H.shape
+        M = _lib.TGCN_GATES[kind] * Hr
+        lstm = kind == _lib.TGCN_LSTM
+        assert tuple(gH.shape) == (T, Hr) and tuple(gates.shape) == (T, 4 * Hr) and tuple(W_hh.shape) == (M, Hr)
+        assert not lstm or tuple(c_rec.shape) == (T, Hr)
+        c_rec = _panel(c_rec, 'cell record') if lstm else None
+        h0 = _panel(h0, 'h0').reshape(-1) if h0 is not None else None
+        c0 = _panel(c0, 'c0').reshape(-1) if c0 is not None else None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=gH.device)
+        GGI, g_Whh, g_bhh, g_h0 = new(T, M), new(M, Hr), new(M), new(Hr)
+        g_c0 = new(Hr) if lstm else None
+        with torch.cuda.device(gH.device):
+            check(_lib.load().ndcn_tgcn_cell_bwd_f32(kind, ptr(gH), ptr(gates), ptr(c_rec), ptr(H), ptr(h0), ptr(c0), ptr(W_hh), ptr(GGI),
+                                                     ptr(g_Whh), ptr(g_bhh), ptr(g_h0), ptr(g_c0), T, Hr, stream_ptr()))
+        return GGI, g_Whh, g_bhh, g_h0, g_c0
 
     @staticmethod
     def rhs_vjp(A, X, W, K, g, S=None, need_x=True, need_b=True, relu=True, premasked=False, acc_scale=1.0, gW=None, gb=None,

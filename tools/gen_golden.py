@@ -23,6 +23,7 @@ Fixture families:
   G14 substep_*.npz   fixed grid, options={'step_size': h}   torchdiffeq/_impl/solvers.py:55-68,79-108
   G15 bashforth_*.npz odeint explicit_adams + nfe            torchdiffeq/_impl/fixed_adams.py:151-211
   G16 moulton_*.npz   odeint fixed_adams + iterations, flags  torchdiffeq/_impl/fixed_adams.py:151-205
+  G17 tgcn_*.npz      TemporalGCN lstm / gru / rnn + gradients neural_dynamics.py:179-238
 """
 import os
 import sys
@@ -759,7 +760,74 @@ MOULTON_ITERATE = (0.015, 1.2e-4, 2.1e-5)
 MOULTON_ONE = (0.02, 3e-4, 3e-6)
 
 
+# ----------------------------------------------------------------------------- G17
+def gen_tgcn():
+    """TemporalGCN (neural_dynamics.py:179-238) of the reference on the CPU: 6 x 6 lattice, Kipf operator, Hg = 5, Hr = 10, 8 input
+    ticks, dropout 0, for each cell type one run with future = 0 (with the gradients of l1_loss against a written target) and one with
+    future = 3.  The weights are written out (sines of the element index), not seeded draws.  Per case the float32 run and the same
+    module in double agree within 1e-5 of each tensor's maximum - the bound the tests hold the kernels to is one the reference itself
+    meets - and no element of Z = A (x w^T + b) is within 1e-4 of the relu's kink."""
+    import torch.nn.functional as F
+    _, OM = grid_operator(6, 'kipf')
+    N, Hg, Hr, T = 36, 5, 10, 8
+    i = torch.arange(N, dtype=torch.float64)[:, None]
+    tau = torch.arange(T, dtype=torch.float64)[None, :]
+    X = (1.0 + 0.5 * torch.sin(0.7 * i + 0.3 * tau) + 0.05 * tau).float()
+    target = (1.1 + 0.4 * torch.cos(0.5 * i - 0.2 * tau)).float()
+
+    def written(shape, scale, phase):
+        n = int(np.prod(shape))
+        return (scale * torch.sin(phase + 0.37 * torch.arange(n, dtype=torch.float64) ** 1.1)).reshape(shape).float()
+
+    for rnn_type in ('lstm', 'gru', 'rnn'):
+        def make(dtype):
+            m = ref_nd.TemporalGCN(1, Hg, N, Hr, OM.to(dtype), dropout=0.0, rnn_type=rnn_type)
+            with torch.no_grad():
+                m.gc.fc.weight.copy_(torch.tensor([[0.9], [-0.7], [0.5], [-0.3], [0.8]]))
+                m.gc.fc.bias.copy_(torch.tensor([0.2, 0.35, -0.4, 0.25, -0.3]))
+                m.rnn.weight_ih.copy_(written(m.rnn.weight_ih.shape, 0.15, 0.1))
+                m.rnn.weight_hh.copy_(written(m.rnn.weight_hh.shape, 0.4, 0.7))
+                m.rnn.bias_ih.copy_(written(m.rnn.bias_ih.shape, 0.2, 1.3))
+                m.rnn.bias_hh.copy_(written(m.rnn.bias_hh.shape, 0.2, 2.1))
+                m.linear.weight.copy_(written(m.linear.weight.shape, 0.5, 0.4))
+                m.linear.bias.copy_(written(m.linear.bias.shape, 0.3, 1.9) + 1.0)
+            return m.to(dtype)
+
+        def run(dtype):
+            m = make(dtype)
+            # the reference's forward builds its initial state in float32 whatever the module's dtype: run the double module with the
+            # default dtype switched, as its own comment at :205-208 describes
+            old = torch.get_default_dtype()
+            torch.set_default_dtype(dtype)
+            try:
+                out0 = m(X.to(dtype))
+                loss = F.l1_loss(out0, target.to(dtype))
+                grads = torch.autograd.grad(loss, list(m.parameters()))
+                with torch.no_grad():
+                    out3 = m(X.to(dtype), future=3)
+            finally:
+                torch.set_default_dtype(old)
+            return m, out0.detach(), out3, dict(zip([k for k, _ in m.named_parameters()], grads))
+
+        m32, out0, out3, g32 = run(torch.float32)
+        m64, out0d, out3d, g64 = run(torch.float64)
+        close = lambda a, b: float((a.double() - b).abs().max()) <= 1e-5 * float(b.abs().max())
+        assert tuple(out0.shape) == (N, T) and tuple(out3.shape) == (N, T + 3)
+        assert close(out0, out0d) and close(out3, out3d), rnn_type
+        for k in g32:
+            assert close(g32[k], g64[k]), (rnn_type, k)
+        # Z of every tick, the three fed-back ones included
+        Zmin = np.inf
+        for col in torch.cat([X.double(), out3d[:, T - 1:-1]], 1).t():
+            Z = OM.double() @ (col[:, None] @ m64.gc.fc.weight.t() + m64.gc.fc.bias)
+            Zmin = min(Zmin, float(Z.abs().min()))
+        assert Zmin >= 1e-4, (rnn_type, Zmin)
+        print('tgcn_%-5s min |Z| %.3e' % (rnn_type, Zmin))
+        save('tgcn_%s' % rnn_type, A=OM, X=X, target=target, out_future0=out0, out_future3=out3,
+             **{k: v for k, v in m32.state_dict().items()}, **{'grad.' + k: v for k, v in g32.items()})
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep', 'bashforth', 'moulton']
+    which = sys.argv[1:] or ['layout', 'gconv', 'rhs', 'fixed', 'dopri5', 'ndcn', 'truth', 'operators', 'dgnn', 'dataset', 'planetoid_raw', 'adjoint', 'resgcn', 'adams', 'substep', 'bashforth', 'moulton', 'tgcn']
     for w in which:
         globals()['gen_' + w]()
