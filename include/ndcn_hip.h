@@ -799,6 +799,28 @@ NDCN_API int ndcn_solve_small_keep_f32(const ndcn_csr *A, const float *W, const 
 NDCN_API int ndcn_solve_small_bwd_keep_f32(const ndcn_csr *A, const ndcn_csr *A_t, const float *W, const float *b, int H, uint32_t flags,
                                            const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks, const float *keep,
                                            float *g_y0, float *g_W, float *g_b, void *stream);
+/* Which instantiation the LAST launch of the ndcn_solve_small_* entry points of this PROCESS ran (a reverse sweep runs on autograd's
+ * thread; tests: every template instantiation
+ * of csrc/solve_small.hip is reached on purpose; an addition to ABI 29, nothing existing changes).  The word is formed from the
+ * template arguments of the kernel that was launched; 0 before the first launch:
+ *   direction | family | MAXIT << 4 | CSR_LDS | HT << 9 | KEEP | GRID | SYMMETRIC | method << 17
+ * MAXIT: the passes the register arrays hold (4, 9 or 12).  CSR_LDS: the CSR arrays were copied into LDS (forward fast kernels
+ * instantiate it set - their ELL image lives there; the fast reverse kernel has no such parameter: clear).  HT: the compile-time
+ * width of the fast kernels (16 / 20), 0 on the generic ones.  SYMMETRIC (reverse only): the transposed gather read A's own
+ * arrays (generic / rk: the `symmetric` argument; fast: always).  method: NDCN_M_*.                                              */
+#define NDCN_SSR_FWD       1
+#define NDCN_SSR_BWD       2
+#define NDCN_SSR_GENERIC   4        /* solve_small_kernel<.., HT = 0> / solve_small_bwd_kernel                                       */
+#define NDCN_SSR_FAST      8        /* solve_small_kernel<.., HT = 16 | 20> / solve_small_bwd_fast_kernel                            */
+#define NDCN_SSR_RK        12       /* solve_small_bwd_rk_kernel (midpoint / RK4 reverse)                                            */
+#define NDCN_SSR_MAXIT_SHIFT 4
+#define NDCN_SSR_CSR_LDS   256
+#define NDCN_SSR_HT_SHIFT  9
+#define NDCN_SSR_KEEP      (1 << 14)
+#define NDCN_SSR_GRID      (1 << 15)
+#define NDCN_SSR_SYMMETRIC (1 << 16)
+#define NDCN_SSR_METHOD_SHIFT 17
+NDCN_API int ndcn_debug_last_small_route(void);
 
 /* ------------------------------------------------------------------------------------------------
  * explicit_adams: the reference's AdamsBashforth (torchdiffeq/_impl/fixed_adams.py:151-211), a fixed-grid linear multistep method - two

@@ -36,6 +36,9 @@ SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 2
 RKF_KERNEL_MASK, RKF_OP_SHIFT, RKF_VEC, RKF_ATEN, RKF_PAR64, RKF_GRID_SHIFT = 0xff, 8, 0x1000, 0x2000, 0x4000, 32
 # ndcn_last_readout_path: what the last ndcn_solver_advance_many_readout call ran (include/ndcn_hip.h NDCN_READOUT_*)
 READOUT_FUSED, READOUT_STAGED, READOUT_FIXED, READOUT_NARROW = 1, 2, 4, 8
+# ndcn_debug_last_small_route: the template arguments of the last one-launch solve / reverse sweep (include/ndcn_hip.h NDCN_SSR_*)
+SSR_FWD, SSR_BWD, SSR_GENERIC, SSR_FAST, SSR_RK = 1, 2, 4, 8, 12
+SSR_MAXIT_SHIFT, SSR_CSR_LDS, SSR_HT_SHIFT, SSR_KEEP, SSR_GRID, SSR_SYMMETRIC, SSR_METHOD_SHIFT = 4, 256, 9, 1 << 14, 1 << 15, 1 << 16, 17
 # ndcn_tgcn_cell_f32 / ndcn_tgcn_cell_bwd_f32: rnn_type, and the gates G of each (the input weight of the cell is (G Hr) x (N Hg))
 TGCN_RNN, TGCN_GRU, TGCN_LSTM = 0, 1, 2
 TGCN_TYPES = {'rnn': TGCN_RNN, 'gru': TGCN_GRU, 'lstm': TGCN_LSTM}
@@ -325,6 +328,7 @@ SIGNATURES = {
     'ndcn_prof_read': (_I, [ctypes.POINTER(_D), _I]),
     'ndcn_prof_kinds': (_I, []),
     'ndcn_debug_last_rhs_path': (_I, []),
+    'ndcn_debug_last_small_route': (_I, []),
     'ndcn_debug_last_linear_path': (_I, []),
     'ndcn_debug_last_rk_bwd_path': (_I, []),
     'ndcn_debug_last_spmm_path': (_I, []),

@@ -41,6 +41,7 @@ extern "C" {
 
 int ndcn_abi_version(void) { return NDCN_ABI_VERSION; }
 int ndcn_debug_last_rhs_path(void) { return g_last_rhs_path; }
+int ndcn_debug_last_small_route(void) { return last_small_route(); }
 int ndcn_debug_last_linear_path(void) { return g_last_linear_path; }
 int ndcn_debug_last_rk_bwd_path(void) { return g_last_rk_bwd_path; }
 int ndcn_debug_last_spmm_path(void) { return g_last_spmm_path; }

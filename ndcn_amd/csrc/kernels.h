@@ -155,6 +155,7 @@ int solve_small_grid_f32(const ndcn_csr *A, const float *W, const float *b, int 
                          const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, int64_t n_ticks,
                          float *out, float *y_end, hipStream_t st);
 int solve_small_keep_supported(const ndcn_csr *A, int H, uint32_t flags);
+int last_small_route();                       // ndcn_debug_last_small_route
 int solve_small_bwd_supported(const ndcn_csr *A, int H, uint32_t flags, int method);
 int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, const float *b, int H, uint32_t flags, int method,
                         const float *traj, const float *g_out, const float *h_dt, int64_t n_ticks, float *g_y0, float *g_W,

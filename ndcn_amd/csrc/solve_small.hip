@@ -138,9 +138,9 @@ __device__ __forceinline__ float eval_rhs(const SolveArgs &a, const Lds &l, cons
 //   * lane o keeps row o of W (its H weights) in registers for the whole solve: the Linear is H/4 16-byte reads of the wave's S
 //     row + H fmas, no weight traffic;
 // the same fma chains in the same order as the generic path (bit-identical), ~1/3 of its instructions and LDS bytes.
-// The fast path keeps the operator in ELL form in LDS: every row padded to `width` (the longest row, <= 16) entries
-// {column * H, value bits}, the padding {offset of an all-zero row, 0.0f}.  A row's gather is then `width` times {one 8-byte LDS read
-// at a constant offset, one add, one 4-byte LDS read, one fma} - no row extents, no predicates, no loop over rounds: a third of
+// The fast path keeps the operator in ELL form in LDS: every row padded to `width` (the longest row rounded up to a multiple of
+// three, <= 18: the gate of solve_small_impl / solve_small_bwd_f32, both sides tested) entries {column * H, value bits}, the
+// padding {offset of an all-zero row, 0.0f}.  A row's gather is then `width` times {one 8-byte LDS read at a constant offset, one add, one 4-byte LDS read, one fma} - no row extents, no predicates, no loop over rounds: a third of
 // the CSR form's instructions, and the solve is bound by instruction issue (one CU: 64 lanes per cycle).  The padding adds
 // 0.0f * 0.0f to a sum that started at +0.0f: the bits of every sum are those of the CSR chain.
 // (NP passes of a wave could be evaluated together - independent chains of LDS round trips - but measured, that buys nothing: 16
@@ -1015,6 +1015,12 @@ int passes(int64_t n_rows, int H) {
     return (int)((wave_passes + kWaves - 1) / kWaves);
 }
 
+// ndcn_debug_last_small_route: the word of one launch, from the template arguments of the kernel that was launched
+constexpr int route_word(int dir, int family, int maxit, bool csr_lds, int ht, bool keep, bool grid, int method) {
+    return dir | family | (maxit << NDCN_SSR_MAXIT_SHIFT) | (csr_lds ? NDCN_SSR_CSR_LDS : 0) | (ht << NDCN_SSR_HT_SHIFT) |
+           (keep ? NDCN_SSR_KEEP : 0) | (grid ? NDCN_SSR_GRID : 0) | (method << NDCN_SSR_METHOD_SHIFT);
+}
+
 template <typename K>
 int set_lds_cap(K kern) {
     NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
@@ -1022,6 +1028,10 @@ int set_lds_cap(K kern) {
 }
 
 }  // namespace
+
+// ndcn_debug_last_small_route: process-wide, like ndcn_debug_last_rhs_vjp_path (a reverse sweep runs on autograd's thread)
+static std::atomic<int> g_last_small_route{0};
+int last_small_route() { return g_last_small_route.load(std::memory_order_relaxed); }
 
 // Which fixed-grid solves run as one launch: a plain (un-sharded) operator, H <= 64, the state + W^T in one CU's LDS, and few
 // enough rows per thread for the row-local panels to stay in registers (<= 12 passes of 16 waves: 576 rows at H = 20; the
@@ -1118,6 +1128,7 @@ static int solve_small_impl(const ndcn_csr *A, const float *W, const float *b, i
             static std::atomic<unsigned long long> cap_seen{0};                                                       \
             if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; }       \
             hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a);                         \
+            g_last_small_route.store(route_word(NDCN_SSR_FWD, HT_ ? NDCN_SSR_FAST : NDCN_SSR_GENERIC, IT_, C_, HT_, false, false, M_), std::memory_order_relaxed); \
         } while (0)
 #define NDCN_GO_IT(M_, C_, HT_)                                                                \
         do {                                                                                   \
@@ -1137,6 +1148,7 @@ static int solve_small_impl(const ndcn_csr *A, const float *W, const float *b, i
                 static std::atomic<unsigned long long> cap_seen{0};                            \
                 if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
                 hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a);                     \
+                g_last_small_route.store(route_word(NDCN_SSR_FWD, HT_ ? NDCN_SSR_FAST : NDCN_SSR_GENERIC, IT_, C_, HT_, false, true, M_), std::memory_order_relaxed); \
             } while (0)
 #define NDCN_GGO_M(C_, HT_)                                                                    \
             do {                                                                               \
@@ -1157,6 +1169,7 @@ static int solve_small_impl(const ndcn_csr *A, const float *W, const float *b, i
                 static std::atomic<unsigned long long> cap_seen{0};                            \
                 if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
                 hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a);                     \
+                g_last_small_route.store(route_word(NDCN_SSR_FWD, NDCN_SSR_FAST, IT_, true, HT_, true, false, NDCN_M_EULER), std::memory_order_relaxed); \
             } while (0)
             if (H == 20) { if (np <= 4) NDCN_KGO(4, 20); else NDCN_KGO(12, 20); }
             else { if (np <= 4) NDCN_KGO(4, 16); else NDCN_KGO(12, 16); }
@@ -1304,6 +1317,7 @@ int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, c
                 static std::atomic<unsigned long long> cap_seen{0};                            \
                 if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
                 hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a, symmetric);          \
+                g_last_small_route.store(route_word(NDCN_SSR_BWD, NDCN_SSR_RK, IT_, C_, 0, false, false, M_) | (symmetric ? NDCN_SSR_SYMMETRIC : 0), std::memory_order_relaxed); \
             } while (0)
 #define NDCN_RGO_IT(M_, C_)                                                                    \
             do {                                                                               \
@@ -1323,11 +1337,13 @@ int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, c
                     static std::atomic<unsigned long long> cap_seen{0};                        \
                     if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
                     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds_fast, st, a, n_groups, rows_per_group); \
+                    g_last_small_route.store(route_word(NDCN_SSR_BWD, NDCN_SSR_FAST, IT_, false, HT_, true, false, NDCN_M_EULER) | NDCN_SSR_SYMMETRIC, std::memory_order_relaxed); \
                 } else {                                                                       \
                     auto kern = solve_small_bwd_fast_kernel<IT_, HT_, false>;                  \
                     static std::atomic<unsigned long long> cap_seen{0};                        \
                     if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; } \
                     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds_fast, st, a, n_groups, rows_per_group); \
+                    g_last_small_route.store(route_word(NDCN_SSR_BWD, NDCN_SSR_FAST, IT_, false, HT_, false, false, NDCN_M_EULER) | NDCN_SSR_SYMMETRIC, std::memory_order_relaxed); \
                 }                                                                              \
             } while (0)
             // (9 passes: the README's 400 x 20 - the 12-pass build of the same kernel spills 22 registers)
@@ -1341,6 +1357,7 @@ int solve_small_bwd_f32(const ndcn_csr *A, const ndcn_csr *At, const float *W, c
             static std::atomic<unsigned long long> cap_seen{0};                                                       \
             if (once_per_device(cap_seen)) { int rc_ = set_lds_cap(kern); if (rc_) return rc_; }       \
             hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, st, a, symmetric);              \
+            g_last_small_route.store(route_word(NDCN_SSR_BWD, NDCN_SSR_GENERIC, IT_, C_, 0, false, false, NDCN_M_EULER) | (symmetric ? NDCN_SSR_SYMMETRIC : 0), std::memory_order_relaxed); \
         } while (0)
         if (np <= 4) { if (csr) NDCN_GO(4, true); else NDCN_GO(4, false); }
         else { if (csr) NDCN_GO(12, true); else NDCN_GO(12, false); }
