@@ -740,6 +740,8 @@ NDCN_API int ndcn_solver_advance_many(ndcn_solver *s, const double *h_ticks, int
 #define NDCN_READOUT_STAGED  2      /* a dopri5 tick was evaluated into `scratch` and decoded from there                            */
 #define NDCN_READOUT_FIXED   4      /* fixed grid: the state decoded after each step                                                */
 #define NDCN_READOUT_NARROW  8      /* beside FUSED: H < 64, the 64-row tile kernel (readout_narrow_kernel<ceil(H / 16)>)           */
+/* (set by the ndcn_solve_*_adams_readout_f32 calls below, which also set FIXED for their staged decodes and NARROW beside ADAMS)  */
+#define NDCN_READOUT_ADAMS   (1 << 4)   /* = 16: the fused Adams-Bashforth step + decode kernel ran (ndcn_ab_step_readout_f32)            */
 NDCN_API int ndcn_solver_advance_many_readout(ndcn_solver *s, const double *h_ticks, int64_t n_ticks, const float *Wd, const float *bd,
                                               int C, float *out, float *scratch, void *stream);
 NDCN_API int ndcn_last_readout_path(void);
@@ -924,6 +926,40 @@ NDCN_API int ndcn_solve_fixed_adams_f32(const ndcn_csr *A, const float *W, const
                                         const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
                                         const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol, int max_iters,
                                         float *out, int *h_iters, int *h_converged, void *workspace, int64_t workspace_bytes, void *stream);
+/* The two multistep solves with the decoder Linear(H, C) inside (inference: neural_dynamics.py:148-160 decodes every tick, and the
+ * (n_ticks, n_rows, H) trajectory is the largest allocation of such a pass).  Three calls added to ABI 29: no existing declaration
+ * changes, the existing calls keep their launches and bits.
+ * ndcn_ab_step_readout_f32: ndcn_ab_step_f32 on a panel of n_rows x H - the same arithmetic, `out` bit for bit - that ALSO writes
+ *     dec [n_rows][C] = Wd * s + bd,   s = the new state (emit_off == 0) or s = state + ((state - state) / dt) * emit_off
+ *   (emit_off != 0: a tick strictly inside the step, the expression of ndcn_tick_emit_f32: -0 becomes +0, Inf becomes NaN; the state
+ *   that is STORED is never transformed) in the same pass, bit for bit ndcn_linear_f32 of that panel: Wd [C][H] and bd [C] (nullable)
+ *   in device memory.  64 <= H <= 512: a wave per row, the fma chain / butterfly / bias of the decoder's row-dot route; H = 16, 20,
+ *   .. 60: a workgroup per tile of 64 rows staged in LDS, one in-order fma chain per (row, output) as its small route.  NDCN_EINVAL -
+ *   before any launch - for C outside 1..15, any other H, n outside 3..11, a null panel, `out` equal to a history panel, `dec` equal to
+ *   `out` or y (out == y is allowed).  Any pointer alignment (H < 64: 16-byte loads where every panel is 16-byte aligned).
+ * ndcn_solve_explicit_adams_readout_f32 / ndcn_solve_fixed_adams_readout_f32: ndcn_solve_explicit_adams_f32 / ndcn_solve_fixed_adams_f32
+ *   - the same arguments, checks, loop, launches, read-backs, h_iters / h_converged and workspace - with Wd, bd, C of the decoder (H and C
+ *   as above, NDCN_EINVAL otherwise) and
+ *     out                    n_ticks panels of n_rows x C: out[j] = Wd * tick_j + bd, bit for bit ndcn_linear_f32 of the tick panel the
+ *                            un-decoded solve writes.  No hidden tick is written: the state alternates between the workspace's two panels.
+ *   explicit_adams at order >= 3: a step that reports ticks runs ndcn_ab_step_readout_f32's kernel (its first 8 ticks in one launch), a
+ *   step that reports none ndcn_ab_step_f32.  RK4 warm-up steps and every step of fixed_adams (which iterate of the corrector is final is
+ *   known only after the read-back) run as in the un-decoded solve, then ndcn_linear_f32 decodes the state's panel - a tick inside the
+ *   step through ndcn_tick_emit_f32 into the workspace's stage-input panel first.  ndcn_last_readout_path (cleared on entry):
+ *   NDCN_READOUT_ADAMS for the fused kernel (NDCN_READOUT_NARROW beside it at H < 64), NDCN_READOUT_FIXED for the staged decodes.      */
+NDCN_API int ndcn_ab_step_readout_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt,
+                                      int64_t n_rows, int H, const float *Wd, const float *bd, int C, float *dec, float emit_off,
+                                      void *stream);
+NDCN_API int ndcn_solve_explicit_adams_readout_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags,
+                                                   const float *y0, const float *h_dt, int64_t n_steps, const int64_t *h_tick_step,
+                                                   const int *h_tick_same, const float *h_tick_off, int64_t n_ticks, int max_order,
+                                                   const float *Wd, const float *bd, int C, float *out, void *workspace,
+                                                   int64_t workspace_bytes, void *stream);
+NDCN_API int ndcn_solve_fixed_adams_readout_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                                const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                                const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol,
+                                                int max_iters, const float *Wd, const float *bd, int C, float *out, int *h_iters,
+                                                int *h_converged, void *workspace, int64_t workspace_bytes, void *stream);
 /* fixed_adams under a gradient (three more calls added to ABI 29: no existing declaration changes).
  * ndcn_fixed_adams_train_f32: ndcn_solve_fixed_adams_f32 - the same loop, launches, checks, read-backs, h_iters / h_converged and bits
  *   in `out` - that KEEPS what a reverse sweep needs in records the caller owns, in place of the history ring, the two state panels and

@@ -35,7 +35,9 @@ SPMM_LANES_SHIFT, SPMM_REC_SHIFT, SPMM_MODE_SHIFT, SPMM_RPB_SHIFT = 8, 16, 18, 2
  RKF_TICK_EMIT, RKF_FIXED_STAGE_EMIT, RKF_SCALE, RKF_COPY, RKF_RELU_BWD) = range(1, 14)
 RKF_KERNEL_MASK, RKF_OP_SHIFT, RKF_VEC, RKF_ATEN, RKF_PAR64, RKF_GRID_SHIFT = 0xff, 8, 0x1000, 0x2000, 0x4000, 32
 # ndcn_last_readout_path: what the last ndcn_solver_advance_many_readout call ran (include/ndcn_hip.h NDCN_READOUT_*)
+# and the ndcn_solve_*_adams_readout_f32 calls (READOUT_ADAMS: the fused Adams-Bashforth step + decode kernel)
 READOUT_FUSED, READOUT_STAGED, READOUT_FIXED, READOUT_NARROW = 1, 2, 4, 8
+READOUT_ADAMS = 16
 # ndcn_debug_last_small_route: the template arguments of the last one-launch solve / reverse sweep (include/ndcn_hip.h NDCN_SSR_*)
 SSR_FWD, SSR_BWD, SSR_GENERIC, SSR_FAST, SSR_RK = 1, 2, 4, 8, 12
 SSR_MAXIT_SHIFT, SSR_CSR_LDS, SSR_HT_SHIFT, SSR_KEEP, SSR_GRID, SSR_SYMMETRIC, SSR_METHOD_SHIFT = 4, 256, 9, 1 << 14, 1 << 15, 1 << 16, 17
@@ -287,6 +289,12 @@ SIGNATURES = {
     'ndcn_fixed_adams_workspace_bytes': (_L, [_L, _I, _I]),
     'ndcn_solve_fixed_adams_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
                                         ctypes.POINTER(_F), _L, _I, _F, _F, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _L, _P]),
+    'ndcn_ab_step_readout_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _F, _L, _I, _P, _P, _I, _P, _F, _P]),
+    'ndcn_solve_explicit_adams_readout_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
+                                                   ctypes.POINTER(_F), _L, _I, _P, _P, _I, _P, _P, _L, _P]),
+    'ndcn_solve_fixed_adams_readout_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),
+                                                ctypes.POINTER(_F), _L, _I, _F, _F, _I, _P, _P, _I, _P, ctypes.POINTER(_I),
+                                                ctypes.POINTER(_I), _P, _L, _P]),
     'ndcn_ab_adjoint_f32': (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_F), _I, _L, _P]),
     'ndcn_explicit_adams_train_workspace_bytes': (_L, [_L, _I]),
     'ndcn_explicit_adams_train_f32': (_I, [_CSR, _P, _P, _I, _U, _P, ctypes.POINTER(_F), _L, ctypes.POINTER(_L), ctypes.POINTER(_I),

@@ -6,6 +6,8 @@
 //                                    state panels in a caller-owned workspace, nothing read back
 //   ndcn_solve_fixed_adams_f32       the same loop with the Adams-Moulton corrector of fixed_adams (its two passes: adams_pc.hip) iterated per
 //                                    step; one 8-byte read-back per iteration - the host decides whether to iterate again
+//   (ab_step_readout_f32             ab_step_f32 that decodes the new state with a Linear(H, C) in the same pass: adams_readout.hip)
+//   ndcn_solve_*_adams_readout_f32   the two solves with that decoder: `out` holds decoded ticks, the state never leaves the workspace
 //   ndcn_explicit_adams_train_f32    the same loop (adams_run) writing every evaluation and every state into a caller-owned record: the
 //                                    forward pass of training (the reverse sweep: adams_bwd.hip, fixed_train.py)
 //   ndcn_fixed_adams_train_f32       the corrector loop with that record AND, per corrector evaluation, the pair (iterate, evaluation) in
@@ -24,28 +26,11 @@
 
 #pragma clang fp contract(off)
 
+#include "adams_step.h"
+
 namespace ndcn {
 
 namespace {
-
-constexpr int kAbMinTerms = 3;         // fixed_adams.py:146,174: below order 3 the step is RK4
-constexpr int kAbMaxTerms = 11;        // :147,163: max_order 12 keeps 11 evaluations
-constexpr int kAbMaxOrder = 12;
-
-struct AbArgs {
-    const float *f[kAbMaxTerms];       // newest first
-    float a[kAbMaxTerms];
-    const float *y;
-    float *out;
-    float dt;
-};
-
-__device__ __forceinline__ float ab1(float y, const float *f, const float *a, int n, float dt) {
-    float s = 0.f + a[0] * f[0];                            // Python's sum() starts from 0: a lone -0 product becomes +0
-#pragma unroll
-    for (int j = 1; j < n; ++j) s = s + a[j] * f[j];
-    return y + dt * s;
-}
 
 // Elements [head, head + 4 n4) by 16 bytes per lane - every panel is 16-byte aligned at element `head` -, the <= 3 elements in front and
 // the <= 3 behind by single lanes (n4 = 0: everything, panels that do not share an offset).  A grid-stride loop: the host sizes the
@@ -233,6 +218,12 @@ struct Corrector {
     int64_t *h_slot = nullptr;
 };
 
+// the decoder Linear(H, C) of a solve that reports decoded ticks: `out` is then n_ticks panels of n_rows x C and no hidden tick is written
+struct Decoder {
+    const float *Wd, *bd;
+    int C;
+};
+
 // an 8-byte pinned mirror of the device counter, owned by one solve
 struct PinnedCount {
     unsigned long long *p = nullptr;
@@ -282,7 +273,7 @@ int slots_exhausted(const char *who, int64_t step, int64_t cap) {
 int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0, const float *h_dt,
               int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same, const float *h_tick_off, int64_t n_ticks, int max_order,
               float *out, float *rec_f, float *rec_y, void *workspace, int64_t workspace_bytes, hipStream_t st,
-              const Corrector *pc = nullptr) {
+              const Corrector *pc = nullptr, const Decoder *dc = nullptr) {
     ADAMS_ARG(A && W && y0 && H > 0 && n_steps >= 0 && n_ticks >= 0, "null argument");
     ADAMS_ARG(A->n_rows >= 0 && A->n_rows < (1ll << 31) - 1 && A->nnz >= 0 && A->rowptr && (A->nnz == 0 || (A->colidx && A->val)), "bad operator");
     ADAMS_ARG(A->n_rows == A->n_cols, "an un-sharded solve: the operator must be square (no halo columns)");
@@ -293,6 +284,8 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
     for (int64_t j = 0; j < n_ticks; ++j)
         ADAMS_ARG(h_tick_step[j] >= (j ? h_tick_step[j - 1] : 0) && h_tick_step[j] < n_steps, "tick steps must be non-decreasing and below n_steps");
     const bool rec = rec_f != nullptr;
+    ADAMS_ARG(!dc || (!rec && dc->Wd && interp_readout_supported(H, dc->C)),
+              "the decoder needs 64 <= H <= 512 or H = 16, 20, .. 60, 1 <= C <= 15 and a solve without a record");
     ADAMS_ARG(!rec || n_steps == 0 || rec_y, "the record of the states is missing");
     ADAMS_ARG(!pc || (pc->max_iters >= 1 && (n_steps == 0 || (pc->h_iters && pc->h_converged))),
               "the corrector needs max_iters >= 1 and the two per-step host arrays");
@@ -348,14 +341,17 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
     int64_t next_slot = 0;                                     // of rec_u / rec_c
     std::vector<float *> outs;
     std::vector<int> zeros;
+    const size_t ostride = dc ? (size_t)A->n_rows * (size_t)dc->C : (size_t)n;      // of the caller's tick panels
     for (int64_t i = 0; i < n_steps; ++i) {
         const float dt = h_dt[i];
         int64_t j1 = j;
         while (j1 < n_ticks && h_tick_step[j1] == i) ++j1;
         // where the new state goes: its panel of the record; without one the caller's panel when the step's LAST tick is the state
         // itself (an end of the step; only the last tick of a step can be), else the state panel the step does not read
+        // (with a decoder the caller's panels hold decoded ticks: the state stays in the workspace)
         float *dst = rec ? rec_y + (size_t)i * (size_t)n
-                         : ((j1 > j && h_tick_same[j1 - 1]) ? out + (size_t)(j1 - 1) * (size_t)n : (y == state[0] ? state[1] : state[0]));
+                         : ((!dc && j1 > j && h_tick_same[j1 - 1]) ? out + (size_t)(j1 - 1) * (size_t)n : (y == state[0] ? state[1] : state[0]));
+        int64_t decoded_to = j;                                // ticks [j, decoded_to) were decoded by the step's own launch
         // fixed_adams.py:166-173: the new evaluation takes the place of the oldest one (a record keeps them all)
         int rc;
         newest = (newest + 1) % ring_n;
@@ -413,9 +409,44 @@ int adams_run(const char *who, const ndcn_csr *A, const float *W, const float *b
         } else {
             const float *f[kAbMaxTerms];
             for (int q = 0; q < order; ++q) f[q] = rec ? rec_f + (size_t)(i - q) * (size_t)n : ring[((newest - q) % ring_n + ring_n) % ring_n];
-            if ((rc = ab_step_f32(dst, y, f, weights[order], order, dt, n, st))) return rc;
+            if (dc && j1 > j) {
+                // the step and the decode of its first <= 8 ticks in one launch: a coincident tick decodes the state (offset 0), a tick
+                // inside the step the value of tick_emit_f32's expression
+                float *decs[kDecMaxTicks];
+                float tms[kDecMaxTicks];
+                const int m = (int)(j1 - j < kDecMaxTicks ? j1 - j : kDecMaxTicks);
+                for (int q = 0; q < m; ++q) {
+                    decs[q] = out + (size_t)(j + q) * ostride;
+                    tms[q] = h_tick_same[j + q] ? 0.f : h_tick_off[j + q];
+                    if (!h_tick_same[j + q] && tms[q] == 0.f) tms[q] = dt;      // (the expression's value does not depend on the offset)
+                }
+                if ((rc = ab_step_readout_f32(dst, y, f, weights[order], order, dt, A->n_rows, H, dc->Wd, dc->bd, dc->C, decs, tms, m, st)))
+                    return rc;
+                g_last_readout_path |= NDCN_READOUT_ADAMS | (H < 64 ? NDCN_READOUT_NARROW : 0);
+                decoded_to = j + m;
+            } else if ((rc = ab_step_f32(dst, y, f, weights[order], order, dt, n, st))) {
+                return rc;
+            }
         }
         y = dst;
+        if (dc) {
+            // the ticks the step's launch did not decode (warm-up steps, the corrector's steps, a ninth tick): the state's panel through
+            // the Linear - a tick inside the step through tick_emit_f32 into the stage input's panel, which no launch reads before the
+            // next warm-up stage writes it
+            for (int64_t q = decoded_to; q < j1; ++q) {
+                const float *src = dst;
+                if (!h_tick_same[q]) {
+                    const int zero = 0;
+                    float *const o1 = ytmp;
+                    if ((rc = tick_emit_f32(dst, dt, &h_tick_off[q], &zero, &o1, 1, n, st))) return rc;
+                    src = ytmp;
+                }
+                if ((rc = linear_f32(src, dc->Wd, dc->bd, out + (size_t)q * ostride, A->n_rows, H, dc->C, 0, st))) return rc;
+                g_last_readout_path |= NDCN_READOUT_FIXED;
+            }
+            j = j1;
+            continue;
+        }
         // solvers.py:95-97: the ticks this step reports - the coincident one IS dst; the others pass through the reference's expression
         outs.clear();
         std::vector<float> tm;
@@ -449,6 +480,33 @@ extern "C" {
 
 int ndcn_ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_elem, void *stream) {
     return ab_step_f32(out, y, h_f, h_a, n, dt, n_elem, static_cast<hipStream_t>(stream));
+}
+
+int ndcn_ab_step_readout_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n, float dt, int64_t n_rows, int H,
+                             const float *Wd, const float *bd, int C, float *dec, float emit_off, void *stream) {
+    return ab_step_readout_f32(out, y, h_f, h_a, n, dt, n_rows, H, Wd, bd, C, &dec, &emit_off, 1, static_cast<hipStream_t>(stream));
+}
+
+int ndcn_solve_explicit_adams_readout_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                          const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                          const float *h_tick_off, int64_t n_ticks, int max_order, const float *Wd, const float *bd, int C,
+                                          float *out, void *workspace, int64_t workspace_bytes, void *stream) {
+    g_last_readout_path = 0;
+    const Decoder dc = {Wd, bd, C};
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
+                     nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), nullptr, &dc);
+}
+
+int ndcn_solve_fixed_adams_readout_f32(const ndcn_csr *A, const float *W, const float *b, int H, uint32_t flags, const float *y0,
+                                       const float *h_dt, int64_t n_steps, const int64_t *h_tick_step, const int *h_tick_same,
+                                       const float *h_tick_off, int64_t n_ticks, int max_order, float rtol, float atol, int max_iters,
+                                       const float *Wd, const float *bd, int C, float *out, int *h_iters, int *h_converged, void *workspace,
+                                       int64_t workspace_bytes, void *stream) {
+    g_last_readout_path = 0;
+    const Corrector pc = {rtol, atol, max_iters, h_iters, h_converged};
+    const Decoder dc = {Wd, bd, C};
+    return adams_run(__func__, A, W, b, H, flags, y0, h_dt, n_steps, h_tick_step, h_tick_same, h_tick_off, n_ticks, max_order, out, nullptr,
+                     nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &pc, &dc);
 }
 
 int64_t ndcn_explicit_adams_workspace_bytes(int64_t n_rows, int H, int max_order) {

@@ -250,6 +250,10 @@ int fixed_stage_emit_f32(int op, float *out, const float *y, const float *k1, co
 // adams.hip: one Adams-Bashforth step of order n_terms = 3..11, out = y + dt * (((0 + a_0 f_0) + a_1 f_1) + ...), every product and sum
 // rounded on its own; h_f newest first; out may be y, never one of h_f; any alignment (16-byte lanes where all panels share an offset)
 int ab_step_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n_terms, float dt, int64_t n, hipStream_t st);
+// adams_readout.hip: the same step with h_dec[t] = Wd * s_t + bd written in the same pass, t < nt <= 8: s_t the new state (h_tm[t] == 0) or tick_emit_f32's
+// expression of it at offset h_tm[t]; bit for bit linear_f32 of that panel.  H, C: interp_readout_supported
+int ab_step_readout_f32(float *out, const float *y, const float *const *h_f, const float *h_a, int n_terms, float dt, int64_t n_rows, int H,
+                        const float *Wd, const float *bd, int C, float *const *h_dec, const float *h_tm, int nt, hipStream_t st);
 // workgroups of a streaming launch over `items` work items of 256 lanes: eight per compute unit of the current device, fewer for less work
 int ab_grid(int64_t items);
 // adams_bwd.hip: the gradient of one evaluation gathered from the adjoints of the Adams-Bashforth steps that used it,

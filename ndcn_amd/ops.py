@@ -40,6 +40,7 @@ def _terms(ks, cs):
 # read-back of one reduction is one critical section.
 _REDUCE_LOCK = threading.RLock()
 _ADAMS_FUSED_OVERRIDE = None        # HipOps.set_adams_fused; None: the environment's NDCN_ADAMS_FUSED
+_ADAMS_READOUT_OVERRIDE = None      # HipOps.set_adams_readout; None: the environment's NDCN_ADAMS_READOUT
 _TGCN_FUSED_OVERRIDE = None         # HipOps.set_tgcn_fused; None: the environment's NDCN_TGCN_FUSED
 
 
@@ -826,6 +827,33 @@ class HipOps:
             return _ADAMS_FUSED_OVERRIDE
         return 1 if _lib.env_int('NDCN_ADAMS_FUSED', 1) > 0 else 0
 
+    # ---------------------------------------------------------------- explicit_adams / fixed_adams inference: the decoder inside the solve
+    @staticmethod
+    def set_adams_readout(mode):
+        """odeint(..., method='explicit_adams' | 'fixed_adams', readout=...) without a gradient decodes each tick inside the library's
+        solve (ndcn_solve_*_adams_readout_f32, csrc/adams.hip): 0 off - the solve stores the hidden trajectory and the Linear runs over
+        it afterwards -, 1 on; < 0: the environment's (NDCN_ADAMS_READOUT, default 1).  The results are the same bits either way.
+        Process-wide; returns the previous mode."""
+        global _ADAMS_READOUT_OVERRIDE
+        prev = HipOps.adams_readout_on()
+        _ADAMS_READOUT_OVERRIDE = None if int(mode) < 0 else (1 if int(mode) else 0)
+        return prev
+
+    @staticmethod
+    def adams_readout_on():
+        if _ADAMS_READOUT_OVERRIDE is not None:
+            return _ADAMS_READOUT_OVERRIDE
+        return 1 if _lib.env_int('NDCN_ADAMS_READOUT', 1) > 0 else 0
+
+    @staticmethod
+    def adams_readout_route(H, C, weight_ok=True, needs_grad=False, enabled=True):
+        """Does a device-resident explicit_adams / fixed_adams solve at hidden width H take the decoder (C, H) inside the library?  The
+        admissible shapes of ndcn_ab_step_readout_f32 - H = 16, 20, .. 60 (the decoder's small route) or 64 <= H <= 512 (its row-dot
+        route), 1 <= C <= 15 -, a float32 device weight of that shape (weight_ok), no gradient asked of the decoder, the switch on."""
+        wide = 64 <= H <= 512
+        narrow = 16 <= H <= 60 and H % 4 == 0
+        return bool(enabled and weight_ok and not needs_grad and (wide or narrow) and 1 <= C <= 15)
+
     @staticmethod
     def adams_fusable(*panels):
         """May core.Adams.step take the three-pass form for these panels of one state tensor?  Contiguous float32 device panels of more
@@ -1107,6 +1135,25 @@ class HipOps:
         with torch.cuda.device(y.device):
             check(_lib.load().ndcn_ab_step_f32(ptr(out), ptr(y), arr_f, arr_a, n, float(dt), y.numel(), stream_ptr()))
         return out
+
+    @staticmethod
+    def ab_step_readout(y, fs, coeffs, dt, weight, bias=None, emit_off=0.0, out=None):
+        """(new state, decoded): ab_step on an (N, H) panel that also writes linear(s, weight, bias), shape (N, C), in the same launch
+        (ndcn_ab_step_readout_f32) - s the new state, or with emit_off != 0 the tick s + ((s - s) / dt) * emit_off of a sub-stepped
+        grid; the bits of hip.linear on that panel.  H = 16, 20, .. 60 or 64 <= H <= 512, C <= 15; out may be y."""
+        y = _panel(y)
+        fs = [_panel(f) for f in fs]
+        assert y.dim() == 2 and weight.dim() == 2 and weight.shape[1] == y.shape[1]
+        weight = _panel(weight)
+        bias = None if bias is None else _panel(bias)
+        if out is None:
+            out = torch.empty_like(y)
+        dec = torch.empty((y.shape[0], weight.shape[0]), dtype=torch.float32, device=y.device)
+        arr_f, arr_a, n = _terms(fs, coeffs)
+        with torch.cuda.device(y.device):
+            check(_lib.load().ndcn_ab_step_readout_f32(ptr(out), ptr(y), arr_f, arr_a, n, float(dt), y.shape[0], y.shape[1], ptr(weight),
+                                                       ptr(bias), weight.shape[0], ptr(dec), float(emit_off), stream_ptr()))
+        return out, dec
 
     @staticmethod
     def abm_predict(y, fs, a, m, dt):

@@ -74,7 +74,11 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_lo
     readout=(weight (C, H), bias (C,) or None): return `linear(odeint(...), weight, bias)`, shape (len(t), N, C), instead of the
     hidden states (neural_dynamics.py:148-160: NDCN decodes every tick).  Where nothing needs a gradient and the solve is
     device-resident, the library decodes each tick as the solver produces it (ndcn_solver_advance_many_readout: H = 16, 20, .. 60
-    or 64 <= H <= 512, C <= 15) and the (len(t), N, H) trajectory is never stored; under a gradient, euler / midpoint / rk4 over ODEFunc on the fused-launch training
+    or 64 <= H <= 512, C <= 15) and the (len(t), N, H) trajectory is never stored - dopri5, euler, midpoint and rk4 on the grid of `t`,
+    and explicit_adams / fixed_adams on any of their grids, `step_size` included (ndcn_solve_explicit_adams_readout_f32 /
+    ndcn_solve_fixed_adams_readout_f32: an Adams-Bashforth step that reports ticks decodes them in its own launch, RK4 warm-up steps
+    and the corrector's steps decode the state they leave in the workspace; NDCN_ADAMS_READOUT=0 / hip.set_adams_readout(0) restores
+    decode-after for these two methods); under a gradient, euler / midpoint / rk4 over ODEFunc on the fused-launch training
     path hold the decoder inside the solve's autograd node: the trajectory is stored once (the reverse sweep needs it) but the
     (len(t), N, H) gradient of it, which the Linear's own backward would write, is not - the sweep forms each tick's g . W where it
     adds it (ndcn_readout_bwd_f32); everywhere else the ordinary solve runs and the Linear is applied to its result - the
@@ -216,17 +220,17 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
     elif method == 'fixed_adams':
         out = None
         if _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-            out = _fixed_adams_solve(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log)
+            out = _fixed_adams_solve(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log, readout)
         if out is not None:
-            return out, False
+            return out                                      # (solution, decoded)
         sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan, max_order=options['max_order'],
                                    max_iters=max_iters, rtol=rtol, atol=atol, step_log=step_log)
     elif method == 'explicit_adams':
         out = None
         if _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-            out = _explicit_adams_solve(user_func, y0[0], t, plan, options['max_order'])
+            out = _explicit_adams_solve(user_func, y0[0], t, plan, options['max_order'], readout)
         if out is not None:
-            return out, False
+            return out                                      # (solution, decoded)
         sol = core.integrate_fixed(hip, func, y0, t, method, autonomous=_autonomous(user_func), plan=plan, max_order=options['max_order'])
     elif _device_resident_ok(user_func, tensor_input, y0, t_user, method, options, allow_truth=True):
         return _device_resident(user_func, y0[0], t, rtol, atol, method, options, step_log, plan, readout)
@@ -459,11 +463,29 @@ def _small_operator(odefunc, y0):
     return csr, csr.view_ref(), flags
 
 
-def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
-    """The whole explicit_adams solve of a plain ODEFunc inside the library (ndcn_solve_explicit_adams_f32: RK4 warm-up, then one
-    right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the current stream without
-    a read-back.  None where the entry point has no form: no_graph / no_control, an operator that does not live with the state, a
-    max_order the reference itself fails on."""
+def _adams_decoder(readout, y0):
+    """(Wd, bd) for the decoder inside the library's explicit_adams / fixed_adams solve (ndcn_solve_*_adams_readout_f32), or None: no
+    readout, a gradient asked of it, a weight that is not a float32 device (C, H) tensor, a shape outside hip.adams_readout_route, or
+    the switch off (NDCN_ADAMS_READOUT=0 / hip.set_adams_readout(0)) - the solve then stores the hidden ticks and odeint decodes them."""
+    if readout is None:
+        return None
+    Wd, bd = readout
+    if not torch.is_tensor(Wd) or Wd.dim() != 2 or (bd is not None and not torch.is_tensor(bd)):
+        return None
+    needs_grad = torch.is_grad_enabled() and (Wd.requires_grad or (bd is not None and bd.requires_grad))
+    weight_ok = Wd.shape[1] == y0.shape[1] and Wd.device == y0.device and Wd.is_cuda and Wd.dtype == torch.float32 and \
+        (bd is None or (bd.shape == (Wd.shape[0],) and bd.device == Wd.device and bd.dtype == torch.float32))
+    if not hip.adams_readout_route(y0.shape[1], Wd.shape[0], weight_ok, needs_grad, hip.adams_readout_on()):
+        return None
+    return Wd.detach().contiguous(), None if bd is None else bd.detach().contiguous()
+
+
+def _explicit_adams_solve(odefunc, y0, t, plan, max_order, readout=None):
+    """(solution, decoded): the whole explicit_adams solve of a plain ODEFunc inside the library (ndcn_solve_explicit_adams_f32: RK4
+    warm-up, then one right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the
+    current stream without a read-back.  With a `readout` that _adams_decoder admits, ndcn_solve_explicit_adams_readout_f32: the
+    solution is (len(t), N, C), each tick decoded by the launch that forms it, and no hidden tick is stored.  None where the entry
+    point has no form: no_graph / no_control, an operator that does not live with the state, a max_order the reference itself fails on."""
     if odefunc.no_graph or odefunc.no_control or max_order < 2:
         return None
     op = _small_operator(odefunc, y0)
@@ -476,27 +498,41 @@ def _explicit_adams_solve(odefunc, y0, t, plan, max_order):
     lib = _lib.load()
     H = odefunc.hidden_size
     n_ticks = len(plan.t)
-    out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-    out[0].copy_(y0)
+    dec = _adams_decoder(readout, y0)
+    if dec is not None:
+        y0 = y0.contiguous()
+        out = torch.empty((n_ticks, y0.shape[0], dec[0].shape[0]), dtype=torch.float32, device=y0.device)
+        out[0].copy_(hip.linear(y0, dec[0], dec[1]))
+    else:
+        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
     dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
     if n_steps == 0 or y0.numel() == 0:
-        return out
+        return out, dec is not None
     csr.ensure_plans(H)
     view = csr.view_ref()
     W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
     b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
     nbytes = int(lib.ndcn_explicit_adams_workspace_bytes(y0.shape[0], H, max_order))
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
+    if dec is not None:
+        with torch.cuda.device(y0.device):
+            _lib.check(lib.ndcn_solve_explicit_adams_readout_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(y0), dts, n_steps, steps,
+                                                                 same, offs, n_emit, max_order, _lib.ptr(dec[0]), _lib.ptr(dec[1]),
+                                                                 dec[0].shape[0], _lib.ptr(out[1:]) if n_emit else None,
+                                                                 _lib.ptr(workspace), nbytes, _lib.stream_ptr()))
+        return out, True
     with torch.cuda.device(y0.device):
         _lib.check(lib.ndcn_solve_explicit_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
                                                      offs, n_emit, max_order, _lib.ptr(out[1:]) if n_emit else None, _lib.ptr(workspace),
                                                      nbytes, _lib.stream_ptr()))
     # (the workspace goes back to torch's stream-ordered allocator: a later allocation on this stream is ordered behind the solve)
-    return out
+    return out, False
 
 
-def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None):
-    """The whole fixed_adams solve of a plain ODEFunc inside the library (ndcn_solve_fixed_adams_f32: the launches of the explicit solve,
+def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None, readout=None):
+    """(solution, decoded; `readout` as in _explicit_adams_solve: ndcn_solve_fixed_adams_readout_f32 decodes the accepted iterate of every
+    reporting step, the iteration counts, warning lines and step_log are those of the un-decoded solve).  The whole fixed_adams solve of a plain ODEFunc inside the library (ndcn_solve_fixed_adams_f32: the launches of the explicit solve,
     then per step one ndcn_abm_predict_f32 and up to max_iters x (right-hand side + ndcn_abm_correct_f32 + an 8-byte read-back)).  The
     reference's warning line is written here, once per step the library reports as not converged.  None where the entry point has no
     form: as _explicit_adams_solve, and a max_iters or tolerances that are not plain numbers (the generic branch fails on them as the
@@ -515,13 +551,19 @@ def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, s
     lib = _lib.load()
     H = odefunc.hidden_size
     n_ticks = len(plan.t)
-    out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-    out[0].copy_(y0)
+    dec = _adams_decoder(readout, y0)
+    if dec is not None:
+        y0 = y0.contiguous()
+        out = torch.empty((n_ticks, y0.shape[0], dec[0].shape[0]), dtype=torch.float32, device=y0.device)
+        out[0].copy_(hip.linear(y0, dec[0], dec[1]))
+    else:
+        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
     dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
     if n_steps == 0 or y0.numel() == 0:
         if step_log is not None:
             step_log.extend([(0, True)] * n_steps + [('nfe', 0)])
-        return out
+        return out, dec is not None
     csr.ensure_plans(H)
     view = csr.view_ref()
     W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
@@ -530,10 +572,16 @@ def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, s
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
     iters, conv = (ctypes.c_int * n_steps)(), (ctypes.c_int * n_steps)()
     with torch.cuda.device(y0.device):
-        _lib.check(lib.ndcn_solve_fixed_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
-                                                  offs, n_emit, max_order, float(rtol), float(atol), max_iters,
-                                                  _lib.ptr(out[1:]) if n_emit else None, iters, conv, _lib.ptr(workspace), nbytes,
-                                                  _lib.stream_ptr()))
+        if dec is not None:
+            _lib.check(lib.ndcn_solve_fixed_adams_readout_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(y0), dts, n_steps, steps, same,
+                                                              offs, n_emit, max_order, float(rtol), float(atol), max_iters, _lib.ptr(dec[0]),
+                                                              _lib.ptr(dec[1]), dec[0].shape[0], _lib.ptr(out[1:]) if n_emit else None,
+                                                              iters, conv, _lib.ptr(workspace), nbytes, _lib.stream_ptr()))
+        else:
+            _lib.check(lib.ndcn_solve_fixed_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
+                                                      offs, n_emit, max_order, float(rtol), float(atol), max_iters,
+                                                      _lib.ptr(out[1:]) if n_emit else None, iters, conv, _lib.ptr(workspace), nbytes,
+                                                      _lib.stream_ptr()))
     for c in conv:
         if not c:
             print(core.NOT_CONVERGED, file=sys.stderr)      # fixed_adams.py:198
@@ -541,7 +589,7 @@ def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, s
         warm = sum(1 for i, c in zip(iters, conv) if i == 0)
         step_log.extend((int(i), bool(c)) for i, c in zip(iters, conv))
         step_log.append(('nfe', n_steps + 3 * warm + sum(iters)))
-    return out
+    return out, dec is not None
 
 
 def _small_solve(odefunc, y0, tt, method, plan=None):
