@@ -13,6 +13,9 @@ autograd nodes, one per route, each differentiated the way the reference's drive
   _FixedAdamsSolve   method='fixed_adams' (the same switch): that loop with the Adams-Moulton corrector, a record of every corrector
                      evaluation too, the reverse of a predictor-corrector step in closed form.
 
+Which solves the two Adams nodes take is decided in one place, with the solve without a gradient: _adams_admission, plus the nodes'
+own declines in _adams_with_grad.
+
 The last five take the decoder of odeint's `readout` as an optional input (Wd, bd; None without one).  With it the node's output is
 the decoded solution (T, N, C) - hip.linear of the trajectory, the bits of the two-step form - the hidden trajectory is saved for the
 reverse sweep only, and that sweep takes the (T, N, C) gradient as it is: the (T, N, H) gradient of the trajectory is never written.
@@ -65,6 +68,19 @@ def _finish(scratch, rc):
         if err is not None:
             raise err
         check(rc)
+
+
+def _small_operator(odefunc, y0):
+    """(csr or None, ctypes view ref, flags) of an ODEFunc for the library's whole-solve entry points, or None when the operator
+    does not live with the state."""
+    from ...csr import as_csr
+    flags = _lib.operator_flags(odefunc)
+    if odefunc.no_graph:
+        return None, ctypes.byref(_lib.empty_csr(y0.shape[0])), flags
+    csr = as_csr(odefunc.A)
+    if csr.device != y0.device or csr.shape[0] != y0.shape[0]:
+        return None
+    return csr, csr.view_ref(), flags
 
 
 def _drop_at(drop, method, step):
@@ -430,7 +446,8 @@ class _SubstepSolve(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------
-# explicit_adams: the library's forward loop with a record, the reverse sweep of a multistep method
+# explicit_adams: the library's forward loop with a record, the reverse sweep of a multistep method - first what it shares with
+# fixed_adams below and with the solve without a gradient (odeint._adams_solve): admission, report, record, the sweeps' tick handling
 # ---------------------------------------------------------------------------------------------------
 
 def plan_arrays(plan):
@@ -444,6 +461,91 @@ def plan_arrays(plan):
     same = (ctypes.c_int * max(n_emit, 1))(*[int(v) for v in plan.tick_coincident[1:]])
     offs = (ctypes.c_float * max(n_emit, 1))(*[float(np.float32(plan.t[j] - plan.grid[plan.tick_step[j]])) for j in range(1, n_ticks)])
     return dts, n_steps, steps, same, offs, n_emit
+
+
+def _adams_admission(odefunc, y0, t, plan, max_order, corrector=None):
+    """May the explicit_adams / fixed_adams solve of a plain ODEFunc run inside the library?  -> (csr, flags, plan, contiguous y0) - the
+    default plan where `plan` is None - or None.  The one statement of the decline reasons, for the solve without a gradient
+    (odeint._adams_solve) and the training nodes (_adams_with_grad) alike:
+      * no_graph or no_control (the entry points have no such form);
+      * max_order < 2 (the reference itself fails on it);
+      * an operator that does not live with the state (_small_operator);
+      * with corrector = (rtol, atol, max_iters, step_log), fixed_adams: a max_iters that is not an int >= 1, tolerances that are not
+        plain numbers (the generic branch fails on them as the reference does).
+    Every decline comes before the check of `t`: a declined solve gets the generic path's own exception."""
+    if odefunc.no_graph or odefunc.no_control or max_order < 2:
+        return None
+    if corrector is not None:
+        rtol, atol, max_iters = corrector[:3]
+        if type(max_iters) is not int or max_iters < 1 or not all(isinstance(v, (int, float)) for v in (rtol, atol)):
+            return None
+    op = _small_operator(odefunc, y0)
+    if op is None:
+        return None
+    csr, _, flags = op
+    core.assert_increasing(t)
+    if plan is None:
+        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    return csr, flags, plan, _lib.require_device(y0, 'state y0').contiguous()
+
+
+def _report_corrector(step_log, iters, conv):
+    """what a fixed_adams solve inside the library tells its caller: the reference's warning line once per step that did not converge,
+    and in step_log one (corrector iterations, converged) pair per grid step - (0, True) for a warm-up step - and ('nfe', evaluations)"""
+    for c in conv:
+        if not c:
+            print(core.NOT_CONVERGED, file=sys.stderr)            # fixed_adams.py:198
+    if step_log is not None:
+        warm = sum(1 for i in iters if i == 0)
+        step_log.extend((int(i), bool(c)) for i, c in zip(iters, conv))
+        step_log.append(('nfe', len(iters) + 3 * warm + sum(iters)))
+
+
+def _adams_record(y0c, plan):
+    """(out, rec_f, rec_y) of a training solve: the ticks (y0 first), f_i = F(y_i) of every grid step and the state after it"""
+    shape = tuple(y0c.shape)
+    new = lambda n: torch.empty((n,) + shape, dtype=torch.float32, device=y0c.device)
+    out = new(len(plan.t))
+    out[0].copy_(y0c)
+    # the default grid: step i reports tick i + 1 and nothing else, the state after it - no state is stored twice
+    return out, new(len(plan.dts)), (out[1:] if plan.default else new(len(plan.dts)))
+
+
+def _adams_sweep_open(ctx, g, out, W, b, Wd, csr, plan):
+    """(ticks, the totals of _sweep_totals, the adjoint at the last tick - None on a step_size plan, whose ticks enter step by step)"""
+    ticks = _ticks(ctx, g, out, Wd)
+    totals = _sweep_totals(out, csr, W, b, False, False, None)
+    return ticks, totals, (ticks.seed(len(plan.dts)) if plan.default else None)
+
+
+def _adams_sweep_enter(ticks, plan, out, a, i):
+    """(the adjoint of the state after grid step i, the step's closing pass): on a step_size plan the ticks the step reported enter at the
+    state it ends in and the step closes without one; on the default grid the tick the step starts from rides in its closing pass"""
+    if plan.default:
+        return a, lambda a, gus: ticks.close(a, gus, i)
+    if plan.emits[i]:
+        a = ticks.enter(a, [e[0] for e in plan.emits[i]])
+    return (torch.zeros_like(out[0]) if a is None else a), _sum_onto
+
+
+def _adams_sweep_close(ticks, plan, a, gW_tot, gb_tot, b, n_rest):
+    """the gradients a node returns: of y0, W, b, the decoder's two, None for the n_rest other inputs"""
+    if not plan.default:
+        a = ticks.enter(a, [0])                                   # the first tick is y0 itself
+    return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * n_rest
+
+
+def _warmup_reverse(csr, Wc, bc, y, f, dt, a, vj, acc, close, gf):
+    """the adjoint before an RK4 warm-up step: its stages re-formed from the stored y and f = F(y) by the forward loop's own calls
+    (fixed_stage ops 2..4, the plain right-hand side: its bits), then _sweep_step's closed form with gf - the gradient f gathers as a
+    history term of later steps - one more addend of the gradient of k1"""
+    u2 = hip.fixed_stage(2, y, f, dt=dt)
+    K2 = hip.rhs(csr, u2, Wc, bc)
+    u3 = hip.fixed_stage(3, y, f, K2, dt=dt)
+    K3 = hip.rhs(csr, u3, Wc, bc)
+    u4 = hip.fixed_stage(4, y, f, K2, K3, dt=dt)
+    K4 = hip.rhs(csr, u4, Wc, bc)
+    return _sweep_step('rk4', dt, [(y, f), (u2, K2), (u3, K3), (u4, K4)], a, vj, acc, close, gk1_extra=gf)
 
 
 class _ExplicitAdamsSolve(torch.autograd.Function):
@@ -468,11 +570,7 @@ class _ExplicitAdamsSolve(torch.autograd.Function):
         y0c, Wc, bc = _detached(y0, W, b)
         dts, n_steps, steps, same, offs, n_emit = plan_arrays(plan)
         shape, H = tuple(y0c.shape), y0c.shape[1]
-        out = torch.empty((n_emit + 1,) + shape, dtype=torch.float32, device=y0c.device)
-        out[0].copy_(y0c)
-        rec_f = torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
-        # the default grid: step i reports tick i + 1 and nothing else, the state after it - no state is stored twice
-        rec_y = out[1:] if plan.default else torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
+        out, rec_f, rec_y = _adams_record(y0c, plan)
         nbytes = int(lib.ndcn_explicit_adams_train_workspace_bytes(shape[0], H))
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0c.device)
         with torch.cuda.device(y0c.device):
@@ -491,16 +589,10 @@ class _ExplicitAdamsSolve(torch.autograd.Function):
         rec_y = own[0] if own else out[1:]
         Wc, bc = _detached(W, b)
         dts = plan.dts
-        n_steps = len(dts)
-        ticks = _ticks(ctx, g, out, Wd)
-        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, False, False, None)
+        ticks, (gW_tot, gb_tot, vj, acc), a = _adams_sweep_open(ctx, g, out, W, b, Wd, csr, plan)
         lam = {}                                                  # the adjoints that evaluations still to come gather from
-        a = ticks.seed(n_steps) if plan.default else None
-        for i in range(n_steps - 1, -1, -1):
-            if not plan.default and plan.emits[i]:                # the ticks step i reported enter at the state it ends in
-                a = ticks.enter(a, [e[0] for e in plan.emits[i]])
-            if a is None:
-                a = torch.zeros_like(out[0])
+        for i in range(len(dts) - 1, -1, -1):
+            a, close = _adams_sweep_enter(ticks, plan, out, a, i)
             lam[i + 1] = a
             lam.pop(i + max_order, None)
             terms = core.ab_adjoint_terms(i, dts, max_order)
@@ -508,19 +600,10 @@ class _ExplicitAdamsSolve(torch.autograd.Function):
             y, f, dt = (out[0] if i == 0 else rec_y[i - 1]), rec_f[i], float(dts[i])
             if min(i + 1, max_order - 1) >= core.AB_MIN_ORDER - 1:
                 gu, _, _ = hip.rhs_vjp(csr, y, Wc, f, gf, need_b=bc is not None, gW=gW_tot, gb=gb_tot)
-                a = ticks.close(a, [gu], i) if plan.default else _sum_onto(a, [gu])
+                a = close(a, [gu])
             else:
-                u2 = hip.fixed_stage(2, y, f, dt=dt)
-                K2 = hip.rhs(csr, u2, Wc, bc)
-                u3 = hip.fixed_stage(3, y, f, K2, dt=dt)
-                K3 = hip.rhs(csr, u3, Wc, bc)
-                u4 = hip.fixed_stage(4, y, f, K2, K3, dt=dt)
-                K4 = hip.rhs(csr, u4, Wc, bc)
-                close = (lambda a, gus, i=i: ticks.close(a, gus, i)) if plan.default else _sum_onto
-                a = _sweep_step('rk4', dt, [(y, f), (u2, K2), (u3, K3), (u4, K4)], a, vj, acc, close, gk1_extra=gf)
-        if not plan.default:
-            a = ticks.enter(a, [0])                               # the first tick is y0 itself
-        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 4
+                a = _warmup_reverse(csr, Wc, bc, y, f, dt, a, vj, acc, close, gf)
+        return _adams_sweep_close(ticks, plan, a, gW_tot, gb_tot, b, 4)
 
 
 def adams_train_enabled():
@@ -529,27 +612,30 @@ def adams_train_enabled():
     return _lib.env_str('NDCN_ADAMS_TRAIN', '0') == '1'
 
 
-def _explicit_adams_with_grad(odefunc, y0, t, plan, max_order, readout=None):
-    """explicit_adams over a plain ODEFunc under a gradient on _ExplicitAdamsSolve, or None where the node has no form: the switch is
-    off, `t` requires grad, no_graph / no_control, an operator that does not live with the state, a max_order the reference fails on,
-    fewer than two ticks.  readout = (Wd, bd) (checked by _readout_for_grad): the decoded solution, the decoder inside the node."""
-    from .odeint import _small_operator
-    if not adams_train_enabled() or t.requires_grad or t.numel() < 2 or max_order < 2 or odefunc.no_graph or odefunc.no_control:
+def _adams_with_grad(odefunc, y0, t, plan, max_order, readout, corrector=None):
+    """explicit_adams (corrector None: _ExplicitAdamsSolve) or fixed_adams (corrector = (rtol, atol, max_iters, step_log):
+    _FixedAdamsSolve) over a plain ODEFunc under a gradient on its node, or None where the node has no form: what _adams_admission
+    declines, and the nodes' own - the switch off, a `t` that requires grad, fewer than two ticks, an empty state.
+    readout = (Wd, bd) (checked by _readout_for_grad): the decoded solution, the decoder inside the node."""
+    if not adams_train_enabled() or t.requires_grad or t.numel() < 2:
         return None
-    op = _small_operator(odefunc, y0)
-    if op is None:
+    admitted = _adams_admission(odefunc, y0, t, plan, max_order, corrector)
+    if admitted is None or admitted[3].numel() == 0:
         return None
-    csr, _, flags = op
-    core.assert_increasing(t)
-    if plan is None:
-        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
-    y0 = _lib.require_device(y0, 'state y0').contiguous()
-    if y0.numel() == 0:
-        return None
+    csr, flags, plan, y0 = admitted
     csr.ensure_plans(y0.shape[1])
-    csr.transpose().ensure_plans(y0.shape[1])
+    csr.transpose().ensure_plans(y0.shape[1])                    # (the reverse sweep's; the solve without a gradient builds none)
     Wd, bd = readout if readout is not None else (None, None)
-    return _ExplicitAdamsSolve.apply(y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order)
+    args = (y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order)
+    return _ExplicitAdamsSolve.apply(*args) if corrector is None else _FixedAdamsSolve.apply(*args, *corrector)
+
+
+def _explicit_adams_with_grad(odefunc, y0, t, plan, max_order, readout=None):
+    return _adams_with_grad(odefunc, y0, t, plan, max_order, readout)
+
+
+def _fixed_adams_with_grad(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None, readout=None):
+    return _adams_with_grad(odefunc, y0, t, plan, max_order, readout, (rtol, atol, max_iters, step_log))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -601,13 +687,9 @@ class _FixedAdamsSolve(torch.autograd.Function):
     def forward(ctx, y0, W, b, Wd, bd, csr, flags, plan, max_order, rtol, atol, max_iters, step_log):
         y0c, Wc, bc = _detached(y0, W, b)
         arrays = plan_arrays(plan)
-        n_steps, n_emit = arrays[1], arrays[5]
-        shape = tuple(y0c.shape)
-        out = torch.empty((n_emit + 1,) + shape, dtype=torch.float32, device=y0c.device)
-        out[0].copy_(y0c)
-        rec_f = torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
-        rec_y = out[1:] if plan.default else torch.empty((n_steps,) + shape, dtype=torch.float32, device=y0c.device)
-        view = _view(csr, shape[0])
+        n_steps = arrays[1]
+        out, rec_f, rec_y = _adams_record(y0c, plan)
+        view = _view(csr, y0c.shape[0])
         full = n_steps * max_iters
         cap = min(_first_cap(n_steps), full)
         res = _fixed_adams_attempt(view, Wc, bc, flags, out, arrays, max_order, rtol, atol, max_iters, rec_f, rec_y, cap)
@@ -616,13 +698,7 @@ class _FixedAdamsSolve(torch.autograd.Function):
             res = _fixed_adams_attempt(view, Wc, bc, flags, out, arrays, max_order, rtol, atol, max_iters, rec_f, rec_y, full)
         rc, iters, conv, slots, rec_u, rec_c = res
         check(rc)
-        for c in conv:
-            if not c:
-                print(core.NOT_CONVERGED, file=sys.stderr)        # fixed_adams.py:198
-        if step_log is not None:                                  # as odeint._fixed_adams_solve fills it
-            warm = sum(1 for i in iters if i == 0)
-            step_log.extend(zip(iters, conv))
-            step_log.append(('nfe', n_steps + 3 * warm + sum(iters)))
+        _report_corrector(step_log, iters, conv)
         ctx.meta = (csr, plan, max_order, iters, conv, slots)
         ctx.save_for_backward(out, rec_f, rec_u, rec_c, W, b, Wd, *(() if plan.default else (rec_y,)))
         return out if Wd is None else hip.linear(out, Wd.detach(), None if bd is None else bd.detach())
@@ -637,18 +713,12 @@ class _FixedAdamsSolve(torch.autograd.Function):
         dts = plan.dts
         n_steps = len(dts)
         lengths = core.abm_history_lengths(n_steps, max_order, conv)
-        ticks = _ticks(ctx, g, out, Wd)
-        gW_tot, gb_tot, vj, acc = _sweep_totals(out, csr, W, b, False, False, None)
+        ticks, (gW_tot, gb_tot, vj, acc), a = _adams_sweep_open(ctx, g, out, W, b, Wd, csr, plan)
         rvjp = lambda u, K, gk: hip.rhs_vjp(csr, u, Wc, K, gk, need_b=bc is not None, gW=gW_tot, gb=gb_tot)[0]
         Ps, Ds = {}, {}                                           # the adjoints that evaluations still to come gather from
-        a = ticks.seed(n_steps) if plan.default else None
         for i in range(n_steps - 1, -1, -1):
-            if not plan.default and plan.emits[i]:                # the ticks step i reported enter at the state it ends in
-                a = ticks.enter(a, [e[0] for e in plan.emits[i]])
-            if a is None:
-                a = torch.zeros_like(out[0])
+            a, close = _adams_sweep_enter(ticks, plan, out, a, i)
             y, f, dt = (out[0] if i == 0 else rec_y[i - 1]), rec_f[i], float(dts[i])
-            close = (lambda a, gus, i=i: ticks.close(a, gus, i)) if plan.default else _sum_onto
             pc_step = lengths[i] >= core.AB_MIN_ORDER - 1
             if pc_step:
                 c0 = float(core.abm_lead(dts[i], lengths[i]))
@@ -666,41 +736,8 @@ class _FixedAdamsSolve(torch.autograd.Function):
             if pc_step:
                 a = close(Ds[i], [Ps[i], rvjp(y, f, gf)])
             else:
-                u2 = hip.fixed_stage(2, y, f, dt=dt)
-                K2 = hip.rhs(csr, u2, Wc, bc)
-                u3 = hip.fixed_stage(3, y, f, K2, dt=dt)
-                K3 = hip.rhs(csr, u3, Wc, bc)
-                u4 = hip.fixed_stage(4, y, f, K2, K3, dt=dt)
-                K4 = hip.rhs(csr, u4, Wc, bc)
-                a = _sweep_step('rk4', dt, [(y, f), (u2, K2), (u3, K3), (u4, K4)], a, vj, acc, close, gk1_extra=gf)
-        if not plan.default:
-            a = ticks.enter(a, [0])                               # the first tick is y0 itself
-        return (a, gW_tot, (gb_tot if b is not None else None)) + ticks.decoder_grads() + (None,) * 8
-
-
-def _fixed_adams_with_grad(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None, readout=None):
-    """fixed_adams over a plain ODEFunc under a gradient on _FixedAdamsSolve, or None where the node has no form: what
-    _explicit_adams_with_grad declines, and a max_iters or tolerances that are not plain numbers (the per-operation branch fails on them as
-    the reference does)."""
-    from .odeint import _small_operator
-    if not adams_train_enabled() or t.requires_grad or t.numel() < 2 or max_order < 2 or odefunc.no_graph or odefunc.no_control:
-        return None
-    if type(max_iters) is not int or max_iters < 1 or not all(isinstance(v, (int, float)) for v in (rtol, atol)):
-        return None
-    op = _small_operator(odefunc, y0)
-    if op is None:
-        return None
-    csr, _, flags = op
-    core.assert_increasing(t)
-    if plan is None:
-        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
-    y0 = _lib.require_device(y0, 'state y0').contiguous()
-    if y0.numel() == 0:
-        return None
-    csr.ensure_plans(y0.shape[1])
-    csr.transpose().ensure_plans(y0.shape[1])
-    Wd, bd = readout if readout is not None else (None, None)
-    return _FixedAdamsSolve.apply(y0, odefunc.wt.weight, odefunc.wt.bias, Wd, bd, csr, flags, plan, max_order, rtol, atol, max_iters, step_log)
+                a = _warmup_reverse(csr, Wc, bc, y, f, dt, a, vj, acc, close, gf)
+        return _adams_sweep_close(ticks, plan, a, gW_tot, gb_tot, b, 8)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -797,7 +834,6 @@ def fixed_grid(y0, W, b, Wd, bd, csr, flags, method, dts):
 def _small_solve_with_grad(odefunc, y0, t, method='euler', plan=None):
     """The one-launch training path when the library supports the shape (H <= 31, the state and three work panels in one
     CU's LDS: the reference's README commands), else None - the caller falls back to the fused-launch nodes."""
-    from .odeint import _small_operator
     if t.requires_grad or not _lib.env_on('NDCN_SOLVE_SMALL_GRAD') or t.numel() < 2:
         return None
     op = _small_operator(odefunc, y0)
@@ -847,7 +883,6 @@ def _readout_for_grad(readout, y0):
 def _fixed_grid_with_grad(odefunc, y0, t, method, plan=None, readout=None):
     """The fused-launch training path of a fixed-grid solve over ODEFunc when the one-launch kernels do not take it (any size).
     readout = (Wd, bd) (checked by _readout_for_grad): the DECODED solution, the decoder's Linear inside the solve's autograd node."""
-    from .odeint import _small_operator
     if t.requires_grad or not _lib.env_on('NDCN_FIXED_GRID_GRAD') or t.numel() < 2:
         return None
     op = _small_operator(odefunc, y0)

@@ -13,7 +13,6 @@ Host tensors are refused: there is no CPU fallback.
 import collections
 import ctypes
 import os
-import sys
 import weakref
 
 import torch
@@ -23,6 +22,7 @@ from ... import dropout as _dropout
 from ...ops import hip, new_solve_epoch
 from ...truth import TRUTH_CLASSES
 from . import core, fixed_train
+from .fixed_train import _small_operator
 
 SOLVERS = {m: m for m in core.METHODS}      # the in-scope subset of odeint.py:8-17
 GRAPH_MAX_ELEMS = 1 << 23                   # below ~8M state elements (Pubmed x 256) a step is launch-bound
@@ -123,22 +123,20 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
 
     explicit_adams is the reference's AdamsBashforth (fixed_adams.py:151-211) on the same grids: two RK4 (3/8 rule) steps, then ONE
     evaluation per step combined with up to ten earlier ones (options={'max_order': m}, default 12: orders 3 .. m - 1; m = 2 or 3
-    never leaves RK4; m < 2 fails as in the reference).  Without a gradient a plain ODEFunc runs the whole solve inside the library
-    (ndcn_solve_explicit_adams_f32: nothing is read back); any other callable, a tuple state or a gradient steps through core.py -
-    except that with NDCN_ADAMS_TRAIN=1 a plain ODEFunc under a gradient (no active dropout, no no_graph / no_control, `t` without grad)
-    trains on one autograd node per solve (fixed_train._ExplicitAdamsSolve), `readout` inside it as for rk4.
+    never leaves RK4; m < 2 fails as in the reference).  A plain ODEFunc that fixed_train._adams_admission admits (the decline reasons
+    are stated there, once, for both methods) runs the whole solve inside the library: without a gradient _adams_solve
+    (ndcn_solve_explicit_adams_f32: nothing is read back), under one and with NDCN_ADAMS_TRAIN=1 one autograd node per solve
+    (fixed_train._ExplicitAdamsSolve, `readout` inside it as for rk4).  Everything else steps through core.py.
 
     fixed_adams is the reference's AdamsBashforthMoulton (fixed_adams.py:151-205): the same history, warm-up and predictor, then the
     Adams-Moulton corrector over the history and the evaluation at the step's end, iterated up to options={'max_iters': n} (default 4)
     times until EVERY element of the increment satisfies |dy_old - dy_new| < atol + rtol * max(|dy_old|, |dy_new|) - `rtol` and `atol`
     are this function's arguments (naming them in `options` is the reference's TypeError).  A step that does not converge writes the
     reference's warning line to stderr and drops the oldest evaluation of its history.  options={'implicit': False} is explicit_adams,
-    bit for bit.  Without a gradient a plain ODEFunc runs inside the library (ndcn_solve_fixed_adams_f32: one 8-byte read-back per
-    corrector iteration, the host decides whether to iterate again); any other callable, a tuple state, dropout, no_graph / no_control
-    or a gradient steps through core.py over ndcn_abm_predict_f32 / ndcn_abm_correct_f32 - under a gradient the iteration counts are
-    constants of the graph.  With NDCN_ADAMS_TRAIN=1 a plain ODEFunc under a gradient (the conditions of the explicit_adams node)
-    trains on one autograd node per solve (fixed_train._FixedAdamsSolve), `readout` inside it.  A host state is refused here, where unsupported methods are, with an exception that is both NdcnHipError
-    and NotImplementedError.
+    bit for bit.  The routes are explicit_adams' own: inside the library ndcn_solve_fixed_adams_f32 (one 8-byte read-back per corrector
+    iteration, the host decides whether to iterate again) and fixed_train._FixedAdamsSolve; everything else steps through core.py over
+    ndcn_abm_predict_f32 / ndcn_abm_correct_f32 - under a gradient the iteration counts are constants of the graph.  A host state is
+    refused here, where unsupported methods are, with an exception that is both NdcnHipError and NotImplementedError.
     """
     user_func = func
     t_user = t
@@ -193,19 +191,15 @@ def _odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_l
                 return sol, dec is not None
         if sol is not None:
             return sol, False
-    if needs_grad and method == 'explicit_adams' and fixed_train.adams_train_enabled() and \
+    if needs_grad and method in ('explicit_adams', 'fixed_adams') and fixed_train.adams_train_enabled() and \
             _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        # NDCN_ADAMS_TRAIN=1: one autograd node per solve - the library's loop forward, the multistep reverse sweep backward (an active
-        # dropout, no_graph / no_control and every other callable stay on the per-operation graph below)
+        # NDCN_ADAMS_TRAIN=1: one autograd node per solve - the library's loop forward (fixed_adams: the predictor-corrector loop, with a
+        # record), its reverse sweep in closed form backward; what the node declines stays on the per-operation graph below
         dec = fixed_train._readout_for_grad(readout, y0[0])
-        sol = fixed_train._explicit_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], readout=dec)
-        if sol is not None:
-            return sol, dec is not None
-    if needs_grad and method == 'fixed_adams' and fixed_train.adams_train_enabled() and \
-            _device_resident_ok(user_func, tensor_input, y0, t_user, method, options):
-        # the same switch: the predictor-corrector loop with a record forward, its closed-form reverse sweep backward
-        dec = fixed_train._readout_for_grad(readout, y0[0])
-        sol = fixed_train._fixed_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log, readout=dec)
+        if method == 'explicit_adams':
+            sol = fixed_train._explicit_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], readout=dec)
+        else:
+            sol = fixed_train._fixed_adams_with_grad(user_func, y0[0], t, plan, options['max_order'], rtol, atol, max_iters, step_log, readout=dec)
         if sol is not None:
             return sol, dec is not None
     if needs_grad:
@@ -450,19 +444,6 @@ class DeviceSolver:
             pass
 
 
-def _small_operator(odefunc, y0):
-    """(csr or None, ctypes view ref, flags) of an ODEFunc for the ndcn_solve_small_* entry points, or None when the operator
-    does not live with the state."""
-    from ...csr import as_csr
-    flags = _lib.operator_flags(odefunc)
-    if odefunc.no_graph:
-        return None, ctypes.byref(_lib.empty_csr(y0.shape[0])), flags
-    csr = as_csr(odefunc.A)
-    if csr.device != y0.device or csr.shape[0] != y0.shape[0]:
-        return None
-    return csr, csr.view_ref(), flags
-
-
 def _adams_decoder(readout, y0):
     """(Wd, bd) for the decoder inside the library's explicit_adams / fixed_adams solve (ndcn_solve_*_adams_readout_f32), or None: no
     readout, a gradient asked of it, a weight that is not a float32 device (C, H) tensor, a shape outside hip.adams_readout_route, or
@@ -480,116 +461,68 @@ def _adams_decoder(readout, y0):
     return Wd.detach().contiguous(), None if bd is None else bd.detach().contiguous()
 
 
-def _explicit_adams_solve(odefunc, y0, t, plan, max_order, readout=None):
+def _adams_solve(odefunc, y0, t, plan, max_order, readout, corrector=None):
     """(solution, decoded): the whole explicit_adams solve of a plain ODEFunc inside the library (ndcn_solve_explicit_adams_f32: RK4
-    warm-up, then one right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the
-    current stream without a read-back.  With a `readout` that _adams_decoder admits, ndcn_solve_explicit_adams_readout_f32: the
-    solution is (len(t), N, C), each tick decoded by the launch that forms it, and no hidden tick is stored.  None where the entry
-    point has no form: no_graph / no_control, an operator that does not live with the state, a max_order the reference itself fails on."""
-    if odefunc.no_graph or odefunc.no_control or max_order < 2:
+    warm-up, then one right-hand side and one ndcn_ab_step_f32 per grid step, ticks through ndcn_tick_emit_f32), enqueued on the current
+    stream without a read-back - or, with corrector = (rtol, atol, max_iters, step_log), the fixed_adams solve (ndcn_solve_fixed_adams_f32:
+    the same launches, then per step one ndcn_abm_predict_f32 and up to max_iters x (right-hand side + ndcn_abm_correct_f32 + an 8-byte
+    read-back)), reported through fixed_train._report_corrector.  With a `readout` that _adams_decoder admits, the *_readout_f32 form of
+    either: the solution is (len(t), N, C), each tick decoded by the launch that forms it (fixed_adams: the accepted iterate of every
+    reporting step; iteration counts, warning lines and step_log are those of the un-decoded solve), and no hidden tick is stored.
+    None where the entry points have no form: fixed_train._adams_admission."""
+    admitted = fixed_train._adams_admission(odefunc, y0, t, plan, max_order, corrector)
+    if admitted is None:
         return None
-    op = _small_operator(odefunc, y0)
-    if op is None:
-        return None
-    csr, view, flags = op
-    core.assert_increasing(t)
-    if plan is None:
-        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
+    csr, flags, plan, y0 = admitted
     lib = _lib.load()
     H = odefunc.hidden_size
-    n_ticks = len(plan.t)
     dec = _adams_decoder(readout, y0)
-    if dec is not None:
-        y0 = y0.contiguous()
-        out = torch.empty((n_ticks, y0.shape[0], dec[0].shape[0]), dtype=torch.float32, device=y0.device)
-        out[0].copy_(hip.linear(y0, dec[0], dec[1]))
-    else:
-        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-    dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
+    first = y0 if dec is None else hip.linear(y0, dec[0], dec[1])
+    out = torch.empty((len(plan.t),) + tuple(first.shape), dtype=torch.float32, device=y0.device)
+    out[0].copy_(first)
+    dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)           # (named: the arrays outlive the call)
     if n_steps == 0 or y0.numel() == 0:
+        if corrector is not None and corrector[3] is not None:
+            corrector[3].extend([(0, True)] * n_steps + [('nfe', 0)])
         return out, dec is not None
     csr.ensure_plans(H)
-    view = csr.view_ref()
+    view = csr.view_ref()                                    # (after ensure_plans: the view is the handle's as of plan-building time)
     W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
     b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
-    nbytes = int(lib.ndcn_explicit_adams_workspace_bytes(y0.shape[0], H, max_order))
+    size = lib.ndcn_explicit_adams_workspace_bytes if corrector is None else lib.ndcn_fixed_adams_workspace_bytes
+    nbytes = int(size(y0.shape[0], H, max_order))
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
-    if dec is not None:
-        with torch.cuda.device(y0.device):
-            _lib.check(lib.ndcn_solve_explicit_adams_readout_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(y0), dts, n_steps, steps,
-                                                                 same, offs, n_emit, max_order, _lib.ptr(dec[0]), _lib.ptr(dec[1]),
-                                                                 dec[0].shape[0], _lib.ptr(out[1:]) if n_emit else None,
-                                                                 _lib.ptr(workspace), nbytes, _lib.stream_ptr()))
-        return out, True
+    # the decoded form reads y0 itself, the hidden one the solution's first panel
+    head = (view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(y0 if dec is not None else out[0]), dts, n_steps, steps, same, offs, n_emit,
+            max_order)
+    decoder = () if dec is None else (_lib.ptr(dec[0]), _lib.ptr(dec[1]), dec[0].shape[0])
+    ticks = _lib.ptr(out[1:]) if n_emit else None
     with torch.cuda.device(y0.device):
-        _lib.check(lib.ndcn_solve_explicit_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
-                                                     offs, n_emit, max_order, _lib.ptr(out[1:]) if n_emit else None, _lib.ptr(workspace),
-                                                     nbytes, _lib.stream_ptr()))
+        tail = (_lib.ptr(workspace), nbytes, _lib.stream_ptr())
+        if corrector is None:
+            if dec is None:
+                _lib.check(lib.ndcn_solve_explicit_adams_f32(*head, ticks, *tail))
+            else:
+                _lib.check(lib.ndcn_solve_explicit_adams_readout_f32(*head, *decoder, ticks, *tail))
+        else:
+            rtol, atol, max_iters, step_log = corrector
+            tol = (float(rtol), float(atol), max_iters)
+            iters, conv = (ctypes.c_int * n_steps)(), (ctypes.c_int * n_steps)()
+            if dec is None:
+                _lib.check(lib.ndcn_solve_fixed_adams_f32(*head, *tol, ticks, iters, conv, *tail))
+            else:
+                _lib.check(lib.ndcn_solve_fixed_adams_readout_f32(*head, *tol, *decoder, ticks, iters, conv, *tail))
+            fixed_train._report_corrector(step_log, iters, conv)
     # (the workspace goes back to torch's stream-ordered allocator: a later allocation on this stream is ordered behind the solve)
-    return out, False
+    return out, dec is not None
+
+
+def _explicit_adams_solve(odefunc, y0, t, plan, max_order, readout=None):
+    return _adams_solve(odefunc, y0, t, plan, max_order, readout)
 
 
 def _fixed_adams_solve(odefunc, y0, t, plan, max_order, rtol, atol, max_iters, step_log=None, readout=None):
-    """(solution, decoded; `readout` as in _explicit_adams_solve: ndcn_solve_fixed_adams_readout_f32 decodes the accepted iterate of every
-    reporting step, the iteration counts, warning lines and step_log are those of the un-decoded solve).  The whole fixed_adams solve of a plain ODEFunc inside the library (ndcn_solve_fixed_adams_f32: the launches of the explicit solve,
-    then per step one ndcn_abm_predict_f32 and up to max_iters x (right-hand side + ndcn_abm_correct_f32 + an 8-byte read-back)).  The
-    reference's warning line is written here, once per step the library reports as not converged.  None where the entry point has no
-    form: as _explicit_adams_solve, and a max_iters or tolerances that are not plain numbers (the generic branch fails on them as the
-    reference does)."""
-    if odefunc.no_graph or odefunc.no_control or max_order < 2:
-        return None
-    if type(max_iters) is not int or max_iters < 1 or not all(isinstance(v, (int, float)) for v in (rtol, atol)):
-        return None
-    op = _small_operator(odefunc, y0)
-    if op is None:
-        return None
-    csr, view, flags = op
-    core.assert_increasing(t)
-    if plan is None:
-        plan = core.fixed_plan(core.host_grid(t).to(y0.dtype).numpy())         # solvers.py:81: the grid is t in the state dtype
-    lib = _lib.load()
-    H = odefunc.hidden_size
-    n_ticks = len(plan.t)
-    dec = _adams_decoder(readout, y0)
-    if dec is not None:
-        y0 = y0.contiguous()
-        out = torch.empty((n_ticks, y0.shape[0], dec[0].shape[0]), dtype=torch.float32, device=y0.device)
-        out[0].copy_(hip.linear(y0, dec[0], dec[1]))
-    else:
-        out = torch.empty((n_ticks,) + tuple(y0.shape), dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-    dts, n_steps, steps, same, offs, n_emit = fixed_train.plan_arrays(plan)
-    if n_steps == 0 or y0.numel() == 0:
-        if step_log is not None:
-            step_log.extend([(0, True)] * n_steps + [('nfe', 0)])
-        return out, dec is not None
-    csr.ensure_plans(H)
-    view = csr.view_ref()
-    W = _lib.require_device(odefunc.wt.weight.detach().contiguous(), 'weight')
-    b = None if odefunc.wt.bias is None else odefunc.wt.bias.detach().contiguous()
-    nbytes = int(lib.ndcn_fixed_adams_workspace_bytes(y0.shape[0], H, max_order))
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=y0.device)
-    iters, conv = (ctypes.c_int * n_steps)(), (ctypes.c_int * n_steps)()
-    with torch.cuda.device(y0.device):
-        if dec is not None:
-            _lib.check(lib.ndcn_solve_fixed_adams_readout_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(y0), dts, n_steps, steps, same,
-                                                              offs, n_emit, max_order, float(rtol), float(atol), max_iters, _lib.ptr(dec[0]),
-                                                              _lib.ptr(dec[1]), dec[0].shape[0], _lib.ptr(out[1:]) if n_emit else None,
-                                                              iters, conv, _lib.ptr(workspace), nbytes, _lib.stream_ptr()))
-        else:
-            _lib.check(lib.ndcn_solve_fixed_adams_f32(view, _lib.ptr(W), _lib.ptr(b), H, flags, _lib.ptr(out[0]), dts, n_steps, steps, same,
-                                                      offs, n_emit, max_order, float(rtol), float(atol), max_iters,
-                                                      _lib.ptr(out[1:]) if n_emit else None, iters, conv, _lib.ptr(workspace), nbytes,
-                                                      _lib.stream_ptr()))
-    for c in conv:
-        if not c:
-            print(core.NOT_CONVERGED, file=sys.stderr)      # fixed_adams.py:198
-    if step_log is not None:
-        warm = sum(1 for i, c in zip(iters, conv) if i == 0)
-        step_log.extend((int(i), bool(c)) for i, c in zip(iters, conv))
-        step_log.append(('nfe', n_steps + 3 * warm + sum(iters)))
-    return out, dec is not None
+    return _adams_solve(odefunc, y0, t, plan, max_order, readout, (rtol, atol, max_iters, step_log))
 
 
 def _small_solve(odefunc, y0, tt, method, plan=None):
