@@ -1028,6 +1028,9 @@ NDCN_API int ndcn_prof_kinds(void);
 #define NDCN_PATH_MID 4096   /* 16 <= H <= 128, H % 4 == 0, any number of rows: gather, fp32 MFMA Linear, ReLU and the COMBINE / RK4
                               * epilogue in one launch (rhs_mid.hip; ndcn_set_rhs_mid below).  An NDCN_RK_ERROR launch reports it for
                               * its K, the record is rk_error_f32's                                                                */
+#define NDCN_PATH_ABL 8192   /* exactly one of NDCN_F_NO_GRAPH / NDCN_F_NO_CONTROL, 16 <= H <= 128, H % 4 == 0, any number of rows: K and the
+                              * COMBINE / RK4 epilogue in one launch (rhs_abl.hip; ndcn_set_rhs_abl below), with NDCN_PATH_DROP_EPI when
+                              * the dropout factor rode in it.  An NDCN_RK_ERROR launch reports it for its K, the record is rk_error_f32's */
 NDCN_API int ndcn_debug_last_rhs_path(void);
 /* Which kernels the LAST ndcn_linear_f32 / ndcn_linear_bwd_f32 call of this thread launched (tests: every dispatch route of the dense
  * Linear is reached on purpose, not merely some correct one); each call replaces the set, 0 for n = 0 and before the first call.
@@ -1146,6 +1149,22 @@ NDCN_API int ndcn_set_range_guard(int on);
 NDCN_API int ndcn_set_rhs_mid(int mode);
 NDCN_API int ndcn_set_rhs_mid_drop(int on);
 NDCN_API int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);
+/* The one-launch right-hand side of the two ablations for hidden widths 16..128 at any size (NDCN_PATH_ABL above, csrc/rhs_abl.hip; the two
+ * calls are additions to ABI 29: no existing declaration changes).  Without it ndcn_rhs_rk_f32 with NDCN_F_NO_CONTROL (K = relu(A X)) or
+ * NDCN_F_NO_GRAPH (K = relu(X W^T + b)) runs composed below H = 256: the SpMM or the MFMA Linear, a stand-alone stage kernel reading K
+ * again and, under dropout, a mask pass.  With it ONE launch forms K - no_control: one fma per stored entry in stored order from +0;
+ * no_graph: the fp32 MFMA sequence of ndcn_linear_f32 -, applies the dropout factor of ndcn_dropout behind the ReLU and runs the stage
+ * algebra on it: plain, NDCN_RK_COMBINE with or without y_aux, NDCN_RK_RK4; NDCN_RK_ERROR and calls whose stage panels are not 16-byte
+ * aligned as the plain launch plus the stand-alone stage kernel.  Every panel it writes - K, y_next, y_aux - and the error record equal the
+ * composed path's bit for bit, so the switch is invisible in the results.
+ * ndcn_set_rhs_abl switches it PROCESS-WIDE at run time and returns the previous value (1 / 0); on < 0 returns to the environment's
+ * (NDCN_RHS_ABL, default 0).  It declines - the launch runs as without it - both flags or neither, other widths (H = 256 included), a halo
+ * panel, x_add / x_mask / s_out, X or K (no_graph: or W) not 16-byte aligned, and an operator that carries a long-row plan for this width.
+ * ndcn_rhs_work_bytes does not depend on it.
+ * ndcn_rhs_abl_supported: the shape part of that decision - exactly one of the two flags, H a multiple of 4 in 16..128, n_rows >= 1; a
+ * host predicate, no device needed.                                                                                                    */
+NDCN_API int ndcn_set_rhs_abl(int on);
+NDCN_API int ndcn_rhs_abl_supported(int64_t n_rows, int H, uint32_t flags);
 /* The reverse of ONE right-hand-side evaluation K = relu(W (A X) + b) as a call (csrc/rhs_mid_bwd.hip; five calls added to ABI 29: no
  * existing declaration changes) - what autograd executes for ODEFunc.forward (neural_dynamics.py:27-36) under the drivers' training
  * step, and what the two native tapes run per evaluation:

@@ -16,6 +16,7 @@ PATH_FUSED2, PATH_FUSED3, PATH_HUB, PATH_HALO, PATH_SWEEP, PATH_REC, PATH_WIDE, 
 PATH_DROP_EPI = 1024      # the dropout factor was applied inside the launch (clear: by the streaming pass behind it)
 PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue (ndcn_dyn_rk_f32; the solver's `dyn` descriptor)
 PATH_MID = 4096           # 16 <= H <= 128 at any size: the whole right-hand side + COMBINE / RK4 epilogue in one launch (csrc/rhs_mid.hip)
+PATH_ABL = 8192           # no_control / no_graph at 16 <= H <= 128, any size: K + COMBINE / RK4 epilogue in one launch (csrc/rhs_abl.hip)
 # ndcn_debug_last_rhs_vjp_path: the route of the process's last reverse evaluation (include/ndcn_hip.h NDCN_VJP_*)
 VJP_COMPOSED, VJP_MID = 1, 2
 DYN_HEAT, DYN_GENE, DYN_MUTUAL = 0, 1, 2
@@ -345,6 +346,8 @@ SIGNATURES = {
     'ndcn_set_rhs_mid': (_I, [_I]),
     'ndcn_set_rhs_mid_drop': (_I, [_I]),
     'ndcn_rhs_mid_supported': (_I, [_L, _I, _U, _I]),
+    'ndcn_set_rhs_abl': (_I, [_I]),
+    'ndcn_rhs_abl_supported': (_I, [_L, _I, _U]),
     'ndcn_rhs_vjp_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U, _I, _F, _I, _P]),
     'ndcn_rhs_vjp_work_bytes': (_L, [_L, _I, _U]),
     'ndcn_set_rhs_mid_bwd': (_I, [_I]),

@@ -118,6 +118,16 @@ int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // 
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
                 const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
+// rhs_abl.hip: the two ablations - no_control K = relu(A X), no_graph K = relu(X W^T + b) - in one launch for 16 <= H <= 128 (H % 4 == 0)
+// at any number of rows, with rhs_mid.hip's epilogue: mode 0, NDCN_RK_COMBINE (RkOpt::y_aux / c_aux) or NDCN_RK_RK4, drop as there; every
+// panel 16-byte aligned, no halo panel; the bits of the composed path.  The switch (ndcn_set_rhs_abl / NDCN_RHS_ABL): 0 off, 1 on
+int rhs_abl_on();
+int set_rhs_abl(int on);                      // ndcn_set_rhs_abl: returns the previous value; < 0: back to the environment's
+int rhs_abl_supported(int64_t n_rows, int H, uint32_t flags);                 // from the sizes alone, no device
+int rhs_abl_takes(const ndcn_csr *A, int H, uint32_t flags);                  // ... and the operator (no long-row plan for this width)
+int rhs_abl_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
+                const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
+                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
 // linear_bwd.hip: the row chunks linear_bwd_f32 cuts the weight gradient into (`used` chunks of rpc rows) and the fixed-order sum of
 // their partial blocks into gW / gb (one of them nullable)
 void wgrad_chunking(int64_t n, int Hi, int Ho, int64_t *rpc, int64_t *used);

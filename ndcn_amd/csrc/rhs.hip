@@ -51,6 +51,8 @@ int64_t rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) {
 //   Mid       stage algebra, mask    `mid` (below), and mode 0, or COMBINE / RK4 with y0, y_next, y_aux and   rhs_mid_f32
 //                                    every kprev 16-byte aligned
 //   Small     stage algebra, mask    small_takes - unless `mid` holds in ERROR mode (MidPlain keeps it)       rhs_small_f32
+//   Abl       stage algebra, mask    `abl` (below), and mode 0, or COMBINE / RK4 with the stage panels aligned  rhs_abl_f32
+//             mask                   `abl` - ERROR mode, or a misaligned stage panel - unless mask_combines   rhs_abl_f32 in mode 0, then rk_stage_f32
 //   Rec       stage algebra          no mask, mode != 0, no_control, aligned panels, spmm_rec_supported,      spmm_rec_f32
 //                                    spmm_rec_variant, rows * 1 KiB < 4 GiB
 //   Wide      stage algebra          no mask, mode != 0, no_control, aligned panels, spmm_wide_rk_supported,  spmm_wide_rk_f32
@@ -62,8 +64,10 @@ int64_t rhs_work_bytes(int64_t n_rows, int H, uint32_t flags) {
 //                                                                                                             dropout_combine_f32 for both
 //   mid: ndcn_set_rhs_mid takes the shape (rhs_mid_supported: graph and control, 16 <= H <= 128 in fours) - with a mask only under
 //   ndcn_set_rhs_mid_drop too -, no halo panel, X, W and K 16-byte aligned, none of the RkOpt fields of mid_declines.
-// Mode 0 reads neither stage arguments nor RkOpt, so only Mid, Small and Composed occur there.  H = 256 under a mask is always Composed.
-enum class Rhs { Fused, Mid, Small, Rec, Wide, MidPlain, Composed };
+//   abl: ndcn_set_rhs_abl is on and rhs_abl_takes the shape (exactly one of no_graph / no_control, 16 <= H <= 128 in fours, no long-row
+//   plan for this width), no halo panel, X and K - no_graph: and W - 16-byte aligned, none of the RkOpt fields of mid_declines.
+// Mode 0 reads neither stage arguments nor RkOpt, so only Mid, Small, Abl and Composed occur there.  H = 256 under a mask is always Composed.
+enum class Rhs { Fused, Mid, Small, Abl, Rec, Wide, MidPlain, Composed };
 
 // the RkOpt fields that exist only inside the H = 256 launches (s_out: and the narrow-panel one); none of them has a dropout form
 static bool fused_only(const RkOpt *o) { return o && (o->xadd || o->xmask || o->s_out || o->c_mid); }
@@ -77,6 +81,19 @@ static bool small_takes(const ndcn_csr *A, int H, uint32_t flags) { return rhs_s
 // (one launch and one panel read fewer than the mask pass and rk_combine_f32; the same bits)
 static bool mask_combines(int mode, const RkOpt *opt) { return mode == NDCN_RK_COMBINE && !(opt && opt->y_aux); }
 
+// COMBINE / RK4: every panel the epilogue of rhs_mid.hip / rhs_abl.hip reads or writes by 16 bytes is aligned (mode 0: none)
+static bool stage_aligned(int mode, const float *y0, const float *const *h_kprev, int n_prev, const float *y_next, const RkOpt *opt) {
+    if (mode == 0) return true;
+    bool epi = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
+    for (int m = 0; m < n_prev; ++m) epi = epi && h_kprev && aligned16(h_kprev[m]);
+    return epi;
+}
+
+// the stage algebra rides in the rhs_abl.hip launch (otherwise that launch runs in mode 0 with rk_stage_f32 behind it)
+static bool abl_epilogue(int mode, const float *y0, const float *const *h_kprev, int n_prev, const float *y_next, const RkOpt *opt) {
+    return mode != NDCN_RK_ERROR && stage_aligned(mode, y0, h_kprev, n_prev, y_next, opt);
+}
+
 static Rhs pick(const ndcn_csr *A, const float *X, const float *Xh, const float *W, const float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, int n_prev, const float *y_next, const RkOpt *opt, bool masked) {
     const bool graph_only = !(flags & NDCN_F_NO_GRAPH) && (flags & NDCN_F_NO_CONTROL);
@@ -85,15 +102,13 @@ static Rhs pick(const ndcn_csr *A, const float *X, const float *Xh, const float 
     const int mid_mode = rhs_mid_mode();
     const bool mid = mid_mode != 0 && (!masked || rhs_mid_drop_on()) && !Xh && !mid_declines(opt) &&
                      rhs_mid_supported(A->n_rows, H, flags, mid_mode) && aligned16(X) && aligned16(W) && aligned16(K);
-    if (mid && mode != NDCN_RK_ERROR) {                 // ERROR: its plain launch and rk_error_f32, which keeps the record's summation
-        bool epi = true;
-        if (mode != 0) {
-            epi = aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux));
-            for (int m = 0; m < n_prev; ++m) epi = epi && h_kprev && aligned16(h_kprev[m]);
-        }
-        if (epi) return Rhs::Mid;
-    }
+    // ERROR: its plain launch and rk_error_f32, which keeps the record's summation
+    if (mid && mode != NDCN_RK_ERROR && stage_aligned(mode, y0, h_kprev, n_prev, y_next, opt)) return Rhs::Mid;
     if (!(mid && mode == NDCN_RK_ERROR) && small_takes(A, H, flags)) return Rhs::Small;
+    if (rhs_abl_on() && !Xh && !mid_declines(opt) && rhs_abl_takes(A, H, flags) && aligned16(X) && aligned16(K) &&
+        (!(flags & NDCN_F_NO_GRAPH) || aligned16(W)) &&
+        (abl_epilogue(mode, y0, h_kprev, n_prev, y_next, opt) || !(masked && mask_combines(mode, opt))))
+        return Rhs::Abl;
     if (bare_stage && graph_only && aligned16(X) && aligned16(K) && (!Xh || aligned16(Xh))) {
         // relu(A X) with the stage algebra in the epilogue of the group-record SpMM (spmm_rec.hip), or of the wide one on any other graph
         if (spmm_rec_supported(A, H) && spmm_rec_variant(mode, n_prev) && A->n_rows * (int64_t)1024 < (1ll << 32)) return Rhs::Rec;
@@ -187,7 +202,8 @@ static int rk_stage_f32(int64_t n, const float *X, const float *K, int rk_mode, 
 // Composed: the epilogues keep the term order of rk_stage_f32 on the (masked) K.
 // ndcn_debug_last_rhs_path: each launch with a stage epilogue or a mask sets the report outright (the H = 256 kernels their own).  A plain
 // p = 0 call owns only the MID bit: below H = 256, with graph and control, it sets or clears that one and leaves the others as the
-// thread's last such launch left them; on any other shape it leaves the report alone.
+// thread's last such launch left them; with exactly one of no_graph / no_control it owns the ABL bit in the same way (rhs_abl.hip sets
+// the report outright); on any other shape it leaves the report alone.
 int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own, const float *W, const float *b, float *K,
                float *work, int H, uint32_t flags, int rk_mode, const float *y0, const float *const *h_kprev,
                const float *h_c, int n_prev, float *y_next, float rtol, float atol, double *d_out, void *d_ws,
@@ -243,6 +259,12 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
         g_last_rhs_path = plain_p0 ? (g_last_rhs_path & ~NDCN_PATH_MID) : (NDCN_PATH_SMALL | drop_epi);
         return rhs_small_f32(A, X, Xh, n_own, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
                              nullptr, opt, drop);
+    case Rhs::Abl:
+        g_last_rhs_path = NDCN_PATH_ABL | drop_epi;
+        if (abl_epilogue(rk_mode, y0, h_kprev, n_prev, y_next, opt))
+            return rhs_abl_f32(A, X, W, b, K, H, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, st, opt, drop);
+        if ((rc = rhs_abl_f32(A, X, W, b, K, H, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, st, nullptr, drop))) return rc;
+        return rk_stage_f32(n, X, K, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st, opt);
     case Rhs::Rec:
         g_last_rhs_path = NDCN_PATH_REC | halo;
         return spmm_rec_f32(A, X, Xh, n_own, K, 1.f, flags, rk_mode, y0, h_kprev, h_c, n_prev, y_next, rtol, atol, d_out, d_ws, st,
@@ -260,6 +282,7 @@ int rhs_rk_f32(const ndcn_csr *A, const float *X, const float *Xh, int64_t n_own
     }
     // composition with the same term order: K first, its mask, then the algebra over {kprev..., K}
     if (!plain_p0) g_last_rhs_path = 0;
+    else if (flags & (NDCN_F_NO_GRAPH | NDCN_F_NO_CONTROL)) g_last_rhs_path &= ~NDCN_PATH_ABL;       // (a plain p = 0 ablation call owns that bit alone)
     if ((rc = rhs_plain(A, X, Xh, n_own, W, b, K, work, H, flags, st))) return rc;
     if (drop && mask_combines(rk_mode, opt)) return dropout_combine_f32(K, n, *drop, y_next, y0, h_kprev, h_c, n_prev, st);
     if (drop && (rc = dropout_apply_f32(K, n, *drop, st))) return rc;

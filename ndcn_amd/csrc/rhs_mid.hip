@@ -29,8 +29,8 @@
 // the record's summation order.  No halo panel, none of the RkOpt fields of the H = 256 launches: rhs.hip declines those.
 #include <atomic>
 
-#include "dropout.h"
 #include "kernels.h"
+#include "rhs_mid_epi.h"
 
 #pragma clang fp contract(off)
 
@@ -38,18 +38,12 @@ namespace ndcn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kMidTile = 64;          // rows per tile: two 32-row MFMA tiles
-constexpr int kMidThreads = 512;
-constexpr int kMidMaxPrev = 5;
-constexpr int kMidMinH = 16, kMidMaxH = 128;
 // Mode 1 stops here.  Beyond it P = 128: 99 072 bytes of LDS, ONE workgroup per CU, so a tile's gather, MFMA and epilogue phases run
 // one after the other with nothing to overlap them - measured slower than the composed path (tools/micro/rhs_mid_time.py, 99 856 rows,
 // H = 128: plain 0.107 ms against 0.080 ms, COMBINE 5 0.185 against 0.160).  Mode 2 still takes those widths.  The dropout form follows
 // the same bound: with --dropout 0.5 there H = 128 ran plain 0.119 ms against 0.095 composed and COMBINE 5 0.188 against 0.164, while
 // H = 96 was not slower (plain 0.076 against 0.076, COMBINE 5 0.120 against 0.131).
 constexpr int kMidMode1MaxH = 96;
-constexpr int kLdsPerCu = 160 * 1024;
-enum { MID_PLAIN = 0, MID_COMBINE = 1, MID_RK4 = 3 };
 
 struct MidArgs {
     const int *rowptr, *colidx;
@@ -60,48 +54,10 @@ struct MidArgs {
     int n_rows, H, relu;
     int lsh;                          // log2 of the lanes that gather one row
 };
-struct MidEpi {
-    const float *y0;
-    const float *kprev[kMidMaxPrev];
-    float *y_next;
-    float *y_aux;                     // COMBINE, nullable: second linear combination (no y0)
-    float c[kMidMaxPrev + 1];
-    float c2[kMidMaxPrev + 1];
-    int n_prev;
-};
 
-__device__ __forceinline__ float4 mid_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void mid_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-__device__ __forceinline__ void mid_fma4(float4 &a, float v, const float4 &x) {
-    a.x = fmaf(v, x.x, a.x); a.y = fmaf(v, x.y, a.y); a.z = fmaf(v, x.z, a.z); a.w = fmaf(v, x.w, a.w);
-}
-
-// rk.hip wsum1 over {km[0..np), kn}: (0 + c_0 k_0) + c_1 k_1 + ..., the new stage last, every product rounded on its own
-__device__ __forceinline__ float mid_wsum(const float *c, const float (&km)[kMidMaxPrev], float kn, int np) {
-    float acc = 0.f + c[0] * (np > 0 ? km[0] : kn);
-#pragma unroll
-    for (int m = 1; m < kMidMaxPrev; ++m)
-        if (m < np) acc = acc + c[m] * km[m];
-    if (np > 0) acc = acc + c[np] * kn;
-    return acc;
-}
-
-// rk.hip stage1<2..5> with the new stage as the last of {km[0..np), kn}  (rk_common.py:75-78).  Stage 1: fixed_stage_kernel<3, true> is
-// compiled as k2 - k1 / 3 for stage1<3>'s k1 / -3 + k2 - every bit the same except the sign of a NaN that k1 carries through.  The
-// quotient is pinned in a register here so that the subtraction stays one and even that sign agrees.
-__device__ __forceinline__ float mid_rk4(float y, const float (&km)[kMidMaxPrev], float kn, int np, float dt) {
-    if (np == 0) return y + dt * kn / 3.f;
-    if (np == 1) {
-        float q = km[0] / 3.f;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(q));
-#endif
-        return y + dt * (kn - q);
-    }
-    if (np == 2) return y + dt * (km[0] - km[1] + kn);
-    return y + (km[0] + 3.f * km[1] + 3.f * km[2] + kn) * (dt / 8.f);
-}
-
+// The tile constants, MidEpi, mid_wsum and mid_rk4 are rhs_mid_epi.h's, shared with rhs_abl.hip.  The epilogue below stays written out
+// in this kernel: calling the header's mid_epi_lane instead - the same statements - made the compiler schedule and allocate the six
+// instantiations differently, and they are to stay the kernels that were measured.
 template <int MODE, bool DROP>
 __global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi e, DropArgs d) {
     extern __shared__ __align__(16) float mid_lds[];
@@ -280,13 +236,7 @@ int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *
     const int P = (H + 31) & ~31;
     a.lsh = P <= 32 ? 3 : (P <= 64 ? 4 : 5);
     MidEpi e = {};
-    if (mode != MID_PLAIN) {
-        e.y0 = y0; e.y_next = y_next; e.n_prev = n_prev;
-        e.y_aux = (mode == MID_COMBINE && opt && opt->y_aux && opt->c_aux) ? opt->y_aux : nullptr;
-        for (int m = 0; m < n_prev; ++m) e.kprev[m] = h_kprev[m];
-        if (mode == MID_RK4) e.c[0] = h_c[0];
-        else for (int m = 0; m <= n_prev; ++m) { e.c[m] = h_c[m]; e.c2[m] = e.y_aux ? opt->c_aux[m] : 0.f; }
-    }
+    if (mode != MID_PLAIN) mid_epi_fill(e, mode, y0, h_kprev, h_c, n_prev, y_next, opt ? opt->y_aux : nullptr, opt ? opt->c_aux : nullptr);
     const size_t lds = mid_lds_bytes(H);
     int per_cu = (int)(kLdsPerCu / lds);                   // H = 128: 1, H = 64: 4
     if (per_cu > 4) per_cu = 4;                            // 2048 threads per CU

@@ -553,6 +553,13 @@ class HipOps:
         return int(_lib.load().ndcn_set_rhs_mid_drop(int(on)))
 
     @staticmethod
+    def set_rhs_abl(on):
+        """The one-launch right-hand side of the no_control / no_graph ablations for hidden widths 16..128 at any size (ndcn_set_rhs_abl,
+        csrc/rhs_abl.hip): 0 off, 1 on - rhs / rhs_rk with exactly one of the two flags form K, the dropout factor and the stage algebra
+        in one launch, the composed launches' bits; < 0: the environment's (NDCN_RHS_ABL).  Process-wide; returns the previous value."""
+        return int(_lib.load().ndcn_set_rhs_abl(int(on)))
+
+    @staticmethod
     def set_rhs_mid_bwd(mode):
         """The one-launch reverse of the right-hand side for hidden widths 16..128 at any size (ndcn_set_rhs_mid_bwd,
         csrc/rhs_mid_bwd.hip): 0 off, 1 on for the widths that measured not slower than the composed launches, 2 on for every
