@@ -1191,6 +1191,7 @@ NDCN_API int ndcn_rhs_abl_supported(int64_t n_rows, int H, uint32_t flags);
  * autograd's thread), whoever ran it; 0 before the first.                                                                          */
 #define NDCN_VJP_COMPOSED 1   /* SpMM (unless S was given), ndcn_linear_bwd_f32's launches, transposed SpMM                           */
 #define NDCN_VJP_MID      2   /* gS and the partials of gW / gb in one launch (rhs_mid_bwd.hip), chunk sum, transposed SpMM           */
+#define NDCN_VJP_ABL      3   /* an ablation's one-launch reverse (rhs_abl_bwd.hip; ndcn_set_rhs_abl_bwd below)                        */
 NDCN_API int ndcn_rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *A_t, const float *X, const float *K, const float *g, const float *W,
                               const float *S, float *gX, float *gW, float *gb, void *work, int H, uint32_t flags, int premasked,
                               float acc_scale, int accumulate, void *stream);
@@ -1198,6 +1199,27 @@ NDCN_API int64_t ndcn_rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
 NDCN_API int ndcn_set_rhs_mid_bwd(int mode);
 NDCN_API int ndcn_rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode);
 NDCN_API int ndcn_debug_last_rhs_vjp_path(void);
+/* The one-launch reverse of the two ablations for hidden widths 16..128 at any size (csrc/rhs_abl_bwd.hip; NDCN_VJP_ABL and the three
+ * calls are additions to ABI 29: no existing declaration changes).  Without it ndcn_rhs_vjp_f32 and the native tapes run the reverse of an
+ * NDCN_F_NO_CONTROL evaluation as two launches (the ReLU mask into a scratch panel, the transposed SpMM over it) and of an NDCN_F_NO_GRAPH
+ * evaluation as ndcn_linear_bwd_f32's three plus a scaling pass whenever acc_scale has no SpMM to ride in.  With it
+ *   NO_CONTROL  ONE launch: gX = acc_scale * A^T (g (.) [K > 0]) with the mask applied to the gathered rows of g - one fma per stored entry
+ *               of A_t in stored order from +0, then the product with acc_scale (also when it is 1)
+ *   NO_GRAPH    the NDCN_VJP_MID launch with S = X forms gS and the row-chunk partials of gW / gb, stores gS straight into gX - times
+ *               acc_scale exactly where the composed call runs its scaling pass - and the chunk sum follows: two launches
+ * with the raw 32-bit words of the composed launches in gX, gW and gb, signs of zero and NaN positions included, for every accumulate /
+ * acc_scale combination; no gS panel is left in `work`.  ndcn_set_rhs_abl_bwd switches it PROCESS-WIDE at run time and returns the
+ * previous value (1 / 0); on < 0 returns to the environment's (NDCN_RHS_ABL_BWD, default 0); independent of ndcn_set_rhs_abl and
+ * ndcn_set_rhs_mid_bwd.  The native tapes follow it.  It declines - the call runs composed, NDCN_VJP_COMPOSED - both flags or neither,
+ * other widths (H = 256 included), NO_CONTROL without a mask to fuse (premasked, or no NDCN_F_RELU: one launch already) or without gX,
+ * NO_GRAPH without gW, a non-square operator, X / g / K / W / gX not 16-byte aligned or gX aliasing an input, and for NO_CONTROL an A_t
+ * that carries a long-row plan for this width.  ndcn_rhs_vjp_work_bytes does not depend on it.
+ * ndcn_rhs_abl_bwd_supported: the shape part of that decision - exactly one of the two flags, H a multiple of 4 in 16..128,
+ * 1 <= n_rows < 2^31 - 64; a host predicate, no device needed.  ndcn_rhs_abl_bwd_on: the switch's current value (1 / 0), read without
+ * changing it - a caller that picks between one ndcn_rhs_vjp_f32 call and its own per-operation calls decides by it.                   */
+NDCN_API int ndcn_set_rhs_abl_bwd(int on);
+NDCN_API int ndcn_rhs_abl_bwd_on(void);
+NDCN_API int ndcn_rhs_abl_bwd_supported(int64_t n_rows, int H, uint32_t flags);
 
 /* ---- training through the adaptive solver: the solve that keeps its tape, and its reverse pass ---------------------------------
  * Replaces, for a plain ODEFunc on one state tensor, what the reference's drivers do by autograd through odeint

@@ -18,7 +18,7 @@ PATH_DYN = 2048           # a ground-truth dynamics launch with the RK epilogue 
 PATH_MID = 4096           # 16 <= H <= 128 at any size: the whole right-hand side + COMBINE / RK4 epilogue in one launch (csrc/rhs_mid.hip)
 PATH_ABL = 8192           # no_control / no_graph at 16 <= H <= 128, any size: K + COMBINE / RK4 epilogue in one launch (csrc/rhs_abl.hip)
 # ndcn_debug_last_rhs_vjp_path: the route of the process's last reverse evaluation (include/ndcn_hip.h NDCN_VJP_*)
-VJP_COMPOSED, VJP_MID = 1, 2
+VJP_COMPOSED, VJP_MID, VJP_ABL = 1, 2, 3
 DYN_HEAT, DYN_GENE, DYN_MUTUAL = 0, 1, 2
 # ndcn_debug_last_linear_path: the kernels of the last ndcn_linear_f32 / ndcn_linear_bwd_f32 call (include/ndcn_hip.h NDCN_LIN_*)
 LIN_ROWDOT, LIN_SMALL, LIN_MFMA64, LIN_MFMA128, LIN_MFMA256, LIN_VEC = 1, 2, 4, 8, 16, 32
@@ -353,6 +353,9 @@ SIGNATURES = {
     'ndcn_set_rhs_mid_bwd': (_I, [_I]),
     'ndcn_rhs_mid_bwd_supported': (_I, [_L, _I, _U, _I]),
     'ndcn_debug_last_rhs_vjp_path': (_I, []),
+    'ndcn_set_rhs_abl_bwd': (_I, [_I]),
+    'ndcn_rhs_abl_bwd_on': (_I, []),
+    'ndcn_rhs_abl_bwd_supported': (_I, [_L, _I, _U]),
     'ndcn_tgcn_chunk': (_I, [_I]),
     'ndcn_tgcn_proj_ws_bytes': (_L, [_L, _I, _I]),
     'ndcn_tgcn_proj_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),

@@ -78,6 +78,10 @@ def rhs_vjp(A, no_graph, no_control, X, W, Y, g, need_x, need_w, need_b, S=None,
             _lib.load().ndcn_rhs_mid_bwd_supported(X.shape[0], X.shape[1], _lib.F_RELU, -1)):
         # the switch is on for this shape (csrc/rhs_mid_bwd.hip): the whole reverse as one call, the same bits in three launches
         return hip.rhs_vjp(A, X.detach(), W, Y, g, S=S, need_x=need_x, need_b=need_b, acc_scale=scale)
+    if (no_graph != no_control and (need_x if no_control else need_w) and hip.rhs_abl_bwd_on() and
+            _lib.load().ndcn_rhs_abl_bwd_supported(X.shape[0], X.shape[1], _lib.F_RELU | (_lib.F_NO_GRAPH if no_graph else _lib.F_NO_CONTROL))):
+        # an ablation under its own switch (csrc/rhs_abl_bwd.hip): the whole reverse as one call, the same bits in one or two launches
+        return hip.rhs_vjp(A, X.detach(), W, Y, g, need_x=need_x, need_b=need_b, acc_scale=scale, no_graph=no_graph, no_control=no_control)
     gW = gb = None
     if not no_control:
         if not need_w:

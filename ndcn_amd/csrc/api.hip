@@ -56,6 +56,9 @@ int ndcn_set_rhs_abl(int on) { return set_rhs_abl(on); }
 int ndcn_rhs_abl_supported(int64_t n_rows, int H, uint32_t flags) { return rhs_abl_supported(n_rows, H, flags); }
 int ndcn_set_rhs_mid_bwd(int mode) { return set_rhs_mid_bwd(mode); }
 int ndcn_rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_bwd_supported(n_rows, H, flags, mode); }
+int ndcn_set_rhs_abl_bwd(int on) { return set_rhs_abl_bwd(on); }
+int ndcn_rhs_abl_bwd_on(void) { return rhs_abl_bwd_on(); }
+int ndcn_rhs_abl_bwd_supported(int64_t n_rows, int H, uint32_t flags) { return rhs_abl_bwd_supported(n_rows, H, flags); }
 int ndcn_debug_last_rhs_vjp_path(void) { return last_rhs_vjp_path(); }
 int64_t ndcn_rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags) { return rhs_vjp_work_bytes(n_rows, H, flags); }
 

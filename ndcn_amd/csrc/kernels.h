@@ -145,6 +145,15 @@ int rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *At, const float *X, const flo
                 bool premasked, float acc_scale, float alpha, bool accumulate, bool direct, bool *packed, hipStream_t st);
 int64_t rhs_vjp_work_bytes(int64_t n_rows, int H, uint32_t flags);
 int64_t rhs_vjp_gs_offset(int64_t n_rows, int H);
+// rhs_abl_bwd.hip: the reverse of one evaluation of the two ablations for 16 <= H <= 128 (H % 4 == 0) at any number of rows, taken at the
+// top of rhs_vjp_f32 - no_control: gX = alpha At (g (.) [K > 0]) in one launch (the mask rides in the transposed gather); no_graph:
+// rhs_mid_bwd.hip's kernel with S = X, gS stored straight into gX (times alpha where the composed branch runs its scaling pass), then the
+// chunk sum: the bits of the composed launches.  The switch (ndcn_set_rhs_abl_bwd / NDCN_RHS_ABL_BWD): 0 off, 1 on
+int rhs_abl_bwd_on();
+int set_rhs_abl_bwd(int on);                  // ndcn_set_rhs_abl_bwd: returns the previous value; < 0: back to the environment's
+int rhs_abl_bwd_supported(int64_t n_rows, int H, uint32_t flags);             // from the sizes alone, no device
+int rhs_abl_vjp_takes(const ndcn_csr *At, int64_t n_rows, int H);             // ... and the transposed operator (square, no long-row plan for H)
+int rhs_abl_vjp_graph_f32(const ndcn_csr *At, const float *g, const float *K, float *gX, int H, float alpha, hipStream_t st);
 // dropout (csrc/dropout.h): the descriptor in the kernels' form (NDCN_EINVAL unless 0 < p < 1) and the streaming pass K *= m.  rhs_f32 /
 // rhs_rk_f32 take the mask as their last argument (NULL: p = 0 or eval mode) and the one dispatch of rhs.hip places it: in the epilogue
 // of the narrow-panel launch and (under ndcn_set_rhs_mid_drop) of the rhs_mid.hip launch, by the streaming pass behind every other route

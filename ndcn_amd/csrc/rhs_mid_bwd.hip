@@ -27,6 +27,10 @@
 //   => gS, gW, gb and gX hold the composed launches' raw words - signs of zero and NaN positions included, for every accumulate /
 //   acc_scale combination: the switch (ndcn_set_rhs_mid_bwd / NDCN_RHS_MID_BWD, off by default) is invisible in the gradients.
 //
+// The kernel's body lives in rhs_mid_bwd_body.h and is included twice: rhs_mid_bwd_kernel as it always was, and rhs_mid_bwd_scaled_kernel,
+// whose gS store multiplies by alpha - the no_graph ablation's reverse (rhs_abl_bwd.hip: S = X, gS straight into gX), taken at the top of
+// rhs_vjp_f32 under ndcn_set_rhs_abl_bwd.
+//
 // LDS: (P + 64 + 64) (P + 1) 4 bytes - 20.6 KiB at P = 32, 48.8 KiB at 64, 84.0 KiB at 96, 129.0 KiB at 128 (one workgroup per CU).
 #include <atomic>
 
@@ -69,162 +73,15 @@ __device__ __forceinline__ void mb_fma4(float4 &a, float v, const float4 &x) {
 __device__ __forceinline__ float mb_mask(float g, float k) { return k <= 0.f ? 0.f : g; }       // linear_bwd.hip masked(): NaN passes
 
 __global__ __launch_bounds__(kMbThreads) void rhs_mid_bwd_kernel(MidBwdArgs a) {
-    extern __shared__ __align__(16) float mb_lds[];
-    const int H = a.H;
-    const int P = (H + 31) & ~31;
-    const int ld = P + 1;                                    // odd leading dimension: the column-ish operand reads are conflict-free
-    const int H4 = H >> 2, P4 = P >> 2;
-    float *s_W = mb_lds;                                     // [P][ld]  s_W[o * ld + i] = W[o][i], zero beyond H
-    float *s_S = mb_lds + P * ld;                            // [64][ld] the S tile
-    float *s_G = s_S + kMbTile * ld;                         // [64][ld] the gZ tile
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, kk = lane >> 5;
-    for (int i = tid; i < P * P; i += kMbThreads) {
-        const int o = i / P, k = i - o * P;
-        s_W[o * ld + k] = (o < H && k < H) ? a.W[o * H + k] : 0.f;
-    }
-    const int r_lo = (int)blockIdx.x * a.rpc;                // (n_rows < 2^31 - 64: the launcher's check)
-    const int r_hi = a.n_rows - r_lo < a.rpc ? a.n_rows : r_lo + a.rpc;
-    // gather roles (rhs_mid.hip)
-    const int lsh = a.lsh;
-    const int gr_row = tid >> lsh, c4 = (tid & ((1 << lsh) - 1)) * 4, rows_per_pass = kMbThreads >> lsh;
-    const bool act = c4 < H, pad = c4 < P;
-    // gS roles
-    const int nI = P >> 5;
-    const int wm = wave & 1, tn = wave >> 1;
-    const bool gs_job = a.gS && wave < 2 * nI;
-    // gW roles: pair p = (o-strip p / nI, i-tile p % nI); this wave's pairs are `wave` and `wave + 8`
-    const int n_pairs = nI * nI;
-    const bool job0 = wave < n_pairs, job1 = wave + 8 < n_pairs;
-    const int os0 = wave / nI, it0 = wave - os0 * nI;
-    const int os1 = (wave + 8) / nI, it1 = (wave + 8) - os1 * nI;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc0[i] = 0.f, acc1[i] = 0.f;
-    float bsum0 = 0.f, bsum1 = 0.f;
-    for (int r0 = r_lo; r0 < r_hi; r0 += kMbTile) {
-        const int rows = r_hi - r0 < kMbTile ? r_hi - r0 : kMbTile;
-        // ---- S tile
-        if (a.S) {
-            for (int i = tid; i < kMbTile * P4; i += kMbThreads) {
-                const int row = i / P4, q = i - row * P4;
-                float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row < rows && q < H4) s = mb_ld4(a.S + (size_t)(r0 + row) * H + 4 * q);
-                float *d = s_S + row * ld + 4 * q;
-                d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w;
-            }
-        } else {
-            for (int row = gr_row; row < kMbTile; row += rows_per_pass) {
-                float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row < rows && act) {
-                    int j = a.rowptr[r0 + row];
-                    const int j1 = a.rowptr[r0 + row + 1];
-                    const float *xc = a.X + c4;
-                    for (; j + 4 <= j1; j += 4) {
-                        const int q0 = a.colidx[j], q1 = a.colidx[j + 1], q2 = a.colidx[j + 2], q3 = a.colidx[j + 3];
-                        const float v0 = a.val[j], v1 = a.val[j + 1], v2 = a.val[j + 2], v3 = a.val[j + 3];
-                        const float4 x0 = mb_ld4(xc + (size_t)q0 * H), x1 = mb_ld4(xc + (size_t)q1 * H);
-                        const float4 x2 = mb_ld4(xc + (size_t)q2 * H), x3 = mb_ld4(xc + (size_t)q3 * H);
-                        mb_fma4(s, v0, x0); mb_fma4(s, v1, x1); mb_fma4(s, v2, x2); mb_fma4(s, v3, x3);
-                    }
-                    for (; j < j1; ++j) mb_fma4(s, a.val[j], mb_ld4(xc + (size_t)a.colidx[j] * H));
-                }
-                if (pad) {
-                    float *d = s_S + row * ld + c4;
-                    d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w;
-                }
-            }
-        }
-        // ---- gZ tile
-        for (int i = tid; i < kMbTile * P4; i += kMbThreads) {
-            const int row = i / P4, q = i - row * P4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < rows && q < H4) {
-                const size_t idx = (size_t)(r0 + row) * H + 4 * q;
-                v = mb_ld4(a.g + idx);
-                if (a.K) {
-                    const float4 k = mb_ld4(a.K + idx);
-                    v.x = mb_mask(v.x, k.x); v.y = mb_mask(v.y, k.y); v.z = mb_mask(v.z, k.z); v.w = mb_mask(v.w, k.w);
-                }
-            }
-            float *d = s_G + row * ld + 4 * q;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-        __syncthreads();
-        // ---- gS = gZ W: one 32 x 32 output tile per wave, k = o ascending from a zero accumulator (linear_gs_kernel)
-        if (gs_job && wm * 32 < rows) {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            const float *pa = s_G + (wm * 32 + l31) * ld + kk;
-            const float *pb = s_W + kk * ld + tn * 32 + l31;
-            for (int k0 = 0; k0 < P; k0 += 32)
-#pragma unroll
-                for (int k = 0; k < 32; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[k0 + k], pb[(k0 + k) * ld], acc, 0, 0, 0);
-            const int col = tn * 32 + l31;
-            if (col < H) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                    if (m < rows) a.gS[(size_t)(r0 + m) * H + col] = acc[r];
-                }
-            }
-        }
-        // ---- gW, gb: row pairs ascending, whole rounds of 8 rows as linear_wgrad_kernel walks them
-        if (job0) {
-            const int n_u = ((rows + 7) & ~7) >> 1;
-            const float *pa0 = s_G + kk * ld + os0 * 32 + l31, *pb0 = s_S + kk * ld + it0 * 32 + l31;
-            const float *pa1 = s_G + kk * ld + os1 * 32 + l31, *pb1 = s_S + kk * ld + it1 * 32 + l31;
-            if (job1) {
-                for (int u = 0; u < n_u; ++u) {
-                    const float a0 = pa0[2 * u * ld], b0 = pb0[2 * u * ld], a1 = pa1[2 * u * ld], b1 = pb1[2 * u * ld];
-                    bsum0 += a0;
-                    bsum1 += a1;
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc1, 0, 0, 0);
-                }
-            } else {
-                for (int u = 0; u < n_u; ++u) {
-                    const float a0 = pa0[2 * u * ld], b0 = pb0[2 * u * ld];
-                    bsum0 += a0;
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc0, 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();                                     // the next tile's loads overwrite both tiles
-    }
-    // ---- the chunk's partial block and bias row (linear_wgrad_kernel's layout)
-    float *pw = a.part_w + (size_t)blockIdx.x * H * H;
-    if (job0) {
-        const int i = it0 * 32 + l31;
-        if (i < H) {
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int oo = os0 * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kk;
-                if (oo < H) pw[(size_t)oo * H + i] = acc0[rr];
-            }
-        }
-        if (a.part_b && it0 == 0) {
-            bsum0 += __shfl_xor(bsum0, 32, 64);              // the two row parities of this column
-            const int o = os0 * 32 + l31;
-            if (lane < 32 && o < H) a.part_b[(size_t)blockIdx.x * H + o] = bsum0;
-        }
-    }
-    if (job1) {
-        const int i = it1 * 32 + l31;
-        if (i < H) {
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int oo = os1 * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kk;
-                if (oo < H) pw[(size_t)oo * H + i] = acc1[rr];
-            }
-        }
-        if (a.part_b && it1 == 0) {
-            bsum1 += __shfl_xor(bsum1, 32, 64);
-            const int o = os1 * 32 + l31;
-            if (lane < 32 && o < H) a.part_b[(size_t)blockIdx.x * H + o] = bsum1;
-        }
-    }
+#define MB_GS_STORE(v) (v)
+#include "rhs_mid_bwd_body.h"
+#undef MB_GS_STORE
+}
+
+__global__ __launch_bounds__(kMbThreads) void rhs_mid_bwd_scaled_kernel(MidBwdArgs a, float alpha) {
+#define MB_GS_STORE(v) (alpha * (v))
+#include "rhs_mid_bwd_body.h"
+#undef MB_GS_STORE
 }
 
 // ---------------------------------------------------------------------------------------------------- the switch
@@ -262,9 +119,11 @@ static size_t mb_lds_bytes(int H) {
     return (P + 2 * kMbTile) * (P + 1) * sizeof(float);
 }
 
-// gS (nullable) and the chunk partials of gW / gb into `work` (linear_bwd_work_bytes(n_rows, H, H) bytes), then their fixed-order sum
+// gS (nullable) and the chunk partials of gW / gb into `work` (linear_bwd_work_bytes(n_rows, H, H) bytes), then their fixed-order sum.
+// scale_gs: gS is stored as alpha * gS (the no_graph ablation, whose S is X: A is read for n_rows alone)
 static int rhs_mid_bwd_f32(const ndcn_csr *A, const float *X, const float *S, const float *g, const float *mask, const float *W, float *gS,
-                           float *gW, float *gb, void *work, int H, float acc_scale, bool accumulate, hipStream_t st) {
+                           float *gW, float *gb, void *work, int H, float acc_scale, bool accumulate, hipStream_t st,
+                           bool scale_gs = false, float alpha = 1.f) {
     const int64_t n = A->n_rows;
     int64_t rpc, used;
     wgrad_chunking(n, H, H, &rpc, &used);
@@ -280,10 +139,17 @@ static int rhs_mid_bwd_f32(const ndcn_csr *A, const float *X, const float *S, co
         const double Pn = 4.0 * H * (double)n;
         ProfScope prof(PROF_LINEAR_WGRAD, st, Pn * (2 + (mask ? 1 : 0) + (gS ? 1 : 0)) + (S ? 0.0 : 8.0 * A->nnz) + 4.0 * (used + 1) * (double)H * H,
                        (gS ? 4.0 : 2.0) * (double)n * H * H + (S ? 0.0 : 2.0 * A->nnz * H));
-        static std::atomic<unsigned long long> attr_seen{0};
-        if (once_per_device(attr_seen))
-            NDCN_HIP(hipFuncSetAttribute((const void *)rhs_mid_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb_lds_bytes(kMbMaxH)));
-        hipLaunchKernelGGL(rhs_mid_bwd_kernel, dim3((unsigned)used), dim3(kMbThreads), lds, st, a);
+        static std::atomic<unsigned long long> attr_seen{0}, attr_seen_scaled{0};
+        if (scale_gs) {
+            if (once_per_device(attr_seen_scaled))
+                NDCN_HIP(hipFuncSetAttribute((const void *)rhs_mid_bwd_scaled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)mb_lds_bytes(kMbMaxH)));
+            hipLaunchKernelGGL(rhs_mid_bwd_scaled_kernel, dim3((unsigned)used), dim3(kMbThreads), lds, st, a, alpha);
+        } else {
+            if (once_per_device(attr_seen))
+                NDCN_HIP(hipFuncSetAttribute((const void *)rhs_mid_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb_lds_bytes(kMbMaxH)));
+            hipLaunchKernelGGL(rhs_mid_bwd_kernel, dim3((unsigned)used), dim3(kMbThreads), lds, st, a);
+        }
         NDCN_LAUNCH_CHECK();
     }
     return wgrad_chunk_sum(a.part_w, a.part_b, gW, gb, H, H, used, acc_scale, accumulate, st);
@@ -305,6 +171,25 @@ int rhs_vjp_f32(const ndcn_csr *A, const ndcn_csr *At, const float *X, const flo
     int rc;
     g_last_vjp_path.store(NDCN_VJP_COMPOSED, std::memory_order_relaxed);
     const float *gS = nullptr;
+    // the ablations under their own switch (rhs_abl_bwd.hip): declined calls run the composed branches below
+    if (no_graph != no_control && rhs_abl_bwd_on() && rhs_abl_bwd_supported(n_rows, H, flags) && A->n_cols == n_rows && aligned16(X) &&
+        aligned16(g) && aligned16(K) && aligned16(W) && aligned16(gx) && !(gx && (gx == g || gx == K || gx == X))) {
+        if (no_control) {
+            // (without a mask the composed path is one launch already; without gx there is nothing to do)
+            if (mask && gx && rhs_abl_vjp_takes(At, n_rows, H)) {
+                rc = rhs_abl_vjp_graph_f32(At, g, mask, gx, H, alpha, st);
+                if (rc) return rc;
+                g_last_vjp_path.store(NDCN_VJP_ABL, std::memory_order_relaxed);
+                return NDCN_OK;
+            }
+        } else if (gW && bwork) {
+            // S = X; gS goes straight into gx, times alpha exactly when the composed branch would run its scale_f32 pass
+            rc = rhs_mid_bwd_f32(A, X, X, g, mask, W, gx, gW, gb, bwork, H, acc_scale, accumulate, st, gx && rescale, alpha);
+            if (rc) return rc;
+            g_last_vjp_path.store(NDCN_VJP_ABL, std::memory_order_relaxed);
+            return NDCN_OK;
+        }
+    }
     if (!no_control) {
         const int mode = rhs_mid_bwd_mode();
         if (mode != 0 && rhs_mid_bwd_supported(n_rows, H, flags, mode) && gW && bwork && A->n_cols == n_rows && aligned16(X) &&

@@ -566,6 +566,19 @@ class HipOps:
         supported shape; < 0: the environment's (NDCN_RHS_MID_BWD).  Process-wide; returns the previous mode."""
         return int(_lib.load().ndcn_set_rhs_mid_bwd(int(mode)))
 
+    @staticmethod
+    def set_rhs_abl_bwd(on):
+        """The one-launch reverse of the no_control / no_graph ablations for hidden widths 16..128 at any size (ndcn_set_rhs_abl_bwd,
+        csrc/rhs_abl_bwd.hip): 0 off, 1 on - rhs_vjp and the native tapes run the reverse of an evaluation with exactly one of the two
+        flags as one launch (no_control) or one launch plus the chunk sum (no_graph), the composed launches' bits; < 0: the environment's
+        (NDCN_RHS_ABL_BWD).  Process-wide; returns the previous value."""
+        return int(_lib.load().ndcn_set_rhs_abl_bwd(int(on)))
+
+    @staticmethod
+    def rhs_abl_bwd_on():
+        """the value set_rhs_abl_bwd would return, read without changing it (autograd_ops.rhs_vjp decides its route by it)"""
+        return int(_lib.load().ndcn_rhs_abl_bwd_on())
+
     # ---------------------------------------------------------------- TemporalGCN: the hoisted input projection and the recurrence (csrc/tgcn.hip)
     @staticmethod
     def set_tgcn_fused(mode):
@@ -669,7 +682,8 @@ class HipOps:
         """The reverse of one evaluation K = relu(W (A X) + b) (ndcn_rhs_vjp_f32): (gX, gW, gb) for the upstream gradient g, None
         where not requested.  S: A X as the forward wrote it (re-formed when None).  gW / gb given: the call ACCUMULATES
         acc_scale * (this evaluation's) into them and returns them; otherwise they are new tensors.  return_gs: a fourth result, the
-        panel gS = gZ W as it stands in the call's scratch (need_x only)."""
+        panel gS = gZ W as it stands in the call's scratch (need_x only).  Under set_rhs_abl_bwd a no_graph / no_control call that
+        the one-launch reverse takes leaves no gS panel in the scratch: return_gs promises nothing there."""
         X, g = _panel(X), _panel(g)
         K = _panel(K) if K is not None else None
         S = _panel(S) if S is not None else None

@@ -202,6 +202,12 @@ def _sweep_totals(out, csr, W, b, no_graph, no_control, drop):
     gb_tot = torch.zeros((H,), dtype=torch.float32, device=out.device) if not no_control else None
     s = 1.0 if drop is None else _dropout.scale(drop[0])
     vj = lambda u, K, gk, alpha: _vjp(csr, u, K, gk, W, b, no_graph, no_control, alpha * s)
+    if (no_graph != no_control and hip.rhs_abl_bwd_on() and _lib.load().ndcn_rhs_abl_bwd_supported(
+            out.shape[1], H, _lib.F_RELU | (_lib.F_NO_GRAPH if no_graph else _lib.F_NO_CONTROL))):
+        # an ablation under hip.set_rhs_abl_bwd (csrc/rhs_abl_bwd.hip): the evaluation's reverse as ONE call, which also accumulates
+        # g_W / g_b with the scale acc() would apply - _sweep_step hands acc the alpha it handed vj - so acc receives None
+        vj = lambda u, K, gk, alpha: (hip.rhs_vjp(csr, u, W, K, gk, acc_scale=alpha * s, gW=gW_tot, gb=gb_tot, no_graph=no_graph,
+                                                  no_control=no_control)[0], None, None)
 
     def acc(gW, gb, scale):
         if gW is not None:
