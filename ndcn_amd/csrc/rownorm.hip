@@ -14,6 +14,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// max(s, 1e-12) as clamp_min computes it: a NaN sum stays NaN (fmaxf would return the clamp and hide the row's NaN)
+__device__ __forceinline__ float clamp_den(float s) { return s < 1e-12f ? 1e-12f : s; }
+
 __device__ __forceinline__ float norm1(float x, float inv_or_den, bool) {
     const float y = x / inv_or_den;
     return (fabsf(y) == INFINITY) ? 0.f : y;
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(256) void rownorm_vec_kernel(const float *__restric
             v[i] = c < h4 ? xr[c] : (f32x4){0.f, 0.f, 0.f, 0.f};
             s += (fabsf(v[i].x) + fabsf(v[i].y)) + (fabsf(v[i].z) + fabsf(v[i].w));
         }
-        const float den = fmaxf(wave_sum(s), 1e-12f);
+        const float den = clamp_den(wave_sum(s));
         f32x4 *yr = reinterpret_cast<f32x4 *>(Y + r * H);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(256) void rownorm_any_kernel(const float *__restric
         const float *xr = X + r * H;
         float s = 0.f;
         for (int c = lane; c < H; c += 64) s += fabsf(xr[c]);
-        const float den = fmaxf(wave_sum(s), 1e-12f);
+        const float den = clamp_den(wave_sum(s));
         float *yr = Y + r * H;
         for (int c = lane; c < H; c += 64) yr[c] = norm1(xr[c], den, true);
     }
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float *__restric
         float s = 0.f;
         for (int c = lane; c < H; c += 64) s += fabsf(xr[c]);
         s = wave_sum(s);
-        const float den = fmaxf(s, 1e-12f);
+        const float den = clamp_den(s);
         float t = 0.f;
         for (int c = lane; c < H; c += 64) {
             const float x = xr[c];
