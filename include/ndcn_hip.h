@@ -1165,6 +1165,40 @@ NDCN_API int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int m
  * host predicate, no device needed.                                                                                                    */
 NDCN_API int ndcn_set_rhs_abl(int on);
 NDCN_API int ndcn_rhs_abl_supported(int64_t n_rows, int H, uint32_t flags);
+/* The two one-launch kernels above inside the device-resident solver (ndcn_solver_*; four calls and the NDCN_SOLVER_RHS_* names added to
+ * ABI 29: no existing declaration changes).  ndcn_solver_create chooses ONE launch kind per solve; without this switch a solve at hidden
+ * widths 16..128 on more than 2^18 state elements - and every NDCN_F_NO_GRAPH solve below H = 256 - evaluates f composed: SpMM into a
+ * scratch panel, MFMA Linear, a stand-alone stage kernel.  Under it such a solve takes NDCN_SOLVER_RHS_MID (graph and control,
+ * ndcn_rhs_mid_supported) or NDCN_SOLVER_RHS_ABL (exactly one of the two flags, ndcn_rhs_abl_supported, no long-row plan for the width):
+ * dopri5 runs one combine and six launches per attempted step, the stage algebra in the launches' epilogues - replayed steps read their
+ * coefficients fl(dt * beta) from device memory as NDCN_SOLVER_RHS_SMALL does - and forms the error record as ndcn_rhs_rk_f32 builds an
+ * NDCN_RK_ERROR launch on these routes, the plain launch plus ndcn_rk_error_f32's record; euler and rk4 carry their stage algebra in the
+ * launches by value; midpoint, which has no such form, keeps its kind.  The kinds come behind every other choice and never apply to a
+ * shard: no solve that has another kind changes it.  Trajectory, decoded ticks, step log and nfe are bit for bit those of the same solve
+ * with the switch off; ndcn_debug_last_rhs_path reports NDCN_PATH_MID / NDCN_PATH_ABL after such a launch.
+ * ndcn_set_solver_mid switches it PROCESS-WIDE at run time - read by ndcn_solver_create, a solver keeps its kind - and returns the previous
+ * mode; mode < 0 returns to the environment's (NDCN_SOLVER_MID, default 0); independent of ndcn_set_rhs_mid / ndcn_set_rhs_abl:
+ *   0  off
+ *   1  on except where a solver step measured slower than the composed form - H > 96, in every variant -
+ *      and the sizes ndcn_rhs_mid_supported leaves to the narrow-panel kernel in its mode 1
+ *   2  on for every supported shape
+ * ndcn_solver_mid_mode: the current mode, read without changing it.  ndcn_solver_mid_takes: the sizes' part of the decision for `mode` - a
+ * host predicate, no device needed.  ndcn_solver_rhs_kind: the kind this solver was created with (NDCN_EINVAL for a null handle); a shard
+ * reports NDCN_SOLVER_RHS_FUSED1 or NDCN_SOLVER_RHS_COMPOSED - whether its weights get packed - and dispatches every launch through
+ * ndcn_rhs_rk_f32's selection.                                                                                                          */
+#define NDCN_SOLVER_RHS_COMPOSED 0   /* ndcn_rhs_f32 picks the kernel, stand-alone stage kernels                                          */
+#define NDCN_SOLVER_RHS_FUSED1   1   /* H = 256 without a row-group plan: packed weights, stand-alone stage kernels                       */
+#define NDCN_SOLVER_RHS_MFMA     2   /* H = 256 on a row-group plan: the split-product launch with its epilogues                          */
+#define NDCN_SOLVER_RHS_REC      3   /* NDCN_F_NO_CONTROL on a group-record plan                                                           */
+#define NDCN_SOLVER_RHS_WIDE     4   /* NDCN_F_NO_CONTROL, the wide row SpMM with epilogues                                                */
+#define NDCN_SOLVER_RHS_SMALL    5   /* dopri5 on a narrow panel (n_rows * H <= 2^18): one launch per evaluation                          */
+#define NDCN_SOLVER_RHS_DYN      6   /* the truth dynamics (ndcn_solver_desc::dyn)                                                        */
+#define NDCN_SOLVER_RHS_MID      7   /* 16 <= H <= 128 at any size under ndcn_set_solver_mid: csrc/rhs_mid.hip                            */
+#define NDCN_SOLVER_RHS_ABL      8   /* the ablations at 16 <= H <= 128 under ndcn_set_solver_mid: csrc/rhs_abl.hip                       */
+NDCN_API int ndcn_set_solver_mid(int mode);
+NDCN_API int ndcn_solver_mid_mode(void);
+NDCN_API int ndcn_solver_mid_takes(int64_t n_rows, int H, uint32_t flags, int mode);
+NDCN_API int ndcn_solver_rhs_kind(const ndcn_solver *solver);
 /* The reverse of ONE right-hand-side evaluation K = relu(W (A X) + b) as a call (csrc/rhs_mid_bwd.hip; five calls added to ABI 29: no
  * existing declaration changes) - what autograd executes for ODEFunc.forward (neural_dynamics.py:27-36) under the drivers' training
  * step, and what the two native tapes run per evaluation:

@@ -55,6 +55,8 @@ F_RELU, F_NO_GRAPH, F_NO_CONTROL, F_PACKED, F_ACCUM = 1, 2, 4, 8, 16
 RK_NONE, RK_COMBINE, RK_ERROR, RK_RK4 = 0, 1, 2, 3
 M_EULER, M_MIDPOINT, M_RK4, M_DOPRI5 = 0, 1, 2, 3
 METHODS = {'euler': M_EULER, 'midpoint': M_MIDPOINT, 'rk4': M_RK4, 'dopri5': M_DOPRI5}
+# ndcn_solver_rhs_kind (NDCN_SOLVER_RHS_*): the launch kind a device-resident solver chose, by value
+SOLVER_RHS_KINDS = ('composed', 'fused1', 'mfma', 'rec', 'wide', 'small', 'dyn', 'mid', 'abl')
 PROF_KINDS = ('spmm', 'linear', 'rhs_fused', 'combine', 'error', 'sumsq', 'interp_fit', 'interp_eval',
               'fixed_stage', 'gather_rows', 'truth_dynamics', 'combine_bwd', 'error_bwd', 'sumsq_bwd', 'dense_bwd', 'linear_gs',
               'linear_wgrad', 'relu_bwd', 'rhs_adjoint_forward_half', 'rhs_adjoint_transposed_half')
@@ -348,6 +350,10 @@ SIGNATURES = {
     'ndcn_rhs_mid_supported': (_I, [_L, _I, _U, _I]),
     'ndcn_set_rhs_abl': (_I, [_I]),
     'ndcn_rhs_abl_supported': (_I, [_L, _I, _U]),
+    'ndcn_set_solver_mid': (_I, [_I]),
+    'ndcn_solver_mid_mode': (_I, []),
+    'ndcn_solver_mid_takes': (_I, [_L, _I, _U, _I]),
+    'ndcn_solver_rhs_kind': (_I, [_P]),
     'ndcn_rhs_vjp_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U, _I, _F, _I, _P]),
     'ndcn_rhs_vjp_work_bytes': (_L, [_L, _I, _U]),
     'ndcn_set_rhs_mid_bwd': (_I, [_I]),

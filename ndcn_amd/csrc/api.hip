@@ -54,6 +54,10 @@ int ndcn_set_rhs_mid_drop(int on) { return set_rhs_mid_drop(on); }
 int ndcn_rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_supported(n_rows, H, flags, mode); }
 int ndcn_set_rhs_abl(int on) { return set_rhs_abl(on); }
 int ndcn_rhs_abl_supported(int64_t n_rows, int H, uint32_t flags) { return rhs_abl_supported(n_rows, H, flags); }
+int ndcn_set_solver_mid(int mode) { return set_solver_mid(mode); }
+int ndcn_solver_mid_mode(void) { return solver_mid_mode(); }
+int ndcn_solver_mid_takes(int64_t n_rows, int H, uint32_t flags, int mode) { return solver_mid_takes(n_rows, H, flags, mode); }
+int ndcn_solver_rhs_kind(const ndcn_solver *s) { return solver_rhs_kind(s); }
 int ndcn_set_rhs_mid_bwd(int mode) { return set_rhs_mid_bwd(mode); }
 int ndcn_rhs_mid_bwd_supported(int64_t n_rows, int H, uint32_t flags, int mode) { return rhs_mid_bwd_supported(n_rows, H, flags, mode); }
 int ndcn_set_rhs_abl_bwd(int on) { return set_rhs_abl_bwd(on); }

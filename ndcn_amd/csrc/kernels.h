@@ -115,9 +115,11 @@ int set_rhs_mid(int mode);                    // ndcn_set_rhs_mid: returns the p
 int rhs_mid_drop_on();
 int set_rhs_mid_drop(int on);                 // ndcn_set_rhs_mid_drop: returns the previous value; < 0: back to the environment's
 int rhs_mid_supported(int64_t n_rows, int H, uint32_t flags, int mode);      // from the sizes alone, no device
+// c_dev (nullable, device; COMBINE without drop or y_aux): the coefficients as rhs_small_f32 / spmm_rec_f32 define them - c_dev[m],
+// m <= n_prev - in place of h_c (a replayed adaptive step: solver.hip).  RK4 has no such form yet: no step replays it (NDCN_EINVAL)
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
+                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr, const float *c_dev = nullptr);
 // rhs_abl.hip: the two ablations - no_control K = relu(A X), no_graph K = relu(X W^T + b) - in one launch for 16 <= H <= 128 (H % 4 == 0)
 // at any number of rows, with rhs_mid.hip's epilogue: mode 0, NDCN_RK_COMBINE (RkOpt::y_aux / c_aux) or NDCN_RK_RK4, drop as there; every
 // panel 16-byte aligned, no halo panel; the bits of the composed path.  The switch (ndcn_set_rhs_abl / NDCN_RHS_ABL): 0 off, 1 on
@@ -127,7 +129,7 @@ int rhs_abl_supported(int64_t n_rows, int H, uint32_t flags);                 //
 int rhs_abl_takes(const ndcn_csr *A, int H, uint32_t flags);                  // ... and the operator (no long-row plan for this width)
 int rhs_abl_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr);
+                const RkOpt *opt = nullptr, const DropArgs *drop = nullptr, const float *c_dev = nullptr);   // c_dev: as rhs_mid_f32's
 // linear_bwd.hip: the row chunks linear_bwd_f32 cuts the weight gradient into (`used` chunks of rpc rows) and the fixed-order sum of
 // their partial blocks into gW / gb (one of them nullable)
 void wgrad_chunking(int64_t n, int Hi, int Ho, int64_t *rpc, int64_t *used);
@@ -323,5 +325,13 @@ int solver_advance_grid(ndcn_solver *s, const float *h_grid, int64_t n_grid, con
                         int64_t n_ticks, float *out, hipStream_t st);
 int solver_stats(const ndcn_solver *s, double h[6]);
 int64_t solver_steplog(const ndcn_solver *s, double *rows, int64_t cap);
+// The solver's own switch for the one-launch kernels of rhs_mid.hip / rhs_abl.hip (ndcn_set_solver_mid / NDCN_SOLVER_MID; read at
+// solver_create): 0 off, 1 the widths that did not measure slower, 2 every supported width.  solver_mid_takes: the sizes' part of the
+// decision (no device, no operator): rhs_mid_supported with graph and control, rhs_abl_supported with exactly one of the two flags -
+// at mode 1 without the widths above rhs_mid.hip's mode-1 bound (H > 96) in any variant
+int solver_mid_mode();
+int set_solver_mid(int mode);                 // returns the previous mode; < 0: back to the environment's
+int solver_mid_takes(int64_t n_rows, int H, uint32_t flags, int mode);
+int solver_rhs_kind(const ndcn_solver *s);    // NDCN_SOLVER_RHS_*
 
 }  // namespace ndcn

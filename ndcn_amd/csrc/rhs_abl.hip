@@ -68,14 +68,16 @@ __device__ __forceinline__ void abl_tiles(int n, int &t0, int &t1) {
     t1 = t0 + base + (b < rem ? 1 : 0);
 }
 
-template <int MODE, bool DROP>
-__global__ __launch_bounds__(kMidThreads) void rhs_abl_graph_kernel(AblArgs a, MidEpi e, DropArgs d) {
+template <int MODE, bool DROP, bool CDEV = false>
+__global__ __launch_bounds__(kMidThreads) void rhs_abl_graph_kernel(AblArgs a, MidEpi e, DropArgs d, const float *c_dev) {
     const int H = a.H, n = a.n_rows;
     int t0, t1;
     abl_tiles(n, t0, t1);
     const int tid = threadIdx.x, lsh = a.lsh;
     const int g = tid >> lsh, c4 = (tid & ((1 << lsh) - 1)) * 4, rows_per_pass = kMidThreads >> lsh;
     if (c4 >= H) return;                                     // (no barrier anywhere below)
+    MidCoef kc = {};
+    if (CDEV) kc = mid_coef_dev(c_dev, e.n_prev);
     const float *xc = a.X + c4;
     for (int t = t0; t < t1; ++t) {
         const int r0 = t * kMidTile;
@@ -94,13 +96,13 @@ __global__ __launch_bounds__(kMidThreads) void rhs_abl_graph_kernel(AblArgs a, M
             }
             for (; j < j1; ++j) mid_fma4(s, a.val[j], mid_ld4(xc + (size_t)a.colidx[j] * H));
             if (a.relu) { s.x = relu_nan(s.x); s.y = relu_nan(s.y); s.z = relu_nan(s.z); s.w = relu_nan(s.w); }
-            mid_epi_lane<MODE, DROP>(s, (size_t)gr * H + c4, a.K, e, d);
+            mid_epi_lane<MODE, DROP, CDEV>(s, (size_t)gr * H + c4, a.K, e, d, kc);
         }
     }
 }
 
-template <int MODE, bool DROP>
-__global__ __launch_bounds__(kMidThreads) void rhs_abl_dense_kernel(AblArgs a, MidEpi e, DropArgs d) {
+template <int MODE, bool DROP, bool CDEV = false>
+__global__ __launch_bounds__(kMidThreads) void rhs_abl_dense_kernel(AblArgs a, MidEpi e, DropArgs d, const float *c_dev) {
     extern __shared__ __align__(16) float abl_lds[];
     const int H = a.H, n = a.n_rows;
     const int P = (H + 31) & ~31;                            // H padded to the MFMA tile: k steps and output columns
@@ -119,6 +121,8 @@ __global__ __launch_bounds__(kMidThreads) void rhs_abl_dense_kernel(AblArgs a, M
     const int wm = wave & 1, tn = wave >> 1;
     const int on = tn * 32 + (lane & 31);
     const float bv = (wave < n_jobs && a.bias && on < H) ? a.bias[on] : 0.f;
+    MidCoef kc = {};
+    if (CDEV) kc = mid_coef_dev(c_dev, e.n_prev);
     for (int t = t0; t < t1; ++t) {
         const int r0 = t * kMidTile;
         // ---- the X tile, 16 bytes per lane
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(kMidThreads) void rhs_abl_dense_kernel(AblArgs a, M
             const int row = i / H4, q = i - row * H4;
             const int gr = r0 + row;
             if (gr >= n) continue;
-            mid_epi_lane<MODE, DROP>(mid_ld4(s_T + row * P + 4 * q), (size_t)gr * H + 4 * q, a.K, e, d);
+            mid_epi_lane<MODE, DROP, CDEV>(mid_ld4(s_T + row * P + 4 * q), (size_t)gr * H + 4 * q, a.K, e, d, kc);
         }
         __syncthreads();                                     // the next tile's load overwrites the K tile
     }
@@ -202,12 +206,13 @@ static size_t abl_lds_bytes(int H) {
 
 int rhs_abl_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt, const DropArgs *drop) {
+                const RkOpt *opt, const DropArgs *drop, const float *c_dev) {
     const int n_rows = (int)A->n_rows;
     if (!rhs_abl_takes(A, H, flags)) { set_error("rhs_abl: one of no_graph / no_control, H a multiple of 4 in 16..128"); return NDCN_EINVAL; }
     if (mode != MID_PLAIN && mode != MID_COMBINE && mode != MID_RK4) { set_error("rhs_abl: bad mode"); return NDCN_EINVAL; }
     if (n_prev < 0 || n_prev > kMidMaxPrev || (mode == MID_RK4 && n_prev > 3)) { set_error("rhs_abl: bad stage count"); return NDCN_EINVAL; }
     if (drop && !(flags & NDCN_F_RELU)) { set_error("rhs_abl: dropout without the ReLU"); return NDCN_EINVAL; }
+    if (c_dev && (mode != MID_COMBINE || drop || (opt && opt->y_aux))) { set_error("rhs_abl: c_dev goes with COMBINE, without dropout or y_aux"); return NDCN_EINVAL; }
     const bool dense = flags & NDCN_F_NO_GRAPH;
     AblArgs a = {};
     a.X = X; a.K = K; a.n_rows = n_rows; a.H = H; a.relu = (flags & NDCN_F_RELU) ? 1 : 0;
@@ -226,25 +231,27 @@ int rhs_abl_f32(const ndcn_csr *A, const float *X, const float *W, const float *
     if (mode != MID_PLAIN) bytes += Pn * (n_prev + 2 + (e.y_aux ? 1 : 0));
     ProfScope prof(PROF_RHS_FUSED, st, bytes, dense ? 2.0 * (double)n_rows * H * H : 2.0 * A->nnz * H);
     const DropArgs dv = drop ? *drop : DropArgs{};
-#define NDCN_ABL(MODE_, DROP_)                                                                                            \
+#define NDCN_ABL(MODE_, DROP_, CDEV_)                                                                                          \
     do {                                                                                                                  \
         if (dense) {                                                                                                      \
-            auto kern = rhs_abl_dense_kernel<MODE_, DROP_>;                                                               \
+            auto kern = rhs_abl_dense_kernel<MODE_, DROP_, CDEV_>;                                                        \
             static std::atomic<unsigned long long> attr_seen{0};                                                          \
             if (once_per_device(attr_seen))                                                                               \
                 NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)abl_lds_bytes(kMidMaxH))); \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e, dv);                                   \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e, dv, c_dev);                            \
         } else {                                                                                                          \
-            hipLaunchKernelGGL((rhs_abl_graph_kernel<MODE_, DROP_>), dim3(grid), dim3(kMidThreads), 0, st, a, e, dv);     \
+            hipLaunchKernelGGL((rhs_abl_graph_kernel<MODE_, DROP_, CDEV_>), dim3(grid), dim3(kMidThreads), 0, st, a, e, dv, c_dev); \
         }                                                                                                                 \
     } while (0)
     if (drop) {
-        if (mode == MID_PLAIN) NDCN_ABL(MID_PLAIN, true);
-        else if (mode == MID_COMBINE) NDCN_ABL(MID_COMBINE, true);
-        else NDCN_ABL(MID_RK4, true);
-    } else if (mode == MID_PLAIN) NDCN_ABL(MID_PLAIN, false);
-    else if (mode == MID_COMBINE) NDCN_ABL(MID_COMBINE, false);
-    else NDCN_ABL(MID_RK4, false);
+        if (mode == MID_PLAIN) NDCN_ABL(MID_PLAIN, true, false);
+        else if (mode == MID_COMBINE) NDCN_ABL(MID_COMBINE, true, false);
+        else NDCN_ABL(MID_RK4, true, false);
+    } else if (c_dev) {                                      // a replayed adaptive step: coefficients from device memory (rhs_mid_epi.h)
+        NDCN_ABL(MID_COMBINE, false, true);
+    } else if (mode == MID_PLAIN) NDCN_ABL(MID_PLAIN, false, false);
+    else if (mode == MID_COMBINE) NDCN_ABL(MID_COMBINE, false, false);
+    else NDCN_ABL(MID_RK4, false, false);
 #undef NDCN_ABL
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;

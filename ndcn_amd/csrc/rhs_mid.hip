@@ -58,8 +58,8 @@ struct MidArgs {
 // The tile constants, MidEpi, mid_wsum and mid_rk4 are rhs_mid_epi.h's, shared with rhs_abl.hip.  The epilogue below stays written out
 // in this kernel: calling the header's mid_epi_lane instead - the same statements - made the compiler schedule and allocate the six
 // instantiations differently, and they are to stay the kernels that were measured.
-template <int MODE, bool DROP>
-__global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi e, DropArgs d) {
+template <int MODE, bool DROP, bool CDEV = false>
+__global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi e, DropArgs d, const float *c_dev) {
     extern __shared__ __align__(16) float mid_lds[];
     const int H = a.H, n = a.n_rows;
     const int P = (H + 31) & ~31;                            // H padded to the MFMA tile: k steps and output columns
@@ -87,6 +87,8 @@ __global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi 
     const int on = tn * 32 + (lane & 31);
     const float bv = (wave < n_jobs && a.bias && on < H) ? a.bias[on] : 0.f;
     const int np = e.n_prev;
+    MidCoef kc = {};                                         // CDEV: the coefficients, scalar loads at the kernel's entry (rhs_mid_epi.h)
+    if (CDEV) kc = mid_coef_dev(c_dev, np);
     for (int t = t0; t < t1; ++t) {
         const int r0 = t * kMidTile;
         // ---- gather: S = (A X)[r0 .. r0 + 64, :]
@@ -163,6 +165,11 @@ __global__ __launch_bounds__(kMidThreads) void rhs_mid_kernel(MidArgs a, MidEpi 
                                                     mid_rk4(y.z, kz, kn.z, np, dt), mid_rk4(y.w, kw, kn.w, np, dt)));
                 continue;
             }
+            if (CDEV) {
+                mid_st4(e.y_next + idx, make_float4(y.x + mid_wsum_dev(kc, kx, kn.x, np), y.y + mid_wsum_dev(kc, ky, kn.y, np),
+                                                    y.z + mid_wsum_dev(kc, kz, kn.z, np), y.w + mid_wsum_dev(kc, kw, kn.w, np)));
+                continue;
+            }
             mid_st4(e.y_next + idx, make_float4(y.x + mid_wsum(e.c, kx, kn.x, np), y.y + mid_wsum(e.c, ky, kn.y, np),
                                                 y.z + mid_wsum(e.c, kz, kn.z, np), y.w + mid_wsum(e.c, kw, kn.w, np)));
             if (e.y_aux)
@@ -223,13 +230,14 @@ static size_t mid_lds_bytes(int H) {
 
 int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *b, float *K, int H, uint32_t flags, int mode,
                 const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next, hipStream_t st,
-                const RkOpt *opt, const DropArgs *drop) {
+                const RkOpt *opt, const DropArgs *drop, const float *c_dev) {
     const int n_rows = (int)A->n_rows;
     if (n_rows == 0) return NDCN_OK;
     if (H < kMidMinH || H > kMidMaxH || (H & 3)) { set_error("rhs_mid: H must be a multiple of 4 in 16..128"); return NDCN_EINVAL; }
     if (mode != MID_PLAIN && mode != MID_COMBINE && mode != MID_RK4) { set_error("rhs_mid: bad mode"); return NDCN_EINVAL; }
     if (n_prev < 0 || n_prev > kMidMaxPrev || (mode == MID_RK4 && n_prev > 3)) { set_error("rhs_mid: bad stage count"); return NDCN_EINVAL; }
     if (drop && !(flags & NDCN_F_RELU)) { set_error("rhs_mid: dropout without the ReLU"); return NDCN_EINVAL; }
+    if (c_dev && (mode != MID_COMBINE || drop || (opt && opt->y_aux))) { set_error("rhs_mid: c_dev goes with COMBINE, without dropout or y_aux"); return NDCN_EINVAL; }
     MidArgs a;
     a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val; a.X = X; a.W = W; a.bias = b; a.K = K;
     a.n_rows = n_rows; a.H = H; a.relu = (flags & NDCN_F_RELU) ? 1 : 0;
@@ -247,21 +255,23 @@ int rhs_mid_f32(const ndcn_csr *A, const float *X, const float *W, const float *
     if (mode != MID_PLAIN) bytes += Pn * (n_prev + 2 + (e.y_aux ? 1 : 0));
     ProfScope prof(PROF_RHS_FUSED, st, bytes, 2.0 * A->nnz * H + 2.0 * (double)n_rows * H * H);
     const DropArgs dv = drop ? *drop : DropArgs{};
-#define NDCN_MID(MODE_, DROP_)                                                                                            \
+#define NDCN_MID(MODE_, DROP_, CDEV_)                                                                                          \
     do {                                                                                                                  \
-        auto kern = rhs_mid_kernel<MODE_, DROP_>;                                                                         \
+        auto kern = rhs_mid_kernel<MODE_, DROP_, CDEV_>;                                                                  \
         static std::atomic<unsigned long long> attr_seen{0};                                                              \
         if (once_per_device(attr_seen))                                                                                   \
             NDCN_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds_bytes(kMidMaxH))); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e, dv);                                       \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMidThreads), lds, st, a, e, dv, c_dev);                                \
     } while (0)
     if (drop) {
-        if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, true);
-        else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, true);
-        else NDCN_MID(MID_RK4, true);
-    } else if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, false);
-    else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, false);
-    else NDCN_MID(MID_RK4, false);
+        if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, true, false);
+        else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, true, false);
+        else NDCN_MID(MID_RK4, true, false);
+    } else if (c_dev) {                                      // a replayed adaptive step: coefficients from device memory (rhs_mid_epi.h)
+        NDCN_MID(MID_COMBINE, false, true);
+    } else if (mode == MID_PLAIN) NDCN_MID(MID_PLAIN, false, false);
+    else if (mode == MID_COMBINE) NDCN_MID(MID_COMBINE, false, false);
+    else NDCN_MID(MID_RK4, false, false);
 #undef NDCN_MID
     NDCN_LAUNCH_CHECK();
     return NDCN_OK;

@@ -59,10 +59,40 @@ __device__ __forceinline__ float mid_rk4(float y, const float (&km)[kMidMaxPrev]
     return y + (km[0] + 3.f * km[1] + 3.f * km[2] + kn) * (dt / 8.f);
 }
 
+// CDEV - a replayed adaptive step (solver.hip), whose step size lives in device memory: the coefficients come from `c_dev` instead of
+// MidEpi::c, with the meaning rhs_small_f32 / spmm_rec_f32 give that argument - COMBINE reads c_dev[m], m <= n_prev, the fl(dt * beta) image
+// that the graph's first kernel writes; never together with y_aux.  (COMBINE only: no step replays an RK4 launch - the fixed grids pass
+// dt by value -, so that form is not instantiated until it has a caller.)  The address is the same for every lane and
+// the loads stand at the kernel's entry, before its first store: scalar loads into SGPRs, once per workgroup, and the new stage's
+// coefficient c[n_prev] is picked there too - the epilogue loop holds no more vector registers than the by-value form, which indexes
+// its kernel argument.  The arithmetic behind the fetch is mid_wsum's / mid_rk4's.
+struct MidCoef {
+    float c[kMidMaxPrev + 1];
+    float cn;                         // c[n_prev]
+};
+
+__device__ __forceinline__ MidCoef mid_coef_dev(const float *c_dev, int np) {
+    MidCoef k;
+#pragma unroll
+    for (int m = 0; m <= kMidMaxPrev; ++m) k.c[m] = m <= np ? c_dev[m] : 0.f;
+    k.cn = c_dev[np];            // (a load of its own: a select chain over c[] would run on the vector unit)
+    return k;
+}
+
+// mid_wsum with the coefficients of MidCoef: the same products and sums in the same order
+__device__ __forceinline__ float mid_wsum_dev(const MidCoef &k, const float (&km)[kMidMaxPrev], float kn, int np) {
+    float acc = 0.f + k.c[0] * (np > 0 ? km[0] : kn);
+#pragma unroll
+    for (int m = 1; m < kMidMaxPrev; ++m)
+        if (m < np) acc = acc + k.c[m] * km[m];
+    if (np > 0) acc = acc + k.cn * kn;
+    return acc;
+}
+
 // One lane's share of the epilogue: kn = K[idx .. idx + 4) as the launch formed it (behind the ReLU).  The statements of
-// rhs_mid_kernel's epilogue loop, which keeps its own copy (see there); rhs_abl.hip's kernels call this one.
-template <int MODE, bool DROP>
-__device__ __forceinline__ void mid_epi_lane(float4 kn, size_t idx, float *K, const MidEpi &e, const DropArgs &d) {
+// rhs_mid_kernel's epilogue loop, which keeps its own copy (see there); rhs_abl.hip's kernels call this one.  kc: read under CDEV only.
+template <int MODE, bool DROP, bool CDEV = false>
+__device__ __forceinline__ void mid_epi_lane(float4 kn, size_t idx, float *K, const MidEpi &e, const DropArgs &d, const MidCoef &kc) {
     if (DROP) {                                          // K' = K * m: stored, and the K of everything below
         const Philox4 o = drop_words<true>(d, (int64_t)(idx >> 2));
         kn.x = kn.x * (o.w[0] >= d.thresh ? d.s : 0.f);
@@ -86,6 +116,11 @@ __device__ __forceinline__ void mid_epi_lane(float4 kn, size_t idx, float *K, co
                                             mid_rk4(y.z, kz, kn.z, np, dt), mid_rk4(y.w, kw, kn.w, np, dt)));
         return;
     }
+    if (CDEV) {
+        mid_st4(e.y_next + idx, make_float4(y.x + mid_wsum_dev(kc, kx, kn.x, np), y.y + mid_wsum_dev(kc, ky, kn.y, np),
+                                            y.z + mid_wsum_dev(kc, kz, kn.z, np), y.w + mid_wsum_dev(kc, kw, kn.w, np)));
+        return;
+    }
     mid_st4(e.y_next + idx, make_float4(y.x + mid_wsum(e.c, kx, kn.x, np), y.y + mid_wsum(e.c, ky, kn.y, np),
                                         y.z + mid_wsum(e.c, kz, kn.z, np), y.w + mid_wsum(e.c, kw, kn.w, np)));
     if (e.y_aux)
@@ -93,7 +128,8 @@ __device__ __forceinline__ void mid_epi_lane(float4 kn, size_t idx, float *K, co
                                            mid_wsum(e.c2, kz, kn.z, np), mid_wsum(e.c2, kw, kn.w, np)));
 }
 
-// the host side of MidEpi: the stage arguments of rhs_rk_f32 (mode != MID_PLAIN)
+// the host side of MidEpi: the stage arguments of rhs_rk_f32 (mode != MID_PLAIN).  Under c_dev the launch reads neither c nor c2 (h_c then
+// holds the bare tableau entries of the replayed step)
 inline void mid_epi_fill(MidEpi &e, int mode, const float *y0, const float *const *h_kprev, const float *h_c, int n_prev, float *y_next,
                          float *y_aux, const float *c_aux) {
     e.y0 = y0; e.y_next = y_next; e.n_prev = n_prev;

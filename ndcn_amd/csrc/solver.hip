@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <new>
 #include <algorithm>
+#include <atomic>
 #include <utility>
 #include <vector>
 
@@ -32,10 +33,18 @@ using namespace ndcn;
 //   Wide      true                un-sharded, no_control, spmm_wide_rk_supported                    spmm_wide_rk_f32
 //   Small     true                un-sharded, graph and control, not H = 256, DOPRI5,               rhs_small_f32
 //                                 rhs_small_supported (fixed-grid methods: Composed)
+//   Mid       true                un-sharded, none of the above, under the solver's own switch      rhs_mid_f32
+//                                 (solver_mid_mode): graph and control, rhs_mid_supported
+//   Abl       true                un-sharded, none of the above, under the same switch: exactly     rhs_abl_f32
+//                                 one of no_graph / no_control, rhs_abl_takes, solver_mid_takes    
 //   Composed  false               everything else                                                   rhs_f32 picks the kernel, rk.hip the algebra
 // A shard (ndcn_solver::sharded) is orthogonal: every launch of it dispatches through rhs_rk_f32 (rhs_sharded), with epi = true;
 // its kind says only whether the weights get packed - Fused1 at H = 256 with graph and control, else Composed.
-enum class Rhs { Composed, Fused1, Mfma, Rec, Wide, Small, Dyn };
+// (The values are the NDCN_SOLVER_RHS_* of the public header: ndcn_solver_rhs_kind.)
+enum class Rhs { Composed, Fused1, Mfma, Rec, Wide, Small, Dyn, Mid, Abl };
+static_assert((int)Rhs::Composed == NDCN_SOLVER_RHS_COMPOSED && (int)Rhs::Fused1 == NDCN_SOLVER_RHS_FUSED1 && (int)Rhs::Mfma == NDCN_SOLVER_RHS_MFMA &&
+              (int)Rhs::Rec == NDCN_SOLVER_RHS_REC && (int)Rhs::Wide == NDCN_SOLVER_RHS_WIDE && (int)Rhs::Small == NDCN_SOLVER_RHS_SMALL &&
+              (int)Rhs::Dyn == NDCN_SOLVER_RHS_DYN && (int)Rhs::Mid == NDCN_SOLVER_RHS_MID && (int)Rhs::Abl == NDCN_SOLVER_RHS_ABL, "ndcn_hip.h");
 
 struct ndcn_solver {
     ndcn_solver_desc d;
@@ -123,7 +132,9 @@ inline size_t align_up(size_t v) { return (v + 255u) & ~(size_t)255u; }
 // `work` holds the packed weights of the H = 256 kernels (packed in solver_begin)
 inline bool packs_weights(const ndcn_solver *s) { return s->kind == Rhs::Mfma || s->kind == Rhs::Fused1; }
 // the epilogue launch is not the MFMA kernel: it can read its coefficients from device memory (c_dev), i.e. be replayed
-inline bool takes_c_dev(const ndcn_solver *s) { return s->kind == Rhs::Rec || s->kind == Rhs::Wide || s->kind == Rhs::Small || (s->kind == Rhs::Dyn && s->epi); }
+inline bool takes_c_dev(const ndcn_solver *s) {
+    return s->kind == Rhs::Rec || s->kind == Rhs::Wide || s->kind == Rhs::Small || s->kind == Rhs::Mid || s->kind == Rhs::Abl || (s->kind == Rhs::Dyn && s->epi);
+}
 // the launch has the options only the split-product MFMA kernel carries (RkOpt::xadd, c_mid with no_k: dense output).  Never true for a
 // shard - whose launches may still be that kernel: a site that serves shards asks for them by its own condition
 inline bool mfma_options(const ndcn_solver *s) { return s->kind == Rhs::Mfma && !s->exact32; }
@@ -187,7 +198,7 @@ int rhs(ndcn_solver *s, const float *x, float *out, hipStream_t st) {
                                   nullptr, 0.f, 0.f, nullptr, nullptr, st, nullptr);
         case Rhs::Fused1:   // weights were packed once in solver_begin
             return rhs_fused_packed_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, out, s->d.rhs_flags, st);
-        default:            // Composed, and the plain evaluations of Rec / Wide / Small: rhs_f32 picks the kernel
+        default:            // Composed, and the plain evaluations of Rec / Wide / Small / Mid / Abl: rhs_f32 picks the kernel
             return rhs_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, out, s->work, s->d.H, s->d.rhs_flags, st);
     }
 }
@@ -222,6 +233,43 @@ int rhs_epi(ndcn_solver *s, const float *x, float *K, int mode, const float *y0,
         case Rhs::Mfma:
             return mfma_launch(s)(&s->d.A, x, nullptr, s->d.A.n_cols, s->work, s->d.b, K, s->d.rhs_flags, mode, y0, kp, cp, n_prev, y_next,
                                   rtol, atol, d_out, d_ws, st, opt);
+        case Rhs::Mid:
+        case Rhs::Abl: {
+            const bool mid = s->kind == Rhs::Mid;
+            auto launch = [&](int m, const float *y0_, const float *const *kp_, const float *cp_, int np_, float *yn_, const RkOpt *o_, const float *cd_) {
+                return mid ? rhs_mid_f32(&s->d.A, x, s->d.W, s->d.b, K, s->d.H, s->d.rhs_flags, m, y0_, kp_, cp_, np_, yn_, st, o_, nullptr, cd_)
+                           : rhs_abl_f32(&s->d.A, x, s->d.W, s->d.b, K, s->d.H, s->d.rhs_flags, m, y0_, kp_, cp_, np_, yn_, st, o_, nullptr, cd_);
+            };
+            // the kernels move 16 bytes per lane: a caller's panel that is not aligned so (the solver's own all are) takes the dispatch
+            // of ndcn_rhs_rk_f32, which composes the same bits
+            bool al = aligned16(x) && aligned16(K) && aligned16(y0) && aligned16(y_next) && !(opt && opt->y_aux && !aligned16(opt->y_aux)) &&
+                      !(opt && opt->y1 && !aligned16(opt->y1)) && (!s->d.W || aligned16(s->d.W));
+            for (int m = 0; m < n_prev; ++m) al = al && aligned16(kp[m]);
+            if (!al) {
+                // (a replayed step runs on the solver's own panels alone: this would be a bug here, and it fails the capture as a whole -
+                // the slice of the coefficient table taken above goes with it)
+                if (c_dev) { set_error("solver: a replayed step on a panel that is not 16-byte aligned"); return NDCN_ESTATE; }
+                return rhs_rk_f32(&s->d.A, x, nullptr, s->d.A.n_cols, s->d.W, s->d.b, K, s->work, s->d.H, s->d.rhs_flags, mode, y0, kp, cp, n_prev,
+                                  y_next, rtol, atol, d_out, d_ws, st, opt);
+            }
+            g_last_rhs_path = mid ? NDCN_PATH_MID : NDCN_PATH_ABL;
+            if (mode == NDCN_RK_ERROR) {
+                // neither kernel forms the record: the K launch, then rk_error_f32's record over {kp..., K} - what ndcn_rhs_rk_f32 builds for
+                // an ERROR launch on these routes, and the words (hence every accept / reject decision) of the composed step.  Replayed:
+                // cp holds the bare tableau entries and rk_error_f32 forms fl(dt * c) from the device-resident step size, as there.
+                int rc = launch(0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+                if (rc) return rc;
+                const float *kk[kCoefCap];
+                for (int m = 0; m < n_prev; ++m) kk[m] = kp[m];
+                kk[n_prev] = K;
+                return rk_error_f32(y0, (opt && opt->y1) ? opt->y1 : x, kk, cp, n_prev + 1, rtol, atol, s->n_elem, d_out, d_ws, st,
+                                    c_dev ? dt_dev : nullptr, (opt && opt->accum) ? 1 : 0);
+            }
+            // of RkOpt the kernels know y_aux / c_aux (eager steps only); no_k is a saving they do not make: K is stored and never read
+            RkOpt o = {};
+            if (opt) { o.y_aux = opt->y_aux; o.c_aux = opt->c_aux; }
+            return launch(mode, y0, kp, cp, n_prev, y_next, &o, c_dev);
+        }
         default: set_error("solver: this right-hand side carries no stage epilogue"); return NDCN_ESTATE;
     }
 }
@@ -288,7 +336,8 @@ int initial_step(ndcn_solver *s, hipStream_t st, double &h_out) {
     const float *kp[1] = {s->k[0]};
     const float cp[1] = {h0};
     // (on the lattice plan the launch that produces f1 forms y0 + h0 f0 on the rows it stages: RkOpt::xadd)
-    const bool fuse_d2 = big && s->epi;
+    // (Mid / Abl form no record in their launch: the probe keeps the composed solve's two launches, and with them its d2 to the bit)
+    const bool fuse_d2 = big && s->epi && s->kind != Rhs::Mid && s->kind != Rhs::Abl;
     const bool xadd = fuse_d2 && !s->sharded && mfma_options(s) && rhs_xadd_supported(&s->d.A, s->d.H, s->d.rhs_flags, 2, 1);
     if (!xadd) {
         rc = rk_combine_f32(s->ytmp, s->ycur, kp, cp, 1, s->n_elem, st);
@@ -748,6 +797,35 @@ int do_fit(ndcn_solver *s, hipStream_t st) {
 
 namespace ndcn {
 
+// ---------------------------------------------------------------------------------------------------- the Mid / Abl switch
+static std::atomic<int> g_solver_mid_override{-1};         // ndcn_set_solver_mid: -1 = the environment's mode
+
+int solver_mid_mode() {
+    const int ov = g_solver_mid_override.load(std::memory_order_relaxed);
+    if (ov >= 0) return ov;
+    static const int env_mode = std::min(2, std::max(0, env_int("NDCN_SOLVER_MID", 0)));
+    return env_mode;
+}
+
+int set_solver_mid(int mode) {
+    const int prev = solver_mid_mode();
+    g_solver_mid_override.store(mode < 0 ? -1 : std::min(mode, 2), std::memory_order_relaxed);
+    return prev;
+}
+
+// Mode 1 leaves composed what measured slower per solver step (tools/bench_solver_mid.py): the widths padded to
+// P = 128, H > 96, in every variant - with graph and control (rhs_mid_supported's own mode-1 bound, the per-launch figures agree), for
+// no_graph (one workgroup per CU) and for no_control (rk4 at H = 128: 1.01 - 1.05 x)
+int solver_mid_takes(int64_t n_rows, int H, uint32_t flags, int mode) {
+    if (mode != 1 && mode != 2) return 0;
+    const bool no_graph = flags & NDCN_F_NO_GRAPH, no_ctl = flags & NDCN_F_NO_CONTROL;
+    if (!no_graph && !no_ctl) return rhs_mid_supported(n_rows, H, flags, mode);
+    if (!rhs_abl_supported(n_rows, H, flags)) return 0;
+    return !(mode == 1 && H > 96);
+}
+
+int solver_rhs_kind(const ndcn_solver *s) { return s ? (int)s->kind : NDCN_EINVAL; }
+
 int64_t solver_workspace_bytes(const ndcn_solver_desc *desc) {
     if (!desc || desc->H <= 0 || desc->A.n_rows < 0) return NDCN_EINVAL;
     return (int64_t)workspace_bytes(desc);
@@ -905,6 +983,14 @@ int solver_create(const ndcn_solver_desc *desc, void *workspace, int64_t ws_byte
             // narrow panels: the adaptive step runs 1 combine + 6 launches; fixed-grid methods keep their replayed step,
             // whose right-hand sides go through the same kernel in plain mode (rhs_f32)
             s->kind = Rhs::Small;
+        } else if (const int sm = solver_mid_mode(); sm != 0 && desc->method != NDCN_M_MIDPOINT &&
+                                                     solver_mid_takes(s->n_rows, desc->H, desc->rhs_flags, sm) &&
+                                                     (both || rhs_abl_takes(&desc->A, desc->H, desc->rhs_flags))) {
+            // behind every choice above, and only under the solver's own switch: no solve that has a kind without it changes kind.
+            // dopri5: 1 combine + 6 launches per attempt (replayed: coefficients from device memory); euler / rk4: the stage algebra in
+            // the launches' epilogues, by value.  Midpoint has no epilogue form (fixed_advance): it would only lose its replayed step, so
+            // it stays Composed.  The plain evaluations go through rhs_f32
+            s->kind = both ? Rhs::Mid : Rhs::Abl;
         }
         if (!s->sharded) s->epi = s->kind != Rhs::Composed && s->kind != Rhs::Fused1;      // the launches named above but the first-generation kernel
     }

@@ -560,6 +560,24 @@ class HipOps:
         return int(_lib.load().ndcn_set_rhs_abl(int(on)))
 
     @staticmethod
+    def set_solver_mid(mode):
+        """The one-launch kernels of set_rhs_mid / set_rhs_abl inside the device-resident solver (ndcn_set_solver_mid; odeint without a
+        gradient, DeviceSolver): 0 off, 1 on except the widths that measured slower per solver step (H > 96), 2 on for every supported shape; < 0: the environment's (NDCN_SOLVER_MID).  Read when a solver is created;
+        the results are the switched-off solve's bit for bit.  Process-wide; returns the previous mode."""
+        return int(_lib.load().ndcn_set_solver_mid(int(mode)))
+
+    @staticmethod
+    def solver_mid_mode():
+        """the mode set_solver_mid would return, read without changing it (odeint keys its kept solvers by it)"""
+        return int(_lib.load().ndcn_solver_mid_mode())
+
+    @staticmethod
+    def solver_mid_takes(n_rows, H, no_graph=False, no_control=False, mode=2):
+        """ndcn_solver_mid_takes: the sizes' part of the solver's decision for the kinds 'mid' / 'abl' under `mode` (no device needed)"""
+        flags = _lib.F_RELU | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
+        return bool(_lib.load().ndcn_solver_mid_takes(int(n_rows), int(H), flags, int(mode)))
+
+    @staticmethod
     def set_rhs_mid_bwd(mode):
         """The one-launch reverse of the right-hand side for hidden widths 16..128 at any size (ndcn_set_rhs_mid_bwd,
         csrc/rhs_mid_bwd.hip): 0 off, 1 on for the widths that measured not slower than the composed launches, 2 on for every

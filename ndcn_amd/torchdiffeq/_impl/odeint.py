@@ -82,7 +82,12 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, step_lo
     path hold the decoder inside the solve's autograd node: the trajectory is stored once (the reverse sweep needs it) but the
     (len(t), N, H) gradient of it, which the Linear's own backward would write, is not - the sweep forms each tick's g . W where it
     adds it (ndcn_readout_bwd_f32); everywhere else the ordinary solve runs and the Linear is applied to its result - the
-    values are the same bits either way, only the memory differs.  A tuple state raises ValueError."""
+    values are the same bits either way, only the memory differs.  A tuple state raises ValueError.
+
+    Without a gradient the device-resident solver evaluates f by one launch kind per solve (DeviceSolver.rhs_kind()).  Under
+    hip.set_solver_mid / NDCN_SOLVER_MID (off by default) hidden widths 16..128 on more than 2^18 state elements, and the no_graph /
+    no_control ablations below H = 256, take the one-launch kernels of csrc/rhs_mid.hip / rhs_abl.hip - dopri5, euler and rk4; solution,
+    decoded ticks, step_log and nfe are bit for bit those of the switched-off solve."""
     with core.grid_scope(t), _dropout.solve_scope():
         if readout is None:
             return _odeint(func, y0, t, rtol, atol, method, options, step_log)[0]
@@ -297,7 +302,9 @@ def _device_resident_ok(user_func, tensor_input, y0, t, method, options, allow_d
 
 class DeviceSolver:
     """RAII wrapper of ndcn_solver_* for one (ODEFunc, method) pair - or one of the ground-truth dynamics of ndcn_amd.truth in
-    ODEFunc's place (an N x 1 state: the descriptor's `dyn` field) -; the workspace is a torch allocation."""
+    ODEFunc's place (an N x 1 state: the descriptor's `dyn` field) -; the workspace is a torch allocation.  The library picks one launch
+    kind per solver at creation (rhs_kind()); under hip.set_solver_mid hidden widths 16..128 beyond the narrow-panel sizes, and the
+    no_graph / no_control ablations, take the one-launch kernels ('mid' / 'abl') with the same bits in every result."""
 
     def __init__(self, odefunc, n_rows, method, rtol=1e-7, atol=1e-9, max_num_steps=2 ** 31 - 1, use_graph=False,
                  safety=core.SAFETY, ifactor=core.IFACTOR, dfactor=core.DFACTOR, shard=None):
@@ -425,6 +432,11 @@ class DeviceSolver:
         _lib.check(self.lib.ndcn_solver_stats(self.handle, buf))
         keys = ('steps', 'accepted', 'nfe', 't1', 'dt_next', 'last_ratio')
         return dict(zip(keys, list(buf)))
+
+    def rhs_kind(self):
+        """The launch kind this solver evaluates f with, chosen when it was created (ndcn_solver_rhs_kind): one of
+        _lib.SOLVER_RHS_KINDS - 'mid' / 'abl', the one-launch kernels for hidden widths 16..128, only under hip.set_solver_mid."""
+        return _lib.SOLVER_RHS_KINDS[_lib.check(self.lib.ndcn_solver_rhs_kind(self.handle))]
 
     def steplog(self):
         n = int(self.lib.ndcn_solver_steplog(self.handle, None, 0))
@@ -584,7 +596,8 @@ def _cached_solver(odefunc, y0, method, rtol, atol, opt, use_graph):
         return make(), None
     from ...csr import as_csr
     solve = (tuple(y0.shape), method, float(rtol), float(atol), tuple(sorted((k, v) for k, v in opt.items() if v is not None)),
-             y0.device.index, torch.cuda.current_stream(y0.device).cuda_stream)
+             y0.device.index, torch.cuda.current_stream(y0.device).cuda_stream,
+             hip.solver_mid_mode())                            # (a solver keeps the launch kind, and the captured graph, it was created under)
     truth = type(odefunc) in TRUTH_CLASSES
     if truth:
         # everything the descriptor is built from: the class, its scalars and the operator the module's attribute converts to NOW
