@@ -27,6 +27,68 @@ def _panel(t, what='panel'):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# The C calls carry pointers and a few sizes, never a tensor's own shape, strides or dtype: whatever reaches `ptr()` is read and written
+# as a dense float32 (or int32) array of the extent the launch derives from its FIRST operand.  Every tensor operand of every wrapper
+# below therefore passes `_operand` (or `_panel`, its form without expectations) before its data_ptr() is taken.
+def _name(what):
+    return what if isinstance(what, str) else '%s[%d]' % what
+
+
+def _refuse(what, expected, t):
+    given = '%s of shape %s, strides %s on %s' % (t.dtype, tuple(t.shape), tuple(t.stride()), t.device) if isinstance(t, torch.Tensor) \
+        else type(t).__name__
+    raise _lib.NdcnHipError(_lib.EINVAL, 'operand %s: expected %s, got %s' % (_name(what), expected, given))
+
+
+def _layout(t, what, dtype=torch.float32, shape=None, numel=None, out=False):
+    """The part of the operand gate that asks nothing of the device (the CPU suite drives it with host tensors): dtype, exact shape or
+    exact element count, strides.  An input that is not contiguous comes back as its contiguous copy; an OUTPUT (out=True: the caller
+    reads the result from this very tensor) must be contiguous already and is returned as it is.  Attribute reads only."""
+    if not isinstance(t, torch.Tensor):
+        _refuse(what, 'a tensor', t)
+    if t.dtype != dtype:
+        _refuse(what, 'dtype %s' % dtype, t)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        _refuse(what, 'shape %s' % (tuple(shape),), t)
+    if numel is not None and t.numel() != numel:
+        _refuse(what, '%d elements' % numel, t)
+    if t.is_contiguous():
+        return t
+    if out:
+        _refuse(what, 'a contiguous output', t)
+    return t.contiguous()
+
+
+def _on_device(t, what, device=None):
+    """The device part of the gate: a ROCm tensor, on the launch's device where one is named."""
+    if not isinstance(t, torch.Tensor):
+        _refuse(what, 'a tensor', t)
+    if not t.is_cuda:
+        raise _lib.NdcnHipError(_lib.EINVAL, 'operand %s lives on %s; ndcn_amd computes on a ROCm device only (no CPU fallback). '
+                                             'Move it with .to("cuda").' % (_name(what), t.device))
+    if device is not None and t.device != device:
+        _refuse(what, 'a tensor on %s, the device of the launch' % device, t)
+    return t
+
+
+def _operand(t, what, device=None, dtype=torch.float32, shape=None, numel=None, out=False):
+    """The one gate between a caller's tensor and a kernel: `_on_device`, then `_layout`.  Returns the tensor to take data_ptr() of."""
+    return _layout(_on_device(t, what, device), what, dtype, shape, numel, out)
+
+
+def _like(t, what, ref, out=False, shape=False):
+    """a nullable operand on ref's device with ref's element count (shape=True: ref's shape)"""
+    if t is None:
+        return None
+    if shape:
+        return _operand(t, what, ref.device, shape=ref.shape, out=out)
+    return _operand(t, what, ref.device, numel=ref.numel(), out=out)
+
+
+def _likes(ts, what, ref):
+    return [_like(t, (what, j), ref) for j, t in enumerate(ts)]
+
+
 def _terms(ks, cs):
     n = len(ks)
     arr_k = (_P * n)(*[k.data_ptr() for k in ks])
@@ -200,13 +262,15 @@ def _grad_ptrs(like, needs):
     return outs, (_P * len(needs))(*[None if o is None else o.data_ptr() for o in outs])
 
 
-def _acc_ptrs(accs, n):
-    """nullable array of the gradients the terms have ALREADY received (accumulating VJPs, include/ndcn_hip.h); the tensors
-    are kept alive by the caller for the duration of the launch (stream-ordered free of the caching allocator)."""
+def _acc_ptrs(accs, n, ref):
+    """(the gated tensors, the nullable array of their pointers) of the gradients the terms have ALREADY received (accumulating VJPs,
+    include/ndcn_hip.h).  The caller holds the first until its launch is queued: the gate's contiguous copy of a strided gradient has no
+    other owner, and its memory would go back to the caching allocator - and out again, to the outputs allocated next."""
     if accs is None or all(a is None for a in accs):
-        return None
+        return None, None
     assert len(accs) == n
-    return (_P * n)(*[None if a is None else _panel(a, 'received gradient').data_ptr() for a in accs])
+    accs = [_like(a, ('accs', j), ref) for j, a in enumerate(accs)]
+    return accs, (_P * n)(*[None if a is None else a.data_ptr() for a in accs])
 
 
 class HipOps:
@@ -219,21 +283,24 @@ class HipOps:
     def spmm(A, X, X_halo=None, alpha=1.0, relu=False, out=None):
         """alpha * (A X) [relu].  Replaces torch.sparse.mm / torch.mm(A, x) (neural_dynamics.py:29,31)."""
         A = as_csr(A)
-        X = _panel(X)
+        X = _panel(X, 'X')
         squeeze = X.dim() == 1
         X2 = X.view(-1, 1) if squeeze else X
         assert X2.dim() == 2
         H = X2.shape[1]
         n_own = X2.shape[0]
         if X_halo is not None:
-            X_halo = _panel(X_halo, 'halo panel')
-            assert X_halo.shape[1] == H
-        assert A.shape[1] == n_own + (0 if X_halo is None else X_halo.shape[0]), \
-            'operator has %d columns, panels supply %d rows' % (A.shape[1], n_own + (0 if X_halo is None else X_halo.shape[0]))
-        if A.device != X2.device:
-            raise _lib.NdcnHipError(_lib.EINVAL, 'operator on %s, panel on %s' % (A.device, X2.device))
+            X_halo = _operand(X_halo, 'X_halo', X2.device)
+            if X_halo.dim() != 2 or X_halo.shape[1] != H:
+                _refuse('X_halo', 'a panel of %d columns' % H, X_halo)
+        HipOps._rhs_operator(A, X2, X_halo)
         A.ensure_plans(H)
-        Y = out if out is not None else torch.empty((A.shape[0], H), dtype=torch.float32, device=X2.device)
+        if out is None:
+            Y = torch.empty((A.shape[0], H), dtype=torch.float32, device=X2.device)
+        elif squeeze and out.dim() == 1:
+            Y = _operand(out, 'out', X2.device, numel=A.shape[0], out=True)
+        else:
+            Y = _operand(out, 'out', X2.device, shape=(A.shape[0], H), out=True)
         with torch.cuda.device(X2.device):
             check(_lib.load().ndcn_spmm_f32(A.view_ref(), ptr(X2), ptr(X_halo), n_own, ptr(Y), H, float(alpha),
                                             _lib.F_RELU if relu else 0, stream_ptr()))
@@ -244,7 +311,10 @@ class HipOps:
         """ndcn_adjoint_rhs_f32: (K, vjp_y, vjp_W, vjp_b) = (ODEFunc(y), -A^T((a.[K>0]) W), -(a.[K>0])^T (A y), -sum_rows a.[K>0]) -
         the right-hand side of odeint_adjoint's augmented system (adjoint.py:34-59) without a torch graph; vjp_W / vjp_b are
         None under no_control."""
-        y, a = _panel(y), _panel(a)
+        y = _panel(y, 'y')
+        if y.dim() != 2:
+            _refuse('y', 'a 2-D panel', y)
+        a = _like(a, 'a', y, shape=True)
         H = y.shape[1]
         flags = _lib.F_RELU | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
         lib = _lib.load()
@@ -252,6 +322,8 @@ class HipOps:
             view = view_t = ctypes.byref(_lib.empty_csr(y.shape[0]))
         else:
             A = as_csr(A)
+            if tuple(A.shape) != (y.shape[0], y.shape[0]) or A.device != y.device:
+                raise _lib.NdcnHipError(_lib.EINVAL, 'operator %s on %s, panel of %d rows on %s' % (tuple(A.shape), A.device, y.shape[0], y.device))
             A.ensure_plans(H)
             At = A.transpose()
             At.ensure_plans(H)
@@ -259,8 +331,8 @@ class HipOps:
         K, vjp_y = torch.empty_like(y), torch.empty_like(y)
         vW = vb = None
         if not no_control:
-            W = _panel(W, 'weight')
-            b = _panel(b, 'bias') if b is not None else None
+            W = _operand(W, 'W', y.device, shape=(H, H))
+            b = _operand(b, 'b', y.device, numel=H) if b is not None else None
             vW = torch.empty((H, H), dtype=torch.float32, device=y.device)
             vb = torch.empty((H,), dtype=torch.float32, device=y.device)
         work = torch.empty(int(lib.ndcn_adjoint_rhs_work_bytes(y.shape[0], H, flags)) + 256, dtype=torch.uint8, device=y.device)
@@ -275,11 +347,16 @@ class HipOps:
     def gcn(A, X, W, b=None, relu=False):
         """A (X W^T + b) [relu]: GraphConvolution.forward of the reference (models.py:14-18) in one library call."""
         A = as_csr(A)
-        X, W = _panel(X), _panel(W, 'weight')
-        if b is not None:
-            b = _panel(b, 'bias')
+        X = _panel(X, 'X')
+        W = _operand(W, 'W', X.device)
+        if W.dim() != 2:
+            _refuse('W', 'a 2-D weight', W)
         Ho, Hi = W.shape
+        if b is not None:
+            b = _operand(b, 'b', X.device, numel=Ho)
         assert X.dim() == 2 and X.shape == (A.shape[1], Hi)
+        if A.device != X.device:
+            raise _lib.NdcnHipError(_lib.EINVAL, 'operator on %s, panel on %s' % (A.device, X.device))
         A.ensure_plans(Ho)
         lib = _lib.load()
         Y = torch.empty((A.shape[0], Ho), dtype=torch.float32, device=X.device)
@@ -292,13 +369,18 @@ class HipOps:
     @staticmethod
     def linear(S, W, b=None, relu=False):
         """S W^T + b [relu] over the last dimension (nn.Linear semantics; neural_dynamics.py:33,143-148)."""
-        S = _panel(S)
-        W = _panel(W, 'weight')
-        if b is not None:
-            b = _panel(b, 'bias')
+        S = _panel(S, 'S')
+        if S.dim() < 1:
+            _refuse('S', 'a panel of at least one dimension', S)
+        W = _operand(W, 'W', S.device)
+        if W.dim() != 2:
+            _refuse('W', 'a 2-D weight (Ho, Hi)', W)
+        if S.shape[-1] != W.shape[1]:
+            _refuse('S', 'a last dimension of %d, the columns of W' % W.shape[1], S)
         lead = S.shape[:-1]
         Hi, Ho = S.shape[-1], W.shape[0]
-        assert W.shape[1] == Hi
+        if b is not None:
+            b = _operand(b, 'b', S.device, numel=Ho)
         S2 = S.reshape(-1, Hi)
         Y = torch.empty((S2.shape[0], Ho), dtype=torch.float32, device=S.device)
         with torch.cuda.device(S.device):
@@ -310,14 +392,20 @@ class HipOps:
     def linear_bwd(g, W, S=None, Y=None, need_gS=True, need_gW=True, need_gb=True):
         """Backward of act(S W^T + b): returns (gS, gW, gb) (None where not requested).  Y: the ReLU output (mask
         gZ = g where Y > 0) or None.  One GEMM launch for gS, one split-row launch + fixed-order sum for gW / gb."""
-        g = _panel(g)
-        W = _panel(W, 'weight')
+        g = _panel(g, 'g')
+        if g.dim() < 1:
+            _refuse('g', 'a panel of at least one dimension', g)
+        W = _operand(W, 'W', g.device)
+        if W.dim() != 2:
+            _refuse('W', 'a 2-D weight (Ho, Hi)', W)
+        if g.shape[-1] != W.shape[0]:
+            _refuse('g', 'a last dimension of %d, the rows of W' % W.shape[0], g)
         Ho, Hi = W.shape
         lead = g.shape[:-1]
         g2 = g.reshape(-1, Ho)
         n = g2.shape[0]
-        S2 = _panel(S).reshape(-1, Hi) if S is not None else None
-        Y2 = _panel(Y).reshape(-1, Ho) if Y is not None else None
+        S2 = _operand(S, 'S', g.device, shape=tuple(lead) + (Hi,)).reshape(-1, Hi) if S is not None else None
+        Y2 = _operand(Y, 'Y', g.device, shape=g.shape).reshape(-1, Ho) if Y is not None else None
         need_gW = need_gW and S2 is not None
         lib = _lib.load()
         gS = torch.empty((n, Hi), dtype=torch.float32, device=g.device) if need_gS else None
@@ -340,7 +428,8 @@ class HipOps:
     @staticmethod
     def relu_bwd(g, y):
         """0 where y <= 0 else g (VJP of relu from its output; threshold_backward: a NaN y passes g)."""
-        g, y = _panel(g), _panel(y)
+        g = _panel(g, 'g')
+        y = _like(y, 'y', g)
         out = torch.empty_like(g)
         with torch.cuda.device(g.device):
             check(_lib.load().ndcn_relu_bwd_f32(ptr(out), ptr(g), ptr(y), g.numel(), stream_ptr()))
@@ -349,10 +438,8 @@ class HipOps:
     @staticmethod
     def copy(x, out=None):
         """out = x as the library's streaming pass (ndcn_copy_f32)."""
-        x = _panel(x)
-        if out is None:
-            out = torch.empty_like(x)
-        assert out.is_contiguous() and out.numel() == x.numel()
+        x = _panel(x, 'x')
+        out = torch.empty_like(x) if out is None else _like(out, 'out', x, out=True)
         with torch.cuda.device(x.device):
             check(_lib.load().ndcn_copy_f32(ptr(out), ptr(x), x.numel(), stream_ptr()))
         return out
@@ -360,11 +447,34 @@ class HipOps:
     @staticmethod
     def scale(x, w):
         """w * x as one streaming kernel."""
-        x = _panel(x)
+        x = _panel(x, 'x')
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
             check(_lib.load().ndcn_scale_f32(ptr(out), ptr(x), float(w), x.numel(), stream_ptr()))
         return out
+
+    @staticmethod
+    def _rhs_input(X, X_halo):
+        """the gate of a right-hand side's input panels: (X, X_halo, H)"""
+        X = _panel(X, 'X')
+        if X.dim() != 2:
+            _refuse('X', 'a 2-D panel', X)
+        if X_halo is not None:
+            X_halo = _operand(X_halo, 'X_halo', X.device)
+            if X_halo.dim() != 2 or X_halo.shape[1] != X.shape[1]:
+                _refuse('X_halo', 'a panel of %d columns' % X.shape[1], X_halo)
+        return X, X_halo, X.shape[1]
+
+    @staticmethod
+    def _rhs_operator(A, X, X_halo):
+        """the operator of a right-hand side against the rows its panels supply (what spmm asserts)"""
+        A = as_csr(A)
+        if A.device != X.device:
+            raise _lib.NdcnHipError(_lib.EINVAL, 'operator on %s, panel on %s' % (A.device, X.device))
+        rows = X.shape[0] + (0 if X_halo is None else X_halo.shape[0])
+        if A.shape[1] != rows:
+            raise _lib.NdcnHipError(_lib.EINVAL, 'operator has %d columns, panels supply %d rows' % (A.shape[1], rows))
+        return A
 
     @staticmethod
     def rhs(A, X, W, b, no_graph=False, no_control=False, X_halo=None, out=None, relu=True, dropout=None):
@@ -373,8 +483,7 @@ class HipOps:
         (A^T gZ) W with the operator / weight pair (A^T, W^T) and no bias (_impl/adjoint_fused.py).
         dropout: None (p = 0, eval mode) or (p, seed, evaluation) with 0 < p < 1 - the result times the mask of csrc/dropout.h,
         a function of those three numbers and the element index alone (ndcn_rhs_drop_f32)."""
-        X = _panel(X)
-        H = X.shape[1]
+        X, X_halo, H = HipOps._rhs_input(X, X_halo)
         flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
         lib = _lib.load()
         if no_graph:
@@ -382,19 +491,15 @@ class HipOps:
             view_ref = ctypes.byref(view)
             n_rows = X.shape[0]
         else:
-            A = as_csr(A)
-            if A.device != X.device:
-                raise _lib.NdcnHipError(_lib.EINVAL, 'operator on %s, panel on %s' % (A.device, X.device))
+            A = HipOps._rhs_operator(A, X, X_halo)
             A.ensure_plans(H)
             view_ref = A.view_ref()
             n_rows = A.shape[0]
         if not no_control:
-            W = _panel(W, 'weight')
-            b = _panel(b, 'bias') if b is not None else None
-            assert W.shape == (H, H)
-        if X_halo is not None:
-            X_halo = _panel(X_halo, 'halo panel')
-        Y = out if out is not None else torch.empty((n_rows, H), dtype=torch.float32, device=X.device)
+            W = _operand(W, 'W', X.device, shape=(H, H))
+            b = _operand(b, 'b', X.device, numel=H) if b is not None else None
+        Y = _operand(out, 'out', X.device, shape=(n_rows, H), out=True) if out is not None \
+            else torch.empty((n_rows, H), dtype=torch.float32, device=X.device)
         work = None
         wbytes = int(lib.ndcn_rhs_work_bytes(n_rows, H, flags))
         if wbytes:
@@ -417,8 +522,7 @@ class HipOps:
     def dropout_apply(K, dropout):
         """K *= mask in place (ndcn_dropout_apply_f32): dropout = (p, seed, evaluation), element index = position in K's memory.
         K: a contiguous float32 device tensor or view (a misaligned one takes the scalar kernel).  Returns K."""
-        require_device(K, 'panel')
-        assert K.is_contiguous()
+        K = _operand(K, 'K', out=True)
         with torch.cuda.device(K.device):
             check(_lib.load().ndcn_dropout_apply_f32(ptr(K), K.numel(), _lib.dropout_desc(dropout), stream_ptr()))
         return K
@@ -428,10 +532,12 @@ class HipOps:
         """K *= mask in place and, in the same pass, out = y0 + sum_j cs[j] kprev[j] + cs[-1] K (ndcn_dropout_combine_f32): the bits of
         dropout_apply(K, dropout) followed by combine(y0, kprev + [K], cs).  y0 None: the sum alone.  Contiguous float32 device
         tensors or views (misaligned ones take the scalar lanes); out must not overlap K.  Returns (K, out)."""
-        require_device(K, 'panel')
-        assert K.is_contiguous() and len(cs) == len(kprev) + 1 and all(k.is_contiguous() and k.numel() == K.numel() for k in kprev)
-        if out is None:
-            out = torch.empty_like(K)
+        K = _operand(K, 'K', out=True)
+        assert len(cs) == len(kprev) + 1
+        # (the terms may be views INTO a record the caller keeps: never copied, like an output)
+        kprev = [_like(k, ('kprev', j), K, out=True) for j, k in enumerate(kprev)]
+        y0 = _like(y0, 'y0', K)
+        out = torch.empty_like(K) if out is None else _like(out, 'out', K, out=True)
         n = len(kprev)
         arr_k = (_P * max(n, 1))(*[k.data_ptr() for k in kprev])
         arr_c = (_F * (n + 1))(*[float(c) for c in cs])
@@ -459,33 +565,34 @@ class HipOps:
         rows / S = A X is written into s_out too - the two halves of odeint_adjoint's right-hand side (_impl/adjoint_fused.py).
         dropout: None or (p, seed, evaluation) as in rhs(): K, as returned and as consumed by the stage algebra, is the masked one
         (ndcn_rhs_rk_drop_f32; not with x_mask / s_out / a halo panel)."""
-        X = _panel(X)
-        H = X.shape[1]
+        X, X_halo, H = HipOps._rhs_input(X, X_halo)
+        dev = X.device
         flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
         lib = _lib.load()
         if no_graph:
             view_ref = ctypes.byref(_lib.empty_csr(X.shape[0]))
             n_rows = X.shape[0]
         else:
-            A = as_csr(A)
+            A = HipOps._rhs_operator(A, X, X_halo)
             A.ensure_plans(H)
             view_ref = A.view_ref()
             n_rows = A.shape[0]
+        panel = (n_rows, H)
         if not no_control:
-            W = _panel(W, 'weight')
-            b = _panel(b, 'bias') if b is not None else None
-        y0 = _panel(y0)
-        kprev = [_panel(k) for k in kprev]
+            W = _operand(W, 'W', dev, shape=(H, H))
+            b = _operand(b, 'b', dev, numel=H) if b is not None else None
+        else:
+            W = b = None                                        # (not read: no pointer of theirs is handed on)
+        y0 = _operand(y0, 'y0', dev, shape=panel)
+        kprev = [_operand(k, ('kprev', j), dev, shape=panel) for j, k in enumerate(kprev)]
         assert len(cs) == (1 if mode == 'rk4' else len(kprev) + 1)
-        if X_halo is not None:
-            X_halo = _panel(X_halo, 'halo panel')
         if y1 is not None:
-            y1 = _panel(y1, 'y1')
-            assert mode == 'error' and tuple(y1.shape) == (n_rows, H)
+            assert mode == 'error'
+            y1 = _operand(y1, 'y1', dev, shape=panel)
         if accum:
             flags |= _lib.F_ACCUM
-        K = out_K if out_K is not None else torch.empty((n_rows, H), dtype=torch.float32, device=X.device)
-        assert K.is_contiguous() and tuple(K.shape) == (n_rows, H)
+        K = _operand(out_K, 'out_K', dev, shape=panel, out=True) if out_K is not None \
+            else torch.empty(panel, dtype=torch.float32, device=dev)
         wbytes = int(lib.ndcn_rhs_work_bytes(n_rows, H, flags))
         work = None
         if wbytes:
@@ -500,13 +607,18 @@ class HipOps:
         if aux_cs is not None:
             assert mode == 'combine' and len(aux_cs) == len(kprev) + 1
             arr_c2 = (_F * len(aux_cs))(*[float(c) for c in aux_cs])
-            y_aux = out_aux if out_aux is not None else torch.empty_like(K)
+            y_aux = _operand(out_aux, 'out_aux', dev, shape=panel, out=True) if out_aux is not None else torch.empty_like(K)
         rk = {'combine': _lib.RK_COMBINE, 'error': _lib.RK_ERROR, 'rk4': _lib.RK_RK4}[mode]
-        y_next = (out_y if out_y is not None else torch.empty_like(K)) if mode in ('combine', 'rk4') else None
+        y_next = None
+        if mode in ('combine', 'rk4'):
+            y_next = _operand(out_y, 'out_y', dev, shape=panel, out=True) if out_y is not None else torch.empty_like(K)
         red = _Reducer.get(X.device)
+        if record is not None and (record.out.device != dev or record.out.dtype != torch.float64 or record.out.numel() != 2):
+            _refuse('record', 'an ErrorRecord of the launch\'s device', record.out)
         if x_mask is not None or s_out is not None:
             assert X_halo is None and aux_cs is None and not accum and dropout is None
-            x_mask = _panel(x_mask, 'mask panel') if x_mask is not None else None
+            x_mask = _like(x_mask, 'x_mask', X, shape=True)
+            s_out = _operand(s_out, 's_out', dev, shape=panel, out=True) if s_out is not None else None
             with _REDUCE_LOCK, torch.cuda.device(X.device):
                 check(lib.ndcn_rhs_rk_adj_f32(view_ref, ptr(X), ptr(x_mask), ptr(s_out), ptr(W), ptr(b), ptr(K), ptr(work), H, flags, rk,
                                               ptr(y0), arr_k, arr_c, len(kprev), ptr(y_next), ptr(y1), float(rtol), float(atol),
@@ -623,11 +735,19 @@ class HipOps:
     def tgcn_proj(S, r, w, b, W_ih, b_ih):
         """GI (T, M) = b_ih + sum_{i,j} W_ih[:, i Hg + j] relu(S[i, :] w_j + r_i b_j) for all T ticks (ndcn_tgcn_proj_f32).  S (N, T) = A X,
         r (N,) = A 1, w / b (Hg,): the graph convolution's Linear(1, Hg), W_ih (M, N Hg), b_ih (M,)."""
-        S, r, W_ih, b_ih = _panel(S, 'S'), _panel(r, 'row sums'), _panel(W_ih, 'input weight'), _panel(b_ih, 'input bias')
-        w, b = _panel(w, 'weight').reshape(-1), _panel(b, 'bias').reshape(-1)
+        S = _panel(S, 'S')
+        if S.dim() != 2:
+            _refuse('S', 'a 2-D panel (N, T)', S)
         N, T = S.shape
-        Hg, M = w.numel(), W_ih.shape[0]
-        assert r.numel() == N and b.numel() == Hg and tuple(W_ih.shape) == (M, N * Hg) and b_ih.numel() == M
+        dev = S.device
+        w = _operand(w, 'w', dev).reshape(-1)
+        Hg = w.numel()
+        r, b = _operand(r, 'r', dev, numel=N), _operand(b, 'b', dev, numel=Hg).reshape(-1)
+        W_ih = _operand(W_ih, 'W_ih', dev)
+        if W_ih.dim() != 2 or W_ih.shape[1] != N * Hg:
+            _refuse('W_ih', 'a weight of shape (M, %d)' % (N * Hg), W_ih)
+        M = W_ih.shape[0]
+        b_ih = _operand(b_ih, 'b_ih', dev, numel=M)
         lib = _lib.load()
         GI = torch.empty((T, M), dtype=torch.float32, device=S.device)
         ws = torch.empty(max(int(lib.ndcn_tgcn_proj_ws_bytes(N, T, M)), 4), dtype=torch.uint8, device=S.device)
@@ -638,11 +758,19 @@ class HipOps:
     @staticmethod
     def tgcn_proj_bwd(S, r, w, b, W_ih, GGI):
         """(g_Wih, g_w, g_b, g_bih) of tgcn_proj for GGI = dL/dGI (T, M) (ndcn_tgcn_proj_bwd_f32): g_Wih is written once, W_ih read once."""
-        S, r, W_ih, GGI = _panel(S, 'S'), _panel(r, 'row sums'), _panel(W_ih, 'input weight'), _panel(GGI, 'gradient')
-        w, b = _panel(w, 'weight').reshape(-1), _panel(b, 'bias').reshape(-1)
+        S = _panel(S, 'S')
+        if S.dim() != 2:
+            _refuse('S', 'a 2-D panel (N, T)', S)
         N, T = S.shape
-        Hg, M = w.numel(), W_ih.shape[0]
-        assert r.numel() == N and b.numel() == Hg and tuple(W_ih.shape) == (M, N * Hg) and tuple(GGI.shape) == (T, M)
+        dev = S.device
+        w = _operand(w, 'w', dev).reshape(-1)
+        Hg = w.numel()
+        r, b = _operand(r, 'r', dev, numel=N), _operand(b, 'b', dev, numel=Hg).reshape(-1)
+        W_ih = _operand(W_ih, 'W_ih', dev)
+        if W_ih.dim() != 2 or W_ih.shape[1] != N * Hg:
+            _refuse('W_ih', 'a weight of shape (M, %d)' % (N * Hg), W_ih)
+        M = W_ih.shape[0]
+        GGI = _operand(GGI, 'GGI', dev, shape=(T, M))
         lib = _lib.load()
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=S.device)
         g_Wih, g_w, g_b, g_bih = new(M, N * Hg), new(Hg), new(Hg), new(M)
@@ -657,13 +785,15 @@ class HipOps:
         """The recurrence of an LSTMCell / GRUCell / RNNCell ('lstm' / 'gru' / 'rnn') over the T rows of GI in one launch
         (ndcn_tgcn_cell_f32): (H (T, Hr), gates (T, 4 Hr), c_rec (T, Hr) or None, hT, cT or None); h0 / c0 None: zeros."""
         kind = _lib.TGCN_TYPES[rnn_type]
-        GI, W_hh, b_hh = _panel(GI, 'GI'), _panel(W_hh, 'hidden weight'), _panel(b_hh, 'hidden bias')
+        GI = _panel(GI, 'GI')
+        if GI.dim() != 2 or GI.shape[1] % _lib.TGCN_GATES[kind]:
+            _refuse('GI', 'a 2-D panel (T, %d Hr)' % _lib.TGCN_GATES[kind], GI)
         T, M = GI.shape
-        Hr = W_hh.shape[1]
-        assert M == _lib.TGCN_GATES[kind] * Hr and tuple(W_hh.shape) == (M, Hr) and b_hh.numel() == M
-        h0 = _panel(h0, 'h0').reshape(-1) if h0 is not None else None
-        c0 = _panel(c0, 'c0').reshape(-1) if c0 is not None else None
-        assert (h0 is None or h0.numel() == Hr) and (c0 is None or c0.numel() == Hr)
+        dev = GI.device
+        Hr = M // _lib.TGCN_GATES[kind]
+        W_hh, b_hh = _operand(W_hh, 'W_hh', dev, shape=(M, Hr)), _operand(b_hh, 'b_hh', dev, numel=M)
+        h0 = _operand(h0, 'h0', dev, numel=Hr).reshape(-1) if h0 is not None else None
+        c0 = _operand(c0, 'c0', dev, numel=Hr).reshape(-1) if c0 is not None else None
         lstm = kind == _lib.TGCN_LSTM
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=GI.device)
         H, gates, hT = new(T, Hr), new(T, 4 * Hr), new(Hr)
@@ -677,15 +807,18 @@ class HipOps:
     def tgcn_cell_bwd(rnn_type, gH, gates, c_rec, H, W_hh, h0=None, c0=None):
         """The reverse of tgcn_cell for gH = dL/dH (T, Hr) (ndcn_tgcn_cell_bwd_f32): (GGI (T, M), g_Whh, g_bhh, g_h0, g_c0 or None)."""
         kind = _lib.TGCN_TYPES[rnn_type]
-        gH, gates, H, W_hh = _panel(gH, 'gradient'), _panel(gates, 'gate record'), _panel(H, 'hidden states'), _panel(W_hh, 'hidden weight')
+        H = _panel(H, 'H')
+        if H.dim() != 2:
+            _refuse('H', 'a 2-D panel (T, Hr)', H)
         T, Hr = H.shape
+        dev = H.device
         M = _lib.TGCN_GATES[kind] * Hr
         lstm = kind == _lib.TGCN_LSTM
-        assert tuple(gH.shape) == (T, Hr) and tuple(gates.shape) == (T, 4 * Hr) and tuple(W_hh.shape) == (M, Hr)
-        assert not lstm or tuple(c_rec.shape) == (T, Hr)
-        c_rec = _panel(c_rec, 'cell record') if lstm else None
-        h0 = _panel(h0, 'h0').reshape(-1) if h0 is not None else None
-        c0 = _panel(c0, 'c0').reshape(-1) if c0 is not None else None
+        gH, gates = _operand(gH, 'gH', dev, shape=(T, Hr)), _operand(gates, 'gates', dev, shape=(T, 4 * Hr))
+        W_hh = _operand(W_hh, 'W_hh', dev, shape=(M, Hr))
+        c_rec = _operand(c_rec, 'c_rec', dev, shape=(T, Hr)) if lstm else None
+        h0 = _operand(h0, 'h0', dev, numel=Hr).reshape(-1) if h0 is not None else None
+        c0 = _operand(c0, 'c0', dev, numel=Hr).reshape(-1) if c0 is not None else None
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=gH.device)
         GGI, g_Whh, g_bhh, g_h0 = new(T, M), new(M, Hr), new(M), new(Hr)
         g_c0 = new(Hr) if lstm else None
@@ -702,31 +835,33 @@ class HipOps:
         acc_scale * (this evaluation's) into them and returns them; otherwise they are new tensors.  return_gs: a fourth result, the
         panel gS = gZ W as it stands in the call's scratch (need_x only).  Under set_rhs_abl_bwd a no_graph / no_control call that
         the one-launch reverse takes leaves no gS panel in the scratch: return_gs promises nothing there."""
-        X, g = _panel(X), _panel(g)
-        K = _panel(K) if K is not None else None
-        S = _panel(S) if S is not None else None
-        H = X.shape[1]
+        X, _, H = HipOps._rhs_input(X, None)
         n = X.shape[0]
+        dev = X.device
+        g, K, S = _like(g, 'g', X, shape=True), _like(K, 'K', X, shape=True), _like(S, 'S', X, shape=True)
         lib = _lib.load()
         flags = (_lib.F_RELU if relu else 0) | (_lib.F_NO_GRAPH if no_graph else 0) | (_lib.F_NO_CONTROL if no_control else 0)
         if no_graph:
             view = view_t = ctypes.byref(_lib.empty_csr(n))
         else:
-            A = as_csr(A)
+            A = HipOps._rhs_operator(A, X, None)
+            if A.shape[0] != n:
+                raise _lib.NdcnHipError(_lib.EINVAL, 'the reverse takes a square operator, got %s' % (tuple(A.shape),))
             A.ensure_plans(H)
             At = A.transpose()
             At.ensure_plans(H)
             view, view_t = A.view_ref(), At.view_ref()
         accumulate = gW is not None
         if no_control:
-            gW = gb = None
+            gW = gb = W = None                                  # (W is not read: no pointer of it is handed on)
         else:
-            W = _panel(W, 'weight')
+            W = _operand(W, 'W', dev, shape=(H, H))
             if gW is None:
                 gW = torch.empty((H, H), dtype=torch.float32, device=X.device)
                 gb = torch.empty((H,), dtype=torch.float32, device=X.device) if need_b else None
-            elif not need_b:
-                gb = None
+            else:
+                gW = _operand(gW, 'gW', dev, shape=(H, H), out=True)
+                gb = _operand(gb, 'gb', dev, numel=H, out=True) if need_b and gb is not None else None
         gX = torch.empty_like(X) if need_x else None
         work = torch.empty(int(lib.ndcn_rhs_vjp_work_bytes(n, H, flags)), dtype=torch.uint8, device=X.device)
         with torch.cuda.device(X.device):
@@ -748,11 +883,13 @@ class HipOps:
         y_next = y0 + (cs[0] * k_prev + cs[1] * K) in one pass, the input formed on the rows the kernel stages - the bits of
         combine(X, [xadd], [xadd_c]) followed by rhs_rk(..., 'combine', y0, [k_prev], cs).  Returns (K, y_next), or None where
         the operator has no such kernel (ndcn_rhs_xadd_supported)."""
-        X, xadd, y0, k_prev = _panel(X), _panel(xadd), _panel(y0), _panel(k_prev)
-        W = _panel(W, 'weight')
-        b = _panel(b, 'bias') if b is not None else None
-        H = X.shape[1]
-        A = as_csr(A)
+        X, _, H = HipOps._rhs_input(X, None)
+        xadd, y0, k_prev = _like(xadd, 'xadd', X, shape=True), _like(y0, 'y0', X, shape=True), _like(k_prev, 'k_prev', X, shape=True)
+        W = _operand(W, 'W', X.device, shape=(H, H))
+        b = _operand(b, 'b', X.device, numel=H) if b is not None else None
+        A = HipOps._rhs_operator(A, X, None)
+        if A.shape[0] != X.shape[0]:
+            raise _lib.NdcnHipError(_lib.EINVAL, 'the step-opening launch takes a square operator, got %s' % (tuple(A.shape),))
         A.ensure_plans(H)
         lib = _lib.load()
         flags = _lib.F_RELU
@@ -769,8 +906,10 @@ class HipOps:
 
     @staticmethod
     def gather_rows(X, idx):
-        X = _panel(X)
-        assert idx.dtype == torch.int32 and idx.is_cuda
+        X = _panel(X, 'X')
+        if X.dim() != 2:
+            _refuse('X', 'a 2-D panel', X)
+        idx = _operand(idx, 'idx', X.device, dtype=torch.int32)
         out = torch.empty((idx.numel(), X.shape[1]), dtype=torch.float32, device=X.device)
         with torch.cuda.device(X.device):
             check(_lib.load().ndcn_gather_rows_f32(ptr(X), ptr(idx), idx.numel(), X.shape[1], ptr(out), stream_ptr()))
@@ -780,8 +919,8 @@ class HipOps:
     @staticmethod
     def combine(y0, ks, cs):
         """y0 + sum_j cs[j] * ks[j]  (cs already dt*beta in fp32; misc.py:22-25 order and rounding)."""
-        y0 = _panel(y0)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        ks = _likes(ks, 'ks', y0)
         out = torch.empty_like(y0)
         arr_k, arr_c, n = _terms(ks, cs)
         with torch.cuda.device(y0.device):
@@ -791,11 +930,13 @@ class HipOps:
     @staticmethod
     def lincomb(ks, cs, y0=None):
         """[y0 +] sum_j cs[j] * ks[j] in one pass (ndcn_rk_combine_f32 with or without the unit-coefficient term)."""
-        ks = [_panel(k) for k in ks]
+        k0 = _panel(ks[0], ('ks', 0))
+        ks = [k0] + [_like(k, ('ks', j + 1), k0) for j, k in enumerate(ks[1:])]
+        y0 = _like(y0, 'y0', k0)
         out = torch.empty_like(ks[0])
         arr_k, arr_c, n = _terms(ks, cs)
         with torch.cuda.device(out.device):
-            check(_lib.load().ndcn_rk_combine_f32(ptr(out), ptr(_panel(y0)) if y0 is not None else None, arr_k, arr_c, n, out.numel(),
+            check(_lib.load().ndcn_rk_combine_f32(ptr(out), ptr(y0), arr_k, arr_c, n, out.numel(),
                                                   stream_ptr()))
         return out
 
@@ -807,18 +948,24 @@ class HipOps:
         as the fp32 fma chain over c, returns base + (sum of the addends, left to right from +0, + gi) - lincomb(addends + [gi], ones,
         y0=base) without gi ever stored - or gi itself without base and addends.  acc (C * H + C float64, zeroed by the caller): += the
         decoder's gradients gd^T y and the column sums of gd for this tick, in a fixed order."""
-        gd, Wd = _panel(gd, 'tick gradient'), _panel(Wd, 'decoder weight')
+        gd = _panel(gd, 'gd')
+        if gd.dim() != 2:
+            _refuse('gd', 'a 2-D panel (N, C)', gd)
         N, C = gd.shape
+        dev = gd.device
+        Wd = _operand(Wd, 'Wd', dev)
+        if Wd.dim() != 2 or Wd.shape[0] != C:
+            _refuse('Wd', 'a decoder weight of shape (%d, H)' % C, Wd)
         H = Wd.shape[1]
-        assert Wd.shape[0] == C and len(addends) <= 5
-        adds = [_panel(k) for k in addends]
-        base = _panel(base) if base is not None else None
+        assert len(addends) <= 5
+        adds = [_operand(k, ('addends', j), dev, shape=(N, H)) for j, k in enumerate(addends)]
+        base = _operand(base, 'base', dev, shape=(N, H)) if base is not None else None
         out = torch.empty((N, H), dtype=torch.float32, device=gd.device)
         lib = _lib.load()
         ws = None
         if acc is not None:
-            y = _panel(y, 'tick state')
-            assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == C * H + C and tuple(y.shape) == (N, H)
+            y = _operand(y, 'y', dev, shape=(N, H))
+            acc = _operand(acc, 'acc', dev, dtype=torch.float64, numel=C * H + C, out=True)
             ws = torch.empty(max(int(lib.ndcn_readout_bwd_ws_bytes(N, H, C)), 8), dtype=torch.uint8, device=gd.device)
         arr = (_P * max(len(adds), 1))(*[k.data_ptr() for k in adds])
         with torch.cuda.device(gd.device):
@@ -829,8 +976,8 @@ class HipOps:
     @staticmethod
     def error(y0, y1, ks, cs, rtol, atol):
         """(sum of squared error ratios, non-finite count of y1) as host floats; one 16-byte read-back."""
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks = _like(y1, 'y1', y0), _likes(ks, 'ks', y0)
         red = _Reducer.get(y0.device)
         arr_k, arr_c, n = _terms(ks, cs)
         with _REDUCE_LOCK, torch.cuda.device(y0.device):
@@ -841,8 +988,8 @@ class HipOps:
     @staticmethod
     def scaled_sumsq(a, b, y, rtol, atol):
         """sum(((a - b) / (atol + |y| rtol))^2) and the non-finite count of a  (misc.py:121-138)."""
-        a, y = _panel(a), _panel(y)
-        b = _panel(b) if b is not None else None
+        a = _panel(a, 'a')
+        y, b = _like(y, 'y', a), _like(b, 'b', a)
         red = _Reducer.get(a.device)
         with _REDUCE_LOCK, torch.cuda.device(a.device):
             check(_lib.load().ndcn_scaled_sumsq_f32(ptr(a), ptr(b), ptr(y), float(rtol), float(atol), a.numel(),
@@ -907,8 +1054,8 @@ class HipOps:
                    for p in panels)
 
     @staticmethod
-    def _adams_phi(phis, betas, order):
-        phis = [_panel(p) for p in phis[:order]]
+    def _adams_phi(phis, betas, order, ref):
+        phis = _likes(phis[:order], 'phis', ref)
         assert len(phis) == order and len(betas) >= order
         arr_p = (_P * order)(*[p.data_ptr() for p in phis])
         arr_b = (_F * order)(*[0.0 if (j == 0 or betas[j] is None) else float(betas[j]) for j in range(order)])
@@ -918,8 +1065,8 @@ class HipOps:
     def adams_predict(y, phis, betas, cs, order):
         """p_next = y + sum_j cs[j] e_j over the first max(1, order - 1) explicit phi e_0 = phis[0], e_j = betas[j] * phis[j] - the bits of
         scale x (order - 2) + combine, the explicit phi never stored (ndcn_adams_predict_f32)."""
-        y = _panel(y)
-        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        y = _panel(y, 'y')
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order, y)
         m = max(1, order - 1)
         assert len(cs) == m
         arr_c = (_F * m)(*[float(c) for c in cs])
@@ -934,8 +1081,9 @@ class HipOps:
         held in registers, and for every coefs[q] that is not None the sum of squared error ratios of coefs[q] * {ip_order, ip_{order-1},
         ip_{order-2}, ip_order}[q] against (y0, y_next) as a host float - what `error` returns above the ATen-order bound -, None for the
         others; one 32-byte read-back (ndcn_adams_correct_f32)."""
-        nf, p_next, y0 = _panel(nf), _panel(p_next), _panel(y0)
-        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        y0 = _panel(y0, 'y0')
+        nf, p_next = _like(nf, 'nf', y0), _like(p_next, 'p_next', y0)
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order, y0)
         assert len(coefs) == 4
         mask = sum(1 << q for q in range(4) if coefs[q] is not None)
         arr_c = (_F * 4)(*[0.0 if c is None else float(c) for c in coefs])
@@ -958,9 +1106,9 @@ class HipOps:
     def adams_update(nf2, phis, betas, order, n_out):
         """The implicit phi of an accepted step: [nf2, nf2 - e_0, (nf2 - e_0) - e_1, ...], n_out panels, the first nf2 itself; one pass,
         out of place (ndcn_adams_update_f32)."""
-        nf2 = _panel(nf2)
+        nf2 = _panel(nf2, 'nf2')
         assert 1 <= n_out <= order + 1
-        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order)
+        phis, arr_p, arr_b = HipOps._adams_phi(phis, betas, order, nf2)
         outs = [nf2] + [torch.empty_like(nf2) for _ in range(n_out - 1)]
         arr_o = (_P * n_out)(*[o.data_ptr() for o in outs])
         with torch.cuda.device(nf2.device):
@@ -973,16 +1121,18 @@ class HipOps:
         """VJP of combine: ([c_j g or None], [<g, k_j>] as host floats or None).  accs / acc_y0: gradients the terms / y0 have
         already received - the outputs become acc_j + c_j g (and a third result acc_y0 + g is returned when acc_y0 is given).
         lazy: the inner products as deferred 0-d float32 host tensors (_BwdDots.lazy) instead of floats."""
-        g = _panel(g)
-        ks = [_panel(k) for k in ks]
+        g = _panel(g, 'g')
+        ks = _likes(ks, 'ks', g)
+        assert len(need_k) == len(ks)
         arr_k, arr_c, n = _terms(ks, cs)
         gk, arr_g = _grad_ptrs(g, need_k)
-        arr_a = _acc_ptrs(accs, n)
+        accs, arr_a = _acc_ptrs(accs, n, g)
         gy0 = torch.empty_like(g) if acc_y0 is not None else None
+        acc_y0 = _like(acc_y0, 'acc_y0', g)
         d = _BwdDots.get(g.device)
         with _REDUCE_LOCK, torch.cuda.device(g.device):
             check(_lib.load().ndcn_rk_combine_bwd_f32(ptr(g), arr_k, arr_c, n, arr_g, arr_a, ptr(gy0),
-                                                      ptr(_panel(acc_y0)) if acc_y0 is not None else None, ptr(d.out), ptr(d.ws),
+                                                      ptr(acc_y0), ptr(d.out), ptr(d.ws),
                                                       g.numel(), stream_ptr()))
             dots = (d.lazy(n) if lazy else d.fetch()[:n]) if need_dots else None
         return (gk, dots) if acc_y0 is None else (gk, dots, gy0)
@@ -991,10 +1141,11 @@ class HipOps:
     def pull(ps, cs, base=None, mask=None, ua=None, ub=None, out=None):
         """The tape's pull: (out, <p_0, ua - ub> as a host float or None).  out = base + ((c_0 p_0 + c_1 p_1) + ...) with combine's
         order and rounding, zeroed where mask <= 0 (threshold_backward: a NaN mask passes); ua / ub / base / mask nullable."""
-        ps = [_panel(p) for p in ps]
-        base, mask, ua, ub = (None if t is None else _panel(t) for t in (base, mask, ua, ub))
+        p0 = _panel(ps[0], ('ps', 0))
+        ps = [p0] + [_like(p, ('ps', j + 1), p0) for j, p in enumerate(ps[1:])]
+        base, mask, ua, ub = _like(base, 'base', p0), _like(mask, 'mask', p0), _like(ua, 'ua', p0), _like(ub, 'ub', p0)
         arr_p, arr_c, n = _terms(ps, cs)
-        out = torch.empty_like(ps[0]) if out is None else out
+        out = torch.empty_like(p0) if out is None else _like(out, 'out', p0, out=True)
         d = _BwdDots.get(ps[0].device)
         with _REDUCE_LOCK, torch.cuda.device(ps[0].device):
             check(_lib.load().ndcn_rk_pull_f32(ptr(out), ptr(base), arr_p, arr_c, n, ptr(mask), ptr(ua), ptr(ub), ptr(d.out), ptr(d.ws),
@@ -1004,8 +1155,8 @@ class HipOps:
     @staticmethod
     def dot_diff(g, a, b=None, scale=1.0, lazy=False):
         """scale * <g, a - b> (fp64 sum, fixed order): a float, or with lazy a deferred 0-d float32 host tensor (_BwdDots.lazy)"""
-        g, a = _panel(g), _panel(a)
-        b = _panel(b) if b is not None else None
+        g = _panel(g, 'g')
+        a, b = _like(a, 'a', g), _like(b, 'b', g)
         d = _BwdDots.get(g.device)
         with _REDUCE_LOCK, torch.cuda.device(g.device):
             check(_lib.load().ndcn_rk_dot_diff_f32(ptr(g), ptr(a), ptr(b), ptr(d.out), ptr(d.ws), g.numel(), stream_ptr()))
@@ -1015,19 +1166,20 @@ class HipOps:
     def error_bwd(y0, y1, ks, cs, rtol, atol, g_r, need_y0, need_y1, need_k, need_dots=True, accs=None, acc_y0=None, acc_y1=None, lazy=False):
         """VJP of the error ratio mean(((sum c_j k_j) / tol)^2) for upstream gradient g_r:
         (gy0, gy1, [gk_j], [d ratio / d c_j] (NOT yet multiplied by g_r) as host floats); accs / acc_y0 / acc_y1 as combine_bwd."""
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks = _like(y1, 'y1', y0), _likes(ks, 'ks', y0)
+        acc_y0, acc_y1 = _like(acc_y0, 'acc_y0', y0), _like(acc_y1, 'acc_y1', y0)
+        assert len(need_k) == len(ks)
         arr_k, arr_c, n = _terms(ks, cs)
         gk, arr_g = _grad_ptrs(y0, need_k)
-        arr_a = _acc_ptrs(accs, n)
+        accs, arr_a = _acc_ptrs(accs, n, y0)
         gy0 = torch.empty_like(y0) if need_y0 else None
         gy1 = torch.empty_like(y0) if need_y1 else None
         d = _BwdDots.get(y0.device)
         with _REDUCE_LOCK, torch.cuda.device(y0.device):
             check(_lib.load().ndcn_rk_error_bwd_f32(ptr(y0), ptr(y1), arr_k, arr_c, n, float(rtol), float(atol), float(g_r),
                                                     1.0 / y0.numel(), ptr(gy0), ptr(gy1), arr_g,
-                                                    ptr(_panel(acc_y0)) if acc_y0 is not None else None,
-                                                    ptr(_panel(acc_y1)) if acc_y1 is not None else None, arr_a, ptr(d.out), ptr(d.ws),
+                                                    ptr(acc_y0), ptr(acc_y1), arr_a, ptr(d.out), ptr(d.ws),
                                                     y0.numel(), stream_ptr()))
             if lazy:                          # deferred, already multiplied by g_r (the eager form leaves that to the caller)
                 return gy0, gy1, gk, (d.lazy(n, float(g_r)) if need_dots else None)
@@ -1036,8 +1188,8 @@ class HipOps:
     @staticmethod
     def rms_bwd(a, b, y, rtol, atol, coef, need_a, need_b, need_y):
         """VJP of ||(a - b) / (atol + |y| rtol)|| / sqrt(N); coef = g / (||.|| sqrt(N))."""
-        a, y = _panel(a), _panel(y)
-        b = _panel(b) if b is not None else None
+        a = _panel(a, 'a')
+        y, b = _like(y, 'y', a), _like(b, 'b', a)
         ga = torch.empty_like(a) if need_a else None
         gb = torch.empty_like(a) if (need_b and b is not None) else None
         gy = torch.empty_like(a) if need_y else None
@@ -1050,19 +1202,19 @@ class HipOps:
     def interp_bwd(g, y0, y1, ks, dt, x, need_y0, need_y1, need_k, need_dots=True, accs=None, acc_y0=None, acc_y1=None):
         """VJP of the dopri5 dense output at abscissa x: (gy0, gy1, [gk_j], <g, do/dx>, <g, do/ddt>); accs / acc_y0 / acc_y1 as
         combine_bwd."""
-        g, y0, y1 = _panel(g), _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
-        assert len(ks) == 7
+        g = _panel(g, 'g')
+        y0, y1, ks = _like(y0, 'y0', g), _like(y1, 'y1', g), _likes(ks, 'ks', g)
+        acc_y0, acc_y1 = _like(acc_y0, 'acc_y0', g), _like(acc_y1, 'acc_y1', g)
+        assert len(ks) == 7 and len(need_k) == 7
         arr_k = (_P * 7)(*[k.data_ptr() for k in ks])
         gk, arr_g = _grad_ptrs(g, need_k)
-        arr_a = _acc_ptrs(accs, 7)
+        accs, arr_a = _acc_ptrs(accs, 7, g)
         gy0 = torch.empty_like(g) if need_y0 else None
         gy1 = torch.empty_like(g) if need_y1 else None
         d = _BwdDots.get(g.device)
         with _REDUCE_LOCK, torch.cuda.device(g.device):
             check(_lib.load().ndcn_dopri5_interp_bwd_f32(ptr(g), ptr(y0), ptr(y1), arr_k, float(dt), float(x), ptr(gy0),
-                                                         ptr(gy1), arr_g, ptr(_panel(acc_y0)) if acc_y0 is not None else None,
-                                                         ptr(_panel(acc_y1)) if acc_y1 is not None else None, arr_a, ptr(d.out),
+                                                         ptr(gy1), arr_g, ptr(acc_y0), ptr(acc_y1), arr_a, ptr(d.out),
                                                          ptr(d.ws), g.numel(), stream_ptr()))
             dots = d.fetch() if need_dots else (0.0, 0.0)
         return gy0, gy1, gk, dots[0], dots[1]
@@ -1070,8 +1222,8 @@ class HipOps:
     @staticmethod
     def interp_direct_multi(y0, y1, ks, cmid, dt, xpows):
         """len(xpows) <= 7 ticks of one step in one pass: [dense output at each tick] - per tick the arithmetic of interp_direct."""
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks = _like(y1, 'y1', y0), _likes(ks, 'ks', y0)
         nt = len(xpows)
         assert len(ks) == 7 and 1 <= nt <= 7
         outs = [torch.empty_like(y0) for _ in range(nt)]
@@ -1086,23 +1238,22 @@ class HipOps:
     @staticmethod
     def interp_bwd_multi(gs, y0, y1, ks, dt, xs, need_y0, need_y1, need_k, accs=None, acc_y0=None, acc_y1=None, lazy=False):
         """VJP of len(gs) <= 7 dense outputs of ONE step: (gy0, gy1, [gk_j], [<g_t, do/dx_t>], sum_t <g_t, do/ddt>)."""
-        gs = [_panel(g) for g in gs]
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks, gs = _like(y1, 'y1', y0), _likes(ks, 'ks', y0), _likes(gs, 'gs', y0)
+        acc_y0, acc_y1 = _like(acc_y0, 'acc_y0', y0), _like(acc_y1, 'acc_y1', y0)
         nt = len(gs)
-        assert len(ks) == 7 and 1 <= nt <= 7 and len(xs) == nt
+        assert len(ks) == 7 and 1 <= nt <= 7 and len(xs) == nt and len(need_k) == 7
         arr_k = (_P * 7)(*[k.data_ptr() for k in ks])
         arr_gs = (_P * nt)(*[g.data_ptr() for g in gs])
         arr_x = (_F * nt)(*[float(v) for v in xs])
         gk, arr_g = _grad_ptrs(y0, need_k)
-        arr_a = _acc_ptrs(accs, 7)
+        accs, arr_a = _acc_ptrs(accs, 7, y0)
         gy0 = torch.empty_like(y0) if need_y0 else None
         gy1 = torch.empty_like(y0) if need_y1 else None
         d = _BwdDots.get(y0.device)
         with _REDUCE_LOCK, torch.cuda.device(y0.device):
             check(_lib.load().ndcn_dopri5_interp_bwd_multi_f32(arr_gs, nt, ptr(y0), ptr(y1), arr_k, float(dt), arr_x, ptr(gy0), ptr(gy1), arr_g,
-                                                               ptr(_panel(acc_y0)) if acc_y0 is not None else None,
-                                                               ptr(_panel(acc_y1)) if acc_y1 is not None else None, arr_a, ptr(d.out),
+                                                               ptr(acc_y0), ptr(acc_y1), arr_a, ptr(d.out),
                                                                ptr(d.ws), y0.numel(), stream_ptr()))
             if lazy:
                 dots = d.lazy(8)
@@ -1112,8 +1263,8 @@ class HipOps:
 
     @staticmethod
     def interp_fit(y0, y1, ks, cmid, dt):
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks = _like(y1, 'y1', y0), _likes(ks, 'ks', y0)
         assert len(ks) == 7
         a, b, c, d = (torch.empty_like(y0) for _ in range(4))
         arr_k, arr_c, _ = _terms(ks, cmid)
@@ -1125,11 +1276,10 @@ class HipOps:
     @staticmethod
     def interp_direct(y0, y1, ks, cmid, dt, xpow, out=None):
         """interp_fit + interp_eval in one pass, coefficients not stored (same arithmetic, bit-identical)."""
-        y0, y1 = _panel(y0), _panel(y1)
-        ks = [_panel(k) for k in ks]
+        y0 = _panel(y0, 'y0')
+        y1, ks = _like(y1, 'y1', y0), _likes(ks, 'ks', y0)
         assert len(ks) == 7
-        if out is None:
-            out = torch.empty_like(y0)
+        out = torch.empty_like(y0) if out is None else _like(out, 'out', y0, out=True)
         arr_k, arr_c, _ = _terms(ks, cmid)
         xp = (_F * 5)(*[float(v) for v in xpow])
         with torch.cuda.device(y0.device):
@@ -1140,10 +1290,9 @@ class HipOps:
     @staticmethod
     def interp_eval(fit, e, xpow, out=None):
         """`fit` = the (a, b, c, d) panels interp_fit returned; e = y at the start of the fitted step."""
-        a, b, c, d = fit
-        e = _panel(e)
-        if out is None:
-            out = torch.empty_like(e)
+        e = _panel(e, 'e')
+        a, b, c, d = _likes(fit, 'fit', e)
+        out = torch.empty_like(e) if out is None else _like(out, 'out', e, out=True)
         xp = (_F * 5)(*[float(v) for v in xpow])
         with torch.cuda.device(e.device):
             check(_lib.load().ndcn_interp_eval_f32(ptr(a), ptr(b), ptr(c), ptr(d), ptr(e), xp, ptr(out), e.numel(),
@@ -1152,10 +1301,9 @@ class HipOps:
 
     @staticmethod
     def fixed_stage(op, y, k1, k2=None, k3=None, k4=None, dt=0.0, out=None):
-        y = _panel(y)
-        ks = [None if k is None else _panel(k) for k in (k1, k2, k3, k4)]
-        if out is None:
-            out = torch.empty_like(y)
+        y = _panel(y, 'y')
+        ks = [_like(k, ('k', j + 1), y) for j, k in enumerate((k1, k2, k3, k4))]
+        out = torch.empty_like(y) if out is None else _like(out, 'out', y, out=True)
         with torch.cuda.device(y.device):
             check(_lib.load().ndcn_fixed_stage_f32(int(op), ptr(out), ptr(y), ptr(ks[0]), ptr(ks[1]), ptr(ks[2]),
                                                    ptr(ks[3]), float(dt), y.numel(), stream_ptr()))
@@ -1166,10 +1314,9 @@ class HipOps:
         """One Adams-Bashforth step (fixed_adams.py:180-182 + solvers.py:92): y + dt * (((0 + a_0 f_0) + a_1 f_1) + ...), every product
         and sum rounded on its own - ndcn_ab_step_f32; fs: the 3..11 newest evaluations, newest first; coeffs: their float32 weights.
         out may be y."""
-        y = _panel(y)
-        fs = [_panel(f) for f in fs]
-        if out is None:
-            out = torch.empty_like(y)
+        y = _panel(y, 'y')
+        fs = _likes(fs, 'fs', y)
+        out = torch.empty_like(y) if out is None else _like(out, 'out', y, out=True)
         arr_f, arr_a, n = _terms(fs, coeffs)
         with torch.cuda.device(y.device):
             check(_lib.load().ndcn_ab_step_f32(ptr(out), ptr(y), arr_f, arr_a, n, float(dt), y.numel(), stream_ptr()))
@@ -1180,13 +1327,12 @@ class HipOps:
         """(new state, decoded): ab_step on an (N, H) panel that also writes linear(s, weight, bias), shape (N, C), in the same launch
         (ndcn_ab_step_readout_f32) - s the new state, or with emit_off != 0 the tick s + ((s - s) / dt) * emit_off of a sub-stepped
         grid; the bits of hip.linear on that panel.  H = 16, 20, .. 60 or 64 <= H <= 512, C <= 15; out may be y."""
-        y = _panel(y)
-        fs = [_panel(f) for f in fs]
+        y = _panel(y, 'y')
+        fs = _likes(fs, 'fs', y)
         assert y.dim() == 2 and weight.dim() == 2 and weight.shape[1] == y.shape[1]
-        weight = _panel(weight)
-        bias = None if bias is None else _panel(bias)
-        if out is None:
-            out = torch.empty_like(y)
+        weight = _operand(weight, 'weight', y.device)
+        bias = None if bias is None else _operand(bias, 'bias', y.device, numel=weight.shape[0])
+        out = torch.empty_like(y) if out is None else _like(out, 'out', y, out=True)
         dec = torch.empty((y.shape[0], weight.shape[0]), dtype=torch.float32, device=y.device)
         arr_f, arr_a, n = _terms(fs, coeffs)
         with torch.cuda.device(y.device):
@@ -1199,8 +1345,8 @@ class HipOps:
         """(dy, delta, u) of a fixed_adams step that holds len(fs) = 3..11 evaluations (fixed_adams.py:180-188): dy = dt * sum a_i f_i,
         delta = dt * sum m_i f_i, u = y + dy - one pass over the history, every product and sum rounded on its own
         (ndcn_abm_predict_f32).  a: the Adams-Bashforth weights, m: the Adams-Moulton weights of the history (core.am_weights)."""
-        y = _panel(y)
-        fs = [_panel(f) for f in fs]
+        y = _panel(y, 'y')
+        fs = _likes(fs, 'fs', y)
         assert len(a) == len(fs) == len(m)
         dy, delta, u = torch.empty_like(y), torch.empty_like(y), torch.empty_like(y)
         arr_f, arr_a, n = _terms(fs, a)
@@ -1215,9 +1361,9 @@ class HipOps:
         """One corrector iteration (fixed_adams.py:192-194): (dy, u, failed) with dy <- c0 * f + delta IN PLACE, u = y + dy a new panel and
         `failed` the number of elements for which |dy_old - dy_new| < atol + rtol * max(|dy_old|, |dy_new|) does not hold, as a host int -
         counted in integers on the device, one 8-byte read-back (ndcn_abm_correct_f32)."""
-        f, delta, y = _panel(f), _panel(delta), _panel(y)
-        require_device(dy, 'dy')
-        assert dy.is_contiguous()
+        y = _panel(y, 'y')
+        f, delta = _like(f, 'f', y), _like(delta, 'delta', y)
+        dy = _like(dy, 'dy', y, out=True)
         u = torch.empty_like(y)
         red = _Reducer.get(y.device)
         with _REDUCE_LOCK, torch.cuda.device(y.device):
@@ -1236,10 +1382,10 @@ class HipOps:
         """The gradient of one evaluation of an explicit_adams solve, gathered from the adjoints of the Adams-Bashforth steps that used
         it (ndcn_ab_adjoint_f32): [base +] (((0 + c_0 g_0) + c_1 g_1) + ...), every product and sum rounded on its own, the base added
         last.  gs: 1..11 panels, cs: their float32 coefficients (core.ab_adjoint_terms).  out may be base, never one of gs."""
-        gs = [_panel(g) for g in gs]
-        base = _panel(base) if base is not None else None
-        if out is None:
-            out = torch.empty_like(gs[0])
+        g0 = _panel(gs[0], ('gs', 0))
+        gs = [g0] + [_like(g, ('gs', j + 1), g0) for j, g in enumerate(gs[1:])]
+        base = _like(base, 'base', g0)
+        out = torch.empty_like(g0) if out is None else _like(out, 'out', g0, out=True)
         arr_g, arr_c, n = _terms(gs, cs)
         with torch.cuda.device(out.device):
             check(_lib.load().ndcn_ab_adjoint_f32(ptr(out), ptr(base), arr_g, arr_c, n, out.numel(), stream_ptr()))
@@ -1251,11 +1397,11 @@ class HipOps:
         it (ndcn_abm_adjoint_f32): [base +] ((((0 + cp_0 P_0) + cd_0 D_0) + cp_1 P_1) + cd_1 D_1 ...), every product and sum rounded on
         its own, the base added last.  ps / ds: 1..11 panels each (P_q may be D_q), cps / cds: their float32 coefficients
         (core.abm_adjoint_terms).  out may be base, never a term."""
-        ps, ds = [_panel(g) for g in ps], [_panel(g) for g in ds]
+        p0 = _panel(ps[0], ('ps', 0))
+        ps, ds = [p0] + [_like(g, ('ps', j + 1), p0) for j, g in enumerate(ps[1:])], _likes(ds, 'ds', p0)
         assert len(ps) == len(ds) == len(cps) == len(cds)
-        base = _panel(base) if base is not None else None
-        if out is None:
-            out = torch.empty_like(ps[0])
+        base = _like(base, 'base', p0)
+        out = torch.empty_like(p0) if out is None else _like(out, 'out', p0, out=True)
         arr_p, arr_cp, n = _terms(ps, cps)
         arr_d, arr_cd, _ = _terms(ds, cds)
         with torch.cuda.device(out.device):
@@ -1266,11 +1412,13 @@ class HipOps:
     def tick_emit(y, dt, tms, outs=None):
         """The ticks a sub-stepped fixed-grid step reports that are NOT an end of the step (solvers.py:92-108, y0 already overwritten
         with y1): [y + ((y - y) / dt) * tm for tm in tms] - one pass over y per 8 ticks (ndcn_tick_emit_f32)."""
-        y = _panel(y)
+        y = _panel(y, 'y')
         nt = len(tms)
         if outs is None:
             outs = [torch.empty_like(y) for _ in range(nt)]
-        assert len(outs) == nt and all(o.is_contiguous() and o.numel() == y.numel() for o in outs)
+        assert len(outs) == nt
+        for j, o in enumerate(outs):
+            _like(o, ('outs', j), y, out=True)
         if nt == 0:
             return outs
         arr_t = (_F * nt)(*[float(v) for v in tms])
@@ -1284,9 +1432,10 @@ class HipOps:
     @staticmethod
     def row_l1_normalize(X, out=None):
         """F.normalize(X, p=1, dim=1) with infinities zeroed (ode_gcn.py:9-26)."""
-        X = _panel(X)
-        if out is None:
-            out = torch.empty_like(X)
+        X = _panel(X, 'X')
+        if X.dim() != 2:
+            _refuse('X', 'a 2-D panel', X)
+        out = torch.empty_like(X) if out is None else _like(out, 'out', X, out=True, shape=True)
         with torch.cuda.device(X.device):
             check(_lib.load().ndcn_row_l1_normalize_f32(ptr(X), ptr(out), X.shape[0], X.shape[1], stream_ptr()))
         return out
@@ -1294,16 +1443,27 @@ class HipOps:
     @staticmethod
     def row_l1_normalize_bwd(g, X):
         """VJP of row_l1_normalize at X for the upstream gradient g."""
-        g, X = _panel(g), _panel(X)
+        X = _panel(X, 'X')
+        if X.dim() != 2:
+            _refuse('X', 'a 2-D panel', X)
+        g = _like(g, 'g', X, shape=True)
         out = torch.empty_like(X)
         with torch.cuda.device(X.device):
             check(_lib.load().ndcn_row_l1_normalize_bwd_f32(ptr(g), ptr(X), ptr(out), X.shape[0], X.shape[1], stream_ptr()))
         return out
 
     @staticmethod
+    def _state(A, x):
+        """the N x 1 state of a truth-dynamics launch on the square operator A"""
+        x = _panel(x, 'x')
+        if not (x.numel() == A.shape[0] == A.shape[1]) or A.device != x.device:
+            raise _lib.NdcnHipError(_lib.EINVAL, 'operator %s on %s, state of %d elements on %s' % (tuple(A.shape), A.device, x.numel(), x.device))
+        return x
+
+    @staticmethod
     def gene_rhs(A, x, b=1.0, f=1.0, h=2.0):
         A = as_csr(A)
-        x = _panel(x)
+        x = HipOps._state(A, x)
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
             check(_lib.load().ndcn_gene_rhs_f32(A.view_ref(), ptr(x), ptr(out), float(b), float(f), float(h), stream_ptr()))
@@ -1312,7 +1472,7 @@ class HipOps:
     @staticmethod
     def mutual_rhs(A, x, b=0.1, k=5., c=1., d=5., e=0.9, h=0.1):
         A = as_csr(A)
-        x = _panel(x)
+        x = HipOps._state(A, x)
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
             check(_lib.load().ndcn_mutual_rhs_f32(A.view_ref(), ptr(x), ptr(out), float(b), float(k), float(c), float(d),
@@ -1328,13 +1488,11 @@ class HipOps:
         'error': (K, (sum of squared error ratios, non-finite count of y1)), y1 defaulting to x.
         c_dev: a float32 device tensor holding the coefficients in place of cs (what a replayed step reads)."""
         A = as_csr(A)
-        x = _panel(x)
-        assert x.numel() == A.shape[0] == A.shape[1]
+        x = HipOps._state(A, x)
         dyn = _lib.dynamics({'heat': _lib.DYN_HEAT, 'gene': _lib.DYN_GENE, 'mutual': _lib.DYN_MUTUAL}.get(kind, kind), params)
         rk = {'plain': _lib.RK_NONE, 'combine': _lib.RK_COMBINE, 'error': _lib.RK_ERROR, 'rk4': _lib.RK_RK4}[mode]
-        kprev = [_panel(k) for k in kprev]
-        y0 = _panel(y0) if y0 is not None else None
-        y1 = _panel(y1, 'y1') if y1 is not None else None
+        kprev = _likes(kprev, 'kprev', x)
+        y0, y1 = _like(y0, 'y0', x), _like(y1, 'y1', x)
         K = torch.empty_like(x)
         y_next = torch.empty_like(x) if mode in ('combine', 'rk4') else None
         arr_k = (_P * max(len(kprev), 1))(*[k.data_ptr() for k in kprev])
@@ -1344,7 +1502,7 @@ class HipOps:
             arr_c2 = (_F * len(aux_cs))(*[float(c) for c in aux_cs])
             y_aux = torch.empty_like(x)
         if c_dev is not None:
-            c_dev = _panel(c_dev, 'coefficients')
+            c_dev = _operand(c_dev, 'c_dev', x.device)          # (how many coefficients the replayed step reads is the C side's knowledge)
         red = _Reducer.get(x.device)
         with _REDUCE_LOCK, torch.cuda.device(x.device):
             check(_lib.load().ndcn_dyn_rk_f32(ctypes.byref(dyn), A.view_ref(), ptr(x), ptr(K), rk, ptr(y0), arr_k, arr_c, len(kprev),

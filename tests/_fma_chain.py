@@ -108,3 +108,23 @@ def row_terms(indptr, threshold=None, seg=256):
         hubs, _, _, nseg = hub_segments(indptr, threshold, seg)
         d[hubs] += nseg
     return d
+
+
+# ---- the float64 bounds the GPU tests hold the kernels to, stated once (u = U = 2^-24; `mag` is the same expression on magnitudes)
+def spmm_bound(indptr, mag, alpha=1.0, threshold=None):
+    """|alpha (A X) - float64| per element: a chain of d fmas and the product with alpha, each rounded once, plus the subnormal floor
+    (tests/test_gpu_spmm_routes.py holds every route to it); mag = |A| |X| in float64, one row of d per row of mag"""
+    d = row_terms(indptr, threshold)[:, None]
+    return 1.01 * (abs(float(alpha)) * ((d + 1) * U * mag + d * 2.0 ** -150) + 2.0 ** -150)
+
+
+def dot_bound(k, mag):
+    """a float32 inner product of k terms plus a bias, in any order: (k + 2) u on the magnitudes (the forward bound of
+    tests/test_gpu_linear_routes.py); mag = |S| |W|^T + |b|"""
+    return (k + 2) * U * mag
+
+
+def sum_bound(n_terms, mag):
+    """y0 + ((c_0 k_0 + c_1 k_1) + ...): one rounding per product and per sum, n_terms + 1 roundings on any path, second order covered
+    by the 1.01 (the combine / pull bound of tests/test_gpu_reverse_routes.py); mag = |y0| + sum |c_j k_j|"""
+    return 1.01 * (n_terms + 1) * U * mag

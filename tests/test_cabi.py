@@ -1,5 +1,6 @@
 """The C-ABI library builds, loads, and exports exactly what include/ndcn_hip.h declares.  No compute
-calls (there is no GPU in the CPU suite)."""
+calls (there is no GPU in the CPU suite).  Names only: tests/test_cabi_signatures.py compares every prototype, struct layout and
+constant of the binding with the header."""
 import os
 import re
 import subprocess
